@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- agent-QP solves/sec of the DMPC per-agent horizon QP (K = 15) on MI355X.
 
-Contract (one JSON line on rank 0):  python bench.py --gpus N --steps K --warmup W
+Contract (one JSON line on rank 0):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up the headline scene, warms up, times the K steps, writes the outputs of the last timed step (--dump-outputs) and prints
+the line.  Everything else -- the workload statistics of the cycle, the multi-rank exchange check, the copy ceiling and the committed counter
+summary next to the roofline, the secondary workloads and the CPU baseline -- runs only with --full.
 
 Headline = the configuration BASELINE.json's metric is quoted on ("at N agents, 1/2/4/8 MI355X"): configs[3] (C4), ONE scene of 10 000
 agents, solveSoftDMPCbound with the constants of test/failure_rate.m, at EVERY N:
@@ -14,7 +18,7 @@ agents, solveSoftDMPCbound with the constants of test/failure_rate.m, at EVERY N
     (dmpc.cpp:1600-1625), dmpc_step_sharded_device = solve of the own cluster + ONE RCCL all-gather of the new predictions inside the
     library per step.  Total work is fixed -> "scaling": "strong"; the N = 1 point of a scaling curve IS this bench line;
   * value = agents x steps / max-over-ranks wall time between barriers.
-`secondary` (N = 1 only) keeps the other configs and variants as replays / closed loops, each with its own fraction of the HBM roofline --
+`secondary` (--full, N = 1 only) keeps the other configs and variants as replays / closed loops, each with its own fraction of the HBM roofline --
 among them C2 x 512 scenes, the headline of rounds 1-4.
 """
 import argparse
@@ -137,6 +141,22 @@ class ClosedLoop:
         self.step()
 
 
+def run_ranks(cmd):
+    """torch.distributed.run and its ranks as a fresh child process (this one has touched the GPU runtime already): SIGTERM / SIGINT are
+    passed on, and the child is sent SIGTERM when this process dies however it dies (a caller's time limit kills only this one)."""
+    import ctypes
+    import signal
+    import subprocess
+
+    def die_with_parent():
+        ctypes.CDLL(None).prctl(1, signal.SIGTERM)     # PR_SET_PDEATHSIG
+    child = subprocess.Popen(cmd, preexec_fn=die_with_parent)
+    for sg in (signal.SIGTERM, signal.SIGINT):
+        signal.signal(sg, lambda num, _frame: child.send_signal(num))
+    rc = child.wait()
+    return 128 - rc if rc < 0 else rc     # (killed by a signal: the shell's convention)
+
+
 def timed(torch, fn, steps, warmup=3):
     for _ in range(warmup):
         fn()
@@ -155,8 +175,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=9)
     ap.add_argument("--agents", type=int, default=10000, help="agents of the headline scene (BASELINE configs[3]: 10 000)")
     ap.add_argument("--scenes", type=int, default=512, help="scenes batched by the secondary replays (512 ~ one Monte-Carlo experiment of the reference)")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the workload statistics, the exchange check (N > 1), the copy ceiling and counter summary, the secondary workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's outputs, the next table, the advanced states) as DIR/<name>.npy")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary workloads")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--emulate-gpus", type=int, default=0,
                     help="tuning aid: on ONE GPU run rank 0's share of a G-GPU job (no collective) to see the per-rank step time; never a headline number")
     ap.add_argument("--debug-option", action="append", default=[], metavar="NAME=VALUE",
@@ -186,7 +210,7 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        sys.exit(run_ranks(cmd))
     if world != args.gpus and world == 1 and args.gpus > 1 and not args.emulate_gpus:
         sys.exit("bench.py --gpus N>1 must be launched with torch.distributed.run (one rank per GPU)")
     G = world
@@ -272,16 +296,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # workload statistics of the cycle (untimed): per MPC step the solved share and the iteration counts
+    # workload statistics of the cycle (untimed, --full): per MPC step the solved share and the iteration counts
     loop.reset()
     stats = []
-    for _ in range(CYCLE):
+    for _ in range(CYCLE if args.full else 0):
         one_step()
         torch.cuda.synchronize()
         st = loop.status.cpu().numpy(); inf = loop.info.cpu().numpy()
         stats.append((float((st & 1).mean()), float(inf[..., 4].mean()), int(inf[..., 4].max()), int(inf[..., 2].max()), int(((st & 48) != 0).sum()),
                       float(inf[..., 1].mean()), int(inf[..., 7].max()), float(((st & 8) != 0).mean())))
-    st_last = loop.status.clone()
+    st_last = loop.status.clone() if args.full else None
     setup_s = time.perf_counter() - t_start
 
     loop.reset()
@@ -304,12 +328,14 @@ def main():
         elapsed, kern_max, scan_max = (float(v) for v in t.tolist())
     else:
         kern_max, scan_max = kern_ms, scan_ms
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, loop, args.dump_outputs)
 
     # outside the timed region: the sharded step must be the UNSHARDED step of the same scene, per agent and bit for bit -- the scene solved
     # once more as ONE chunk of all N agents on this GPU from the initDMPC state, this rank's agents compared; and every rank must hold the
     # same gathered table
     exchange_ok = None
-    if use_dist:
+    if use_dist and args.full:
         loop.reset(); one_step(); torch.cuda.synchronize()
         ds = mp.Dmpc("bound", device=local_rank, **kw4)
         one = ClosedLoop(torch, ds, dev, po4, pf4, 1, 0, sharded=False)
@@ -328,19 +354,19 @@ def main():
 
     # ---------------------------------------------------------------- secondary workloads (N = 1; reported, not the headline)
     secondary = None
-    if not args.no_secondary and G == 1 and rank == 0:
+    if args.full and not args.no_secondary and G == 1 and rank == 0:
         secondary = secondary_workloads(torch, mp, wl, dev, local_rank, args)
 
     if rank == 0:
         N_loc = loop.cnt
         ba = b_alg(N4, N_loc)
         achieved = N_loc * ba / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
-        # PMC counters cannot be read inside the timed run: traffic and the per-wave counters come from the committed rocprofv3 passes of this
+        # PMC counters cannot be read inside the timed run (--full): traffic and the per-wave counters come from the committed rocprofv3 passes of this
         # same workload (profiles/r05_c4_pmc_summary.json, made by tools/gpu_profile_round.sh + tools/profile_summary.py) -- and only when that
         # summary was taken on THESE kernel sources (its source_hash: sha256 over multiagent_planning_amd/csrc/*.hip|*.h)
         traffic, pmc, pmc_note = None, None, None
         tj = os.path.join(ROOT, "profiles", PMC_SUMMARY)
-        if os.path.exists(tj) and G == 1:
+        if args.full and os.path.exists(tj) and G == 1:
             try:
                 jt = json.load(open(tj))
                 if jt.get("solves_per_launch") != N_loc:
@@ -352,29 +378,30 @@ def main():
                     traffic = jt.get("hbm_bytes_per_launch")
             except Exception as e:   # noqa: BLE001
                 pmc, pmc_note = None, f"profiles/{PMC_SUMMARY}: {e}"
-        # the box's practical HBM ceiling next to the 8 TB/s of the data sheet: a 1 GiB device-to-device copy, best of 5
+        # the box's practical HBM ceiling next to the 8 TB/s of the data sheet (--full): a 1 GiB device-to-device copy, best of 5
         copy_gbs = None
-        try:
-            src_c = torch.empty(1 << 28, dtype=torch.float32, device=dev); dst_c = torch.empty_like(src_c)
-            dst_c.copy_(src_c); torch.cuda.synchronize()
-            best_c = 1e9
-            for _ in range(5):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); dst_c.copy_(src_c); e1.record(); torch.cuda.synchronize()
-                best_c = min(best_c, e0.elapsed_time(e1))
-            copy_gbs = 2.0 * src_c.numel() * 4 / (best_c * 1e-3) / 1e9
-            del src_c, dst_c
-        except Exception:   # noqa: BLE001
-            copy_gbs = None
+        if args.full:
+            try:
+                src_c = torch.empty(1 << 28, dtype=torch.float32, device=dev); dst_c = torch.empty_like(src_c)
+                dst_c.copy_(src_c); torch.cuda.synchronize()
+                best_c = 1e9
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(); dst_c.copy_(src_c); e1.record(); torch.cuda.synchronize()
+                    best_c = min(best_c, e0.elapsed_time(e1))
+                copy_gbs = 2.0 * src_c.numel() * 4 / (best_c * 1e-3) / 1e9
+                del src_c, dst_c
+            except Exception:   # noqa: BLE001
+                copy_gbs = None
         ms_step = elapsed / args.steps * 1e3
-        sa = np.array([s[:2] for s in stats])
-        stl = st_last.cpu().numpy()
+        sa = np.array([s[:2] for s in stats]) if stats else None
+        stl = st_last.cpu().numpy() if st_last is not None else None
         line = {
             "metric": "agent-QP solves/sec (K=15 horizon)",
             "value": value, "unit": "solves/s", "n_gpus": (1 if emu else G), "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_step, "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic" + (" [SHARED-GPU FUNCTIONAL CHECK, not a measurement]" if share else ""),
-            "config": {"workload": f"C4 (BASELINE configs[3]): ONE scene of {N4} agents, solveSoftDMPCbound (test/failure_rate.m constants), K=15, first `coll` return at MPC step 4 (value counts such early returns as solves: value_solved_only), "
+            "config": {"workload": f"C4 (BASELINE configs[3]): ONE scene of {N4} agents, solveSoftDMPCbound (test/failure_rate.m constants), K=15, first `coll` return at MPC step 4 (value counts such early returns as solves" + (": value_solved_only" if args.full else "") + "), "
                                    f"device-resident closed loop over MPC steps 2-{CYCLE + 1} (from the initDMPC state again every {CYCLE} steps), "
                                    f"agents sharded over {G} GPU(s)" + (" [rank 0's cluster only, emulated]" if emu else ""),
                        "agents_per_scene": N4, "scenes": 1, "solves_per_step": (N4 if not emu else loop.cnt), "agents_per_gpu": N_loc,
@@ -395,7 +422,7 @@ def main():
                          "other_kernels_ms_avg": {"neighbour lists (bbox, table copy, grid_bin/scan/fill/query) + dmpc_scan_kernel + order_kernel": scan_ms},
                          "alg_bytes_per_solve": ba, "solves_per_launch": N_loc,
                          "whole_step_frac": (N_loc * ba / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS),
-                         "secondary": (dict(wave_time=pmc.get("wave_time"), instructions_per_solve=pmc.get("instructions_per_solve"),
+                         "secondary": None if not args.full else (dict(wave_time=pmc.get("wave_time"), instructions_per_solve=pmc.get("instructions_per_solve"),
                                             whole_step_traffic=pmc.get("whole_step_bytes_per_launch"), fp64=pmc.get("fp64"),
                                             traffic_calibration=pmc.get("traffic_calibration"), git_commit=pmc.get("git_commit"), source_hash=pmc.get("source_hash"),
                                             source=f"profiles/{PMC_SUMMARY} (rocprofv3 passes of this workload on these kernel sources, committed; not re-measured in this run)") if pmc else pmc_note),
@@ -404,16 +431,17 @@ def main():
                                  "(counters, not a model).  No MFMA: the reduced solver of solveSoftDMPCbound (dmpc_rsolve.hip, round 6) has no dense contraction at all -- "
                                  "per axis a tridiagonal + rank-1 Hessian (parallel cyclic reduction in DPP rows + Sherman-Morrison), the soft rows as a 3x3 penalty, "
                                  "hard rows / walls / entering constraint as a system of at most eight unknowns, one per lane"},
-            "value_solved_only": value * float(sa[:, 0].mean()),
-            "workload_stats": {"per_mpc_step": [{"mpc_step": i + 2, "solved_frac": s[0], "mean_iters": s[1], "max_iters": s[2], "max_tries": s[3]} for i, s in enumerate(stats)],
+        }
+        if args.full:
+            line["value_solved_only"] = value * float(sa[:, 0].mean())
+            line["workload_stats"] = {"per_mpc_step": [{"mpc_step": i + 2, "solved_frac": s[0], "mean_iters": s[1], "max_iters": s[2], "max_tries": s[3]} for i, s in enumerate(stats)],
                                "solved_frac": float(sa[:, 0].mean()), "mean_iters": float(sa[:, 1].mean()), "max_iters": int(max(s[2] for s in stats)),
                                "invalid": int(sum(s[4] for s in stats)), "mean_rows": float(np.mean([s[5] for s in stats])),
                                "max_working_set": int(max(s[6] for s in stats)), "infeasible_frac": float(np.mean([s[7] for s in stats])),
-                               "last_step_status_histogram": {str(int(v)): int(c) for v, c in zip(*np.unique(stl, return_counts=True))}},
-        }
+                               "last_step_status_histogram": {str(int(v)): int(c) for v, c in zip(*np.unique(stl, return_counts=True))}}
         if secondary is not None:
             line["secondary"] = secondary
-        if not args.no_cpu_baseline and G == 1:
+        if args.full and not args.no_cpu_baseline and G == 1:
             line["cpu_baseline"] = cpu_baseline(wl, cfg4, kw4, N4, po4, pf4, dmpc)
     if use_dist:
         dist.destroy_process_group()
@@ -426,6 +454,31 @@ def main():
             pass
         sys.stdout.flush()
         print(json.dumps(line), flush=True)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(torch, loop, out_dir):
+    """What the last timed step returned to its caller, as float64 .npy files: this rank's p / v / a horizons [S][agents][45], status
+    [S][agents] and records [S][agents][8], the next table [G][S][45][C] and the advanced states [S][agents][3].  More than 64 MB in all
+    (--agents far above the default): the same seeded sample of agents from every array."""
+    torch.cuda.synchronize()
+    arrs = {"p": loop.out[0], "v": loop.out[1], "a": loop.out[2], "status": loop.status, "info": loop.info,
+            "state_p": loop.x[0], "state_v": loop.x[1], "state_a": loop.x[2]}
+    arrs = {k: v.cpu().numpy().astype(np.float64) for k, v in arrs.items()}
+    table = loop.tab[loop.cur].cpu().numpy().astype(np.float64)
+    total = sum(a.nbytes for a in arrs.values()) + table.nbytes
+    if total > DUMP_BYTES:
+        n = loop.cnt
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * (DUMP_BYTES - (4 << 20)) / total)), replace=False))   # (headroom: index, headers)
+        arrs = {k: a[:, keep] for k, a in arrs.items()}
+        arrs["agent_index"] = keep.astype(np.float64)
+        table = table[..., keep[keep < table.shape[-1]]]
+    arrs["next_table"] = table
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(wl, cfg4, kw4, N4, po4, pf4, dmpc):

@@ -241,3 +241,45 @@ def test_reached_goal_is_checked_on_the_first_column_too():
         r = getattr(mp.Dmpc("bound", **kw), fn)(po, pf, 40, 0.01)
         assert int(r["K_T_used"][0]) == 1 and int(r["scene_status"][0]) == (mp.ST_SOLVED | mp.ST_REACHED), fn
         assert int(r["K_T_used"][1]) > 1, fn
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run, no --full): the line carries the headline fields and nothing of --full; the arrays of
+    the last timed step are written as float64 .npy, and a second run with the same arguments writes the same arrays"""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for rep in range(2):
+        out = tmp_path / f"run{rep}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--agents", "2000",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["roofline"]["launches"] == 4                   # the library counted exactly --steps solve launches in the timed region
+    assert "workload_stats" not in line and "secondary" not in line and "cpu_baseline" not in line
+    d = dumps[0]
+    assert {"p", "v", "a", "status", "info", "next_table", "state_p", "state_v", "state_a"} <= set(d)
+    assert d["p"].shape == (1, 2000, 45) and d["status"].shape == (1, 2000) and d["next_table"].shape == (1, 1, 45, 2000)
+    assert all(a.dtype == np.float64 for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 << 20
+    assert ((d["status"].astype(np.int64) & 1) == 1).any() and np.abs(d["p"]).max() > 0
+    for k in d:
+        assert np.array_equal(d[k], dumps[1][k]), k
+    # the dump is the LAST timed step: warm-up, reset to the initDMPC state, then MPC steps 2-5 -- replayed through the host API
+    cfg = dict(wl.CONFIGS["C4"])
+    kw = wl.solver_kwargs(cfg, 2000)
+    po, pf = wl.make_scenes(cfg, 1, 2000, wl.SEED0 + 4)
+    h = mp.Dmpc("bound", **kw)
+    l, _, _ = h.init_batch(po, pf)
+    xp, xv, xa = po.copy(), np.zeros_like(po), np.zeros_like(po)
+    for _ in range(4):
+        out = h.step_batch(l, xp, xv, xa, pf)
+        ok = ((out["status"] & 1) == 1)[..., None]
+        l = np.where(ok, out["p"], l); xp = np.where(ok, out["p"][..., :3], xp)
+        xv = np.where(ok, out["v"][..., :3], xv); xa = np.where(ok, out["a"][..., :3], xa)
+    assert np.array_equal(d["status"], out["status"]) and np.array_equal(d["p"], out["p"]) and np.array_equal(d["a"], out["a"])
+    assert np.array_equal(d["state_p"], xp) and np.array_equal(d["state_v"], xv) and np.array_equal(d["next_table"][0, 0].T, l[0])

@@ -224,19 +224,39 @@ def test_campaign_acceptance_floor_regression():
         xv = np.where(okb[:, None], out["v"][:, :3], xv); xa = np.where(okb[:, None], out["a"][:, :3], xa)
 
 
+CAMPAIGN_SEED, CAMPAIGN_SCENES = 2963, 30
+SLACK_VARIANTS = ("softall", "repair", "cpp1", "softall_c")
+
+
+def _slack_tolerance(prm, kw, l, xp, xv, xa, pf, out, ea, tol, what):
+    """the slack variants against the oracle: every agent within `tol` -- except where the slack penalties are 1e6 (|term| >= 1e6, the C5
+    constants), the top of DESIGN.md section 2's stated range "2e-8 ... 5e-7 where the multipliers are 1e5 ... 1e6": there an agent may
+    sit up to 5e-7 off the oracle, and only if the GPU's answer carries the solver-independent KKT certificate (tests/certificates.py)
+    -- a certified minimiser, the deviation being the conditioning of the dense oracle at multipliers of 1e6"""
+    loose = np.nonzero(ea > tol)[0]
+    if loose.size == 0:
+        return 0
+    assert abs(kw["term"]) >= 1e6 and (ea <= 5e-7).all(), f"{what}: l_inf {ea.max():.2e}"
+    check_batch(prm, l, xp, xv, xa, pf, out["a"], out["status"], out["info"][:, 2], what + " (certificate of the agents above the bar)", agents=loose)
+    return int(loose.size)
+
+
 def test_randomized_campaign_time_boxed():
-    """One fresh seed of the randomized campaign (tests/dev/gpu_campaign.py: random scenes of 2-90 agents in the C2/C5 boxes, all 10
-    variants, 2-6 teacher-forced MPC steps) for 25 s of wall time: every status, branch record and retry count identical to the oracle,
-    trajectories to the stated tolerance.  The full campaigns (four seeds, 1.9 M agent-steps) found two real solver defects in round 2;
-    this slice keeps a moving sample of them in the collected suite -- the seed changes with the calendar week, and is printed."""
-    import time
-    seed = int(time.time() // (7 * 86400))
+    """A fixed slice of the randomized campaign (tests/dev/gpu_campaign.py: random scenes of 2-90 agents in the C2/C5 boxes, all 10
+    variants, 2-6 teacher-forced MPC steps): every status, branch record and retry count identical to the oracle,
+    trajectories to the stated tolerance.  The full campaigns (four seeds, 1.9 M agent-steps) found two real solver defects in round 2.
+    The slice is the same on every run and every machine: seed and scene count are fixed (it used to take its seed from the calendar
+    week and end after 25 s of wall time, so the verdict depended on the date and the speed of the box; the seed is the one that week
+    drew when the slice was pinned, 30 scenes are what 25 s covered).  Its scene 18 holds a cpp1 agent 5.7e-8 off the oracle at
+    multipliers of 1e6, a certified minimiser: see _slack_tolerance and test_campaign_cpp1_multiplier_1e6_regression.  Fresh seeds
+    belong to tests/dev/gpu_campaign.py."""
+    seed = CAMPAIGN_SEED
     rng = np.random.default_rng(seed)
-    t0 = time.time()
     total = 0
     worst = 0.0
     scenes = 0
-    while time.time() - t0 < 25.0:
+    certified = 0
+    while scenes < CAMPAIGN_SCENES:
         N = int(rng.integers(2, 90))
         cfgname = "C5" if rng.random() < 0.5 else "C2"
         cfg = wl.CONFIGS[cfgname]
@@ -252,7 +272,7 @@ def test_randomized_campaign_time_boxed():
         for variant in ALL_VARIANTS:
             d = mp.Dmpc(variant, **kw); prm = orc.make_params(variant, **kw)
             l = init_table(po, pf); xp, xv, xa = po.copy(), np.zeros_like(po), np.zeros_like(po)
-            tol = 5e-8 if variant in ("softall", "repair", "cpp1", "softall_c") else 1e-9 * max(1.0, abs(kw["term"]) / 5e4)
+            tol = 5e-8 if variant in SLACK_VARIANTS else 1e-9 * max(1.0, abs(kw["term"]) / 5e4)
             for k in range(int(rng.integers(2, 7))):
                 out = d.step_batch(l, xp, xv, xa, pf); ref = orc.step(prm, l, xp, xv, xa, pf, nthreads=8)
                 total += N
@@ -270,10 +290,51 @@ def test_randomized_campaign_time_boxed():
                     # the reduced solver (round 6) forms its small system explicitly: its stated tolerance where the multipliers are huge
                     ladder = ref["info"][:, 2] > 1
                     assert (ea[~ladder] <= max(tol, 5e-8)).all() and (ea[ladder] <= 5e-7).all(), f"{what}: l_inf {e:.2e}"
+                elif variant in SLACK_VARIANTS:
+                    certified += _slack_tolerance(prm, kw, l, xp, xv, xa, pf, out, ea, tol, what)
                 else:
                     assert e <= tol, f"{what}: l_inf {e:.2e}"
                 okb = out["status"] & 1 == 1
                 l = np.where(okb[:, None], out["p"], l); xp = np.where(okb[:, None], out["p"][:, :3], xp)
                 xv = np.where(okb[:, None], out["v"][:, :3], xv); xa = np.where(okb[:, None], out["a"][:, :3], xa)
-    print(f"time-boxed campaign, seed {seed}: {scenes} scenes, {total} agent-steps compared, worst l_inf {worst:.2e}")
+    print(f"campaign slice, seed {seed}: {scenes} scenes, {total} agent-steps compared, worst l_inf {worst:.2e}, "
+          f"{certified} slack-variant agent(s) above 5e-8 at multipliers of 1e6, each a certified minimiser")
     assert total > 1000
+
+
+def test_campaign_cpp1_multiplier_1e6_regression():
+    """Scene 18 of campaign seed 2963 (C5 constants: term = -1e6, 86 agents), solveQP of the first C++ version (cpp1), MPC steps 2-6
+    teacher-forced on the GPU's own states.  At step 4 agent 27 ends 5.7e-8 off the oracle, above the 5e-8 the campaign asks of first-level
+    agents, with identical status and records.  Both answers are KKT points with multipliers of 1e6 (the slack penalty); the GPU's has
+    complementarity 6e-9 where the oracle's has 3e-5, so the deviation is the conditioning of the dense oracle there, inside DESIGN.md
+    section 2's stated 5e-7 at multipliers of 1e6.  This pins the scene: records identical, every other agent within 5e-8, the ones above
+    it within 5e-7 AND certified minimisers with multipliers of at least 1e6."""
+    import certificates as cert
+    cfg, N = wl.CONFIGS["C5"], 86
+    kw = wl.solver_kwargs(cfg, N)
+    po, pf = wl.make_scenes(dict(cfg), 1, N, 652817902)       # (the scene seed campaign seed 2963 draws for its scene 18)
+    po, pf = po[0], pf[0]
+    d, prm = mp.Dmpc("cpp1", **kw), orc.make_params("cpp1", **kw)
+    l = init_table(po, pf); xp, xv, xa = po.copy(), np.zeros_like(po), np.zeros_like(po)
+    above = []
+    for step in range(2, 7):
+        out = d.step_batch(l, xp, xv, xa, pf); ref = orc.step(prm, l, xp, xv, xa, pf, nthreads=8)
+        what = f"campaign seed 2963 scene 18 cpp1 step {step}"
+        assert np.array_equal(out["status"], ref["status"]), what
+        assert np.array_equal(out["info"][:, 0], ref["info"][:, 0]) and np.array_equal(out["info"][:, 1], ref["info"][:, 7]) \
+            and np.array_equal(out["info"][:, 2], ref["info"][:, 2]), what + ": branch record"
+        ok = (ref["status"] & 1) == 1
+        ea = np.zeros(N)
+        for key in ("p", "v", "a"):
+            ea = np.maximum(ea, np.abs(out[key] - ref[key]).max(axis=1) * ok)
+        assert (ea <= 5e-7).all(), f"{what}: l_inf {ea.max():.2e}"
+        loose = np.nonzero(ea > 5e-8)[0]
+        for n in loose:
+            qp = orc.assemble_one(prm, l, n, xp[n], xv[n], xa[n], pf[n], level=max(int(out["info"][n, 2]) - 1, 0))
+            assert cert.kkt_certificate(qp, out["a"][n])["lam_max"] >= 0.999e6, f"{what}: agent {n} above 5e-8 without multipliers of 1e6"
+        check_batch(prm, l, xp, xv, xa, pf, out["a"], out["status"], out["info"][:, 2], what, agents=loose)
+        above += [f"step {step} agent {n}: {ea[n]:.2e}" for n in loose]
+        okb = out["status"] & 1 == 1
+        l = np.where(okb[:, None], out["p"], l); xp = np.where(okb[:, None], out["p"][:, :3], xp)
+        xv = np.where(okb[:, None], out["v"][:, :3], xv); xa = np.where(okb[:, None], out["a"][:, :3], xa)
+    print("cpp1 agents above 5e-8 (certified minimisers, multipliers of 1e6):", ", ".join(above) or "none")

@@ -72,7 +72,7 @@ def test_two_real_gpus_in_one_process():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DMPC_BENCH_SHARE_GPU"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "9", "--warmup", "2", "--no-secondary", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "9", "--warmup", "2", "--full", "--no-secondary", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -260,14 +260,15 @@ def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` without torch.distributed.run: bench.py starts the two ranks itself.  On this one-GPU box they share the
     GPU and the exchange is staged through gloo (a functional check of the multi-rank path, flagged as such in the JSON line): the headline
     scene (here 2 000 agents of it) sharded over the two ranks in a device-resident closed loop; the sharded step must equal the unsharded
-    step of the same scene per agent, bit for bit, and every rank must hold the same gathered table (config.exchange_verified)."""
+    step of the same scene per agent, bit for bit, and every rank must hold the same gathered table (config.exchange_verified, a check
+    of `bench.py --full`)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DMPC_BENCH_SHARE_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--agents", "2000", "--no-secondary",
-                        "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--agents", "2000", "--full",
+                        "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["exchange_verified"] is True and line["scaling"] == "strong"

@@ -112,14 +112,19 @@ def test_wall_leaving_while_a_row_enters_regression():
         xp = np.where(ok[:, None], ref["p"][:, :3], xp); xv = np.where(ok[:, None], ref["v"][:, :3], xv); xa = np.where(ok[:, None], ref["a"][:, :3], xa)
 
 
+TIGHT_SEED, TIGHT_SCENES = 2963 + 17, 160
+
+
 def test_tight_workspace_campaign_time_boxed():
-    """a time-boxed slice (15 s) of tests/dev/gpu_campaign_walls.py: scenes at the headline's density squeezed into boxes of 0.5-0.8 of their size, the
+    """a fixed slice of tests/dev/gpu_campaign_walls.py: scenes at the headline's density squeezed into boxes of 0.5-0.8 of their size, the
     four variants of the reduced solver, 4-8 teacher-forced MPC steps: walls enter and leave the working set while collision rows do (the regime of
-    the gather defect of round 6).  Statuses, branch records, retry counts identical; 1e-8 on the first ladder level, 1e-7 above"""
-    import time
-    rng = np.random.default_rng(int(time.time() // (7 * 86400)) + 17)
-    t0, total, walls = time.time(), 0, 0
-    while time.time() - t0 < 15.0:
+    the gather defect of round 6).  Statuses, branch records, retry counts identical; 1e-8 on the first ladder level, 1e-7 above.  Seed and scene
+    count are fixed, so the slice is the same on every run and box (it used to take a seed from the calendar week and stop after 15 s; the
+    seed is the one that week drew when the slice was pinned, and 160 scenes are what 15 s covered: tests/dev/gpu_campaign_walls.py runs
+    about 11 scenes per second)."""
+    rng = np.random.default_rng(TIGHT_SEED)
+    total, walls = 0, 0
+    for _ in range(TIGHT_SCENES):
         N = int(rng.integers(30, 160))
         cfg = dict(wl.CONFIGS["C4"]); cfg["N"] = N
         kw = dict(wl.solver_kwargs(cfg, N))

@@ -1,6 +1,8 @@
 """CPU: the reference's result-file formats (dmpc_trajectories2file / dmpc_test2file, host code of libdmpc_hip.so).
 Known answers are the reference's own result files: the header + po + pf lines of
-`dmpc/cpp_results/trajectories (200-agents).txt` and the whole `cluster_test.txt` (tests/golden/)."""
+`dmpc/cpp_results/trajectories (200-agents).txt` and the whole `cluster_test.txt` (tests/golden/); the whole 200-agent file is stored
+xz-compressed as tests/golden/trajectories_200.txt.xz."""
+import lzma
 import os
 
 import numpy as np
@@ -9,7 +11,7 @@ import pytest
 from multiagent_planning_amd import resultio
 from helpers import GOLD
 
-REF_DUMP = "/root/reference/dmpc/cpp_results/trajectories (200-agents).txt"
+REF_DUMP_XZ = os.path.join(GOLD, "trajectories_200.txt.xz")   # the reference's `trajectories (200-agents).txt`, byte for byte
 
 
 def test_trajectories_head_bytes_match_reference_file(tmp_path):
@@ -55,10 +57,11 @@ def test_trajectories_roundtrip_random(tmp_path):
         resultio.write_trajectories(tmp_path / "no_such_dir" / "x.txt", po, pf, pos, vel, acc, 0.2, (0, 0, 0), (1, 1, 1))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_DUMP), reason="reference checkout not present (only in the build container)")
 def test_full_reference_dump_rewrites_byte_identically(tmp_path):
-    r = resultio.read_trajectories(REF_DUMP)
+    ref = tmp_path / "ref.txt"
+    ref.write_bytes(lzma.decompress(open(REF_DUMP_XZ, "rb").read()))
+    r = resultio.read_trajectories(ref)
     assert r["pk"].shape == (200, 83, 3)
     out = tmp_path / "full.txt"
     resultio.write_trajectories(out, r["po"], r["pf"], r["pk"], r["vk"], r["ak"], r["h_scaled"], r["pmin"], r["pmax"])
-    assert open(out, "rb").read() == open(REF_DUMP, "rb").read()
+    assert open(out, "rb").read() == ref.read_bytes()

@@ -18,7 +18,8 @@ from multiagent_planning_amd import workload as wl  # noqa: E402
 K = 15
 NRMAX = 256
 HERE = os.path.dirname(os.path.abspath(__file__))
-SO = "/tmp/librqp.so"
+SO = os.path.join(ROOT, "build", "proto", "librqp.so")   # (build/ is ignored; a fixed path outside the tree may belong to another user)
+os.makedirs(os.path.dirname(SO), exist_ok=True)
 subprocess.check_call(["gcc", "-O2", "-fPIC", "-shared", "-std=gnu11", "-o", SO, os.path.join(HERE, "rqp_proto.c"), "-lm"])
 lib = C.CDLL(SO)
 
