@@ -69,7 +69,10 @@ enum {
      * maxDeviation(p, prev_p) <= dmpc_params.tol (:17,69; maxDeviation.m:3 looks at the first length(p)/3 = 5 steps of the 3 x 15 matrix).
      * The whole loop of an agent runs inside ONE kernel launch.  info: VIOLK = smallest step of addConstr, NROWS = rows of the last pass,
      * TRIES = passes made, CASE = 0 / 2 of the last pass; an infeasible pass ends the loop with DMPC_ST_INFEAS (`success = 0`, :58-63).
-     * c and order are not used (sphere); no in-bounds test, no first-step collision test. */
+     * c and order are not used (sphere); no in-bounds test, no first-step collision test.
+     * Row capacity: N-1 rows per step added to addConstr, at most 4096 rows over all passes, counted after exact pruning.  An agent can
+     * overflow from N = 275 on (15 * 274 > 4096), and only when more than 4096 of its rows can become active; it then gets
+     * DMPC_ST_CAPACITY with zero outputs. */
     DMPC_VAR_SCP = 12
 };
 

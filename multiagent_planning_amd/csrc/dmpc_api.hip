@@ -870,6 +870,7 @@ static int launch_step(dmpc_ctx *ctx, int S, int G, int C, int g_local, int c_fi
         if (ctx->profile) HIPCHK(ctx, hipEventRecord(ev.t1, st));
         hipLaunchKernelGGL(dmpc_scp_kernel, grid, block, lds_scp, st, P);
         HIPCHK(ctx, hipGetLastError());
+        ctx->last_kernel = "dmpc_scp_kernel";
         if (ctx->profile) {
             HIPCHK(ctx, hipEventRecord(ev.t2, st));
             ctx->events.push_back(ev);

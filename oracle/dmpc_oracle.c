@@ -395,17 +395,18 @@ static hcase_t *ctx_case(ctx_t *c, double q, double s)
 /* a5/a6: scan + collision rows                                                               */
 /* ------------------------------------------------------------------------------------------ */
 
-/* ||E1 (p - pj)||_2 with E1 = diag(1,1,1/c)  (CheckCollSoftDMPC.m:10, order = 2) */
+/* ||E1 (p - pj)||_2 with E1 = diag(1,1,1/c)  (CheckCollSoftDMPC.m:10, order = 2).  E1 = E^-1 is applied as a product, as the reference
+ * does (E1*(p - pj)): dz * (1/c), not dz / c -- the two differ by an ulp for c = 1.5, which decides a neighbour on a threshold */
 static double edist(const double *p, const double *pj, double c)
 {
-    double dx = p[0] - pj[0], dy = p[1] - pj[1], dz = (p[2] - pj[2]) / c;
+    double dx = p[0] - pj[0], dy = p[1] - pj[1], dz = (p[2] - pj[2]) * (1.0 / c);
     return sqrt(dx * dx + dy * dy + dz * dz);
 }
 /* norm(E1*(p - pj), order) for the super-ellipsoid of order 4 (CheckCollEllipDMPC.m:7, test/comp_test_ellipconstr.m:158-163) */
 static double edist_o(const double *p, const double *pj, double c, int order)
 {
     if (order == 2) return edist(p, pj, c);
-    double dx = p[0] - pj[0], dy = p[1] - pj[1], dz = (p[2] - pj[2]) / c;
+    double dx = p[0] - pj[0], dy = p[1] - pj[1], dz = (p[2] - pj[2]) * (1.0 / c);
     return sqrt(sqrt(dx * dx * dx * dx + dy * dy * dy * dy + dz * dz * dz * dz));
 }
 /* order 4 exists for the variants whose scan is CheckCollEllipDMPC + rows for every neighbour (the one script of the reference that sets

@@ -1,0 +1,354 @@
+"""GPU: the solve path at its capacity limits and hand-over boundaries, on the synthetic crowds of tests/crowds.py (a probe agent with an
+exact number of collision rows), against the oracle, which has no caps.  Each limit is tested at the limit and one past it."""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+import multiagent_planning_amd as mp
+from multiagent_planning_amd import api
+from multiagent_planning_amd._lib import ST_CAPACITY, ST_SOLVED, DmpcError
+from oracle import oracle as orc
+from helpers import compare_to_oracle
+from test_gpu_reduced import _agree
+import crowds as cr
+
+pytestmark = pytest.mark.gpu
+
+NT = min(os.cpu_count() or 1, 16)
+KW = cr.solver_kw()
+RSOLVE = "dmpc_rsolve_persist_kernel"
+
+
+def _oracle(variant, sc, kw=KW, skip=()):
+    """orc.step, or -- with agents to skip (past the capacity: a dense solve of thousands of slack variables is not needed there) --
+    orc.solve_one of every other agent on NT host threads"""
+    prm = orc.make_params(variant, **kw)
+    if not len(skip):
+        return orc.step(prm, *sc, nthreads=NT)
+    l, xp, xv, xa, pf = sc
+    N = len(l)
+    ref = dict(status=np.zeros(N, np.int32), info=np.zeros((N, 8), np.int32), p=np.zeros((N, 45)), v=np.zeros((N, 45)), a=np.zeros((N, 45)))
+    todo = [n for n in range(N) if n not in set(skip)]
+    with ThreadPoolExecutor(NT) as ex:
+        for n, r in zip(todo, ex.map(lambda n: orc.solve_one(prm, l, n, xp[n], xv[n], xa[n], pf[n]), todo)):
+            ref["status"][n], ref["info"][n] = r["status"], r["info"]
+            for k in ("p", "v", "a"):
+                ref[k][n] = r[k] if r["status"] & 1 else 0.0
+    return ref
+
+
+def _sub(d, m):
+    return {k: v[m] for k, v in d.items()}
+
+
+def _agree_or_capacity(out, ref, reduced, skip=()):
+    """every agent the GPU flags with ST_CAPACITY -- past the row capacity, or with a working set that outgrows the solver's 64 slots
+    (full_qcap, dmpc_api.hip:626) -- has zero outputs and is not "solved"; every other agent agrees with the oracle (_agree of
+    test_gpu_reduced for the reduced solver's variants, helpers.compare_to_oracle otherwise).  Returns the flag mask."""
+    flag = (out["status"] & ST_CAPACITY) != 0
+    assert not (out["status"][flag] & ST_SOLVED).any()
+    for k in ("p", "v", "a"):
+        assert np.all(out[k][flag] == 0.0)
+    keep = ~flag & ~np.isin(np.arange(len(flag)), list(skip))
+    if reduced:
+        _agree(_sub(out, keep), _sub(ref, keep))
+    else:
+        compare_to_oracle(_sub(out, keep), _sub(ref, keep), 1e-9, "crowd")
+    return flag
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (a) the reduced solver's lane limit
+# ------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("rows", [63, 64, 65])
+@pytest.mark.parametrize("variant", ["bound", "bound2", "cpp", "cpp2"])
+def test_reduced_solver_lane_limit(variant, rows):
+    """dmpc_rsolve.hip:175 (`giveup = nr > 64`): one collision row per lane.  A probe with 63 / 64 rows is solved by the reduced solver
+    (its record is not the general solver's), one with 65 is handed to the general solver in the tier-2 launch -- bit-identical to a
+    context with reduced_solver = 0.  All three agree with the oracle."""
+    sc = cr.soft_crowd(variant, rows, kc=11 if variant in ("bound2", "cpp2") else 10)
+    ref = _oracle(variant, sc)
+    assert ref["info"][0, 7] == rows
+    red, gen = mp.Dmpc(variant, **KW), mp.Dmpc(variant, **KW)
+    gen.debug_option("reduced_solver", 0)
+    o_r, o_g = red.step_batch(*sc), gen.step_batch(*sc)
+    assert not _agree_or_capacity(o_r, ref, True)[0]
+    assert red.last_solve_kernel == RSOLVE
+    same = all(np.array_equal(o_r[k][0], o_g[k][0]) for k in ("p", "v", "a")) and np.array_equal(o_r["info"][0, :5], o_g["info"][0, :5])
+    if rows > 64:
+        assert same, "an agent past 64 rows must be the general solver's, bit for bit"
+    else:
+        assert not same, "an agent of at most 64 rows is the reduced solver's (its record differs from the general solver's)"
+
+
+@pytest.mark.parametrize("variant", ["bound", "bound2", "cpp", "cpp2"])
+def test_reduced_solver_64_rows_on_the_ladder(variant):
+    """dmpc_rsolve.hip RCERT_PLANES = 70 (64 rows + 6 box faces): a 64-row probe pinned between the violator and the lattice neighbour
+    opposite to it climbs the retry ladder (tries >= 3), so the ladder certificate runs with every plane in use"""
+    sc = cr.ladder_crowd(variant, 64)
+    ref = _oracle(variant, sc)
+    assert ref["info"][0, 7] == 64 and ref["info"][0, 2] >= 3
+    out = mp.Dmpc(variant, **KW).step_batch(*sc)
+    assert not _agree_or_capacity(out, ref, True)[0]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (b) walls of the reduced solver's small system
+# ------------------------------------------------------------------------------------------------------------------------------
+
+def _corner(vo):
+    """a probe 1 m from the corner (1, 1, 1) of a 3 m box, its goal 0.2 m beyond the corner, initial velocity vo toward it"""
+    kw = cr.solver_kw(pmin=(-2.0, -2.0, -2.0), pmax=(1.0, 1.0, 1.0))
+    xp = np.zeros((1, 3))
+    l = np.repeat(xp, 15, 0).reshape(1, 45)
+    return kw, (l, xp, np.full_like(xp, vo), np.zeros_like(xp), np.full_like(xp, 1.2))
+
+
+def _walls(ref, kw):
+    p = ref["p"][0].reshape(15, 3)
+    return int((np.abs(p - np.array(kw["pmax"])) < 1e-9).sum() + (np.abs(p - np.array(kw["pmin"])) < 1e-9).sum())
+
+
+@pytest.mark.parametrize("vo,walls", [(0.0, 3), (1.0, 6)])
+def test_reduced_solver_wall_limit(vo, walls):
+    """dmpc_rsolve.hip:37, 311 (R_NW = 3, `ent == RE_WALL && nw >= R_NW` gives up): a probe pressed into a corner of the workspace.  At rest
+    it ends on three walls (x, y, z at the last step) and the reduced solver's answer agrees with the oracle.  Arriving at 1 m/s it
+    ends on six (two steps on each axis: the oracle's minimiser and active-set count prove it); the reduced solver hands it to the
+    general solver, whose answer it returns bit for bit"""
+    kw, sc = _corner(vo)
+    ref = _oracle("bound", sc, kw)
+    assert _walls(ref, kw) == walls and ref["info"][0, orc.I_NACTIVE] == walls
+    red, gen = mp.Dmpc("bound", **kw), mp.Dmpc("bound", **kw)
+    gen.debug_option("reduced_solver", 0)
+    o_r, o_g = red.step_batch(*sc), gen.step_batch(*sc)
+    _agree(o_r, ref)
+    assert red.last_solve_kernel == RSOLVE
+    if walls > 3:
+        for k in ("p", "v", "a", "status"):
+            assert np.array_equal(o_r[k], o_g[k]), k
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (c) the scan's row capacity
+# ------------------------------------------------------------------------------------------------------------------------------
+
+def _capacity_case(variant, rows):
+    if variant == "hard":
+        return cr.hard_crowd(rows)
+    return cr.soft_crowd(variant, rows, kc=10)
+
+
+def _matlab_call(variant, sc, n):
+    l, xp, xv, xa, pf = sc
+    l3 = l.reshape(-1, 15, 3).transpose(2, 1, 0)
+    A, Av, A0, Dl = mp.model_matrices(KW["h"])
+    c = KW["c"]
+    E1, E2 = np.diag([1, 1, 1 / c]), np.diag([1, 1, 1 / c ** 2])
+    args = (xp[n], pf[n], xv[n], xa[n], n + 1, KW["h"], l3, 15, KW["rmin"], KW["pmin"], KW["pmax"], KW["alim"], A, A0, A, Av, Dl,
+            KW["Q1"], KW["S1"], E1, E2, 2)
+    if variant == "bound":
+        return api.solveSoftDMPCbound(*args, KW["term"])
+    if variant == "all3":
+        return api.solveSoftDMPCall(*args, KW["term"])
+    return api.solveHardDMPC(*args)
+
+
+@pytest.mark.parametrize("variant,cap", [("bound", 128), ("all3", 384), ("hard", 640)])
+@pytest.mark.parametrize("past", [False, True], ids=["at", "past"])
+def test_row_capacity(variant, cap, past):
+    """dmpc_api.hip:600-614 row_capacity (bound family 128, all3 384, hard 640) and dmpc_kernels.hip:817 (`nr > nrmax` ->
+    DMPC_ST_CAPACITY): a probe with exactly `cap` rows agrees with the oracle; with one row more (all3: one neighbour, three rows)
+    it carries ST_CAPACITY with zero outputs, the MATLAB-signature wrapper raises DmpcError for it, and every other agent of the
+    scene still agrees with the oracle.  The rows sit on late horizon steps, where none is pruned."""
+    rows = cap + ((3 if variant == "all3" else 1) if past else 0)
+    sc = _capacity_case(variant, rows)
+    N = len(sc[0])
+    assert cr.row_capacity(variant, N) == cap
+    ref = _oracle(variant, sc, skip=(0,) if past else ())
+    out = mp.Dmpc(variant, **KW).step_batch(*sc)
+    assert out["info"][0, 1] == rows
+    flag = _agree_or_capacity(out, ref, variant == "bound", skip=(0,) if past else ())
+    assert bool(flag[0]) == past
+    if past:
+        with pytest.raises(DmpcError):
+            _matlab_call(variant, sc, 0)
+    else:
+        assert ref["info"][0, 7] == rows
+
+
+@pytest.mark.parametrize("N", [4, 6, 10])
+def test_row_capacity_of_small_scenes(N):
+    """small scenes, where row_capacity's floor of 8 and rounding to an even number (dmpc_api.hip:612-613) set the buffer: N - 1 = 3, 5
+    (below 8) and 9 (odd, rounded to 10) neighbours, a probe with a row for each agrees with the oracle, without ST_CAPACITY (bound,
+    all3, hard).  The floor and the rounding are not observable from outputs: a probe has at most N - 1 rows (all3: 3 (N - 1), hard:
+    15 (N - 1)), never more than the unrounded capacity, so this test would pass without them; it guards the small buffers only"""
+    for variant in ("bound", "all3"):
+        per = 3 if variant == "all3" else 1
+        sc = cr.soft_crowd(variant, per * (N - 1), kc=10)
+        assert len(sc[0]) == N
+        ref = _oracle(variant, sc)
+        out = mp.Dmpc(variant, **KW).step_batch(*sc)
+        assert ref["info"][0, 7] == per * (N - 1) and not (out["status"] & ST_CAPACITY).any()
+        if variant == "bound":
+            _agree(out, ref)
+        else:
+            compare_to_oracle(out, ref)
+    sc = cr.hard_crowd(6 * (N - 1))
+    ref = _oracle("hard", sc)
+    out = mp.Dmpc("hard", **KW).step_batch(*sc)
+    assert not (out["status"] & ST_CAPACITY).any()
+    compare_to_oracle(out, ref)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (d) working-set tiers on the crowds
+# ------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("variant,rows", [("bound", 128), ("all3", 384)])
+def test_tier_forms_are_bit_identical_on_crowds(variant, rows):
+    """tier1_qcap / full_qcap (dmpc_api.hip:626-649, 718): the working-set capacity of the first solve launch (32, 48, 56, 64) only
+    decides which agents are re-solved from scratch in the second launch -- the crowd's outputs are the same bits in every form, and
+    (bound) agree with the oracle, agents flagged ST_CAPACITY (working set past 64 slots) with zero outputs.  Some agent's working set
+    outgrows 32 slots, so the 32-slot form does hand agents to the second launch.  Not covered: the 48/49/56/57 peaks one by one and
+    the 56-slot default of scenes of 1024 agents or more"""
+    sc = cr.soft_crowd(variant, rows, kc=10)
+    outs = []
+    for q in (32, 48, 56, 64):
+        d = mp.Dmpc(variant, **KW)
+        d.debug_option("reduced_solver", 0)
+        d.debug_option("tier1_qcap", q)
+        outs.append(d.step_batch(*sc))
+    for o in outs[1:]:
+        for k in ("status", "p", "v", "a"):
+            assert np.array_equal(o[k], outs[0][k]), k
+        assert np.array_equal(o["info"][:, :5], outs[0]["info"][:, :5])
+    peaks = outs[0]["info"][:, 7]
+    print(f"{variant}: peak working sets {np.unique(peaks)}, flagged {int(((outs[0]['status'] & ST_CAPACITY) != 0).sum())}")
+    assert peaks.max() > 32 and ((outs[0]["status"] & ST_CAPACITY) != 0).any()   # (bound: peaks up to 64, five agents past it)
+    if variant == "bound":
+        _agree_or_capacity(outs[0], _oracle(variant, sc), True)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (e) the hard-row scan's candidate buffer
+# ------------------------------------------------------------------------------------------------------------------------------
+
+def _mid_walk_flushes(l, n=0, cap=1024, ur=4):
+    """the flushes of the candidate buffer before the end of the walk (dmpc_kernels.hip:625, restated): the flat index
+    e = k * N + j in groups of 64 * ur pairs; before each group, a buffer holding more than cap - 64 ur candidates is flushed"""
+    N = len(l)
+    L = l.reshape(N, 15, 3)
+    d2 = ((L - L[n]) ** 2 * [1, 1, 1 / KW["c"] ** 2]).sum(2)
+    cand = (d2 < 1.0 + 4e-9).T.ravel().astype(int)      # (step-major)
+    cand[n::N] = 0
+    buf = fl = 0
+    for e0 in range(0, cand.size, 64 * ur):
+        if buf + 64 * ur > cap:
+            buf, fl = 0, fl + 1
+        buf += int(cand[e0:e0 + 64 * ur].sum())
+    return fl
+
+
+@pytest.mark.parametrize("pairs", [767, 768, 769, 1024, 1025, 2049])
+def test_hard_row_candidate_buffer(pairs):
+    """dmpc_kernels.hip:582-600, 625 (SCAN_CAND_CAP = 1024, flushed when ncand + 256 > 1024): a probe with `pairs` (step, neighbour)
+    candidates at d < 1.  Its rows from the GPU scan (api.collision_rows, the exact-size buffer of dmpc_rows_one) equal the oracle's in
+    the reference's order; the full step through step_batch (nrmax = 640) flags it ST_CAPACITY and agrees with the oracle elsewhere.
+    The candidates sit on the last six steps, so 767 / 768 / 769 do not meet the flush test with 768 candidates in the buffer: they
+    check the counts around the buffer's size, not the flush threshold.  From 1024 on at least one flush falls in the middle of the
+    walk (asserted above 1024 by a restatement of the rule); a flush that dropped or doubled a candidate fails there"""
+    sc = cr.hard_crowd(pairs)
+    l, xp, xv, xa, pf = sc
+    if pairs > 1024:
+        assert _mid_walk_flushes(l) >= 1
+    prm = orc.make_params("hard", **KW)
+    ref_rows = orc.rows_one(prm, l, 0, xp[0], xv[0])
+    assert ref_rows["nrows"] == pairs
+    l3 = l.reshape(-1, 15, 3).transpose(2, 1, 0)
+    E1 = np.diag([1, 1, 1 / KW["c"]])
+    Ain, bin_, dist, vk, coll = api.collision_rows("hard", xp[0], xv[0], 1, KW["h"], l3, 15, KW["rmin"], KW["pmin"], KW["pmax"],
+                                                  KW["alim"], KW["Q1"], KW["S1"], E1, 2, KW["term"])
+    assert Ain.shape[0] == pairs and vk == ref_rows["viol_k"] and coll == 0
+    assert np.abs(Ain - ref_rows["G"]).max() <= 1e-14 and np.abs(bin_ - ref_rows["b"]).max() <= 1e-13
+    assert np.abs(dist - ref_rows["dist"]).max() <= 1e-14
+    out = mp.Dmpc("hard", **KW).step_batch(*sc)
+    ref = _oracle("hard", sc, skip=(0,))
+    flag = _agree_or_capacity(out, ref, False, skip=(0,))
+    assert flag[0] and out["info"][0, 1] == pairs
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (f) threshold ties
+# ------------------------------------------------------------------------------------------------------------------------------
+
+TIE_VARIANT = dict(rmin="bound", hard1="hard", cut="bound", cpp="cpp", cppcut="cpp")
+TIE_VARIANT["3rmin"] = "bound"
+
+
+@pytest.mark.parametrize("c", [2.0, 1.5])
+@pytest.mark.parametrize("axis", ["x", "z"])
+@pytest.mark.parametrize("kind", cr.TIE_KINDS)
+def test_threshold_ties(kind, axis, c):
+    """the scan's distance tests (dmpc_kernels.hip:566-600, 790-812: d < rmin, d < 3 rmin, d < 1, rmin - 0.05 at step 1, the cpp
+    radius float(rmin)(1 + k/K) and float cut): a neighbour exactly on the threshold and one ulp either side, along x and z, at
+    c = 2 and 1.5.  First violating step, row count, status and rows equal the oracle's, through the table scan and through the
+    cell-grid lists (forced by cull_min / grid_min)"""
+    kw = cr.solver_kw(c=c)
+    variant = TIE_VARIANT[kind]
+    t = cr.threshold(kind, kw["rmin"])
+    prm = orc.make_params(variant, **kw)
+    plain = mp.Dmpc(variant, **kw)
+    grid = mp.Dmpc(variant, **kw)
+    grid.debug_option("cull_min", 2)
+    grid.debug_option("grid_min", 2)
+    E1 = np.diag([1, 1, 1 / c])
+    for d in (np.nextafter(t, 0.0), t, np.nextafter(t, 9.0)):
+        sc = cr.tie_scene(kind, d, axis, c=c)
+        l, xp, xv, xa, pf = sc
+        ref = orc.step(prm, *sc, nthreads=2)
+        o_p, o_g = plain.step_batch(*sc), grid.step_batch(*sc)
+        what = f"{kind} {axis} c={c} d={d!r}"
+        for o in (o_p, o_g):
+            assert np.array_equal(o["status"], ref["status"]), what
+            assert np.array_equal(o["info"][:, 0], ref["info"][:, 0]) and np.array_equal(o["info"][:, 1], ref["info"][:, 7]), what
+        for k in ("status", "info", "p", "v", "a"):
+            assert np.array_equal(o_p[k], o_g[k]), (what, k)
+        if variant == "hard" or not (ref["status"] & 1).any():
+            compare_to_oracle(o_p, ref, 1e-9, what)
+        else:
+            _agree(o_p, ref)
+        r = orc.rows_one(prm, l, 0, xp[0], xv[0])
+        Ain, bin_, dist, vk, coll = api.collision_rows(variant, xp[0], xv[0], 1, kw["h"], l.reshape(-1, 15, 3).transpose(2, 1, 0), 15,
+                                                      kw["rmin"], kw["pmin"], kw["pmax"], kw["alim"], kw["Q1"], kw["S1"], E1, 2, kw["term"])
+        assert vk == r["viol_k"] and coll == int(bool(r["status"] & 4)) and Ain.shape[0] == r["nrows"], what
+        if r["nrows"]:
+            assert np.abs(Ain - r["G"]).max() <= 1e-14 and np.abs(bin_ - r["b"]).max() <= 1e-13, what
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# (g) SCP row capacity
+# ------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("N", [274, 275])
+def test_scp_crossing_crowd_around_the_row_cap_size(N):
+    """DMPC_VAR_SCP (dmpc_scp_kernel) at the scene sizes where 15 (N - 1) crosses its row cap of 4096 (row_capacity, dmpc_api.hip:606):
+    a crossing crowd (every agent heads for the mirror of its start).  Every agent either matches the oracle or carries ST_CAPACITY
+    with zero outputs, and dmpc_last_solve_kernel names the SCP kernel.  The cap itself is NOT reached here: these agents add at most
+    four steps (about 1100 rows); an agent needs all 15 steps, with more than 4096 rows that can become active, to overflow"""
+    side = int(np.ceil(np.sqrt(N)))
+    i = np.arange(N)
+    po = np.stack([0.4 * (i % side - (side - 1) / 2), 0.4 * (i // side - (side - 1) / 2), 1.2 + 0.05 * (i % 3)], 1)
+    pf = po * [-1, -1, 1]
+    from helpers import init_table
+    l = init_table(po, pf)
+    z = np.zeros_like(po)
+    sc = (l, po, z, z.copy(), pf)
+    kw = cr.solver_kw(tol=0.05)
+    d = mp.Dmpc("scp", **kw)
+    out = d.step_batch(*sc)
+    assert d.last_solve_kernel == "dmpc_scp_kernel"
+    ref = orc.step(orc.make_params("scp", **kw), *sc, nthreads=NT)
+    _agree_or_capacity(out, ref, False)
