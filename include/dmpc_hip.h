@@ -165,7 +165,7 @@ enum {
 /* ABI revision of this header.  The special device values changed once (the round-3 header had DMPC_DEVICE_ALL = -1, DMPC_DEVICE_CURRENT = -2;
  * since revision 4 they are the two values above and any other negative device is refused), so a binding compiled against another header
  * should compare dmpc_abi_version() with the DMPC_ABI_VERSION it was built with before its first dmpc_create. */
-#define DMPC_ABI_VERSION 7
+#define DMPC_ABI_VERSION 8
 DMPC_API int dmpc_abi_version(void);
 DMPC_API dmpc_ctx *dmpc_create(const dmpc_params *prm, int device, int precision);
 /* number of GPUs the context drives (1 unless created with DMPC_DEVICE_ALL on a multi-GPU node) */
@@ -199,6 +199,25 @@ DMPC_API int dmpc_step_batch(dmpc_ctx *ctx, int S, int N, const double *l, const
                     const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out,
                     int32_t *status, int32_t *info);
 
+/* Uncommanded vehicles (ABI revision 8).  The C++ class plans for N vehicles of which only N_cmd are commanded: N = _po.cols(),
+ * N_cmd = _pf.cols() (DMPC::solveParallelDMPCv2 dmpc/cpp/dmpc.cpp:1572-1573, solveDMPC :1295-1430, solveParallelDMPC :1435-1565).
+ * Agents 0 .. N_cmd-1 are commanded; agents N_cmd .. N-1 stay where they are, and their "prediction" is their start position
+ * replicated over the horizon at every MPC step (:1633-1649, :1320-1330).  A commanded agent treats such a column like any
+ * neighbour -- same ellipsoid, same thresholds, same row order by neighbour index (check_collisionsv2 loops over all N, :395-448);
+ * static agents are never solved, never advanced, have no status and do not enter ReachedGoal or the scene verdict
+ * (reached_goalv2 and the recorded solution cover the N_cmd commanded ones, :1600, :1684, :1691).
+ * The *_cmd entries below take 1 <= N_cmd <= N (anything else: -1 and a message, nothing launched); with N_cmd == N each returns
+ * bit for bit what the entry without the suffix returns.  On a DMPC_DEVICE_ALL context a call with N_cmd < N runs on the first GPU
+ * (the rule for N < 2 G).  The RCCL entries (dmpc_step_sharded_device, dmpc_transition_sharded*) have NO *_cmd form: a fleet with
+ * uncommanded vehicles is planned by one process.
+ *
+ * dmpc_step_batch_cmd: dmpc_step_batch for the commanded agents against the caller's table of all N vehicles (the caller keeps
+ * the static rows constant).  l: [S][N][3K]; x_p, x_v, x_a, pf: [S][N_cmd][3]; p_out, v_out, a_out: [S][N_cmd][3K];
+ * status: [S][N_cmd]; info: [S][N_cmd][8] or NULL. */
+DMPC_API int dmpc_step_batch_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *l, const double *x_p, const double *x_v,
+                        const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out,
+                        int32_t *status, int32_t *info);
+
 /* a7/a8: one agent (0-based n) of one scene: the per-call entry the signature-preserving MATLAB
  * wrappers use ([p,v,a,feasible,outbound,coll] = solveSoftDMPCbound(...), solveSoftDMPCbound.m:1).
  * Host pointers.  l: [N][3K]; po,vo,ao,pf: [3]; p,v,a: [3K]; info: [8] or NULL. */
@@ -231,6 +250,14 @@ DMPC_API int dmpc_step_device(dmpc_ctx *ctx, int S, int G, int C, int g_local, c
                      const double *x_v, const double *x_a, const double *pf, double *p_out, double *v_out,
                      double *a_out, double *lT_next, int32_t *status, int32_t *info, void *stream);
 
+/* dmpc_step_device for N_cmd commanded agents of a table of N vehicles, one chunk (G = 1): lT, lT_next: [S][3K][N];
+ * x_p, x_v, x_a, pf: [S][N_cmd][3]; p_out, v_out, a_out: [S][N_cmd][3K]; status [S][N_cmd], info [S][N_cmd][8] or NULL.
+ * Only columns < N_cmd of lT_next are written: its static columns (N_cmd .. N-1) are the CALLER'S -- fill them once, in both
+ * tables of a ping-pong pair (dmpc_table_from_rows_device builds either table from rows [S][N][3K]). */
+DMPC_API int dmpc_step_device_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *lT, const double *x_p, const double *x_v,
+                         const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out, double *lT_next,
+                         int32_t *status, int32_t *info, void *stream);
+
 /* layout helpers (device pointers, asynchronous on `stream`):
  * rows [S][N][3K] -> lT [G][S][3K][C] with N = G*C, and first columns x_next = out(:,1). */
 DMPC_API int dmpc_table_from_rows_device(dmpc_ctx *ctx, int S, int G, int C, const double *rows, double *lT, void *stream);
@@ -241,7 +268,8 @@ DMPC_API int dmpc_advance_device(dmpc_ctx *ctx, int count, const double *p_out, 
                         const int32_t *status, double *x_p, double *x_v, double *x_a, void *stream);
 
 /* Whole transition on one device: the `for k = 1:K_T` loop of dmpc_soft_bound.m:115-148 /
- * DMPC::solveParallelDMPCv2 (dmpc/cpp/dmpc.cpp:1656-1686) incl. initDMPC at k = 1, the table
+ * DMPC::solveParallelDMPCv2 (dmpc/cpp/dmpc.cpp:1656-1686) with every vehicle commanded (N_cmd == N; dmpc_transition_cmd below
+ * covers N_cmd < N) incl. initDMPC at k = 1, the table
  * swap l = new_l and the ReachedGoal.m test.  Host pointers.
  * K_T_max = number of history COLUMNS, the initial state (k = 1, initDMPC) included: at most K_T_max - 1 solves per agent.
  * `for k = 1:K_T` of dmpc_soft_bound.m:115 is K_T_max = K_T; `while ~reached_goal && k < max_K` of test/failure_rate.m:99
@@ -264,6 +292,15 @@ DMPC_API int dmpc_advance_device(dmpc_ctx *ctx, int count, const double *p_out, 
 DMPC_API int dmpc_transition(dmpc_ctx *ctx, int S, int N, const double *po, const double *pf, int K_T_max,
                     double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
                     int32_t *scene_status);
+
+/* dmpc_transition with uncommanded vehicles: DMPC::solveParallelDMPCv2 (dmpc/cpp/dmpc.cpp:1570-1730; solveDMPC :1295-1430 and
+ * solveParallelDMPC :1435-1565 plan the same problem) for N = _po.cols() vehicles of which N_cmd = _pf.cols() are commanded.
+ * po: [S][N][3], pf: [S][N_cmd][3]; pk, vk, ak: [S][N_cmd][K_T_max][3] or all NULL; the columns N_cmd .. N-1 of the table hold
+ * po replicated K times at every MPC step, the first included.  Stopping rule, verdict read-back, batch split, K_T_used and
+ * scene_status as for dmpc_transition, over the commanded agents only; the histories of the commanded agents stay resident for
+ * dmpc_postcheck_cmd (or dmpc_postcheck with N = N_cmd). */
+DMPC_API int dmpc_transition_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
+                        double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used, int32_t *scene_status);
 
 /* Multi-GPU: the agents of every scene sharded over the GPUs of one node, ONE PROCESS (rank) PER GPU, each with its own
  * context.  Replaces the thread clusters of DMPC::solveParallelDMPCv2 (dmpc/cpp/dmpc.cpp:1570-1686): contiguous agent ranges,
@@ -329,6 +366,21 @@ DMPC_API int dmpc_postcheck(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int
                    const double *pk, const double *vk, const double *ak, const double *pf, double vmax, double amax, double Ts,
                    double *r_factor, double *h_scaled, int32_t *n_samples, double *min_dist, int32_t *violation,
                    double *totdist, double *traj_time, double *p_interp, int ns_alloc);
+
+/* dmpc_postcheck after a transition with uncommanded vehicles.  r_factor, h_scaled, the spline, totdist, traj_time and
+ * min_dist / violation are computed over the N_cmd commanded agents exactly as dmpc_postcheck does for N = N_cmd -- what the
+ * reference checks: collision_violation(solution) sees the N_cmd trajectories only (dmpc/cpp/dmpc.cpp:2052-2086).  Two more
+ * outputs cover what it leaves out: min_dist_static[S] = the smallest |E1 (p_i(t) - po_j)| over every 100 Hz sample of every
+ * commanded agent i and every static vehicle j (the same fp64 expression; a static vehicle has no spline, its position is po_j),
+ * violation_static[S] = min_dist_static < rmin - 0.05.  Static-static pairs are not examined.
+ * pk, vk, ak, pf: [S][N_cmd][..] as for dmpc_postcheck (NULL histories: the resident ones of dmpc_transition_cmd);
+ * po_static: [S][N - N_cmd][3], required when N_cmd < N; with N_cmd == N the two outputs are +inf / 0 and everything else is
+ * dmpc_postcheck bit for bit.  Either new output may be NULL; masked scenes report NaN / 0. */
+DMPC_API int dmpc_postcheck_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                       const double *pk, const double *vk, const double *ak, const double *pf, const double *po_static,
+                       double vmax, double amax, double Ts, double *r_factor, double *h_scaled, int32_t *n_samples,
+                       double *min_dist, int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
+                       double *min_dist_static, int32_t *violation_static);
 
 /* f-3: dense collision rows behind the CollConstr / AddCollConstr helpers named in the north star.  All of them
  * compute, per neighbour j (E1 = diag(1,1,1/c), E2 = E1^order; the ORDER is the context's, dmpc_params.order: 2, or 4 on a context of an

@@ -19,7 +19,7 @@ ST_REACHED = 256   # scene_status of transition(): every agent reached its goal
 INFO_LEN = 8
 I_VIOLK, I_NROWS, I_TRIES, I_CASE, I_ITERS, I_NSLACK, I_NACTIVE, I_MAXQ = range(8)
 K_HOR = 15
-ABI_VERSION = 7    # DMPC_ABI_VERSION of include/dmpc_hip.h
+ABI_VERSION = 8    # DMPC_ABI_VERSION of include/dmpc_hip.h
 
 # every symbol include/dmpc_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "dmpc_partition", "dmpc_comm_unique_id", "dmpc_comm_init", "dmpc_comm_destroy", "dmpc_step_sharded_device",
     "dmpc_transition_sharded", "dmpc_transition_sharded_gather", "dmpc_group_size", "dmpc_comm_size", "dmpc_abi_version", "dmpc_last_solve_kernel",
     "dmpc_max_deviation",
+    "dmpc_step_batch_cmd", "dmpc_step_device_cmd", "dmpc_transition_cmd", "dmpc_postcheck_cmd",
 ]
 
 
@@ -115,6 +116,12 @@ def load():
     L.dmpc_max_deviation.argtypes = [vp, C.c_int, dp, dp, dp]
     L.dmpc_postcheck.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, dp, C.c_double, C.c_double, C.c_double,
                                  dp, dp, ip, dp, ip, dp, dp, dp, C.c_int]
+    # uncommanded vehicles (ABI revision 8)
+    L.dmpc_step_batch_cmd.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, ip, ip]
+    L.dmpc_step_device_cmd.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 12
+    L.dmpc_transition_cmd.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, C.c_double, dp, dp, dp, ip, ip]
+    L.dmpc_postcheck_cmd.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_double,
+                                     dp, dp, ip, dp, ip, dp, dp, dp, C.c_int, dp, ip]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -167,6 +174,23 @@ def _strided_base(A):
 
 def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _n_cmd(lead_table, cmd, what):
+    """The reference's rule (DMPC::solveParallelDMPCv2, dmpc/cpp/dmpc.cpp:1572-1573): N = _po.cols(), N_cmd = _pf.cols().
+    lead_table: leading shape ([N] or [S,N]) of the table-sized array (l, po); cmd: a commanded-sized array (pf [..,3]).
+    Returns (S, N, N_cmd, leading shape of the commanded-sized outputs).  As many goals as vehicles: every vehicle is commanded, whatever
+    the goals' shape.  More commanded agents than vehicles, or another batch shape, is refused."""
+    S, N = (1, lead_table[0]) if len(lead_table) == 1 else lead_table
+    if cmd.size == S * N * 3:
+        return int(S), int(N), int(N), tuple(lead_table)
+    lead_cmd = cmd.shape[:-1]
+    if len(lead_table) != len(lead_cmd) or tuple(lead_table[:-1]) != tuple(lead_cmd[:-1]) or cmd.shape[-1] != 3:
+        raise DmpcError(f"{what}: pf {tuple(cmd.shape)} does not batch like the table {tuple(lead_table)}")
+    n_cmd = lead_cmd[-1]
+    if n_cmd < 1 or n_cmd > N:
+        raise DmpcError(f"{what}: pf has {n_cmd} agents, the table {N}: the commanded agents are the FIRST N_cmd <= N vehicles")
+    return int(S), int(N), int(n_cmd), tuple(lead_cmd)
 
 
 def model_matrices(h, K=K_HOR):
@@ -261,15 +285,23 @@ class Dmpc:
         return l, v, a
 
     def step_batch(self, l, x_p, x_v, x_a, pf):
-        """l: [N,45] or [S,N,45]; states/goals [..,3]. Returns dict(p,v,a,status,info)."""
+        """l: [N,45] or [S,N,45]; states/goals [..,3]. Returns dict(p,v,a,status,info).
+        States and goals with FEWER agents than the table (N_cmd < N, dmpc_step_batch_cmd): the first N_cmd vehicles are commanded, the
+        rows behind them are uncommanded vehicles the caller keeps constant; the outputs cover the commanded agents."""
         l, x_p, x_v, x_a, pf = _f(l), _f(x_p), _f(x_v), _f(x_a), _f(pf)
         lead = l.shape[:-1]
-        S, N = (1, lead[0]) if len(lead) == 1 else lead
-        p, v, a = np.zeros(lead + (45,)), np.zeros(lead + (45,)), np.zeros(lead + (45,))
-        status = np.zeros(lead, dtype=np.int32)
-        info = np.zeros(lead + (INFO_LEN,), dtype=np.int32)
-        self._chk(self._L.dmpc_step_batch(self._ctx, S, N, _dp(l), _dp(x_p), _dp(x_v), _dp(x_a), _dp(pf), _dp(p), _dp(v),
-                                          _dp(a), _ip(status), _ip(info)))
+        S, N, n_cmd, lead_c = _n_cmd(lead, pf, "step_batch")
+        if n_cmd < N and not (x_p.shape == x_v.shape == x_a.shape == pf.shape):
+            raise DmpcError("step_batch: x_p, x_v, x_a and pf must cover the same commanded agents")
+        p, v, a = np.zeros(lead_c + (45,)), np.zeros(lead_c + (45,)), np.zeros(lead_c + (45,))
+        status = np.zeros(lead_c, dtype=np.int32)
+        info = np.zeros(lead_c + (INFO_LEN,), dtype=np.int32)
+        if n_cmd == N:
+            self._chk(self._L.dmpc_step_batch(self._ctx, S, N, _dp(l), _dp(x_p), _dp(x_v), _dp(x_a), _dp(pf), _dp(p), _dp(v),
+                                              _dp(a), _ip(status), _ip(info)))
+        else:
+            self._chk(self._L.dmpc_step_batch_cmd(self._ctx, S, N, n_cmd, _dp(l), _dp(x_p), _dp(x_v), _dp(x_a), _dp(pf), _dp(p), _dp(v),
+                                                  _dp(a), _ip(status), _ip(info)))
         return dict(p=p, v=v, a=a, status=status, info=info)
 
     def solve_one(self, l, n, po, vo, ao, pf):
@@ -293,10 +325,11 @@ class Dmpc:
         return dict(xi=xi[:k], rhs=rhs[:k], slack_coef=sc[:k], kc=kc[:k], nrows=int(nr[0]), viol_k=int(vk[0]), status=int(st[0]))
 
     def transition(self, po, pf, K_T_max, error_tol=0.01, histories=True):
-        """histories=False: pk/vk/ak are not downloaded (they stay on the device for postcheck())."""
+        """histories=False: pk/vk/ak are not downloaded (they stay on the device for postcheck()).
+        pf with FEWER agents than po (N_cmd = pf's agents < N = po's, the reference's _pf.cols() / _po.cols(); dmpc_transition_cmd): the vehicles
+        behind the first N_cmd are not commanded and stay at po as static obstacles; histories, K_T_used and scene_status cover the commanded ones."""
         po, pf = _f(po), _f(pf)
-        shp = po.shape[:-1]
-        S, N = (1, shp[0]) if len(shp) == 1 else shp
+        S, N, n_cmd, shp = _n_cmd(po.shape[:-1], pf, "transition")
         used = np.zeros(S, dtype=np.int32)
         sst = np.zeros(S, dtype=np.int32)
         if histories:
@@ -306,8 +339,12 @@ class Dmpc:
         else:
             pk = vk = ak = None
             hp = (C.POINTER(C.c_double)(),) * 3
-        self._chk(self._L.dmpc_transition(self._ctx, S, N, _dp(po), _dp(pf), int(K_T_max), float(error_tol), hp[0], hp[1], hp[2],
-                                          _ip(used), _ip(sst)))
+        if n_cmd == N:
+            self._chk(self._L.dmpc_transition(self._ctx, S, N, _dp(po), _dp(pf), int(K_T_max), float(error_tol), hp[0], hp[1], hp[2],
+                                              _ip(used), _ip(sst)))
+        else:
+            self._chk(self._L.dmpc_transition_cmd(self._ctx, S, N, n_cmd, _dp(po), _dp(pf), int(K_T_max), float(error_tol), hp[0], hp[1], hp[2],
+                                                  _ip(used), _ip(sst)))
         return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst)
 
     # ---- multi-GPU (one process per GPU): dmpc_multigpu.hip ----
@@ -353,9 +390,11 @@ class Dmpc:
         return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, lo=lo, count=cnt)
 
     def postcheck(self, K_T_used, pf, pk=None, vk=None, ak=None, KT_alloc=None, vmax=2.0, amax=1.0, Ts=0.01, interp=False,
-                  mask=None):
+                  mask=None, po_static=None):
         """failure_rate.m:136-195 for S scenes.  pk/vk/ak [S,N,KT_alloc,3] (or [N,KT,3]); None: use the histories the
-        last transition() left on the device (then KT_alloc = its K_T_max)."""
+        last transition() left on the device (then KT_alloc = its K_T_max).
+        po_static [S,M,3] (or [M,3]): positions of M uncommanded vehicles (dmpc_postcheck_cmd; pf and the histories are the commanded
+        agents'): the result gains min_dist_static / violation_static, the commanded-against-static check; everything else is unchanged."""
         pf = _f(pf)
         shp = pf.shape[:-1]
         S, N = (1, shp[0]) if len(shp) == 1 else shp
@@ -368,11 +407,27 @@ class Dmpc:
                    violation=np.zeros(S, dtype=np.int32), totdist=np.zeros(S), traj_time=np.zeros(S))
         ns_alloc, p_i = 0, None
         if interp:   # upper bound of the sample count: r_factor is not known yet, so run once without and size from it
-            pre = self.postcheck(K_T_used, pf, pk, vk, ak, KT_alloc, vmax, amax, Ts, False, mask)
+            pre = self.postcheck(K_T_used, pf, pk, vk, ak, KT_alloc, vmax, amax, Ts, False, mask)   # (sizes only: no static pass)
             ns_alloc = max(int(pre["n_samples"].max()), 1)
             p_i = np.zeros((S, N, ns_alloc, 3))
         nul = C.POINTER(C.c_double)()
         msk = None if mask is None else np.ascontiguousarray(np.atleast_1d(mask), dtype=np.int32)
+        if po_static is not None:
+            pos = _f(po_static)
+            if pos.shape[:-2] != shp[:-1] or pos.shape[-1] != 3:
+                raise DmpcError(f"postcheck: po_static {pos.shape} does not batch like pf {pf.shape}")
+            M = pos.shape[-2]
+            out["min_dist_static"], out["violation_static"] = np.zeros(S), np.zeros(S, dtype=np.int32)
+            self._chk(self._L.dmpc_postcheck_cmd(self._ctx, S, N + M, N, int(KT_alloc), _ip(used),
+                                                 _ip(msk) if msk is not None else C.POINTER(C.c_int32)(), _dp(pk) if pk is not None else nul,
+                                                 _dp(vk) if pk is not None else nul, _dp(ak) if pk is not None else nul, _dp(pf),
+                                                 _dp(pos) if M else nul, float(vmax), float(amax), float(Ts), _dp(out["r_factor"]), _dp(out["h_scaled"]),
+                                                 _ip(out["n_samples"]), _dp(out["min_dist"]), _ip(out["violation"]), _dp(out["totdist"]),
+                                                 _dp(out["traj_time"]), _dp(p_i) if p_i is not None else nul, ns_alloc,
+                                                 _dp(out["min_dist_static"]), _ip(out["violation_static"])))
+            if p_i is not None:
+                out["p"] = p_i
+            return out
         self._chk(self._L.dmpc_postcheck(self._ctx, S, N, int(KT_alloc), _ip(used),
                                          _ip(msk) if msk is not None else C.POINTER(C.c_int32)(), _dp(pk) if pk is not None else nul,
                                          _dp(vk) if pk is not None else nul, _dp(ak) if pk is not None else nul, _dp(pf),
@@ -473,6 +528,11 @@ class Dmpc:
         return Ain, b
 
     # ---- device-pointer entry points (torch tensors: pass t.data_ptr()) ------------------------
+    def step_device_cmd(self, S, N, n_cmd, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out, lT_next, status, info, stream=0):
+        """dmpc_step_device_cmd: the first n_cmd agents of a one-chunk table lT [S,45,N]; only columns < n_cmd of lT_next are written"""
+        self._chk(self._L.dmpc_step_device_cmd(self._ctx, S, N, n_cmd, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out,
+                                               lT_next or None, status, info or None, stream or None))
+
     def step_device(self, S, G, Cn, g_local, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out, lT_next, status, info, stream=0):
         self._chk(self._L.dmpc_step_device(self._ctx, S, G, Cn, g_local, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out,
                                            lT_next or None, status, info or None, stream or None))

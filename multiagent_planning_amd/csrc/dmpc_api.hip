@@ -142,6 +142,7 @@ struct dmpc_ctx {
     int queue_chunk = 0;     // development option queue_chunk: positions per ticket of the persistent queue's light bulk (0: chosen per launch)
     int static_queue = 0;    // development option static_queue: persistent waves take queue positions round-robin instead of by ticket
     DevBuf pc_p, pc_v, pc_a, pc_M, pc_w, pc_scene, pc_agent, pc_interp;   // post-check work buffers
+    DevBuf pc_static;                                                      // post-check: positions of the uncommanded vehicles + their per-scene minimum
     DevBuf pc_pts, pc_cell, pc_fill, pc_start, pc_sorted, pc_on;           // post-check, large scenes: cell grid of a batch of samples
     // multi-GPU (dmpc_multigpu.hip): RCCL communicator of this rank, exchange buffers
     void *comm = nullptr;
@@ -785,7 +786,9 @@ static int launch_step(dmpc_ctx *ctx, int S, int G, int C, int g_local, int c_fi
         // side all-pairs / grid: hard rows 400 agents per scene 0.81 / 0.81 ms, 800: 1.07 / 0.91, 1 600: 1.42 / 1.06, 3 200: 1.92 / 1.24;
         // solveSoftDMPCbound 400: 0.62 / 0.66, 800: 0.71 / 0.69, 1 600: 0.84 / 0.73, 3 200: 1.04 / 0.81.  A rank that queries ONE chunk of
         // 8 x 100 agents per scene still bins all 800: 0.87 against 0.64 ms, `bench.py --emulate-gpus 8 --debug-option grid_min=512`)
-        const int grid_from = (c_count == G * C) ? ctx->grid_min : ctx->grid_min_part;
+        // (one chunk of which at least half is queried -- the commanded agents of a scene with uncommanded vehicles -- counts as the whole scene: binning
+        // all C columns is then at most twice the query's own share; grid_min_part was fitted on a rank's chunk, an eighth of the scene.  Not measured.)
+        const int grid_from = (c_count == G * C || (G == 1 && 2L * c_count >= (long)C)) ? ctx->grid_min : ctx->grid_min_part;
         const bool use_grid = ctx->nbr_grid && G * C >= grid_from && gq_lds <= 64 * 1024;
         // (grid geometry and buffer first: the counters are zeroed by the neighbour-major copy kernel, which runs anyway -- a memset of an odd
         // size is two fill launches, 9 us)
@@ -916,7 +919,8 @@ static int launch_step(dmpc_ctx *ctx, int S, int G, int C, int g_local, int c_fi
         int *hint = nullptr;
         if (ctx->order_hint) {   // the previous step's work estimates: valid while the batch keeps its shape
             if (ctx->prev_cost.ensure((size_t)total * 4)) FAIL(ctx, "device allocation failed (order hint)");
-            const long shape = ((long)S << 32) ^ ((long)c_count << 8) ^ (long)p.variant;
+            // (the agents of the launch: which columns of how large a table -- a sub-range of another start or of another table is another set of agents)
+            const long shape = ((((long)S * 1000003L + (long)G * C) * 1000003L + c_first) * 1000003L + c_count) * 16L + (long)p.variant;
             if (shape != ctx->prev_cost_shape) { HIPCHK(ctx, hipMemsetAsync(ctx->prev_cost.p, 0, (size_t)total * 4, st)); ctx->prev_cost_shape = shape; }
             hint = ctx->prev_cost.as<int>();
             P.cost_out = hint;
@@ -1191,6 +1195,29 @@ extern "C" int dmpc_step_device(dmpc_ctx *ctx, int S, int G, int C, int g_local,
                        (hipStream_t)stream, nullptr, 0, mixed ? ctx->lTf.as<float>() : nullptr);
 }
 
+// uncommanded vehicles: 1 <= N_cmd <= N (the shared argument check of the *_cmd entries)
+static int check_cmd(dmpc_ctx *ctx, const char *entry, int S, int N, int N_cmd)
+{
+    if (S < 1 || N < 1) FAIL(ctx, std::string(entry) + ": S and N must be >= 1");
+    if (N_cmd < 1 || N_cmd > N) FAIL(ctx, std::string(entry) + ": N_cmd must be in 1 .. N (commanded agents first, uncommanded vehicles behind them)");
+    return 0;
+}
+
+extern "C" int dmpc_step_device_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *lT, const double *x_p, const double *x_v,
+                                    const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out, double *lT_next,
+                                    int32_t *status, int32_t *info, void *stream)
+{
+    if (!ctx) { g_err = "dmpc_step_device_cmd: ctx is NULL"; return -1; }
+    if (check_cmd(ctx, "dmpc_step_device_cmd", S, N, N_cmd)) return -1;
+    if (!lT || !x_p || !x_v || !x_a || !pf || !p_out || !v_out || !a_out || !status) FAIL(ctx, "dmpc_step_device_cmd: NULL pointer");
+    if (ctx->grp) FAIL(ctx, "dmpc_step_device_cmd: device pointers belong to ONE GPU; a DMPC_DEVICE_ALL context drives several (use the host-pointer entry points)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;   // (the fp32 copy covers all N columns, the static ones included)
+    if (mixed && table_f32(ctx, lT, ctx->lTf, (size_t)S * N3 * N, (hipStream_t)stream)) return -1;
+    return launch_step(ctx, S, 1, N, 0, 0, N_cmd, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out, lT_next, status, info,
+                       (hipStream_t)stream, nullptr, 0, mixed ? ctx->lTf.as<float>() : nullptr);
+}
+
 extern "C" int dmpc_table_from_rows_device(dmpc_ctx *ctx, int S, int G, int C, const double *rows, double *lT, void *stream)
 {
     if (!ctx) { g_err = "dmpc_table_from_rows_device: ctx is NULL"; return -1; }
@@ -1246,27 +1273,24 @@ static int table_f32(dmpc_ctx *ctx, const double *src, DevBuf &dst, size_t n, hi
     return 0;
 }
 
-extern "C" int dmpc_step_batch(dmpc_ctx *ctx, int S, int N, const double *l, const double *x_p, const double *x_v,
-                               const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out,
-                               int32_t *status, int32_t *info)
+// one MPC step of the first N_cmd agents of every scene against a table of N rows, on this context's device (N_cmd == N: dmpc_step_batch)
+static int step_batch_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *l, const double *x_p, const double *x_v,
+                          const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out,
+                          int32_t *status, int32_t *info)
 {
-    if (!ctx) { g_err = "dmpc_step_batch: ctx is NULL"; return -1; }
-    if (S < 1 || N < 1) FAIL(ctx, "dmpc_step_batch: S and N must be >= 1");
-    if (!l || !x_p || !x_v || !x_a || !pf || !p_out || !v_out || !a_out || !status) FAIL(ctx, "dmpc_step_batch: NULL pointer");
-    if (ctx->grp && N >= ctx->grp->G) return group_step_batch(ctx, S, N, l, x_p, x_v, x_a, pf, p_out, v_out, a_out, status, info);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t A = (size_t)S * N;
-    if (ensure_step_scratch(ctx, A, A)) return -1;
+    const size_t T = (size_t)S * N, A = (size_t)S * N_cmd;   // table rows, agents solved
+    if (ensure_step_scratch(ctx, T, A)) return -1;
     hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rows.p, l, A * N3 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->rows.p, l, T * N3 * 8, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->xp.p, x_p, A * 24, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->xv.p, x_v, A * 24, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->xa.p, x_a, A * 24, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, pf, A * 24, hipMemcpyHostToDevice, st));
     if (dmpc_table_from_rows_device(ctx, S, 1, N, ctx->rows.as<double>(), ctx->lT.as<double>(), st)) return -1;
     const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;
-    if (mixed && table_f32(ctx, ctx->lT.as<double>(), ctx->lTf, A * N3, st)) return -1;
-    if (launch_step(ctx, S, 1, N, 0, 0, N, ctx->lT.as<double>(), ctx->xp.as<double>(), ctx->xv.as<double>(),
+    if (mixed && table_f32(ctx, ctx->lT.as<double>(), ctx->lTf, T * N3, st)) return -1;
+    if (launch_step(ctx, S, 1, N, 0, 0, N_cmd, ctx->lT.as<double>(), ctx->xp.as<double>(), ctx->xv.as<double>(),
                     ctx->xa.as<double>(), ctx->pf.as<double>(), ctx->pout.as<double>(), ctx->vout.as<double>(),
                     ctx->aout.as<double>(), nullptr, ctx->status.as<int32_t>(), ctx->info.as<int32_t>(), st, nullptr, 0,
                     mixed ? ctx->lTf.as<float>() : nullptr))
@@ -1278,6 +1302,29 @@ extern "C" int dmpc_step_batch(dmpc_ctx *ctx, int S, int N, const double *l, con
     if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->info.p, A * 32, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return 0;
+}
+
+extern "C" int dmpc_step_batch(dmpc_ctx *ctx, int S, int N, const double *l, const double *x_p, const double *x_v,
+                               const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out,
+                               int32_t *status, int32_t *info)
+{
+    if (!ctx) { g_err = "dmpc_step_batch: ctx is NULL"; return -1; }
+    if (S < 1 || N < 1) FAIL(ctx, "dmpc_step_batch: S and N must be >= 1");
+    if (!l || !x_p || !x_v || !x_a || !pf || !p_out || !v_out || !a_out || !status) FAIL(ctx, "dmpc_step_batch: NULL pointer");
+    if (ctx->grp && N >= ctx->grp->G) return group_step_batch(ctx, S, N, l, x_p, x_v, x_a, pf, p_out, v_out, a_out, status, info);
+    return step_batch_one(ctx, S, N, N, l, x_p, x_v, x_a, pf, p_out, v_out, a_out, status, info);
+}
+
+// DMPC::solveParallelDMPCv2's cluster_solvev2 (dmpc.cpp:1792-1841) for the N_cmd = _pf.cols() commanded vehicles of N = _po.cols() (:1572-1573)
+extern "C" int dmpc_step_batch_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *l, const double *x_p, const double *x_v,
+                                   const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out,
+                                   int32_t *status, int32_t *info)
+{
+    if (!ctx) { g_err = "dmpc_step_batch_cmd: ctx is NULL"; return -1; }
+    if (check_cmd(ctx, "dmpc_step_batch_cmd", S, N, N_cmd)) return -1;
+    if (!l || !x_p || !x_v || !x_a || !pf || !p_out || !v_out || !a_out || !status) FAIL(ctx, "dmpc_step_batch_cmd: NULL pointer");
+    if (N_cmd == N) return dmpc_step_batch(ctx, S, N, l, x_p, x_v, x_a, pf, p_out, v_out, a_out, status, info);
+    return step_batch_one(ctx, S, N, N_cmd, l, x_p, x_v, x_a, pf, p_out, v_out, a_out, status, info);   // (a DMPC_DEVICE_ALL context: its first GPU)
 }
 
 extern "C" int dmpc_solve_one(dmpc_ctx *ctx, int N, int n, const double *l, const double *po, const double *vo,
@@ -1407,24 +1454,26 @@ extern "C" int dmpc_init_batch(dmpc_ctx *ctx, int S, int N, const double *po, co
     return 0;
 }
 
-// the whole `for k = 1:K_T` loop on the device (dmpc_soft_bound.m:115-148, failure_rate.m:99-127)
-static int transition_one(dmpc_ctx *ctx, int S, int N, const double *po, const double *pf, int K_T_max,
+// the whole `for k = 1:K_T` loop on the device (dmpc_soft_bound.m:115-148, failure_rate.m:99-127) for the N_cmd commanded agents of N vehicles
+// (DMPC::solveParallelDMPCv2, dmpc.cpp:1570-1730: N = _po.cols(), N_cmd = _pf.cols()).  State, goals, outputs, histories, status and the
+// scene verdict are sized and strided by N_cmd (A agents); the tables and neighbour structures by N (T columns).  N_cmd == N: dmpc_transition.
+static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
                           double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
                           int32_t *scene_status)
 {
     if (!ctx) { g_err = "dmpc_transition: ctx is NULL"; return -1; }
-    if (S < 1 || N < 1 || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status || ((pk || vk || ak) && !(pk && vk && ak)))
+    if (S < 1 || N < 1 || N_cmd < 1 || N_cmd > N || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status || ((pk || vk || ak) && !(pk && vk && ak)))
         FAIL(ctx, "dmpc_transition: bad arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t A = (size_t)S * N;
-    if (ensure_step_scratch(ctx, A, A)) return -1;
+    const size_t A = (size_t)S * N_cmd, T = (size_t)S * N;
+    if (ensure_step_scratch(ctx, T, A)) return -1;
     const size_t hist = A * (size_t)K_T_max * 24;
-    if (ctx->lT2.ensure(A * N3 * 8) || ctx->po.ensure(A * 24) || ctx->hist_p.ensure(hist) || ctx->hist_v.ensure(hist) ||
+    if (ctx->lT2.ensure(T * N3 * 8) || ctx->po.ensure(T * 24) || ctx->hist_p.ensure(hist) || ctx->hist_v.ensure(hist) ||
         ctx->hist_a.ensure(hist) || ctx->flags.ensure((size_t)K_T_max * S * 8) || ctx->scene_done.ensure((size_t)S * 4))
         FAIL(ctx, "device allocation failed");
     hipStream_t st = ctx->stream;
     double *xp = ctx->xp.as<double>(), *xv = ctx->xv.as<double>(), *xa = ctx->xa.as<double>();
-    HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, po, A * 24, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, po, T * 24, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, pf, A * 24, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemsetAsync(ctx->flags.p, 0, (size_t)K_T_max * S * 8, st));
     HIPCHK(ctx, hipMemsetAsync(ctx->scene_done.p, 0, (size_t)S * 4, st));
@@ -1432,18 +1481,29 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, const double *po, const d
     HIPCHK(ctx, hipMemsetAsync(ctx->hist_v.p, 0, hist, st));
     HIPCHK(ctx, hipMemsetAsync(ctx->hist_a.p, 0, hist, st));
     // k = 1: initDMPC (dmpc_soft_bound.m:117-121): state = (po, 0, 0), table = straight lines
-    HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
+    if (N_cmd == N) HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
+    else HIPCHK(ctx, hipMemcpy2DAsync(xp, (size_t)N_cmd * 24, ctx->po.p, (size_t)N * 24, (size_t)N_cmd * 24, (size_t)S, hipMemcpyDeviceToDevice, st));   // the commanded agents' starts, packed
     HIPCHK(ctx, hipMemsetAsync(xv, 0, A * 24, st));
     HIPCHK(ctx, hipMemsetAsync(xa, 0, A * 24, st));
     hipLaunchKernelGGL(init_rows_kernel, dim3((unsigned)((A * N3 + 255) / 256)), dim3(256), 0, st, (int)A, ctx->prm.h,
-                       ctx->po.as<double>(), ctx->pf.as<double>(), ctx->rows.as<double>());
-    if (dmpc_table_from_rows_device(ctx, S, 1, N, ctx->rows.as<double>(), ctx->lT.as<double>(), st)) return -1;
+                       (const double *)(N_cmd == N ? ctx->po.as<double>() : xp), ctx->pf.as<double>(), ctx->rows.as<double>());
+    if (N_cmd == N) {
+        if (dmpc_table_from_rows_device(ctx, S, 1, N, ctx->rows.as<double>(), ctx->lT.as<double>(), st)) return -1;
+    } else {
+        // the commanded columns of the first table from the initDMPC rows; the static columns -- po replicated over the horizon (dmpc.cpp:1633-1649)
+        // -- into BOTH tables of the ping-pong pair, once: the solve kernels write the columns of the agents they solved and nothing else
+        const size_t nc = A * N3, ns = (T - A) * N3;
+        hipLaunchKernelGGL(cmd_cols_from_rows_kernel, dim3((unsigned)((nc + 255) / 256 > 4096 ? 4096 : (nc + 255) / 256)), dim3(256), 0, st, S, N, N_cmd,
+                           (const double *)ctx->rows.as<double>(), ctx->lT.as<double>());
+        hipLaunchKernelGGL(static_cols_kernel, dim3((unsigned)((ns + 255) / 256 > 4096 ? 4096 : (ns + 255) / 256)), dim3(256), 0, st, S, N, N_cmd,
+                           (const double *)ctx->po.as<double>(), ctx->lT.as<double>(), ctx->lT2.as<double>());
+    }
     const unsigned rb = (unsigned)((A * 3 + 255) / 256);
-    hipLaunchKernelGGL(record_kernel, dim3(rb), dim3(256), 0, st, S, N, K_T_max, 0, xp, xv, xa, ctx->hist_p.as<double>(),
+    hipLaunchKernelGGL(record_kernel, dim3(rb), dim3(256), 0, st, S, N_cmd, K_T_max, 0, xp, xv, xa, ctx->hist_p.as<double>(),
                        ctx->hist_v.as<double>(), ctx->hist_a.as<double>());
     // ReachedGoal is also evaluated on the initDMPC column (failure_rate.m:125 runs after k = 1 as well)
     HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->status.p, DMPC_ST_SOLVED, A, st));
-    hipLaunchKernelGGL(scene_reduce_kernel, dim3((unsigned)S), dim3(256), 0, st, N, error_tol, xp, ctx->pf.as<double>(),
+    hipLaunchKernelGGL(scene_reduce_kernel, dim3((unsigned)S), dim3(256), 0, st, N_cmd, error_tol, xp, ctx->pf.as<double>(),
                        (const int *)ctx->status.as<int32_t>(), ctx->flags.as<int>(), ctx->scene_done.as<int>());
     double *cur = ctx->lT.as<double>(), *nxt = ctx->lT2.as<double>();
     ctx->post_acc_S = 0;   // the scene accumulators of the fused post-step start from zero in every transition
@@ -1485,16 +1545,16 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, const double *po, const d
         return 0;
     };
     for (int k = 1; k < K_T_max && ndone < S; ++k) {
-        if (mixed && table_f32(ctx, cur, ctx->lTf, A * N3, st)) return -1;
+        if (mixed && table_f32(ctx, cur, ctx->lTf, T * N3, st)) return -1;   // (all N columns, the static ones included)
         const PostStep post{K_T_max, k, error_tol, xp, xv, xa, ctx->hist_p.as<double>(), ctx->hist_v.as<double>(), ctx->hist_a.as<double>(),
                             ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>()};
-        if (launch_step(ctx, S, 1, N, 0, 0, N, cur, xp, xv, xa, ctx->pf.as<double>(), ctx->pout.as<double>(),
+        if (launch_step(ctx, S, 1, N, 0, 0, N_cmd, cur, xp, xv, xa, ctx->pf.as<double>(), ctx->pout.as<double>(),
                         ctx->vout.as<double>(), ctx->aout.as<double>(), nxt, ctx->status.as<int32_t>(), nullptr, st,
                         ctx->scene_done.as<int>(), 0, mixed ? ctx->lTf.as<float>() : nullptr, &post))
             return -1;
         // state advance + history column + scene verdict in one launch (unless the solve kernel did them: tiny launches)
         if (!ctx->post_fused)
-        hipLaunchKernelGGL(post_step_kernel, dim3((unsigned)S), dim3(N >= 256 ? 256 : 128), 0, st, N, K_T_max, k, error_tol,
+        hipLaunchKernelGGL(post_step_kernel, dim3((unsigned)S), dim3(N_cmd >= 256 ? 256 : 128), 0, st, N_cmd, K_T_max, k, error_tol,
                            (const double *)ctx->pout.as<double>(), (const double *)ctx->vout.as<double>(), (const double *)ctx->aout.as<double>(),
                            (const int *)ctx->status.as<int32_t>(), xp, xv, xa, (const double *)ctx->pf.as<double>(), ctx->hist_p.as<double>(),
                            ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>(),
@@ -1518,7 +1578,7 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, const double *po, const d
         HIPCHK(ctx, hipMemcpyAsync(ak, ctx->hist_a.p, hist, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(ctx, hipStreamSynchronize(st));
-    ctx->hist_S = S; ctx->hist_N = N; ctx->hist_KT = K_T_max;
+    ctx->hist_S = S; ctx->hist_N = N_cmd; ctx->hist_KT = K_T_max;   // (the resident histories are the commanded agents')
     return 0;
 }
 
@@ -1536,13 +1596,13 @@ static void copy_debug_options(dmpc_ctx *dst, const dmpc_ctx *src)
 // Batched transitions are bound, MPC step by MPC step, by the slowest agent of the whole batch while most of the GPU
 // idles.  Scenes are independent, so a large batch is run as two halves on two contexts (= two HIP streams, two host
 // threads): the tail of one half overlaps the bulk of the other (512 transitions of 100 agents: 103 -> 60 ms).
-extern "C" int dmpc_transition(dmpc_ctx *ctx, int S, int N, const double *po, const double *pf, int K_T_max,
-                               double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                               int32_t *scene_status)
+static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
+                          double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
+                          int32_t *scene_status)
 {
-    if (!ctx) { g_err = "dmpc_transition: ctx is NULL"; return -1; }
     ctx->split_at.clear();
-    if (ctx->grp) {   // every visible GPU: the agents of each scene sharded over them (dmpc_multigpu.hip)
+    // uncommanded vehicles on a DMPC_DEVICE_ALL context: the first GPU alone (the rule for N < 2 G below); the batch split further down applies unchanged
+    if (ctx->grp && N_cmd == N) {   // every visible GPU: the agents of each scene sharded over them (dmpc_multigpu.hip)
         if (S < 1 || N < 1 || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status || ((pk || vk || ak) && !(pk && vk && ak))) FAIL(ctx, "dmpc_transition: bad arguments");
         // Batches of 64 or more scenes run as TWO groups side by side (a second set of rank contexts, threads and streams on the same
         // GPUs): scenes are independent, so while one half's ranks exchange their predictions (peer copies, barrier, events) the
@@ -1550,7 +1610,7 @@ extern "C" int dmpc_transition(dmpc_ctx *ctx, int S, int N, const double *po, co
         const int gparts = ctx->no_split ? 1 : (ctx->split_parts > 0 ? (ctx->split_parts > 2 ? 2 : ctx->split_parts) : (S >= 64 ? 2 : 1));
         // fewer agents than twice the GPUs (the reference's small swarms on an 8-GPU node): the first GPU alone, as dmpc_step_batch does --
         // sharding N = 4 agents over 8 GPUs is impossible and over 2-3 of them nothing but barriers and peer copies
-        if (N < 2 * ctx->grp->G) return transition_one(ctx, S, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
+        if (N < 2 * ctx->grp->G) return transition_one(ctx, S, N, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
         if (gparts < 2) return group_transition(ctx, S, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
         if (ctx->children.empty()) {
             const int keep = g_emulate_devices.load();
@@ -1584,8 +1644,8 @@ extern "C" int dmpc_transition(dmpc_ctx *ctx, int S, int N, const double *po, co
     // hardware interleaves across streams freely (persistent launches hold a CU's whole LDS), so many small parts overlap best
     int parts = ctx->split_parts > 0 ? ctx->split_parts : (S >= 128 ? 4 : (S >= 32 ? 2 : 1));
     if (parts > S) parts = S;
-    if (parts < 2 || ctx->no_split || N < 1 || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status)
-        return transition_one(ctx, S, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
+    if (parts < 2 || ctx->no_split || ctx->grp || N < 1 || N_cmd < 1 || N_cmd > N || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status)
+        return transition_one(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
     while ((int)ctx->children.size() < parts - 1) {
         dmpc_ctx *ch = dmpc_create(&ctx->prm, ctx->device, ctx->precision);
         if (!ch) FAIL(ctx, "dmpc_transition: further context: " + g_err);
@@ -1602,8 +1662,8 @@ extern "C" int dmpc_transition(dmpc_ctx *ctx, int S, int N, const double *po, co
     auto run = [&](int i) {
         dmpc_ctx *c = i ? ctx->children[(size_t)i - 1] : ctx;
         const int s0 = at[(size_t)i], sn = at[(size_t)i + 1] - s0;
-        const size_t a0 = (size_t)s0 * N, h0 = a0 * (size_t)K_T_max * 3;
-        rc[(size_t)i] = transition_one(c, sn, N, po + a0 * 3, pf + a0 * 3, K_T_max, error_tol, pk ? pk + h0 : nullptr, vk ? vk + h0 : nullptr,
+        const size_t t0 = (size_t)s0 * N, a0 = (size_t)s0 * N_cmd, h0 = a0 * (size_t)K_T_max * 3;   // po is strided by N, everything else by N_cmd
+        rc[(size_t)i] = transition_one(c, sn, N, N_cmd, po + t0 * 3, pf + a0 * 3, K_T_max, error_tol, pk ? pk + h0 : nullptr, vk ? vk + h0 : nullptr,
                                        ak ? ak + h0 : nullptr, K_T_used + s0, scene_status + s0);
     };
     std::vector<std::thread> th;
@@ -1618,13 +1678,34 @@ extern "C" int dmpc_transition(dmpc_ctx *ctx, int S, int N, const double *po, co
     return 0;
 }
 
+extern "C" int dmpc_transition(dmpc_ctx *ctx, int S, int N, const double *po, const double *pf, int K_T_max,
+                               double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
+                               int32_t *scene_status)
+{
+    if (!ctx) { g_err = "dmpc_transition: ctx is NULL"; return -1; }
+    return transition_any(ctx, S, N, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
+}
+
+// DMPC::solveParallelDMPCv2 (dmpc.cpp:1570-1730) with N_cmd = _pf.cols() < N = _po.cols(): the uncommanded vehicles are static columns of the table
+extern "C" int dmpc_transition_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
+                                   double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
+                                   int32_t *scene_status)
+{
+    if (!ctx) { g_err = "dmpc_transition_cmd: ctx is NULL"; return -1; }
+    if (check_cmd(ctx, "dmpc_transition_cmd", S, N, N_cmd)) return -1;
+    if (K_T_max < 2 || !po || !pf || !K_T_used || !scene_status || ((pk || vk || ak) && !(pk && vk && ak))) FAIL(ctx, "dmpc_transition_cmd: bad arguments");
+    return transition_any(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
+}
+
 // post-checks of S finished transitions (failure_rate.m:136-195): rescale, 100 Hz not-a-knot spline, pairwise
 // ellipsoidal collision check, path length, trajectory time.  pk == NULL: use the histories dmpc_transition left
 // resident on the device (no PCIe round trip).
 static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
                          const double *pk, const double *vk, const double *ak, const double *pf, double vmax, double amax, double Ts,
                          double *r_factor, double *h_scaled, int32_t *n_samples, double *min_dist,
-                         int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc)
+                         int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
+                         int M = 0 /* uncommanded vehicles per scene */, const double *po_static = nullptr /* [S][M][3] */,
+                         double *min_dist_static = nullptr, int32_t *violation_static = nullptr)
 {
     if (!ctx) { g_err = "dmpc_postcheck: ctx is NULL"; return -1; }
     if (S < 1 || N < 1 || KT_alloc < 2 || !K_T_used || !pf || !(vmax > 0) || !(amax > 0) || !(Ts > 0))
@@ -1751,6 +1832,21 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
     hipLaunchKernelGGL(pc::pairdist_kernel, dim3((unsigned)((ns_max + PC_SAMPLES_PER_BLOCK - 1) / PC_SAMPLES_PER_BLOCK), (unsigned)S),
                        dim3(256), (size_t)N * 24, st, N, KT_alloc, (const int *)d_kt, (const double *)d_hs, (const int *)d_ns, Ts,
                        1.0 / ctx->prm.c, (const double *)dp, (const double *)ctx->pc_M.as<double>(), d_min, d_interp, ns_alloc);
+    // uncommanded vehicles: every (commanded agent, sample) against every static vehicle (all pairs, exact)
+    const bool with_static = M > 0 && (min_dist_static || violation_static);
+    unsigned long long *d_min_st = nullptr;
+    std::vector<double> mds(S, 0.0);
+    if (with_static) {
+        if (ctx->pc_static.ensure((size_t)S * M * 24 + (size_t)S * 8)) FAIL(ctx, "device allocation failed (post-check, static vehicles)");
+        d_min_st = (unsigned long long *)(ctx->pc_static.as<char>() + (size_t)S * M * 24);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_static.p, po_static, (size_t)S * M * 24, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemsetAsync(d_min_st, 0x7f, (size_t)S * 8, st));
+        if (ns_max > 0)
+            hipLaunchKernelGGL(pc::static_pairs_kernel, dim3((unsigned)(((size_t)N * ns_max + 255) / 256), (unsigned)S), dim3(256), 0, st, N, M, KT_alloc,
+                               (const int *)d_kt, (const double *)d_hs, (const int *)d_ns, Ts, 1.0 / ctx->prm.c, (const double *)dp,
+                               (const double *)ctx->pc_M.as<double>(), (const double *)ctx->pc_static.as<double>(), d_min_st);
+        HIPCHK(ctx, hipMemcpyAsync(mds.data(), d_min_st, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+    }
     double *d_dist = ctx->pc_agent.as<double>();
     int *d_tidx = (int *)(ctx->pc_agent.as<char>() + A * 8);
     hipLaunchKernelGGL(pc::path_kernel, dim3((unsigned)((A + 63) / 64)), dim3(64), 0, st, S, N, KT_alloc, (const int *)d_kt,
@@ -1788,8 +1884,13 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
             if (violation) violation[s] = 0;
             if (totdist) totdist[s] = NAN;
             if (traj_time) traj_time[s] = NAN;
+            if (min_dist_static) min_dist_static[s] = NAN;
+            if (violation_static) violation_static[s] = 0;
             continue;
         }
+        const double ds = with_static ? std::sqrt(mds[s]) : INFINITY;
+        if (min_dist_static) min_dist_static[s] = ds;
+        if (violation_static) violation_static[s] = ds < ctx->prm.rmin - 0.05;
         const double d = (N > 1) ? std::sqrt(md[s]) : INFINITY;
         if (r_factor) r_factor[s] = rf[s];
         if (h_scaled) h_scaled[s] = hs[s];
@@ -1802,16 +1903,17 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
     return 0;
 }
 
-extern "C" int dmpc_postcheck(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
-                              const double *pk, const double *vk, const double *ak, const double *pf, double vmax, double amax, double Ts,
-                              double *r_factor, double *h_scaled, int32_t *n_samples, double *min_dist,
-                              int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc)
+// N: the agents the histories cover (the commanded ones); M, po_static, min_dist_static, violation_static: the uncommanded vehicles (dmpc_postcheck_cmd) or 0 / null
+static int postcheck_any(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                         const double *pk, const double *vk, const double *ak, const double *pf, double vmax, double amax, double Ts,
+                         double *r_factor, double *h_scaled, int32_t *n_samples, double *min_dist,
+                         int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
+                         int M, const double *po_static, double *min_dist_static, int32_t *violation_static)
 {
-    if (!ctx) { g_err = "dmpc_postcheck: ctx is NULL"; return -1; }
     const int parts = (int)ctx->split_at.size() - 1;
     if (pk || parts < 2 || ctx->split_at.back() != S || ctx->hist_S != S || (int)ctx->children.size() < parts - 1 || !K_T_used || !pf)
         return postcheck_one(ctx, S, N, KT_alloc, K_T_used, scene_mask, pk, vk, ak, pf, vmax, amax, Ts, r_factor, h_scaled, n_samples,
-                             min_dist, violation, totdist, traj_time, p_interp, ns_alloc);
+                             min_dist, violation, totdist, traj_time, p_interp, ns_alloc, M, po_static, min_dist_static, violation_static);
     // histories left resident by a split dmpc_transition: each part is checked where it lives, concurrently
     auto off = [&](auto *ptr, size_t o) { return ptr ? ptr + o : ptr; };
     std::vector<int> rc((size_t)parts, 0);
@@ -1824,7 +1926,8 @@ extern "C" int dmpc_postcheck(dmpc_ctx *ctx, int S, int N, int KT_alloc, const i
         rc[(size_t)i] = postcheck_one(c, sn, N, KT_alloc, K_T_used + s0, off(scene_mask, (size_t)s0), nullptr, nullptr, nullptr, pf + a0 * 3, vmax, amax, Ts,
                                       off(r_factor, (size_t)s0), off(h_scaled, (size_t)s0), off(n_samples, (size_t)s0), off(min_dist, (size_t)s0),
                                       off(violation, (size_t)s0), off(totdist, (size_t)s0), off(traj_time, (size_t)s0),
-                                      off(p_interp, a0 * (size_t)ns_alloc * 3), ns_alloc);
+                                      off(p_interp, a0 * (size_t)ns_alloc * 3), ns_alloc, M, off(po_static, (size_t)s0 * M * 3),
+                                      off(min_dist_static, (size_t)s0), off(violation_static, (size_t)s0));
         c->hist_S = keep;
     };
     std::vector<std::thread> th;
@@ -1834,6 +1937,31 @@ extern "C" int dmpc_postcheck(dmpc_ctx *ctx, int S, int N, int KT_alloc, const i
     for (int i = 1; i < parts; ++i)
         if (rc[(size_t)i]) FAIL(ctx, ctx->children[(size_t)i - 1]->err);
     return rc[0];
+}
+
+extern "C" int dmpc_postcheck(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                              const double *pk, const double *vk, const double *ak, const double *pf, double vmax, double amax, double Ts,
+                              double *r_factor, double *h_scaled, int32_t *n_samples, double *min_dist,
+                              int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc)
+{
+    if (!ctx) { g_err = "dmpc_postcheck: ctx is NULL"; return -1; }
+    return postcheck_any(ctx, S, N, KT_alloc, K_T_used, scene_mask, pk, vk, ak, pf, vmax, amax, Ts, r_factor, h_scaled, n_samples, min_dist,
+                         violation, totdist, traj_time, p_interp, ns_alloc, 0, nullptr, nullptr, nullptr);
+}
+
+// the post-checks after a transition with uncommanded vehicles: collision_violation(solution) over the N_cmd trajectories (dmpc.cpp:2052-2086)
+// as dmpc_postcheck, plus the commanded-against-static distances the reference leaves out
+extern "C" int dmpc_postcheck_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                                  const double *pk, const double *vk, const double *ak, const double *pf, const double *po_static,
+                                  double vmax, double amax, double Ts, double *r_factor, double *h_scaled, int32_t *n_samples,
+                                  double *min_dist, int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
+                                  double *min_dist_static, int32_t *violation_static)
+{
+    if (!ctx) { g_err = "dmpc_postcheck_cmd: ctx is NULL"; return -1; }
+    if (check_cmd(ctx, "dmpc_postcheck_cmd", S, N, N_cmd)) return -1;
+    if (N_cmd < N && !po_static) FAIL(ctx, "dmpc_postcheck_cmd: po_static is NULL with N_cmd < N");
+    return postcheck_any(ctx, S, N_cmd, KT_alloc, K_T_used, scene_mask, pk, vk, ak, pf, vmax, amax, Ts, r_factor, h_scaled, n_samples, min_dist,
+                         violation, totdist, traj_time, p_interp, ns_alloc, N - N_cmd, po_static, min_dist_static, violation_static);
 }
 
 

@@ -1862,6 +1862,36 @@ __global__ void table_from_rows_kernel(int S, int G, int C, const double *__rest
     }
 }
 
+// Uncommanded vehicles (columns N_cmd .. N-1 of a one-chunk table lT[S][3K][N]): po replicated over the horizon (dmpc.cpp:1633-1649),
+// written into BOTH tables of the transition's ping-pong pair once -- the solve kernels only ever write the columns of the agents they solved.
+// po: [S][N][3]
+__global__ void static_cols_kernel(int S, int N, int N_cmd, const double *__restrict__ po, double *__restrict__ lTa, double *__restrict__ lTb)
+{
+    const int M = N - N_cmd;
+    const size_t total = (size_t)S * N3 * M;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int c = N_cmd + (int)(t % M);   // t enumerates the destination: [s][j][c - N_cmd]
+        const size_t u = t / M;
+        const int j = (int)(u % N3), s = (int)(u / N3);
+        const double v = po[((size_t)s * N + c) * 3 + j % 3];
+        const size_t o = ((size_t)s * N3 + j) * N + c;
+        lTa[o] = v;
+        lTb[o] = v;
+    }
+}
+
+// rows[S][N_cmd][3K] of the commanded agents -> columns 0 .. N_cmd-1 of the one-chunk table lT[S][3K][N]
+__global__ void cmd_cols_from_rows_kernel(int S, int N, int N_cmd, const double *__restrict__ rows, double *__restrict__ lT)
+{
+    const size_t total = (size_t)S * N3 * N_cmd;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(t % N_cmd);
+        const size_t u = t / N_cmd;
+        const int j = (int)(u % N3), s = (int)(u / N3);
+        lT[((size_t)s * N3 + j) * N + c] = rows[((size_t)s * N_cmd + c) * N3 + j];
+    }
+}
+
 // mixed precision: the fp32 copy of a table the scan of the next step reads
 __global__ void table_to_f32_kernel(size_t n, const double *__restrict__ src, float *__restrict__ dst)
 {

@@ -323,6 +323,42 @@ __global__ void pairs_brute_pts_kernel(int N, int SB, double cinv, const double 
     if (threadIdx.x == 0 && m < INFINITY) atomicMin(&mind2[s], (unsigned long long)__double_as_longlong(m));
 }
 
+// Uncommanded vehicles: every (commanded agent, sample) against every static vehicle, all pairs, exact.  block = (tile of 256 (agent, sample)
+// items, scene); a thread evaluates its item's spline position once, the static positions po_static[S][M][3] stream through LDS in tiles.
+// The same fp64 distance expression as the agent-agent check (pair_d2); a static vehicle has no spline.
+__global__ void static_pairs_kernel(int N, int M, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs,
+                                    const int *__restrict__ ns, double Ts, double cinv, const double *__restrict__ y,
+                                    const double *__restrict__ Msp, const double *__restrict__ po_static,
+                                    unsigned long long *__restrict__ mind2)
+{
+    __shared__ double tile[256 * 3];
+    __shared__ double sh[256];
+    const int s = blockIdx.y, n = kt_used[s], nsamp = ns[s];
+    if (n < 2 || nsamp < 1) return;   // masked scene
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if ((size_t)blockIdx.x * 256 >= (size_t)N * nsamp) return;   // (uniform per block: the grid is sized for the longest scene)
+    const bool vi = e < (size_t)N * nsamp;
+    double xi = 0.0, yi = 0.0, zi = 0.0;
+    if (vi) {
+        const int i = (int)(e / nsamp), smp = (int)(e - (size_t)i * nsamp);
+        const double h = hs[s], t = smp * Ts;
+        const size_t o = ((size_t)s * N + i) * (size_t)KTa * 3;
+        xi = spline_eval2(y, Msp, o, n, h, t); yi = spline_eval2(y, Msp, o + 1, n, h, t); zi = spline_eval2(y, Msp, o + 2, n, h, t);
+    }
+    const double *ps = po_static + (size_t)s * M * 3;
+    double m = INFINITY;
+    for (int j0 = 0; j0 < M; j0 += 256) {
+        const int cntj = M - j0 < 256 ? M - j0 : 256;
+        __syncthreads();
+        for (int q = threadIdx.x; q < cntj * 3; q += 256) tile[q] = ps[3 * (size_t)j0 + q];
+        __syncthreads();
+        if (vi)
+            for (int jj = 0; jj < cntj; ++jj) m = fmin(m, pair_d2(xi, yi, zi, tile[3 * jj], tile[3 * jj + 1], tile[3 * jj + 2], cinv));
+    }
+    m = block_min(m, sh);
+    if (threadIdx.x == 0 && m < INFINITY) atomicMin(&mind2[s], (unsigned long long)__double_as_longlong(m));
+}
+
 // per agent: path length sum |p(t_{s+1}) - p(t_s)| (failure_rate.m:183) and the 1-based index after the last
 // sample farther than 5 cm from the goal (failure_rate.m:186-193)
 __global__ void path_kernel(int S, int N, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs,

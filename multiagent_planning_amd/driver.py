@@ -57,7 +57,8 @@ def chunked_to_rows(lT, N=None):
 
 
 def run_transition(dmpc, po, pf, K_T_max, error_tol=0.01):
-    """Whole transitions of S scenes on one device. Returns dict(pk,vk,ak,K_T_used,scene_status)."""
+    """Whole transitions of S scenes on one device. Returns dict(pk,vk,ak,K_T_used,scene_status).
+    pf with fewer agents than po: the vehicles behind the first N_cmd are uncommanded static obstacles (Dmpc.transition)."""
     return dmpc.transition(po, pf, K_T_max, error_tol)
 
 

@@ -6,8 +6,9 @@
 //
 // One gateway, dispatched on a command string, keeps ONE persistent context per parameter set:
 //   [p,v,a,status,info] = dmpc_mex('solve_one', params, l, n, po, vo, ao, pf)
-//   [P,V,A,status,info] = dmpc_mex('step_batch', params, l, x_p, x_v, x_a, pf)
+//   [P,V,A,status,info] = dmpc_mex('step_batch', params, l, x_p, x_v, x_a, pf)          states / pf 3 x N_cmd, N_cmd <= N: see below
 //   [r_factor,h_scaled,violation,totdist,traj_time,p] = dmpc_mex('postcheck', params, pk, vk, ak, pf, vmax, amax, Ts)
+//   [r_factor,h_scaled,violation,totdist,traj_time,p,violation_static,min_dist_static] = dmpc_mex('postcheck', ..., Ts, po_static)
 //   [Lambda,Av,A0,Delta] = dmpc_mex('model_matrices', params)
 //   [Ain,bin,dist] = dmpc_mex('coll_rows', params, l, sel0, k_cmp0, k_blk0, p, a0, rmin, c, A)     (0-based indices)
 //   [Ain,bin]      = dmpc_mex('add_coll_constr', params, p, po, rmin, c, A)
@@ -22,11 +23,15 @@
 //   tol            = dmpc_mex('max_deviation', params, p, prev_p)                      maxDeviation.m (p, prev_p: 3 x K)
 //   [po,pf]        = dmpc_mex('random_test', params, N, pmin, pmax, rmin, c, seed)      randomTest.m
 //   [po,pf]        = dmpc_mex('random_exchange', params, N, pmin, pmax, rmin, seed)     randomExchange.m
+// Uncommanded vehicles (DMPC::solveParallelDMPCv2, dmpc/cpp/dmpc.cpp:1572-1573: N = _po.cols(), N_cmd = _pf.cols()): 'transition' and
+// 'step_batch' take pf (and the states) with FEWER columns than po / l -- the first N_cmd vehicles are commanded, the others stay at po as
+// static obstacles, and the outputs cover the commanded ones; 'postcheck' takes po_static (3 x M) behind Ts.
 // `params` is a struct with the fields of dmpc_params (variant as the DMPC_VAR_* integer).
 // The signature-preserving wrappers (solveSoftDMPCbound.m, ...) in this directory call 'solve_one'
 // and convert status bits into the reference's [] + flag conventions.
 #include "mex.h"
 
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -148,32 +153,43 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         need(nrhs == 7, "step_batch: (cmd, params, l, x_p, x_v, x_a, pf)");
         const mwSize *dl = mxGetDimensions(prhs[2]);
         need(mxGetNumberOfDimensions(prhs[2]) == 3 && dl[0] == 3 && (int)dl[1] == p.K, "l must be 3 x K x N");
-        const int N = (int)dl[2];
-        for (int i = 3; i < 7; ++i) need(mxGetNumberOfElements(prhs[i]) == (size_t)3 * N, "states must be 3 x N");
-        const mwSize d3[3] = {3, (mwSize)p.K, (mwSize)N};
+        const int N = (int)dl[2], Nc = (int)(mxGetNumberOfElements(prhs[6]) / 3);   // N_cmd = columns of pf
+        need(Nc >= 1 && Nc <= N, "pf must be 3 x N_cmd with 1 <= N_cmd <= N");
+        for (int i = 3; i < 7; ++i) need(mxGetNumberOfElements(prhs[i]) == (size_t)3 * Nc, "states and pf must be 3 x N_cmd");
+        const mwSize d3[3] = {3, (mwSize)p.K, (mwSize)Nc};
         plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
         mxArray *v = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), *a = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
-        mxArray *st = mxCreateNumericMatrix(1, N, mxINT32_CLASS, mxREAL), *inf = mxCreateNumericMatrix(8, N, mxINT32_CLASS, mxREAL);
-        if (dmpc_step_batch(ctx, 1, N, mxGetPr(prhs[2]), mxGetPr(prhs[3]), mxGetPr(prhs[4]), mxGetPr(prhs[5]), mxGetPr(prhs[6]),
-                            mxGetPr(plhs[0]), mxGetPr(v), mxGetPr(a), (int32_t *)mxGetData(st), (int32_t *)mxGetData(inf)))
+        mxArray *st = mxCreateNumericMatrix(1, Nc, mxINT32_CLASS, mxREAL), *inf = mxCreateNumericMatrix(8, Nc, mxINT32_CLASS, mxREAL);
+        const int rc = Nc == N ? dmpc_step_batch(ctx, 1, N, mxGetPr(prhs[2]), mxGetPr(prhs[3]), mxGetPr(prhs[4]), mxGetPr(prhs[5]), mxGetPr(prhs[6]),
+                                                 mxGetPr(plhs[0]), mxGetPr(v), mxGetPr(a), (int32_t *)mxGetData(st), (int32_t *)mxGetData(inf))
+                                 : dmpc_step_batch_cmd(ctx, 1, N, Nc, mxGetPr(prhs[2]), mxGetPr(prhs[3]), mxGetPr(prhs[4]), mxGetPr(prhs[5]), mxGetPr(prhs[6]),
+                                                       mxGetPr(plhs[0]), mxGetPr(v), mxGetPr(a), (int32_t *)mxGetData(st), (int32_t *)mxGetData(inf));
+        if (rc)
             mexErrMsgIdAndTxt("dmpc:step", "%s", dmpc_last_error(ctx));
         if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a; if (nlhs > 3) plhs[3] = st; if (nlhs > 4) plhs[4] = inf;
         return;
     }
     if (!std::strcmp(cmd, "postcheck")) {   // failure_rate.m:136-195 for one trial
-        need(nrhs == 9, "postcheck: (cmd, params, pk, vk, ak, pf, vmax, amax, Ts)");
+        need(nrhs == 9 || nrhs == 10, "postcheck: (cmd, params, pk, vk, ak, pf, vmax, amax, Ts[, po_static])");
         const mwSize *dh = mxGetDimensions(prhs[2]);
         need(mxGetNumberOfDimensions(prhs[2]) == 3 && dh[0] == 3, "pk must be 3 x KT x N");
         const int KT = (int)dh[1], N = (int)dh[2];
         for (int i = 3; i < 5; ++i) need(mxGetNumberOfElements(prhs[i]) == (size_t)3 * KT * N, "vk, ak must match pk");
         need(mxGetNumberOfElements(prhs[5]) == (size_t)3 * N, "pf must be 1 x 3 x N");
         const double vmax = mxGetScalar(prhs[6]), amax = mxGetScalar(prhs[7]), Ts = mxGetScalar(prhs[8]);
-        double rf = 0, hs = 0, tot = 0, tt = 0;
-        int32_t ns = 0, viol = 0, kt = KT;
+        double rf = 0, hs = 0, tot = 0, tt = 0, mds = 0;
+        int32_t ns = 0, viol = 0, kt = KT, viol_st = 0;
+        // uncommanded vehicles: po_static is 3 x M; the histories and pf are the N commanded agents'
+        const int M = nrhs == 10 ? (int)(mxGetNumberOfElements(prhs[9]) / 3) : 0;
+        if (nrhs == 10) need(mxGetNumberOfElements(prhs[9]) == (size_t)3 * M, "po_static must be 3 x M");
         // MATLAB pk(3,KT,N) column-major IS the [N][KT][3] history layout
-        if (dmpc_postcheck(ctx, 1, N, KT, &kt, nullptr, mxGetPr(prhs[2]), mxGetPr(prhs[3]), mxGetPr(prhs[4]), mxGetPr(prhs[5]), vmax,
-                           amax, Ts, &rf, &hs, &ns, nullptr, &viol, &tot, &tt, nullptr, 0))
+        if (M > 0 ? dmpc_postcheck_cmd(ctx, 1, N + M, N, KT, &kt, nullptr, mxGetPr(prhs[2]), mxGetPr(prhs[3]), mxGetPr(prhs[4]), mxGetPr(prhs[5]),
+                                       mxGetPr(prhs[9]), vmax, amax, Ts, &rf, &hs, &ns, nullptr, &viol, &tot, &tt, nullptr, 0, &mds, &viol_st)
+                  : dmpc_postcheck(ctx, 1, N, KT, &kt, nullptr, mxGetPr(prhs[2]), mxGetPr(prhs[3]), mxGetPr(prhs[4]), mxGetPr(prhs[5]), vmax,
+                                   amax, Ts, &rf, &hs, &ns, nullptr, &viol, &tot, &tt, nullptr, 0))
             mexErrMsgIdAndTxt("dmpc:postcheck", "%s", dmpc_last_error(ctx));
+        if (nlhs > 6) plhs[6] = mxCreateDoubleScalar((double)viol_st);
+        if (nlhs > 7) plhs[7] = mxCreateDoubleScalar(M > 0 ? mds : (double)INFINITY);
         plhs[0] = mxCreateDoubleScalar(rf);
         if (nlhs > 1) plhs[1] = mxCreateDoubleScalar(hs);
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar((double)viol);
@@ -322,14 +338,16 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     }
     if (!std::strcmp(cmd, "transition")) {   // the whole `for k = 1:K_T` loop (dmpc_soft_bound.m:115-148) of one trial
         need(nrhs == 6, "transition: (cmd, params, po, pf, K_T_max, error_tol)");
-        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3), KT = (int)mxGetScalar(prhs[4]);
-        need(N >= 1 && mxGetNumberOfElements(prhs[3]) == (size_t)3 * N && KT >= 2, "po, pf must be 3 x N, K_T_max >= 2");
-        const mwSize d3[3] = {3, (mwSize)KT, (mwSize)N};
+        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3), Nc = (int)(mxGetNumberOfElements(prhs[3]) / 3), KT = (int)mxGetScalar(prhs[4]);
+        need(N >= 1 && Nc >= 1 && Nc <= N && mxGetNumberOfElements(prhs[3]) == (size_t)3 * Nc && KT >= 2, "po must be 3 x N, pf 3 x N_cmd (N_cmd <= N), K_T_max >= 2");
+        const mwSize d3[3] = {3, (mwSize)KT, (mwSize)Nc};   // the histories of the commanded agents (_pf.cols(), dmpc.cpp:1573)
         plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
         mxArray *v = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), *a = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
         int32_t used = 0, sst = 0;
-        if (dmpc_transition(ctx, 1, N, mxGetPr(prhs[2]), mxGetPr(prhs[3]), KT, mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v),
-                            mxGetPr(a), &used, &sst))
+        if (Nc == N ? dmpc_transition(ctx, 1, N, mxGetPr(prhs[2]), mxGetPr(prhs[3]), KT, mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v),
+                                      mxGetPr(a), &used, &sst)
+                    : dmpc_transition_cmd(ctx, 1, N, Nc, mxGetPr(prhs[2]), mxGetPr(prhs[3]), KT, mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v),
+                                          mxGetPr(a), &used, &sst))
             mexErrMsgIdAndTxt("dmpc:transition", "%s", dmpc_last_error(ctx));
         if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
         if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);

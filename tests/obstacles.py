@@ -1,0 +1,147 @@
+"""Test helper: scenes with uncommanded vehicles (N_cmd < N, DMPC::solveParallelDMPCv2 dmpc/cpp/dmpc.cpp:1572-1573), the oracle's closed
+loop over them, and raw ctypes calls of the *_cmd entries of the C ABI (the methods of _lib.Dmpc route calls with N_cmd == N to the
+entries without the suffix; the tests also need the *_cmd entries themselves with N_cmd == N and with bad arguments)."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+
+from helpers import ROOT, init_table
+
+KW = dict(h=0.2, rmin=0.35, c=2.0, alim=1.0, Q1=1000.0, S1=100.0, term=-5e4, pmin=(-2.5, -2.5, 0.2), pmax=(2.5, 2.5, 2.2))
+ERROR_TOL = 0.01
+NTHREADS = int(os.environ.get("OMP_NUM_THREADS", "4") or 4)
+
+
+def launch_thresholds():
+    """the list-regime thresholds of launch_step as the library's source states them (context defaults in dmpc_api.hip)"""
+    src = open(os.path.join(ROOT, "multiagent_planning_amd", "csrc", "dmpc_api.hip")).read()
+    get = lambda name: int(re.search(r"\bint " + name + r" = (\d+);", src).group(1))
+    return dict(cull_min=get("cull_min"), grid_min=get("grid_min"), grid_min_part=get("grid_min_part"))
+
+
+def wall_scene(n_cmd=8, seed=0):
+    """n_cmd commanded agents crossing a plane of static vehicles inside the reference workspace: the commanded agents start on
+    x = -2 and go to the mirrored side x = +2 (y swapped about the axis, so their straight lines also cross each other); the static
+    vehicles sit on the plane x = 0 in a grid of 1 m (y) x 0.9 m (z).  seed jitters the commanded starts / goals by up to 5 cm.
+    Returns po [N,3], pf [n_cmd,3]."""
+    rng = np.random.default_rng(1000 + seed)
+    ys = np.linspace(-1.75, 1.75, n_cmd // 2)
+    po_c = np.array([(-2.0, y, z) for z in (0.8, 1.6) for y in ys])[:n_cmd]
+    pf_c = np.array([(2.0, -y, z) for z in (1.6, 0.8) for y in ys])[:n_cmd]
+    po_c = po_c + rng.uniform(-0.05, 0.05, po_c.shape)
+    pf_c = pf_c + rng.uniform(-0.05, 0.05, pf_c.shape)
+    st = np.array([(0.0, y, z) for z in (0.75, 1.65) for y in (-2.0, -1.0, 0.0, 1.0, 2.0)])
+    return np.vstack([po_c, st]), pf_c
+
+
+def random_scene(n, n_cmd, seed, kw=KW):
+    """a seed of the reference's randomTest (numpy restatement, workload.random_test): the first n_cmd vehicles commanded, the others static"""
+    from multiagent_planning_amd import workload as wl
+    po, pf = wl.random_test(n, kw["pmin"], kw["pmax"], kw["rmin"], kw["c"], np.random.default_rng(wl.SEED0 + 500 + seed))
+    return po, pf[:n_cmd]
+
+
+def closed_loop_scenes():
+    """the batch of the closed-loop test: [(po [N,3], pf [N_cmd,3])], all with N = 18, N_cmd = 8"""
+    return [wall_scene(8, 0), wall_scene(8, 1), random_scene(18, 8, 0), random_scene(18, 8, 1)]
+
+
+def oracle_loop(orc, prm, po, pf, KT, error_tol=ERROR_TOL, nthreads=NTHREADS, without_static=False):
+    """dmpc_transition_cmd restated over oracle.step on the N-row table: static rows re-inserted each step, the static agents' own
+    outputs discarded; the stopping rule of dmpc_transition over the commanded agents.  Returns dict(pk, vk, ak [N_cmd,KT,3], K_T_used,
+    scene_status, nrows [K_T_used-1, N_cmd]); without_static: additionally nrows_free, the row counts of the same agent-steps (same
+    states, same commanded rows) with the static rows REMOVED from the table."""
+    po, pf = np.asarray(po, float), np.asarray(pf, float)
+    N, nc = po.shape[0], pf.shape[0]
+    pf_all = np.vstack([pf, po[nc:]])
+    l = init_table(po, pf_all)
+    static_rows = l[nc:].copy()
+    assert np.array_equal(static_rows, np.tile(po[nc:], (1, 15)))
+    xp, xv, xa = po.copy(), np.zeros((N, 3)), np.zeros((N, 3))
+    pk, vk, ak = (np.zeros((nc, KT, 3)) for _ in range(3))
+    pk[:, 0] = po[:nc]
+    used, sst, nrows, nrows_free = KT, 1, [], []
+    if np.linalg.norm(po[:nc] - pf, axis=1).max() < error_tol:
+        return dict(pk=pk, vk=vk, ak=ak, K_T_used=1, scene_status=1 | 256, nrows=np.zeros((0, nc), int), nrows_free=np.zeros((0, nc), int))
+    for k in range(1, KT):
+        l[nc:] = static_rows
+        o = orc.step(prm, l, xp, xv, xa, pf_all, nthreads=nthreads)
+        if without_static:
+            nrows_free.append(orc.step(prm, l[:nc], xp[:nc], xv[:nc], xa[:nc], pf, nthreads=nthreads)["info"][:, 7].copy())
+        st = o["status"][:nc]
+        nrows.append(o["info"][:nc, 7].copy())
+        ok = (st & 1) == 1
+        l[:nc][ok] = o["p"][:nc][ok]
+        xp[:nc][ok], xv[:nc][ok], xa[:nc][ok] = o["p"][:nc, :3][ok], o["v"][:nc, :3][ok], o["a"][:nc, :3][ok]
+        pk[:, k], vk[:, k], ak[:, k] = xp[:nc], xv[:nc], xa[:nc]
+        bits = int(np.bitwise_or.reduce(st))
+        if bits & ~1:
+            used, sst = k + 1, bits
+            break
+        if np.linalg.norm(xp[:nc] - pf, axis=1).max() < error_tol:
+            used, sst = k + 1, 1 | 256
+            break
+    return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, nrows=np.array(nrows), nrows_free=np.array(nrows_free))
+
+
+# ---- raw calls of the *_cmd entries -----------------------------------------------------------------------------------------------
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else C.POINTER(C.c_double)()
+
+
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else C.POINTER(C.c_int32)()
+
+
+def _f(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def raw_step_batch_cmd(d, l, x_p, x_v, x_a, pf, n_cmd, ctx="own"):
+    """dmpc_step_batch_cmd on [S,N,45] / [S,n_cmd,3] arrays; returns (rc, dict(p, v, a, status, info))"""
+    l, x_p, x_v, x_a, pf = _f(l), _f(x_p), _f(x_v), _f(x_a), _f(pf)
+    S, N = l.shape[0], l.shape[1]
+    m = max(n_cmd, 1)
+    p, v, a = np.zeros((S, m, 45)), np.zeros((S, m, 45)), np.zeros((S, m, 45))
+    status, info = np.zeros((S, m), dtype=np.int32), np.zeros((S, m, 8), dtype=np.int32)
+    rc = d._L.dmpc_step_batch_cmd(d._ctx if ctx == "own" else ctx, S, N, n_cmd, _dp(l), _dp(x_p), _dp(x_v), _dp(x_a), _dp(pf), _dp(p), _dp(v), _dp(a),
+                                  _ip(status), _ip(info))
+    return rc, dict(p=p, v=v, a=a, status=status, info=info)
+
+
+def raw_transition_cmd(d, po, pf, n_cmd, KT, error_tol=ERROR_TOL, ctx="own"):
+    """dmpc_transition_cmd on po [S,N,3], pf [S,n_cmd,3]; returns (rc, dict(pk, vk, ak, K_T_used, scene_status))"""
+    po, pf = _f(po), _f(pf)
+    S, N = po.shape[0], po.shape[1]
+    m = max(n_cmd, 1)
+    pk, vk, ak = (np.zeros((S, m, KT, 3)) for _ in range(3))
+    used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+    rc = d._L.dmpc_transition_cmd(d._ctx if ctx == "own" else ctx, S, N, n_cmd, _dp(po), _dp(pf), int(KT), float(error_tol), _dp(pk), _dp(vk), _dp(ak),
+                                  _ip(used), _ip(sst))
+    return rc, dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst)
+
+
+def raw_postcheck_cmd(d, n, n_cmd, K_T_used, pk, vk, ak, pf, po_static, vmax=2.0, amax=1.0, Ts=0.01, ns_alloc=0, ctx="own"):
+    """dmpc_postcheck_cmd on [S,n_cmd,KT,3] histories (None: the resident ones, then pk = KT_alloc); returns (rc, dict)"""
+    pf = _f(pf)
+    S = pf.shape[0]
+    used = np.ascontiguousarray(K_T_used, dtype=np.int32)
+    if isinstance(pk, int):
+        KT, pk, vk, ak = pk, None, None, None
+    else:
+        pk, vk, ak = _f(pk), _f(vk), _f(ak)
+        KT = pk.shape[2]
+    po_static = _f(po_static) if po_static is not None else None
+    out = dict(r_factor=np.zeros(S), h_scaled=np.zeros(S), n_samples=np.zeros(S, dtype=np.int32), min_dist=np.zeros(S),
+               violation=np.zeros(S, dtype=np.int32), totdist=np.zeros(S), traj_time=np.zeros(S), min_dist_static=np.zeros(S),
+               violation_static=np.zeros(S, dtype=np.int32))
+    p_i = np.zeros((S, max(n_cmd, 1), ns_alloc, 3)) if ns_alloc else None
+    rc = d._L.dmpc_postcheck_cmd(d._ctx if ctx == "own" else ctx, S, n, n_cmd, KT, _ip(used), _ip(None), _dp(pk), _dp(vk), _dp(ak), _dp(pf), _dp(po_static),
+                                 float(vmax), float(amax), float(Ts), _dp(out["r_factor"]), _dp(out["h_scaled"]), _ip(out["n_samples"]),
+                                 _dp(out["min_dist"]), _ip(out["violation"]), _dp(out["totdist"]), _dp(out["traj_time"]), _dp(p_i), int(ns_alloc),
+                                 _dp(out["min_dist_static"]), _ip(out["violation_static"]))
+    if p_i is not None:
+        out["p"] = p_i
+    return rc, out
