@@ -126,6 +126,26 @@ def ladder_crowd(variant, rows, kc=10, rmin=RMIN, c=2.0):
     return soft_crowd(variant, rows, kc=kc, rmin=rmin, c=c, depth=0.03)
 
 
+CORNER_BOX = dict(pmin=(-2.0, -2.0, -2.0), pmax=(1.0, 1.0, 1.0))
+CORNER_KC = 6
+
+
+def corner_hard_rows(fourth=False, rmin=RMIN, c=2.0):
+    """the three-wall corner of the wall-limit test (a probe at rest 1 m from the corner (1, 1, 1) of its box, the goal 0.2 m beyond it: its
+    last step ends on three walls) with three neighbours in general position just ahead of it, in the cone about the diagonal: two at
+    rmin + 0.005 and rmin + 0.0075 at every step, the violator at rmin - 0.0025 from step 6 on.  Their planes meet in a vertex a few
+    millimetres from the probe's start, the pull toward the goal presses the probe into it with multipliers of 80 ... 700 -- far below the
+    slack penalty of 5e4, so all three slacks stay pinned at zero: three HARD rows on step kc = 6, and three walls on step 15.
+    fourth: one more neighbour inside the cone at 1.01 rmin, whose plane cuts the vertex off: its row becomes active (hard), the first
+    neighbour's row gives way -- the entering row meets three hard rows that already span w_kc.  Returns (solver kw, scene)."""
+    dirs = [(1.0, 0.2, 0.1), (0.2, 1.0, 0.3)] + ([(0.6, 0.5, 0.55)] if fourth else [])
+    dist = [rmin + 0.005, rmin + 0.0075] + ([1.01 * rmin] if fourth else [])
+    off = [np.asarray(d) / np.linalg.norm(d) * r for d, r in zip(dirs, dist)]
+    vd = np.array([0.3, 0.1, 1.0]) / np.linalg.norm([0.3, 0.1, 1.0])
+    sc = scene(off, np.ones((len(off), K), dtype=bool), c=c, violator=(CORNER_KC, (rmin - 0.0025) * vd, 1.2 * rmin * vd), goal=(1.2, 1.2, 1.2))
+    return solver_kw(rmin=rmin, c=c, **CORNER_BOX), sc
+
+
 def row_capacity(variant, N):
     """rows per agent the scan builds (dmpc_api.hip row_capacity): want = rows of the worst case, capped per variant, at least 8,
     rounded up to an even number; one row more sets DMPC_ST_CAPACITY"""

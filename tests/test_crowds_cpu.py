@@ -50,6 +50,41 @@ def test_hard_crowd_has_the_intended_rows(pairs):
     assert (d < 1).sum() == pairs and (d[:, :9] < 1).sum() == 0
 
 
+@pytest.mark.parametrize("fourth", [False, True], ids=["three", "four"])
+def test_corner_probe_has_three_hard_rows_and_three_walls(fourth):
+    """crowds.corner_hard_rows, from the oracle's answer and the solver-independent working set of tests/exactqp.py: the probe's minimiser
+    has exactly three collision rows active (|C a - d| <= 1e-9) with their slack at zero -- the row AND its slack's bound eps <= 0 are in
+    the working set, so eps = 0 exactly at x* --, all on step kc = 6, and three walls at the last step.  The oracle's active-set count
+    is 9 (four neighbours: 10): the three rows, the three walls and the bound eps <= 0 of EVERY slack, which the dense QP carries as
+    a row of its own (multiplier 5e4 minus the row's share) -- the six constraints that act on the accelerations are counted apart.
+    With the fourth neighbour its row (index 2) is one of the three and the first neighbour's row (index 0) is inactive."""
+    import certificates as cert
+    import exactqp as ex
+    kw, sc = cr.corner_hard_rows(fourth)
+    l, xp, xv, xa, pf = sc
+    prm = orc.make_params("bound", **kw)
+    ref = orc.solve_one(prm, l, 0, xp[0], xv[0], xa[0], pf[0])
+    nrows = 4 if fourth else 3
+    assert ref["status"] == 1 and ref["info"][orc.I_VIOLK] == cr.CORNER_KC and ref["info"][orc.I_NROWS] == nrows and ref["info"][orc.I_TRIES] == 1
+    qp = orc.assemble_one(prm, l, 0, xp[0], xv[0], xa[0], pf[0])
+    nc = qp["ncoll"]
+    assert nc == nrows
+    x = cert.complete_slack(qp, ref["a"])
+    r = qp["C"] @ x - qp["d"]
+    active = [i for i in range(nc) if abs(r[i]) <= 1e-9]
+    assert active == ([1, 2, 3] if fourth else [0, 1, 2]) and np.abs(x[45:]).max() <= 1e-15
+    W = ex.working_set(qp, ref["a"]).tolist()
+    eps_ub = nc + 4 * 45                                     # the rows eps_i <= 0 (certificates.complete_slack)
+    assert all(i in W and eps_ub + i in W for i in active)   # hard: the row holds with its slack pinned at zero
+    on_a = [w for w in W if np.abs(qp["C"][w, :45]).max() > 0]
+    p = ref["p"].reshape(15, 3)
+    walls = np.abs(p - np.array(kw["pmax"])) < 1e-9
+    assert walls.sum() == 3 and walls[14].all()
+    assert len(on_a) == 6 and ref["info"][orc.I_NACTIVE] == 6 + nc
+    e = ex.exact_minimiser(qp, ref["a"])
+    assert e["resolved"] and np.abs(e["x"] - ref["a"]).max() <= 1e-10 and 100 < e["lam_max"] <= 5e4
+
+
 def test_row_capacity_restated():
     """the capacity the GPU tests assume (dmpc_api.hip row_capacity): per-variant want/cap, at least 8, rounded up to even"""
     row_capacity = cr.row_capacity

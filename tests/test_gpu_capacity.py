@@ -43,7 +43,12 @@ def _sub(d, m):
     return {k: v[m] for k, v in d.items()}
 
 
-def _agree_or_capacity(out, ref, reduced, skip=()):
+def _qp(variant, sc, kw=KW):
+    """the inputs _agree needs to vouch for an agent above its tight bar"""
+    return orc.make_params(variant, **kw), sc
+
+
+def _agree_or_capacity(out, ref, reduced, skip=(), qp=None):
     """every agent the GPU flags with ST_CAPACITY -- past the row capacity, or with a working set that outgrows the solver's 64 slots
     (full_qcap, dmpc_api.hip:626) -- has zero outputs and is not "solved"; every other agent agrees with the oracle (_agree of
     test_gpu_reduced for the reduced solver's variants, helpers.compare_to_oracle otherwise).  Returns the flag mask."""
@@ -53,7 +58,7 @@ def _agree_or_capacity(out, ref, reduced, skip=()):
         assert np.all(out[k][flag] == 0.0)
     keep = ~flag & ~np.isin(np.arange(len(flag)), list(skip))
     if reduced:
-        _agree(_sub(out, keep), _sub(ref, keep))
+        _agree(_sub(out, keep), _sub(ref, keep), qp=qp, index=np.nonzero(keep)[0])
     else:
         compare_to_oracle(_sub(out, keep), _sub(ref, keep), 1e-9, "crowd")
     return flag
@@ -75,7 +80,7 @@ def test_reduced_solver_lane_limit(variant, rows):
     red, gen = mp.Dmpc(variant, **KW), mp.Dmpc(variant, **KW)
     gen.debug_option("reduced_solver", 0)
     o_r, o_g = red.step_batch(*sc), gen.step_batch(*sc)
-    assert not _agree_or_capacity(o_r, ref, True)[0]
+    assert not _agree_or_capacity(o_r, ref, True, qp=_qp(variant, sc))[0]
     assert red.last_solve_kernel == RSOLVE
     same = all(np.array_equal(o_r[k][0], o_g[k][0]) for k in ("p", "v", "a")) and np.array_equal(o_r["info"][0, :5], o_g["info"][0, :5])
     if rows > 64:
@@ -92,7 +97,7 @@ def test_reduced_solver_64_rows_on_the_ladder(variant):
     ref = _oracle(variant, sc)
     assert ref["info"][0, 7] == 64 and ref["info"][0, 2] >= 3
     out = mp.Dmpc(variant, **KW).step_batch(*sc)
-    assert not _agree_or_capacity(out, ref, True)[0]
+    assert not _agree_or_capacity(out, ref, True, qp=_qp(variant, sc))[0]
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -124,7 +129,7 @@ def test_reduced_solver_wall_limit(vo, walls):
     red, gen = mp.Dmpc("bound", **kw), mp.Dmpc("bound", **kw)
     gen.debug_option("reduced_solver", 0)
     o_r, o_g = red.step_batch(*sc), gen.step_batch(*sc)
-    _agree(o_r, ref)
+    _agree(o_r, ref, qp=_qp("bound", sc, kw))
     assert red.last_solve_kernel == RSOLVE
     if walls > 3:
         for k in ("p", "v", "a", "status"):
@@ -170,7 +175,7 @@ def test_row_capacity(variant, cap, past):
     ref = _oracle(variant, sc, skip=(0,) if past else ())
     out = mp.Dmpc(variant, **KW).step_batch(*sc)
     assert out["info"][0, 1] == rows
-    flag = _agree_or_capacity(out, ref, variant == "bound", skip=(0,) if past else ())
+    flag = _agree_or_capacity(out, ref, variant == "bound", skip=(0,) if past else (), qp=_qp(variant, sc))
     assert bool(flag[0]) == past
     if past:
         with pytest.raises(DmpcError):
@@ -193,7 +198,7 @@ def test_row_capacity_of_small_scenes(N):
         out = mp.Dmpc(variant, **KW).step_batch(*sc)
         assert ref["info"][0, 7] == per * (N - 1) and not (out["status"] & ST_CAPACITY).any()
         if variant == "bound":
-            _agree(out, ref)
+            _agree(out, ref, qp=_qp(variant, sc))
         else:
             compare_to_oracle(out, ref)
     sc = cr.hard_crowd(6 * (N - 1))
@@ -229,7 +234,7 @@ def test_tier_forms_are_bit_identical_on_crowds(variant, rows):
     print(f"{variant}: peak working sets {np.unique(peaks)}, flagged {int(((outs[0]['status'] & ST_CAPACITY) != 0).sum())}")
     assert peaks.max() > 32 and ((outs[0]["status"] & ST_CAPACITY) != 0).any()   # (bound: peaks up to 64, five agents past it)
     if variant == "bound":
-        _agree_or_capacity(outs[0], _oracle(variant, sc), True)
+        _agree_or_capacity(outs[0], _oracle(variant, sc), True, qp=_qp(variant, sc))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -319,7 +324,7 @@ def test_threshold_ties(kind, axis, c):
         if variant == "hard" or not (ref["status"] & 1).any():
             compare_to_oracle(o_p, ref, 1e-9, what)
         else:
-            _agree(o_p, ref)
+            _agree(o_p, ref, qp=_qp(variant, sc, kw))
         r = orc.rows_one(prm, l, 0, xp[0], xv[0])
         Ain, bin_, dist, vk, coll = api.collision_rows(variant, xp[0], xv[0], 1, kw["h"], l.reshape(-1, 15, 3).transpose(2, 1, 0), 15,
                                                       kw["rmin"], kw["pmin"], kw["pmax"], kw["alim"], kw["Q1"], kw["S1"], E1, 2, kw["term"])

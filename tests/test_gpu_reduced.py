@@ -20,7 +20,11 @@ def _c4_like(N, seed):
     return cfg, kw, po[0], pf[0]
 
 
-def _agree(out, ref, tol_plain=1e-9, tol_ladder=5e-8):
+def _agree(out, ref, tol_plain=1e-9, tol_ladder=5e-8, qp=None, index=None):
+    """statuses, branch records and retry counts identical; p, v, a within tol_plain (1e-9) of `ref`.  An agent on a ladder level above the
+    first may sit up to tol_ladder off -- but only if the extended-precision minimiser of tests/exactqp.py resolves it from the GPU's answer
+    and that answer meets the bar of its multipliers' decade (test_gpu_exact.vouch).  qp = (prm, (l, xp, xv, xa, pf)): the step's inputs,
+    without which nothing above tol_plain is accepted; index: the scene's agent numbers of the rows of out / ref, when they are a subset"""
     st_o, st_r = out["status"].ravel(), ref["status"].ravel()
     assert np.array_equal(st_o, st_r)
     io, ir = out["info"].reshape(-1, 8), ref["info"].reshape(-1, 8)
@@ -28,13 +32,28 @@ def _agree(out, ref, tol_plain=1e-9, tol_ladder=5e-8):
     assert np.array_equal(io[:, 2], ir[:, 2]), "retry-ladder counts"
     ok = (st_r & 1) == 1
     worst = 0.0
+    above = np.zeros(int(ok.sum()), bool)
     for key in ("p", "v", "a"):
         e = np.abs(out[key].reshape(-1, 45)[ok] - ref[key].reshape(-1, 45)[ok]).max(axis=1)
         first = ir[ok, 2] == 1
         assert (e[first] <= tol_plain).all(), (key, float(e[first].max()))
         assert (e <= tol_ladder).all(), (key, float(e.max()))
         worst = max(worst, float(e.max()))
+        above = above | (e > tol_plain)
+    if above.any():
+        assert qp is not None, f"{int(above.sum())} agent(s) above {tol_plain:.0e} and no inputs to vouch for them"
+        from test_gpu_exact import vouch
+        rows = np.nonzero(ok)[0][above]
+        agents = rows if index is None else np.asarray(index)[rows]
+        full = out if index is None else dict(out, info=_scatter(out["info"].reshape(-1, 8), index, len(qp[1][0])), a=_scatter(out["a"].reshape(-1, 45), index, len(qp[1][0])))
+        vouch(agents, qp[0], qp[1], full, "above the tight bar")
     return worst
+
+
+def _scatter(rows, index, N):
+    full = np.zeros((N,) + rows.shape[1:], rows.dtype)
+    full[np.asarray(index)] = rows
+    return full
 
 
 def test_reduced_solver_is_what_runs_for_solveSoftDMPCbound():
@@ -61,7 +80,7 @@ def test_reduced_against_general_and_oracle_closed_loop():
     for k in range(2, 7):
         ref = orc.step(prm, l, xp, xv, xa, pf, nthreads=os.cpu_count())
         o_r, o_g = red.step_batch(l, xp, xv, xa, pf), gen.step_batch(l, xp, xv, xa, pf)
-        _agree(o_r, ref)
+        _agree(o_r, ref, qp=(prm, (l, xp, xv, xa, pf)))
         assert np.array_equal(o_r["status"], o_g["status"]) and np.array_equal(o_r["info"][..., :4], o_g["info"][..., :4])
         ok = (ref["status"] & 1) == 1
         l = np.where(ok[:, None], ref["p"], l)
@@ -81,7 +100,7 @@ def test_level_skip_extrapolation_changes_no_retry_count():
         b.debug_option("no_level_skip", 1)
         oa, ob = a.step_batch(l, xp, xv, xa, pf), b.step_batch(l, xp, xv, xa, pf)
         assert oa["info"][..., 2].max() >= 3, "the scene must climb the ladder"
-        worst = _agree(oa, ob)
+        worst = _agree(oa, ob, qp=(orc.make_params("bound", **kw), (l, xp, xv, xa, pf)))
         assert worst <= 5e-8
         assert ob["info"][..., 4].sum() >= oa["info"][..., 4].sum()   # (equal when the level certificate settles every level the extrapolation would have skipped)
 
@@ -106,7 +125,7 @@ def test_wall_leaving_while_a_row_enters_regression():
     l = init_table(po, pf); xp, xv, xa = po.copy(), np.zeros_like(po), np.zeros_like(po)
     for k in range(2, 7):
         out, ref = d.step_batch(l, xp, xv, xa, pf), orc.step(prm, l, xp, xv, xa, pf, nthreads=8)
-        _agree(out, ref)
+        _agree(out, ref, qp=(prm, (l, xp, xv, xa, pf)))
         ok = (ref["status"] & 1) == 1
         l = np.where(ok[:, None], ref["p"], l)
         xp = np.where(ok[:, None], ref["p"][:, :3], xp); xv = np.where(ok[:, None], ref["v"][:, :3], xv); xa = np.where(ok[:, None], ref["a"][:, :3], xa)
@@ -118,12 +137,15 @@ TIGHT_SEED, TIGHT_SCENES = 2963 + 17, 160
 def test_tight_workspace_campaign_time_boxed():
     """a fixed slice of tests/dev/gpu_campaign_walls.py: scenes at the headline's density squeezed into boxes of 0.5-0.8 of their size, the
     four variants of the reduced solver, 4-8 teacher-forced MPC steps: walls enter and leave the working set while collision rows do (the regime of
-    the gather defect of round 6).  Statuses, branch records, retry counts identical; 1e-8 on the first ladder level, 1e-7 above.  Seed and scene
+    the gather defect of round 6).  Statuses, branch records, retry counts identical; 1e-8 against the oracle -- up to 1e-7 on ladder levels above the
+    first, and then only for an agent whose answer the extended-precision minimiser resolves and finds within the bar of its multipliers' decade
+    (test_gpu_exact.vouch).  Seed and scene
     count are fixed, so the slice is the same on every run and box (it used to take a seed from the calendar week and stop after 15 s; the
     seed is the one that week drew when the slice was pinned, and 160 scenes are what 15 s covered: tests/dev/gpu_campaign_walls.py runs
     about 11 scenes per second)."""
     rng = np.random.default_rng(TIGHT_SEED)
-    total, walls = 0, 0
+    from test_gpu_exact import vouch
+    total, walls, vouched = 0, 0, 0
     for _ in range(TIGHT_SCENES):
         N = int(rng.integers(30, 160))
         cfg = dict(wl.CONFIGS["C4"]); cfg["N"] = N
@@ -148,12 +170,13 @@ def test_tight_workspace_campaign_time_boxed():
                     e = np.maximum(e, np.abs(out[key] - ref[key]).max(axis=1) * ok)
                 first = ref["info"][:, 2] == 1
                 assert (e[first] <= 1e-8).all() and (e <= 1e-7).all(), f"{what}: {e.max():.2e}"
+                vouched += vouch(np.nonzero(e > 1e-8)[0], prm, (l, xp, xv, xa, pf), out, what)
                 rel = ref["p"].reshape(-1, 15, 3)[ok]
                 walls += int(((np.abs(rel - np.array(kw["pmax"])) < 1e-9) | (np.abs(rel - np.array(kw["pmin"])) < 1e-9)).any(axis=(1, 2)).sum())
                 total += N
                 l = np.where(ok[:, None], ref["p"], l)
                 xp = np.where(ok[:, None], ref["p"][:, :3], xp); xv = np.where(ok[:, None], ref["v"][:, :3], xv); xa = np.where(ok[:, None], ref["a"][:, :3], xa)
-    print(f"tight-workspace campaign: {total} agent-steps, {walls} of them with a horizon step on a wall")
+    print(f"tight-workspace campaign: {total} agent-steps, {walls} of them with a horizon step on a wall, {vouched} above 1e-8 and vouched for by x*")
     assert total > 5000 and walls > 100
 
 
@@ -169,7 +192,7 @@ def test_hand_over_to_the_general_solver_changes_nothing():
     z = np.zeros_like(po)
     o_r, o_g = red.step_batch(l, po, z, z, pf), gen.step_batch(l, po, z, z, pf)
     ref = orc.step(prm, l, po, z, z, pf, nthreads=os.cpu_count())
-    _agree(o_r, ref)
+    _agree(o_r, ref, qp=(prm, (l, po, z, z, pf)))
     handed = o_r["info"][:, 4] == o_g["info"][:, 4]          # (the general solver's iteration count in the record)
     assert handed.sum() > 100
     same = np.all(o_r["a"] == o_g["a"], axis=1)
@@ -191,7 +214,7 @@ def test_walls_of_a_tight_workspace():
     for k in range(2, 9):
         ref = orc.step(prm, l, xp, xv, xa, pf, nthreads=os.cpu_count())
         out = red.step_batch(l, xp, xv, xa, pf)
-        _agree(out, ref)
+        _agree(out, ref, qp=(prm, (l, xp, xv, xa, pf)))
         ok = (ref["status"] & 1) == 1
         rel = ref["p"].reshape(-1, 15, 3)[ok]
         walls += int(((np.abs(rel - np.array(kw["pmax"])) < 1e-9) | (np.abs(rel - np.array(kw["pmin"])) < 1e-9)).any(axis=(1, 2)).sum())
