@@ -78,6 +78,42 @@ struct GroupShared {
     }
 };
 
+// Development / test options of a context (dmpc_debug_option; the table of their names is dev_options below).  They select launch forms and
+// tiers, never arithmetic.
+struct DevOptions {
+    int no_fuse = 0;         // development option no_fuse: always launch post_step_kernel
+    int no_persist = 0;      // development option no_persist: one-agent-per-workgroup solve launches
+    int force_persist = 0;   // development option force_persist (tests): the persistent kernel on small launches
+    int cull_min = 256;      // development option cull_min: neighbour lists from this many agents per scene on
+    int order_slices = 0;    // development option order_slices: workgroups of the order kernel (0: by launch size)
+    int no_cull = 0;         // development option no_cull: no neighbour lists in the scan of large scenes (A/B runs, tests)
+    int no_lpt = 0;          // development option no_lpt: no heaviest-first solve order
+    int order_hint = 0;      // option order_hint = 1: the launch order also uses the agents' work estimates of the context's previous step (measured: no gain in
+                             // closed loops -- the heavy agents of a step are not the heavy agents of the step before -- so off; a replay of ONE step would flatter it)
+    int crash_min = CRASH_MIN_DEFAULT;   // see StepParams::crash_min (development option crash_min; crash_any: also for the slack-free variants)
+    int crash_any = 0;
+    int pivot_explore = 0;   // development option pivot_explore (DMPC_PIVOT_EXPLORE builds)
+    int no_fast_exit = 0;    // development option no_fast_exit (tests): every agent through the solve kernel (the unconstrained exit of the scan off)
+    int iter_cap = ITER_CAP; // development option iter_cap: cap of the active-set iterations (agents beyond it end DMPC_ST_ITERCAP)
+    int tier1_env = 0;       // development option tier1_qcap (tests): 32 = two tiers for the slack variants (any value: no shallow-launch shortcut)
+    int split_parts = 0;     // development option split_parts: number of parts (0: the built-in rule)
+    int no_split = 0;        // development option no_split
+    int reduced_solver = 1;  // solveSoftDMPCbound: the reduced solver (dmpc_rsolve.hip) in front of the general one; 0: the general solver alone (A/B runs, tests)
+    int rsolve_cap = 0;      // development option rsolve_cap: the reduced solver hands an agent over after this many equality solves of a ladder level (0: its default; tests of the hand-over)
+    int no_split_t = 0;      // development option no_split_t: slack-free persistent solve with the whole inverse factor in every wave's block (nine waves per CU; A/B runs, tests)
+    int grid_min = 768;      // development option grid_min: cell-grid neighbour lists from this many agents per scene on (below: nbr_kernel) ...
+    int grid_min_part = 2048; // ... and when the query covers only a PART of the scene's agents (a rank's chunk: the grid is still built over all of them)
+    int prep_fuse = 1;       // development option prep_fuse: 0 = the cell grid of a single scene by the five kernels of round 4 instead of grid_prep_kernel + grid_fill2_kernel
+    int nbr_grid = 1;        // development option nbr_grid: 0 = neighbour lists of large scenes from the all-pairs box test of round 3 (nbr_kernel) instead of the cell grid + distance filter
+    int no_level_skip = 0;   // development option no_level_skip (see StepParams)
+    int no_level_check = 0;  // development option no_level_check (see StepParams)
+    int lds_pad_kb = 0;      // development option lds_pad_kb: KB of unused LDS per one-agent solve workgroup (occupancy experiments: fewer resident agents per CU)
+    int f32_dep_exp = 8;     // development option f32_dep_exp: fp32-factor kernels treat a pivot as dependent below delta / s_pp = 10^-n
+    int ext_cap = 0;         // development option ext_cap (tests): at most this many T extensions per workgroup (1: every agent that needs one waits for the same slot)
+    int queue_chunk = 0;     // development option queue_chunk: positions per ticket of the persistent queue's light bulk (0: chosen per launch)
+    int static_queue = 0;    // development option static_queue: persistent waves take queue positions round-robin instead of by ticket
+};
+
 struct dmpc_ctx {
     int device = 0;
     int precision = DMPC_PREC_F64;   // DMPC_PREC_MIXED: fp32 table / scan / rows, fp64 QP (host-pointer entry points)
@@ -91,26 +127,12 @@ struct dmpc_ctx {
     int max_lds_set = 0;
     // scratch for the host-pointer entry points
     DevBuf post_acc; int post_acc_S = 0, post_fused = 0;
-    int no_fuse = 0;         // development option no_fuse: always launch post_step_kernel
     DevBuf rowbuf, rowkc, hdr, order, bbox, bbox_nm, nbr_list, nbr_cnt, lrow, counter, flag_list, scene_done;
     int num_cu = 0;
-    int no_persist = 0;      // development option no_persist: one-agent-per-workgroup solve launches
+    DevOptions opt;          // development options (dmpc_debug_option)
     int max_lds_persist = 0;
-    int force_persist = 0;   // development option force_persist (tests): the persistent kernel on small launches
-    int cull_min = 256;      // development option cull_min: neighbour lists from this many agents per scene on
-    int order_slices = 0;    // development option order_slices: workgroups of the order kernel (0: by launch size)
-    int no_cull = 0;         // development option no_cull: no neighbour lists in the scan of large scenes (A/B runs, tests)
-    int no_lpt = 0;          // development option no_lpt: no heaviest-first solve order
-    int order_hint = 0;      // option order_hint = 1: the launch order also uses the agents' work estimates of the context's previous step (measured: no gain in
-                             // closed loops -- the heavy agents of a step are not the heavy agents of the step before -- so off; a replay of ONE step would flatter it)
     DevBuf prev_cost;        // [S * c_count] work estimates of the previous step (solve kernel -> order kernel)
     long prev_cost_shape = -1;
-    int crash_min = CRASH_MIN_DEFAULT;   // see StepParams::crash_min (development option crash_min; crash_any: also for the slack-free variants)
-    int crash_any = 0;
-    int pivot_explore = 0;   // development option pivot_explore (DMPC_PIVOT_EXPLORE builds)
-    int no_fast_exit = 0;    // development option no_fast_exit (tests): every agent through the solve kernel (the unconstrained exit of the scan off)
-    int iter_cap = ITER_CAP; // development option iter_cap: cap of the active-set iterations (agents beyond it end DMPC_ST_ITERCAP)
-    int tier1_env = 0;       // development option tier1_qcap (tests): 32 = two tiers for the slack variants (any value: no shallow-launch shortcut)
     int single_tier = 0;         // 1: solve with the full working-set capacity in one launch
     DevBuf lTf, lTf2;            // mixed precision: fp32 copies of the tables the scan reads
     DevBuf rows, lT, lT2, xp, xv, xa, pf, po, pout, vout, aout, status, info, hist_p, hist_v, hist_a, flags;
@@ -120,27 +142,11 @@ struct dmpc_ctx {
     int pc_fallback_scenes = 0;   // last dmpc_postcheck: scenes of a cell-grid search that were searched again by brute force
     std::vector<dmpc_ctx *> children;   // further contexts (own stream and buffers) for the other parts of a split batch of transitions
     std::vector<int> split_at;          // non-empty: the last dmpc_transition left scenes [split_at[i], split_at[i+1]) in part i (0: here, i > 0: children[i-1])
-    int split_parts = 0;     // development option split_parts: number of parts (0: the built-in rule)
-    int no_split = 0;        // development option no_split
     std::string last_kernel; // the solve kernel the last step launched for the bulk of its agents (dmpc_last_solve_kernel)
-    int reduced_solver = 1;  // solveSoftDMPCbound: the reduced solver (dmpc_rsolve.hip) in front of the general one; 0: the general solver alone (A/B runs, tests)
-    int rsolve_cap = 0;      // development option rsolve_cap: the reduced solver hands an agent over after this many equality solves of a ladder level (0: its default; tests of the hand-over)
     int rsolve_blocks = 0;   // workgroups of dmpc_rsolve_persist_kernel a CU holds (occupancy query, once per context)
-    int no_split_t = 0;      // development option no_split_t: slack-free persistent solve with the whole inverse factor in every wave's block (nine waves per CU; A/B runs, tests)
-    int grid_min = 768;      // development option grid_min: cell-grid neighbour lists from this many agents per scene on (below: nbr_kernel) ...
-    int grid_min_part = 2048; // ... and when the query covers only a PART of the scene's agents (a rank's chunk: the grid is still built over all of them)
-    int prep_fuse = 1;       // development option prep_fuse: 0 = the cell grid of a single scene by the five kernels of round 4 instead of grid_prep_kernel + grid_fill2_kernel
     bool grid_clean = false; // the cell grid's counters were left zero by the last scan launch (grid_clean_key: for which buffer / size)
     unsigned long long grid_clean_key = 0;
-    int nbr_grid = 1;        // development option nbr_grid: 0 = neighbour lists of large scenes from the all-pairs box test of round 3 (nbr_kernel) instead of the cell grid + distance filter
     DevBuf grid;             // cell grid of the neighbour lists (counts, starts, entries)
-    int no_level_skip = 0;   // development option no_level_skip (see StepParams)
-    int no_level_check = 0;  // development option no_level_check (see StepParams)
-    int lds_pad_kb = 0;      // development option lds_pad_kb: KB of unused LDS per one-agent solve workgroup (occupancy experiments: fewer resident agents per CU)
-    int f32_dep_exp = 8;     // development option f32_dep_exp: fp32-factor kernels treat a pivot as dependent below delta / s_pp = 10^-n
-    int ext_cap = 0;         // development option ext_cap (tests): at most this many T extensions per workgroup (1: every agent that needs one waits for the same slot)
-    int queue_chunk = 0;     // development option queue_chunk: positions per ticket of the persistent queue's light bulk (0: chosen per launch)
-    int static_queue = 0;    // development option static_queue: persistent waves take queue positions round-robin instead of by ticket
     DevBuf pc_p, pc_v, pc_a, pc_M, pc_w, pc_scene, pc_agent, pc_interp;   // post-check work buffers
     DevBuf pc_static;                                                      // post-check: positions of the uncommanded vehicles + their per-scene minimum
     DevBuf pc_pts, pc_cell, pc_fill, pc_start, pc_sorted, pc_on;           // post-check, large scenes: cell grid of a batch of samples
@@ -410,18 +416,26 @@ extern "C" int dmpc_debug_emulate_devices(int n)
 // Development / test options of a context (not in the public header; nothing in the library reads the environment per call).  They select
 // launch forms and tiers, never arithmetic: every combination returns the same bits (tests/test_gpu_paths.py).  A process can preset them for
 // the contexts it creates with ONE environment variable, DMPC_DEBUG_OPTIONS="name=value,name=value" (the probes under tools/).
+// One table of the options: the name dmpc_debug_option takes, the member, and whether a context hands its value to the contexts it creates for
+// itself (copy_debug_options).  split_parts and no_split describe the splitting itself and stay with their context.
+struct DevOptionEntry { const char *name; int DevOptions::*member; bool inherited; };
+static const DevOptionEntry dev_options[] = {
+    {"no_fuse", &DevOptions::no_fuse, true}, {"no_persist", &DevOptions::no_persist, true}, {"force_persist", &DevOptions::force_persist, true}, {"no_cull", &DevOptions::no_cull, true},
+    {"order_slices", &DevOptions::order_slices, true}, {"cull_min", &DevOptions::cull_min, true}, {"no_lpt", &DevOptions::no_lpt, true}, {"order_hint", &DevOptions::order_hint, true},
+    {"crash_min", &DevOptions::crash_min, true}, {"crash_any", &DevOptions::crash_any, true}, {"no_fast_exit", &DevOptions::no_fast_exit, true}, {"pivot_explore", &DevOptions::pivot_explore, true},
+    {"iter_cap", &DevOptions::iter_cap, true}, {"tier1_qcap", &DevOptions::tier1_env, true}, {"split_parts", &DevOptions::split_parts, false}, {"no_split", &DevOptions::no_split, false},
+    {"no_level_skip", &DevOptions::no_level_skip, true}, {"prep_fuse", &DevOptions::prep_fuse, true}, {"static_queue", &DevOptions::static_queue, true}, {"queue_chunk", &DevOptions::queue_chunk, true},
+    {"no_split_t", &DevOptions::no_split_t, true}, {"ext_cap", &DevOptions::ext_cap, true}, {"nbr_grid", &DevOptions::nbr_grid, true}, {"f32_dep_exp", &DevOptions::f32_dep_exp, true},
+    {"grid_min", &DevOptions::grid_min, true}, {"grid_min_part", &DevOptions::grid_min_part, true}, {"no_level_check", &DevOptions::no_level_check, true}, {"lds_pad_kb", &DevOptions::lds_pad_kb, true},
+    {"reduced_solver", &DevOptions::reduced_solver, true}, {"rsolve_cap", &DevOptions::rsolve_cap, true}};
+
 extern "C" int dmpc_debug_option(dmpc_ctx *ctx, const char *name, int value)
 {
     if (!ctx || !name) return -1;
-    struct { const char *n; int dmpc_ctx::*f; } tab[] = {
-        {"no_fuse", &dmpc_ctx::no_fuse}, {"no_persist", &dmpc_ctx::no_persist}, {"force_persist", &dmpc_ctx::force_persist}, {"no_cull", &dmpc_ctx::no_cull}, {"order_slices", &dmpc_ctx::order_slices}, {"cull_min", &dmpc_ctx::cull_min},
-        {"no_lpt", &dmpc_ctx::no_lpt}, {"order_hint", &dmpc_ctx::order_hint}, {"crash_min", &dmpc_ctx::crash_min}, {"crash_any", &dmpc_ctx::crash_any}, {"no_fast_exit", &dmpc_ctx::no_fast_exit}, {"pivot_explore", &dmpc_ctx::pivot_explore},
-        {"iter_cap", &dmpc_ctx::iter_cap}, {"tier1_qcap", &dmpc_ctx::tier1_env}, {"split_parts", &dmpc_ctx::split_parts}, {"no_split", &dmpc_ctx::no_split},
-        {"no_level_skip", &dmpc_ctx::no_level_skip}, {"prep_fuse", &dmpc_ctx::prep_fuse}, {"static_queue", &dmpc_ctx::static_queue}, {"queue_chunk", &dmpc_ctx::queue_chunk}, {"no_split_t", &dmpc_ctx::no_split_t}, {"ext_cap", &dmpc_ctx::ext_cap}, {"nbr_grid", &dmpc_ctx::nbr_grid}, {"f32_dep_exp", &dmpc_ctx::f32_dep_exp}, {"grid_min", &dmpc_ctx::grid_min}, {"no_level_check", &dmpc_ctx::no_level_check}, {"lds_pad_kb", &dmpc_ctx::lds_pad_kb}, {"reduced_solver", &dmpc_ctx::reduced_solver}, {"rsolve_cap", &dmpc_ctx::rsolve_cap}};
-    for (auto &t : tab)
-        if (!std::strcmp(t.n, name)) {
-            ctx->*(t.f) = value;
-            if (t.f == &dmpc_ctx::grid_min) ctx->grid_min_part = value;   // (the option forces the grid for every query from that size on)
+    for (const DevOptionEntry &t : dev_options)
+        if (!std::strcmp(t.name, name)) {
+            ctx->opt.*(t.member) = value;
+            if (t.member == &DevOptions::grid_min) ctx->opt.grid_min_part = value;   // (the option forces the grid for every query from that size on; grid_min_part after it: that threshold alone)
             for (dmpc_ctx *pc : ctx->peers) (void)dmpc_debug_option(pc, name, value);
             for (dmpc_ctx *ch : ctx->children) (void)dmpc_debug_option(ch, name, value);
             return 0;
@@ -589,492 +603,7 @@ extern "C" int dmpc_profile(dmpc_ctx *ctx, int enable)
 // launches
 // ---------------------------------------------------------------------------------------------
 
-static bool variant_soft(int v)
-{
-    return v == DMPC_VAR_BOUND || v == DMPC_VAR_BOUND2 || v == DMPC_VAR_ALL3 || v == DMPC_VAR_SOFTALL || v == DMPC_VAR_REPAIR ||
-           v == DMPC_VAR_CPP || v == DMPC_VAR_CPP2 || v == DMPC_VAR_CPP1 || v == DMPC_VAR_SOFTALL_C;
-}
-
-// row capacity per agent.  Rows live in global scratch (40-64 B each); LDS only holds 4-12 B per row
-// (working-set flags, slack value), so the exact worst case is affordable up to a few thousand rows.
-// The kernel flags DMPC_ST_CAPACITY if a cap is ever exceeded (never silently truncated).
-static int row_capacity(int variant, int N)
-{
-    const long nb = N > 1 ? N - 1 : 1;
-    long want, cap;
-    switch (variant) {
-    case DMPC_VAR_HARD: want = (long)K * nb; cap = 640; break;
-    case DMPC_VAR_SCP: want = (long)K * nb; cap = 4096; break;     // every neighbour at every step of addConstr (up to all k_hor of them), after exact pruning     // every k, neighbours with d < 1 (CollConstrHardDMPC.m:19), after exact pruning
-    case DMPC_VAR_ALL3: want = 3 * nb; cap = 384; break;           // three steps x neighbours with d < 3 rmin
-    case DMPC_VAR_BOUND: case DMPC_VAR_BOUND2: case DMPC_VAR_ONDEMAND: case DMPC_VAR_CPP: case DMPC_VAR_CPP2: want = nb; cap = 128; break;   // d < 3 rmin only
-    default: want = nb; cap = 4096; break;                         // ellip / softall / repair: all N-1 neighbours
-    }
-    long r = want < cap ? want : cap;
-    if (r < 8) r = 8;
-    return (int)((r + 1) & ~1L);
-}
-
-// Working-set capacity of the first solve launch.  The capacity is a template parameter of the solve kernels: 32 / 48 / 64
-// (slack-carrying variants), 48 (slack-free: 45 variables => at most 45 independent active rows, one tier).
-// Slack variants, deep launches: 48 slots first -- 17 KB of LDS per wave, still 8 resident agents per CU -- and a second launch
-// with 64 for the agents that outgrow them (none at N = 100; 4 in 10^4 at N = 10^4).  Round 1 used 32 slots first: the agents
-// that outgrow 32 are exactly the long ones (several retry-ladder levels, many active rows) and re-solving them in a second,
-// serialized launch cost more than anything else in the step.  Measured (bench secondaries, 51 200 agents of
-// solveSoftDMPCbound): 32/64 tiers 1.38 ms per step, one 64-slot tier (5 agents per CU) 1.07 ms, 48/64 tiers 1.02 ms;
-// 512 whole transitions 110 / 107 / 100 ms.  development option tier1_qcap = 32 | 64 selects the other forms (tests cover the 32/64 hand-off).
-static int tier1_qcap(const dmpc_ctx *ctx, int variant, int scene_agents);
-// hard: 45 variables => at most 45 independent active rows; 48 leaves room for a numerically near-dependent addition
-static int full_qcap(int variant) { return variant_soft(variant) ? QMAX : 48; }
-
-// what follows a solve in a closed loop (post_step_kernel); launch_step folds it into the solve kernel when the launch is tiny and
-// single-tier, and reports that in ctx->post_fused
-struct PostStep {
-    int KT, k;
-    double tol;
-    double *xp, *xv, *xa, *pk, *vk, *ak;
-    int *flags, *done;
-};
-
-static int tier1_qcap(const dmpc_ctx *ctx, int variant, int scene_agents)
-{
-    if (!variant_soft(variant)) return 48;
-    if (ctx->tier1_env == 32 || ctx->tier1_env == 48 || ctx->tier1_env == 56 || ctx->tier1_env == 64) return ctx->tier1_env;
-    // Large scenes: 56 slots first.  Far from its goal an agent saturates most of its 45 acceleration bounds (the crash start appends up
-    // to 44 of them), and with a handful of rows and their pins the working set peaks at 48-50 slots: at N = 10^4 (C4) 50-75 agents per
-    // step outgrew a 48-slot tier, none needs more than 50 -- and the few that overflow are re-solved from scratch in a second,
-    // serialized launch that lasts as long as its slowest agent (0.56 ms of a 2.7 ms step).  56 slots cost 3.6 KB of LDS per agent
-    // (5 instead of 6 one-agent workgroups per CU) and take them all: solve 1.81 -> 1.44 ms per step.
-    // (round 5: solveSoftDMPCall too, at any scene size -- its agents carry three rows per neighbour, 2-3 % of them outgrow 48 slots, and the second
-    // launch that re-solves those from scratch lasted 1.6 ms of a 4.5 ms step of 512 scenes: 3.16 -> 2.17 ms of solve launches per step)
-    return (scene_agents >= 1024 || variant == DMPC_VAR_ALL3) ? 56 : 48;
-}
-
-static int launch_step(dmpc_ctx *ctx, int S, int G, int C, int g_local, int c_first, int c_count, const double *lT,
-                       const double *x_p, const double *x_v, const double *x_a, const double *pf, double *p_out,
-                       double *v_out, double *a_out, double *lT_next, int32_t *status, int32_t *info, hipStream_t st,
-                       const int *scene_done = nullptr, int short_from = 0, const float *lTf = nullptr, const PostStep *post = nullptr,
-                       const double *own_prev = nullptr /* mixed: fp64 predictions of chunk g_local [S][3K][C] when lT is not the full fp64 table */)
-{
-    const dmpc_params &p = ctx->prm;
-    const bool soft = variant_soft(p.variant);
-    StepParams P;
-    memset(&P, 0, sizeof(P));
-    P.variant = p.variant; P.S = S; P.G = G; P.C = C; P.g_local = g_local;
-    P.c_first = c_first; P.c_count = c_count;
-    P.nrmax = row_capacity(p.variant, G * C);
-    if (p.variant == DMPC_VAR_HARD && (G > 256 || C >= (1 << 20)))   // packing of the scan's candidate list
-        FAIL(ctx, "solveHardDMPC scan: at most 256 chunks of fewer than 2^20 agents");
-    P.max_tries = p.max_tries;
-    P.ell_order = p.order;
-    P.h = p.h; P.rmin = p.rmin; P.e1z = 1.0 / p.c; P.e2z = p.order == 4 ? 1.0 / (p.c * p.c * p.c * p.c) : 1.0 / (p.c * p.c);   // E1 = E^-1, E2 = E^-order
-    if (p.variant == DMPC_VAR_SCP) { P.e1z = 1.0; P.e2z = 1.0; }   // solveDMPC: plain Euclidean norm (CheckCollDMPC.m:6, CollConstrDMPC.m:12-13)
-    P.alim = p.alim; P.Q1 = p.Q1; P.S1 = p.S1; P.term = p.term;
-    P.Qfar = p.Qfar > 0 ? p.Qfar : 1000.0; P.Qnear = p.Qnear > 0 ? p.Qnear : 10000.0; P.Sfree = p.Sfree > 0 ? p.Sfree : 10.0;
-    for (int d = 0; d < 3; ++d) { P.pmin[d] = p.pmin[d]; P.pmax[d] = p.pmax[d]; }
-    P.tables = ctx->d_tables;
-    for (int i = 0; i < 3; ++i) P.hsum[i] = ctx->hsum[i];
-    // mixed precision: the scan reads the fp32 copy lTf of the table; lT (fp64, chunk g_local) is the solve's fallback
-    P.lT = lTf ? (const double *)lTf : lT; P.own_prev = lTf ? (own_prev ? own_prev : lT + (size_t)g_local * S * N3 * C) : nullptr; P.x_p = x_p; P.x_v = x_v; P.x_a = x_a; P.pf = pf;
-    P.p_out = p_out; P.v_out = v_out; P.a_out = a_out; P.lT_next = lT_next;
-    P.status = status; P.info = info;
-    {
-        const size_t agents = (size_t)S * c_count;
-        if (ctx->rowbuf.ensure(agents * P.nrmax * (soft ? 7 : 4) * 8) || ctx->rowkc.ensure(agents * P.nrmax * 4) ||
-            ctx->hdr.ensure(agents * 8 * 4) || ctx->order.ensure(agents * 4) || ctx->counter.ensure(16) || ctx->flag_list.ensure(agents * 4))
-            FAIL(ctx, "device allocation failed (row scratch)");
-        P.rowbuf = ctx->rowbuf.as<double>(); P.rowkc = ctx->rowkc.as<int>(); P.hdr = ctx->hdr.as<int>();
-    }
-    P.dbg = ctx->dbg; P.dbg_agent = ctx->dbg_agent; P.dbg_cap = ctx->dbg_cap;
-    P.iter_cap = ctx->iter_cap;
-    P.rsolve_cap = ctx->rsolve_cap;
-    P.scp_tol = p.tol;
-    P.dep_tol_f32 = std::pow(10.0, -(double)ctx->f32_dep_exp);
-    P.no_level_check = ctx->no_level_check;
-    P.no_level_skip = ctx->no_level_skip;
-    // (not for solveHardDMPC: rows at every horizon step, 3 % of the agents would qualify and every scan would pay for the test)
-    P.fast_exit = (ctx->no_fast_exit || p.variant == DMPC_VAR_HARD || p.variant == DMPC_VAR_SCP || p.order == 4) ? 0 : 1;
-    // measured: the crash start pays for the slack-carrying variants (C4, N = 10^4: solve launch -16 %) and costs on solveHardDMPC
-    // (C2: -16 % throughput: with rows at every horizon step the bounds violated at the unconstrained minimiser are a poor guess)
-    P.crash_min = (soft || ctx->crash_any) ? ctx->crash_min : 0;
-    P.pivot_explore = ctx->pivot_explore;
-    // tiny launches (a scene or a few, every agent resident at once: bound by the latency of their slowest agent, LDS is no
-    // constraint) solve with the full working-set capacity in one launch; larger ones use the first tier and re-solve the few
-    // agents that outgrow it (the smaller footprint also puts 6 instead of 4 one-agent workgroups on a CU: 512 transitions
-    // in two halves of 25 600 agents 75 -> 63 ms); from `shallow` up the first tier runs as persistent waves
-    const long ncu = ctx->num_cu > 0 ? ctx->num_cu : 256;
-    const bool tiny = (long)S * c_count < 8L * ncu && !ctx->force_persist && !ctx->tier1_env;
-    // (round 4, with the fitted launch-order key: launches whose agents are HEAVY -- the all-neighbour variants in scenes of >= 200 agents, every
-    // violating agent carries a row per neighbour: C3 16 x 1 000 agents 37 iterations each, C5 64 x 200 agents 29 -- are throughput-bound from a
-    // quarter of that depth on: persistent waves 1.50 / 0.89 ms against 1.77 / 1.05.  Light launches of the same depth -- 128 scenes x 100 agents
-    // of solveSoftDMPC at MPC step 12, one iteration per agent -- stay with one agent per workgroup: 0.21 against 0.25 ms.)
-    const bool heavy_agents = (p.variant == DMPC_VAR_SOFTALL || p.variant == DMPC_VAR_SOFTALL_C || p.variant == DMPC_VAR_REPAIR || p.variant == DMPC_VAR_ELLIP || p.variant == DMPC_VAR_CPP1) && G * C >= 200;
-    // (crossover, agents per launch: C3 4 000: 0.72 / 0.71 ms, 8 000: 1.06 / 0.96; C5 3 200: 0.37 / 0.47, 6 400: 0.59 / 0.61 -- one agent per workgroup / persistent)
-    // (round 5: the slack variants in LARGE scenes -- the 56-slot tier, agents of ~100 us each -- are bound by their work per wave slot: persistent
-    // waves with the split factor, seven per CU, from two launches' worth of one-agent workgroups on)
-    const bool f32t = (ctx->precision & DMPC_PREC_F32FACTOR) != 0 && p.variant != DMPC_VAR_ALL3;   // (solveSoftDMPCall keeps the fp64 factor under every precision)
-    const bool big_soft = soft && G * C >= 1024 && !ctx->no_split_t && !f32t && !ctx->single_tier && !ctx->tier1_env;
-    const bool shallow = (long)S * c_count < (big_soft ? 8L : (heavy_agents ? 28L : 128L)) * ncu && !ctx->force_persist && !ctx->tier1_env;
-    // fp32 inverse factor: one tier with the full capacity, no split T.  Not for solveSoftDMPCall: its three nearly parallel rows per neighbour
-    // need the fp64 factor (sweep of round 4: 1 % of its agent-steps ended on another ladder level) -- that variant keeps it whatever the context says.
-    const int q1 = (ctx->single_tier || tiny || f32t) ? full_qcap(p.variant) : tier1_qcap(ctx, p.variant, G * C), q2 = full_qcap(p.variant);
-    const bool two_tier = q1 < q2;
-    ctx->post_fused = 0;
-    if (post && tiny && !two_tier && g_local == 0 && G == 1 && !ctx->no_fuse && p.variant != DMPC_VAR_SCP) {
-        if (ctx->post_acc.ensure((size_t)S * 16 + 64)) FAIL(ctx, "device allocation failed (post-step accumulators)");
-        if (ctx->post_acc_S != S) {   // zero once per batch shape; the last wave of a scene leaves them zeroed again
-            HIPCHK(ctx, hipMemsetAsync(ctx->post_acc.p, 0, (size_t)S * 16 + 64, st));
-            ctx->post_acc_S = S;
-        }
-        P.post_on = 1; P.post_KT = post->KT; P.post_k = post->k; P.post_tol = post->tol;
-        P.post_xp = post->xp; P.post_xv = post->xv; P.post_xa = post->xa; P.post_pk = post->pk; P.post_vk = post->vk; P.post_ak = post->ak;
-        P.post_flags = post->flags; P.post_done = post->done;
-        P.post_max = ctx->post_acc.as<unsigned long long>();
-        P.post_or = (int *)(ctx->post_acc.as<unsigned long long>() + S); P.post_cnt = P.post_or + S;
-        ctx->post_fused = 1;
-    }
-    P.scene_done = scene_done;
-    P.short_from = short_from;   // unequal clusters: chunks from here on hold C-1 agents (dmpc_multigpu.hip)
-    const size_t lds0 = scan_lds_bytes();
-    const size_t lds1 = solve_lds_bytes(P.nrmax, soft, q1, false, 0, f32t) + (size_t)ctx->lds_pad_kb * 1024, lds2 = solve_lds_bytes(P.nrmax, soft, q2, false, 0, f32t) + (size_t)ctx->lds_pad_kb * 1024;
-    const size_t ldsmax = lds2 > lds1 ? lds2 : lds1;
-    if (ctx->lds_pad_kb < 0 || ldsmax > 160 * 1024) FAIL(ctx, "development option lds_pad_kb: the solve workgroup's LDS block would exceed the CU's 160 KB");
-    if ((int)ldsmax > ctx->max_lds_set) {
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_kernel<true, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_kernel<true, 48>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_kernel<true, 56>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_kernel<true, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_kernel<false, 48>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_kernel<true, 64, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_kernel<false, 48, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsmax));
-        ctx->max_lds_set = (int)ldsmax;
-    }
-    dmpc_ctx::Ev ev{nullptr, nullptr, nullptr};
-    if (ctx->profile) {   // event triples are recycled (dmpc_profile_read2 returns them to the pool): no event is created inside a timed loop
-        if (!ctx->ev_pool.empty()) { ev = ctx->ev_pool.back(); ctx->ev_pool.pop_back(); }
-        else {
-            HIPCHK(ctx, hipEventCreate(&ev.t0));
-            HIPCHK(ctx, hipEventCreate(&ev.t1));
-            HIPCHK(ctx, hipEventCreate(&ev.t2));
-        }
-        HIPCHK(ctx, hipEventRecord(ev.t0, st));
-    }
-    const dim3 grid((unsigned)(S * c_count)), block(64);
-    // neighbour culling boxes (worth it once a scene has more than a few chunks of neighbours)
-    // only for the variants whose scan and rows have a finite neighbour radius (d < 1 for the hard rows, d < 3 rmin for the
-    // near-neighbour selections); solveEllipDMPC / solveSoftDMPC / solveSoftDMPCrepair take every neighbour
-    const bool finite_radius = p.variant == DMPC_VAR_HARD || p.variant == DMPC_VAR_BOUND || p.variant == DMPC_VAR_BOUND2 ||
-                               p.variant == DMPC_VAR_ALL3 || p.variant == DMPC_VAR_ONDEMAND || p.variant == DMPC_VAR_CPP ||
-                               p.variant == DMPC_VAR_CPP2;
-    if (G * C >= ctx->cull_min && !ctx->no_cull && finite_radius) {
-        const int total = G * S * C;
-        if (ctx->bbox.ensure((size_t)total * 6 * NSEG * 4) || ctx->bbox_nm.ensure((size_t)total * NBOX_NM * 4)) FAIL(ctx, "device allocation failed (bbox)");
-        if (C >= (1 << 20) || G > 2047)   // a list entry packs (chunk << 20) | column into an int
-            FAIL(ctx, "neighbour lists: at most 2047 chunks of fewer than 2^20 agents");
-        // neighbour lists from the boxes (nbr_kernel): up to 4096 entries per agent, within 1 GB of scratch
-        const size_t agents = (size_t)S * c_count;
-        long cap = ((long)G * C + 63) & ~63L;
-        if (cap > 4096) cap = 4096;
-        while (cap > 256 && agents * (size_t)cap * 4 > ((size_t)1 << 30)) cap >>= 1;
-        if (ctx->nbr_list.ensure(agents * (size_t)cap * 4) || ctx->nbr_cnt.ensure(agents * 4 * NBR_PARTS)) FAIL(ctx, "device allocation failed (neighbour lists)");
-        const double Rsel = (p.variant == DMPC_VAR_HARD) ? 1.0 : 3.0 * p.rmin;
-        const double R = Rsel * 1.0001 + 1e-4;   // a little more than the scan's radius: conservative in fp32 too
-        // round 4: lists from a cell grid, filtered by the fp32 distance test (grid_query_kernel); the all-pairs box test of round 3 stays
-        // behind option nbr_grid = 0 (A/B runs, tests) and for scenes whose bitmap would not fit a wave's LDS
-        const size_t gq_lds = grid_query_lds(G * C);
-        // (from grid_min agents per scene on: in a scene of a few hundred agents the reach of a query covers most of the workspace and the
-        // all-pairs test with the neighbours' boxes as scalar operands is the cheaper pass -- tools/gpu_grid_min_ab.py, 102 400 agents, scan
-        // side all-pairs / grid: hard rows 400 agents per scene 0.81 / 0.81 ms, 800: 1.07 / 0.91, 1 600: 1.42 / 1.06, 3 200: 1.92 / 1.24;
-        // solveSoftDMPCbound 400: 0.62 / 0.66, 800: 0.71 / 0.69, 1 600: 0.84 / 0.73, 3 200: 1.04 / 0.81.  A rank that queries ONE chunk of
-        // 8 x 100 agents per scene still bins all 800: 0.87 against 0.64 ms, `bench.py --emulate-gpus 8 --debug-option grid_min=512`)
-        // (one chunk of which at least half is queried -- the commanded agents of a scene with uncommanded vehicles -- counts as the whole scene: binning
-        // all C columns is then at most twice the query's own share; grid_min_part was fitted on a rank's chunk, an eighth of the scene.  Not measured.)
-        const int grid_from = (c_count == G * C || (G == 1 && 2L * c_count >= (long)C)) ? ctx->grid_min : ctx->grid_min_part;
-        const bool use_grid = ctx->nbr_grid && G * C >= grid_from && gq_lds <= 64 * 1024;
-        // (grid geometry and buffer first: the counters are zeroed by the neighbour-major copy kernel, which runs anyway -- a memset of an odd
-        // size is two fill launches, 9 us)
-        GridGeom gg{};
-        int ncell = 1;
-        int *g_cnt = nullptr, *g_mh = nullptr, *g_st = nullptr, *g_cell = nullptr, *g_pos = nullptr;
-        f4_t *g_ent = nullptr;
-        size_t n_zero = 0;
-        bool fused = false;   // ONE scene: the grid in two launches (grid_prep_kernel, grid_fill2_kernel) instead of five
-        if (use_grid) {
-            // cells: R along x (the cells of a run along x are contiguous in the entry array: their granularity is free), 1.5 R along y
-            // and 1.5 R c along z (the metric's z scale), at most 32 per axis
-            const double cell[3] = {R, 1.5 * R, 1.5 * R * p.c};
-            for (int a = 0; a < 3; ++a) {
-                const double span = p.pmax[a] - p.pmin[a];
-                int n = (int)(span / cell[a]);
-                n = n < 1 ? 1 : (n > 32 ? 32 : n);
-                gg.n[a] = n; gg.org[a] = (float)p.pmin[a]; gg.inv[a] = (float)(n / (span > 0 ? span : 1.0));
-                ncell *= n;
-            }
-            // one grid per third of the horizon (keyed by the centre of that segment's box: a third of the extent of the whole horizon's).  One
-            // buffer: [S][3][ncell] counts, [S][3][3] largest half extents (zeroed together), [S][3][ncell + 1] starts, [3][G S C] cells, [S][3][G C] entries
-            const size_t n_cnt = (size_t)S * NSEG * ncell, n_mh = (size_t)S * NSEG * 3, n_st = (size_t)S * NSEG * (ncell + 1);
-            const size_t n_hd = (n_cnt + n_mh + n_st + 2 * (size_t)NSEG * total + 7) & ~(size_t)7;   // (the entry records behind it are 32-byte aligned)
-            if (ctx->grid.ensure((n_hd + 8 * (size_t)NSEG * total) * 4)) FAIL(ctx, "device allocation failed (neighbour grid)");
-            g_cnt = ctx->grid.as<int>(); g_mh = g_cnt + n_cnt; g_st = g_mh + n_mh; g_cell = g_st + n_st; g_pos = g_cell + (size_t)NSEG * total;
-            g_ent = (f4_t *)(g_cnt + n_hd);
-            n_zero = n_cnt + n_mh;
-            fused = S == 1 && ctx->prep_fuse && (size_t)NSEG * (ncell + 1) * 4 <= 48 * 1024;
-        }
-        if (!fused) {
-            if (lTf) hipLaunchKernelGGL(bbox_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, C, lTf, ctx->bbox.as<float>(), ctx->bbox_nm.as<float>());
-            else hipLaunchKernelGGL(bbox_kernel<double>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, C, lT, ctx->bbox.as<float>(), ctx->bbox_nm.as<float>());
-        }
-        if (p.variant != DMPC_VAR_HARD || use_grid) {   // neighbour-major fp32 copy of the table: the list walk of the per-step distance scan, the distance test of the grid query
-            const size_t tot = (size_t)total * 64;
-            if (ctx->lrow.ensure(tot * 4)) FAIL(ctx, "device allocation failed (neighbour-major table)");
-            if (fused) {}   // (grid_prep_kernel below makes the copy)
-            else if (lTf) hipLaunchKernelGGL(table_nbrmajor_kernel<float>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, tot, C, lTf, ctx->lrow.as<float>(), g_cnt, n_zero);
-            else hipLaunchKernelGGL(table_nbrmajor_kernel<double>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, tot, C, lT, ctx->lrow.as<float>(), g_cnt, n_zero);
-            if (p.variant != DMPC_VAR_HARD) P.lrow = ctx->lrow.p;
-        }
-        if (use_grid && fused) {
-            // the counters are zero when the last scan launch left them so (for this buffer and size); a memset otherwise (first step, another batch shape in between)
-            const unsigned long long key = (unsigned long long)(size_t)g_cnt ^ ((unsigned long long)n_zero << 48) ^ ((unsigned long long)total << 20);
-            if (!ctx->grid_clean || ctx->grid_clean_key != key) HIPCHK(ctx, hipMemsetAsync(g_cnt, 0, n_zero * 4, st));
-            ctx->grid_clean = false; ctx->grid_clean_key = key;
-            P.gzero = g_cnt; P.gzero_n = (int)n_zero;
-            const int nbA = (total + 255) / 256, nbC = (int)(((size_t)total * 64 + 255) / 256);
-            if (lTf) hipLaunchKernelGGL(grid_prep_kernel<float>, dim3((unsigned)(nbA + nbC)), dim3(256), 0, st, total, C, short_from, gg, nbA, lTf, ctx->bbox.as<float>(), ctx->bbox_nm.as<float>(), ctx->lrow.as<float>(), g_cell, g_pos, g_cnt, g_mh);
-            else hipLaunchKernelGGL(grid_prep_kernel<double>, dim3((unsigned)(nbA + nbC)), dim3(256), 0, st, total, C, short_from, gg, nbA, lT, ctx->bbox.as<float>(), ctx->bbox_nm.as<float>(), ctx->lrow.as<float>(), g_cell, g_pos, g_cnt, g_mh);
-            hipLaunchKernelGGL(grid_fill2_kernel, dim3((unsigned)nbA), dim3(256), (size_t)NSEG * (ncell + 1) * 4, st, total, C, ncell, (float)(1.0 / p.c), (const int *)g_cell, (const int *)g_pos, (const int *)g_cnt, g_st, (const float *)ctx->lrow.as<float>(), g_ent);
-        } else if (use_grid) {
-            ctx->grid_clean = false;
-            hipLaunchKernelGGL(grid_bin_kernel, dim3((unsigned)((total + 255) / 256), NSEG), dim3(256), 0, st, total, S, C, short_from, gg, (const float *)ctx->bbox_nm.as<float>(), g_cell, g_cnt, g_mh);
-            hipLaunchKernelGGL(grid_scan_kernel, dim3((unsigned)(S * NSEG)), dim3(ncell > 512 ? 1024 : 256), 0, st, ncell, g_cnt, g_st);
-            hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, S, C, ncell, (float)(1.0 / p.c), (const int *)g_cell, g_cnt, (const int *)g_st, (const float *)ctx->lrow.as<float>(), g_ent);
-        }
-        if (use_grid) {
-            const int nq = S * c_count;
-            hipLaunchKernelGGL(grid_query_kernel, dim3((unsigned)nq), dim3(64 * GQ_WAVES), gq_lds, st, S, G, C, g_local, c_first, c_count, gg,
-                               (float)R, (float)(R * p.c), (float)(1.0 / p.c), (float)(Rsel * Rsel * 1.002), (const float *)ctx->bbox_nm.as<float>(), (const float *)ctx->lrow.as<float>(),
-                               (const int *)g_st, (const f4_t *)g_ent, (const int *)g_mh, (int)cap, (G == 1 && c_first == 0 && c_count == C && !short_from) ? 1 : 0,
-                               ctx->nbr_list.as<int>(), ctx->nbr_cnt.as<int>());
-        } else {
-            const int nblk = (c_count + 63) / 64;
-            hipLaunchKernelGGL(nbr_kernel, dim3((unsigned)(S * nblk * NBR_PARTS)), dim3(64), 0, st, S, G, C, g_local, c_first, c_count, short_from, (float)R, (float)(R * p.c),
-                               (const float *)ctx->bbox.as<float>(), (const float *)ctx->bbox_nm.as<float>(), (int)cap, ctx->nbr_list.as<int>(), ctx->nbr_cnt.as<int>());
-        }
-        P.nbr_cap = (int)cap; P.nbr_list = ctx->nbr_list.as<int>(); P.nbr_cnt = ctx->nbr_cnt.as<int>();
-    }
-    if (p.variant == DMPC_VAR_SCP) {
-        // solveDMPC.m: the whole SCP loop of an agent -- up to k_hor passes of {scan about the previous pass's prediction, slack-free QP} -- in ONE
-        // launch, one agent per 64-thread workgroup (dmpc_scp_kernel); no neighbour lists (rows for every other agent), no launch order
-        if (lTf) FAIL(ctx, "solveDMPC (DMPC_VAR_SCP) runs in fp64 only: create the context with DMPC_PREC_F64");
-        P.qcap = 48; P.only_flagged = 0; P.qover_bit = ST_CAPACITY; P.lds_per_wave = (int)lds0;
-        const size_t lds_scp = solve_lds_bytes(P.nrmax, false, 48, false) > lds0 ? solve_lds_bytes(P.nrmax, false, 48, false) : lds0;
-        if ((int)lds_scp > ctx->max_lds_scp) {
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_scp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_scp));
-            ctx->max_lds_scp = (int)lds_scp;
-        }
-        if (ctx->profile) HIPCHK(ctx, hipEventRecord(ev.t1, st));
-        hipLaunchKernelGGL(dmpc_scp_kernel, grid, block, lds_scp, st, P);
-        HIPCHK(ctx, hipGetLastError());
-        ctx->last_kernel = "dmpc_scp_kernel";
-        if (ctx->profile) {
-            HIPCHK(ctx, hipEventRecord(ev.t2, st));
-            ctx->events.push_back(ev);
-        }
-        ctx->solves += (int64_t)S * c_count;
-        return 0;
-    }
-    const bool run_order = ctx->forced_n != S * c_count && S * c_count >= 512 && !ctx->no_lpt;
-    // the reduced solver (dmpc_rsolve.hip) takes solveSoftDMPCbound / bound2 and DMPC::solveQPv2 in every launch form: which kernel solves an agent must not depend on how deep the launch is
-    const bool reduced = ctx->reduced_solver && (p.variant == DMPC_VAR_BOUND || p.variant == DMPC_VAR_BOUND2 || p.variant == DMPC_VAR_CPP || p.variant == DMPC_VAR_CPP2) && !f32t && ctx->num_cu >= 1;   // the variants with slack rows on ONE horizon step
-    P.zero4 = (!tiny || run_order || reduced) ? ctx->counter.as<int>() : nullptr;   // queue heads of the persistent solve launches, tier-2 count, live bound: zeroed by the scan kernel (a memset is a launch of its own, 5 us)
-    // phase 0: scan + rows
-    P.qcap = q1; P.only_flagged = 0; P.qover_bit = two_tier ? ST_QOVER : ST_CAPACITY;
-    {
-        // several independent waves per workgroup (fewer workgroups to dispatch), as many as fit the default 64 KB of
-        // dynamic LDS (the neighbour list of large scenes can take 37 KB per wave)
-        const int total = S * c_count;
-        int W = SCAN_WAVES_PER_WG;
-        while (W > 1 && lds0 * W > 64 * 1024) W >>= 1;
-        const dim3 sgrid((unsigned)((total + W - 1) / W)), sblock(64u * W);
-        P.lds_per_wave = (int)lds0;
-        const bool fx = P.fast_exit != 0;
-        if (p.order == 4) {   // super-ellipsoid of order 4 (all-neighbour variants): its own scan kernels, without the unconstrained exit
-            if (lTf) { if (soft) hipLaunchKernelGGL((dmpc_scan_kernel<true, float, false, true>), sgrid, sblock, lds0 * W, st, P); else hipLaunchKernelGGL((dmpc_scan_kernel<false, float, false, true>), sgrid, sblock, lds0 * W, st, P); }
-            else { if (soft) hipLaunchKernelGGL((dmpc_scan_kernel<true, double, false, true>), sgrid, sblock, lds0 * W, st, P); else hipLaunchKernelGGL((dmpc_scan_kernel<false, double, false, true>), sgrid, sblock, lds0 * W, st, P); }
-        } else if (lTf) {
-            if (soft) { if (fx) hipLaunchKernelGGL((dmpc_scan_kernel<true, float, true>), sgrid, sblock, lds0 * W, st, P); else hipLaunchKernelGGL((dmpc_scan_kernel<true, float, false>), sgrid, sblock, lds0 * W, st, P); }
-            else { if (fx) hipLaunchKernelGGL((dmpc_scan_kernel<false, float, true>), sgrid, sblock, lds0 * W, st, P); else hipLaunchKernelGGL((dmpc_scan_kernel<false, float, false>), sgrid, sblock, lds0 * W, st, P); }
-        } else {
-            if (soft) { if (fx) hipLaunchKernelGGL((dmpc_scan_kernel<true, double, true>), sgrid, sblock, lds0 * W, st, P); else hipLaunchKernelGGL((dmpc_scan_kernel<true, double, false>), sgrid, sblock, lds0 * W, st, P); }
-            else { if (fx) hipLaunchKernelGGL((dmpc_scan_kernel<false, double, true>), sgrid, sblock, lds0 * W, st, P); else hipLaunchKernelGGL((dmpc_scan_kernel<false, double, false>), sgrid, sblock, lds0 * W, st, P); }
-        }
-    }
-    if (P.gzero) ctx->grid_clean = true;   // (this scan launch leaves the cell grid's counters zero for the next step's grid_prep_kernel)
-    // heaviest-first launch order for the solve phase (key left by the scan in hdr[7]).  Tiny launches do not need it.
-    if (ctx->forced_n == S * c_count) P.order = ctx->forced_order.as<int>();   // development aid: externally supplied launch order
-    else if (run_order) {
-        // (slices: the kernel is a chain of dependent memory round trips per thread -- 8 workgroups of 1024 threads took 20 us for 51 200
-        // agents, six agents per thread one after the other; with one agent per thread 7 us: headline 52.3 -> 53.2 M solves/s)
-        const int total = S * c_count;
-        int nb = ctx->order_slices > 0 ? ctx->order_slices : (total >= 65536 ? 64 : (total >= 1024 ? total / 1024 : 1));
-        if ((total + nb - 1) / nb > 24576) nb = (total + 24575) / 24576;   // (a slice's keys live in LDS, 2 bytes each next to the histograms: at most 48 KB of them)
-        int *hint = nullptr;
-        if (ctx->order_hint) {   // the previous step's work estimates: valid while the batch keeps its shape
-            if (ctx->prev_cost.ensure((size_t)total * 4)) FAIL(ctx, "device allocation failed (order hint)");
-            // (the agents of the launch: which columns of how large a table -- a sub-range of another start or of another table is another set of agents)
-            const long shape = ((((long)S * 1000003L + (long)G * C) * 1000003L + c_first) * 1000003L + c_count) * 16L + (long)p.variant;
-            if (shape != ctx->prev_cost_shape) { HIPCHK(ctx, hipMemsetAsync(ctx->prev_cost.p, 0, (size_t)total * 4, st)); ctx->prev_cost_shape = shape; }
-            hint = ctx->prev_cost.as<int>();
-            P.cost_out = hint;
-        }
-        hipLaunchKernelGGL(order_kernel, dim3((unsigned)nb), dim3(1024), (size_t)((total + nb - 1) / nb) * 2, st, total, (const int *)P.hdr, ctx->order.as<int>(), ctx->counter.as<int>() + 3,
-                           hint, ctx->order_hint);
-        P.order = ctx->order.as<int>();
-        P.live_bound = ctx->counter.as<int>() + 3;
-    }
-    if (ctx->profile) HIPCHK(ctx, hipEventRecord(ev.t1, st));
-    // phase 1: persistent waves (one workgroup per CU, shared tables, agents claimed from a queue) when at least two
-    // waves fit next to the shared tables; otherwise one agent per workgroup
-    const size_t LDS_CU = 160 * 1024;
-    // Slack-free variants (round 4): split T -- HARD_TS columns of the inverse factor in every wave's block, the rest of the 48 in
-    // extensions that the waves of a workgroup take from a pool when an agent's working set outgrows them (dmpc_solve.hip) -- so that
-    // twelve waves (three per SIMD: what 168 registers per lane allow) share a CU's LDS instead of nine.
-    // Slack variants, 56-slot tier of large scenes (round 5): the same split with 48 own columns -- the eight columns beyond them (3.6 KB) come from
-    // the pool for the 2 % of the agents whose working set outgrows 48 slots -- so that SEVEN waves share a CU where five one-agent workgroups
-    // (30 KB each, their own copy of the tables) or six unsplit persistent waves did: the 10^4-agent scene is bound by its work per wave slot
-    // (four / five resident agents per CU: 1.03 / 0.88 ms, option lds_pad_kb).
-    const int tsplit_hard = (!soft && !ctx->no_split_t && !f32t) ? HARD_TS : 0;
-    int tsplit = tsplit_hard;
-    int n_ext = 0;
-    auto persist_waves = [&](int qcap, size_t &per) -> int {
-        tsplit = soft ? ((qcap == 56 && !ctx->no_split_t && !f32t) ? SOFT_TS : 0) : tsplit_hard;
-        per = solve_lds_bytes(P.nrmax, soft, qcap, true, tsplit, f32t);
-        int pw = (int)((LDS_CU - PERSIST_TABLE_BYTES) / per);
-#ifdef DMPC_DEV_PW   // development builds: fewer persistent waves per CU (how much does a long agent lose to the wave it shares a SIMD with?)
-        if (pw > DMPC_DEV_PW) pw = DMPC_DEV_PW;
-#endif
-        const int cap = soft ? 8 : ((tsplit || f32t) ? HARD_PW : 9);   // waves per workgroup the kernels are compiled for (launch bounds)
-        pw = pw > cap ? cap : pw;
-        if (tsplit) {   // the extensions need room too: at least a third as many as waves (3 % of the headline launch's agents need one, for 15 % of its iterations)
-            const size_t eb = (size_t)ext_doubles(qcap, tsplit) * 8;
-            for (;; --pw) {
-                n_ext = (int)((LDS_CU - PERSIST_TABLE_BYTES - EXT_PAD_BYTES - (size_t)pw * per) / eb);
-                if (n_ext > 31) n_ext = 31;
-                if (pw < 2 || 3 * n_ext >= pw) break;
-            }
-            if (ctx->ext_cap > 0 && n_ext > ctx->ext_cap) n_ext = ctx->ext_cap;
-        }
-        return pw;
-    };
-    // the working-set capacity is a template parameter of the solve kernels
-    auto launch_plain = [&](int qcap, size_t lds) {
-        if (!P.only_flagged) ctx->last_kernel = std::string("dmpc_solve_kernel<") + (soft ? "true, " : "false, ") + std::to_string(f32t ? (soft ? 64 : 48) : (soft ? qcap : 48)) + (f32t ? ", float>" : ", double>");
-        if (f32t) { if (soft) hipLaunchKernelGGL((dmpc_solve_kernel<true, 64, float>), grid, block, lds, st, P); else hipLaunchKernelGGL((dmpc_solve_kernel<false, 48, float>), grid, block, lds, st, P); }
-        else if (soft && qcap == 32) hipLaunchKernelGGL((dmpc_solve_kernel<true, 32>), grid, block, lds, st, P);
-        else if (soft && qcap == 48) hipLaunchKernelGGL((dmpc_solve_kernel<true, 48>), grid, block, lds, st, P);
-        else if (soft && qcap == 56) hipLaunchKernelGGL((dmpc_solve_kernel<true, 56>), grid, block, lds, st, P);
-        else if (soft) hipLaunchKernelGGL((dmpc_solve_kernel<true, 64>), grid, block, lds, st, P);
-        else hipLaunchKernelGGL((dmpc_solve_kernel<false, 48>), grid, block, lds, st, P);
-    };
-    auto launch_persist = [&](int qcap, dim3 g, dim3 b, size_t lds) {
-        if (!P.only_flagged) {
-            const int qc = f32t ? (soft ? 64 : 48) : (soft ? qcap : 48);
-            const int ts = f32t ? qc : (tsplit ? (soft ? SOFT_TS : HARD_TS) : qc);
-            ctx->last_kernel = std::string("dmpc_solve_persist_kernel<") + (soft ? "true, " : "false, ") + std::to_string(qc) + ", " + std::to_string(ts) + (f32t ? ", float>" : ", double>");
-        }
-        if (f32t) { if (soft) hipLaunchKernelGGL((dmpc_solve_persist_kernel<true, 64, 64, float>), g, b, lds, st, P); else hipLaunchKernelGGL((dmpc_solve_persist_kernel<false, 48, 48, float>), g, b, lds, st, P); }
-        else if (soft && qcap == 32) hipLaunchKernelGGL((dmpc_solve_persist_kernel<true, 32>), g, b, lds, st, P);
-        else if (soft && qcap == 48) hipLaunchKernelGGL((dmpc_solve_persist_kernel<true, 48>), g, b, lds, st, P);
-        else if (soft && qcap == 56 && tsplit) hipLaunchKernelGGL((dmpc_solve_persist_kernel<true, 56, SOFT_TS>), g, b, lds, st, P);
-        else if (soft && qcap == 56) hipLaunchKernelGGL((dmpc_solve_persist_kernel<true, 56>), g, b, lds, st, P);
-        else if (soft) hipLaunchKernelGGL((dmpc_solve_persist_kernel<true, 64>), g, b, lds, st, P);
-        else if (tsplit) hipLaunchKernelGGL((dmpc_solve_persist_kernel<false, 48, HARD_TS>), g, b, lds, st, P);
-        else hipLaunchKernelGGL((dmpc_solve_persist_kernel<false, 48>), g, b, lds, st, P);
-    };
-    auto solve_launch = [&](int qcap, size_t lds_plain, int tier, bool want_persist) -> int {
-        size_t per = 0;
-        const int pw = persist_waves(qcap, per);
-        const int total = S * c_count;
-        if (!want_persist || ctx->no_persist || pw < 2 || ctx->num_cu < 1) {
-            launch_plain(qcap, lds_plain);
-            return 0;
-        }
-        const size_t lds = PERSIST_TABLE_BYTES + (size_t)pw * per + (tsplit ? (size_t)n_ext * ext_doubles(qcap, tsplit) * 8 + EXT_PAD_BYTES : 0);
-        P.n_ext = tsplit ? n_ext : 0;
-        if ((int)lds > ctx->max_lds_persist) {
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_persist_kernel<true, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_persist_kernel<true, 48>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_persist_kernel<true, 56>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_persist_kernel<true, 56, SOFT_TS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_persist_kernel<true, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_persist_kernel<false, 48>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_persist_kernel<false, 48, HARD_TS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_persist_kernel<true, 64, 64, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)dmpc_solve_persist_kernel<false, 48, 48, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            ctx->max_lds_persist = (int)lds;
-        }
-        P.counter = ctx->static_queue ? nullptr : ctx->counter.as<int>() + tier;
-        P.lds_per_wave = (int)per;
-        int wgs = (total + pw - 1) / pw;
-        if (wgs > ctx->num_cu) wgs = ctx->num_cu;
-        // tickets of the queue's light bulk: single positions where a wave solves few, heavy agents (fewer than 12 per wave, or solveSoftDMPCall)
-        P.queue_chunk = ctx->queue_chunk > 0 ? ctx->queue_chunk : ((total < 12 * wgs * pw || ctx->prm.variant == DMPC_VAR_ALL3) ? 1 : 2);
-        launch_persist(qcap, dim3((unsigned)wgs), dim3((unsigned)(64 * pw)), lds);
-        return 0;
-    };
-    // Measured on C2 (hard, 100 agents/scene): persistent waves win once the launch is deep enough to be
-    // throughput-bound (+6 % at 102 400 agents: 8 instead of 7 resident agents per CU), while short launches are
-    // bound by their single slowest agent, which runs ~4 % faster in the leaner one-agent-per-workgroup kernel.
-    size_t per1 = 0, per2 = 0;
-    const int pw1 = persist_waves(q1, per1), pw2 = persist_waves(q2, per2);
-    const bool deep = !shallow && (big_soft || (long)S * c_count >= (heavy_agents ? 28L : 16L * (pw1 > 0 ? pw1 : 1)) * ctx->num_cu);
-    // tier 2 as persistent waves over the flagged list (nearly always empty: the launch then costs a few microseconds
-    // instead of one workgroup per agent just to find out that there is nothing to do)
-    const bool t2_list = two_tier && !tiny && !ctx->no_persist && pw2 >= 2 && ctx->num_cu >= 1;
-    if (reduced) {
-        // tier 0: the reduced solver over every agent of the launch (persistent waves, as many workgroups per CU as its registers allow); the agents it
-        // does not take -- more than 64 rows, a third active wall, more than five hard constraints -- go to the general solver with its full capacity
-        if (ctx->rsolve_blocks == 0) {
-            int nb = 0;
-            HIPCHK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)dmpc_rsolve_persist_kernel, RSOLVE_WAVES * 64, (size_t)RSOLVE_WAVES * RSOLVE_LDS_PER_WAVE));
-            ctx->rsolve_blocks = nb > 0 ? nb : 1;
-        }
-        const int total = S * c_count;
-        P.qcap = 0; P.only_flagged = 0; P.qover_bit = ST_QOVER;
-        if (P.post_on) P.live_bound = nullptr;   // fused post-step: the agents the scan finished are visited too (their part of the state advance and of the scene's verdict)
-        P.flag_count = ctx->counter.as<int>() + 2; P.flag_list = ctx->flag_list.as<int>();
-        P.counter = ctx->static_queue ? nullptr : ctx->counter.as<int>();
-        P.lds_per_wave = RSOLVE_LDS_PER_WAVE;
-        int wgs = (total + RSOLVE_WAVES - 1) / RSOLVE_WAVES;
-        if (wgs > ctx->rsolve_blocks * ctx->num_cu) wgs = ctx->rsolve_blocks * ctx->num_cu;
-        P.queue_chunk = ctx->queue_chunk > 0 ? ctx->queue_chunk : (total < 12 * wgs * RSOLVE_WAVES ? 1 : 2);
-        ctx->last_kernel = "dmpc_rsolve_persist_kernel";
-        hipLaunchKernelGGL(dmpc_rsolve_persist_kernel, dim3((unsigned)wgs), dim3(RSOLVE_WAVES * 64), (size_t)RSOLVE_WAVES * RSOLVE_LDS_PER_WAVE, st, P);
-        P.qcap = q2; P.only_flagged = 1; P.qover_bit = ST_CAPACITY;
-        const bool t2p = !ctx->no_persist && pw2 >= 2;   // persistent waves over the flagged list (nearly always empty); else one workgroup per agent, each looking at its agent's flag
-        P.order = t2p ? ctx->flag_list.as<int>() : nullptr; P.flag_list = nullptr; P.live_bound = nullptr;
-        if (solve_launch(q2, lds2, 1, t2p)) return -1;
-        HIPCHK(ctx, hipGetLastError());
-        if (ctx->profile) {
-            HIPCHK(ctx, hipEventRecord(ev.t2, st));
-            ctx->events.push_back(ev);
-        }
-        ctx->solves += (int64_t)S * c_count;
-        return 0;
-    }
-    if (t2_list) { P.flag_count = ctx->counter.as<int>() + 2; P.flag_list = ctx->flag_list.as<int>(); }
-    if (solve_launch(q1, lds1, 0, deep || ctx->force_persist)) return -1;
-    if (two_tier) {   // tier 2: only agents flagged ST_QOVER do any work
-        P.qcap = q2; P.only_flagged = 1; P.qover_bit = ST_CAPACITY;
-        if (t2_list) { P.order = ctx->flag_list.as<int>(); P.flag_list = nullptr; }
-        if (solve_launch(q2, lds2, 1, t2_list)) return -1;
-    }
-    HIPCHK(ctx, hipGetLastError());
-    if (ctx->profile) {
-        HIPCHK(ctx, hipEventRecord(ev.t2, st));
-        ctx->events.push_back(ev);
-    }
-    ctx->solves += (int64_t)S * c_count;
-    return 0;
-}
+#include "dmpc_launch.hip"   // plan_step, the five stages, launch_step
 
 // development aid (not part of the public header): trace the active-set iterations of one agent
 extern "C" int dmpc_debug_trace(dmpc_ctx *ctx, int agent, int cap, double *host_out)
@@ -1191,8 +720,12 @@ extern "C" int dmpc_step_device(dmpc_ctx *ctx, int S, int G, int C, int g_local,
     // mixed precision: the caller's table stays fp64; the scan reads an fp32 copy made here (half the bytes of the O(N) part)
     const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;
     if (mixed && table_f32(ctx, lT, ctx->lTf, (size_t)G * S * N3 * C, (hipStream_t)stream)) return -1;
-    return launch_step(ctx, S, G, C, g_local, 0, C, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out, lT_next, status, info,
-                       (hipStream_t)stream, nullptr, 0, mixed ? ctx->lTf.as<float>() : nullptr);
+    StepIO io;
+    io.lT = lT; io.x_p = x_p; io.x_v = x_v; io.x_a = x_a; io.pf = pf;
+    io.p_out = p_out; io.v_out = v_out; io.a_out = a_out; io.lT_next = lT_next; io.status = status; io.info = info;
+    io.lTf = mixed ? ctx->lTf.as<float>() : nullptr;
+    const StepShape sh{S, G, C, g_local, /*c_first*/ 0, /*c_count*/ C};
+    return launch_step(ctx, sh, io, (hipStream_t)stream);
 }
 
 // uncommanded vehicles: 1 <= N_cmd <= N (the shared argument check of the *_cmd entries)
@@ -1214,8 +747,12 @@ extern "C" int dmpc_step_device_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, cons
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;   // (the fp32 copy covers all N columns, the static ones included)
     if (mixed && table_f32(ctx, lT, ctx->lTf, (size_t)S * N3 * N, (hipStream_t)stream)) return -1;
-    return launch_step(ctx, S, 1, N, 0, 0, N_cmd, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out, lT_next, status, info,
-                       (hipStream_t)stream, nullptr, 0, mixed ? ctx->lTf.as<float>() : nullptr);
+    StepIO io;
+    io.lT = lT; io.x_p = x_p; io.x_v = x_v; io.x_a = x_a; io.pf = pf;
+    io.p_out = p_out; io.v_out = v_out; io.a_out = a_out; io.lT_next = lT_next; io.status = status; io.info = info;
+    io.lTf = mixed ? ctx->lTf.as<float>() : nullptr;
+    const StepShape sh{S, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ 0, /*c_count*/ N_cmd};
+    return launch_step(ctx, sh, io, (hipStream_t)stream);
 }
 
 extern "C" int dmpc_table_from_rows_device(dmpc_ctx *ctx, int S, int G, int C, const double *rows, double *lT, void *stream)
@@ -1290,11 +827,13 @@ static int step_batch_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
     if (dmpc_table_from_rows_device(ctx, S, 1, N, ctx->rows.as<double>(), ctx->lT.as<double>(), st)) return -1;
     const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;
     if (mixed && table_f32(ctx, ctx->lT.as<double>(), ctx->lTf, T * N3, st)) return -1;
-    if (launch_step(ctx, S, 1, N, 0, 0, N_cmd, ctx->lT.as<double>(), ctx->xp.as<double>(), ctx->xv.as<double>(),
-                    ctx->xa.as<double>(), ctx->pf.as<double>(), ctx->pout.as<double>(), ctx->vout.as<double>(),
-                    ctx->aout.as<double>(), nullptr, ctx->status.as<int32_t>(), ctx->info.as<int32_t>(), st, nullptr, 0,
-                    mixed ? ctx->lTf.as<float>() : nullptr))
-        return -1;
+    StepIO io;
+    io.lT = ctx->lT.as<double>(); io.x_p = ctx->xp.as<double>(); io.x_v = ctx->xv.as<double>(); io.x_a = ctx->xa.as<double>(); io.pf = ctx->pf.as<double>();
+    io.p_out = ctx->pout.as<double>(); io.v_out = ctx->vout.as<double>(); io.a_out = ctx->aout.as<double>();
+    io.status = ctx->status.as<int32_t>(); io.info = ctx->info.as<int32_t>();
+    io.lTf = mixed ? ctx->lTf.as<float>() : nullptr;
+    const StepShape sh{S, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ 0, /*c_count*/ N_cmd};
+    if (launch_step(ctx, sh, io, st)) return -1;
     HIPCHK(ctx, hipMemcpyAsync(p_out, ctx->pout.p, A * N3 * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(v_out, ctx->vout.p, A * N3 * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(a_out, ctx->aout.p, A * N3 * 8, hipMemcpyDeviceToHost, st));
@@ -1345,11 +884,13 @@ extern "C" int dmpc_solve_one(dmpc_ctx *ctx, int N, int n, const double *l, cons
     if (dmpc_table_from_rows_device(ctx, 1, 1, N, ctx->rows.as<double>(), ctx->lT.as<double>(), st)) return -1;
     const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;
     if (mixed && table_f32(ctx, ctx->lT.as<double>(), ctx->lTf, (size_t)N * N3, st)) return -1;
-    if (launch_step(ctx, 1, 1, N, 0, n, 1, ctx->lT.as<double>(), ctx->xp.as<double>(), ctx->xv.as<double>(),
-                    ctx->xa.as<double>(), ctx->pf.as<double>(), ctx->pout.as<double>(), ctx->vout.as<double>(),
-                    ctx->aout.as<double>(), nullptr, ctx->status.as<int32_t>(), ctx->info.as<int32_t>(), st, nullptr, 0,
-                    mixed ? ctx->lTf.as<float>() : nullptr))
-        return -1;
+    StepIO io;
+    io.lT = ctx->lT.as<double>(); io.x_p = ctx->xp.as<double>(); io.x_v = ctx->xv.as<double>(); io.x_a = ctx->xa.as<double>(); io.pf = ctx->pf.as<double>();
+    io.p_out = ctx->pout.as<double>(); io.v_out = ctx->vout.as<double>(); io.a_out = ctx->aout.as<double>();
+    io.status = ctx->status.as<int32_t>(); io.info = ctx->info.as<int32_t>();
+    io.lTf = mixed ? ctx->lTf.as<float>() : nullptr;
+    const StepShape sh{/*S*/ 1, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ n, /*c_count*/ 1};
+    if (launch_step(ctx, sh, io, st)) return -1;
     HIPCHK(ctx, hipMemcpyAsync(p, ctx->pout.p, N3 * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(v, ctx->vout.p, N3 * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(a, ctx->aout.p, N3 * 8, hipMemcpyDeviceToHost, st));
@@ -1548,10 +1089,13 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
         if (mixed && table_f32(ctx, cur, ctx->lTf, T * N3, st)) return -1;   // (all N columns, the static ones included)
         const PostStep post{K_T_max, k, error_tol, xp, xv, xa, ctx->hist_p.as<double>(), ctx->hist_v.as<double>(), ctx->hist_a.as<double>(),
                             ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>()};
-        if (launch_step(ctx, S, 1, N, 0, 0, N_cmd, cur, xp, xv, xa, ctx->pf.as<double>(), ctx->pout.as<double>(),
-                        ctx->vout.as<double>(), ctx->aout.as<double>(), nxt, ctx->status.as<int32_t>(), nullptr, st,
-                        ctx->scene_done.as<int>(), 0, mixed ? ctx->lTf.as<float>() : nullptr, &post))
-            return -1;
+        StepIO io;
+        io.lT = cur; io.x_p = xp; io.x_v = xv; io.x_a = xa; io.pf = ctx->pf.as<double>();
+        io.p_out = ctx->pout.as<double>(); io.v_out = ctx->vout.as<double>(); io.a_out = ctx->aout.as<double>(); io.lT_next = nxt;
+        io.status = ctx->status.as<int32_t>();
+        io.scene_done = ctx->scene_done.as<int>(); io.lTf = mixed ? ctx->lTf.as<float>() : nullptr; io.post = &post;
+        const StepShape sh{S, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ 0, /*c_count*/ N_cmd};
+        if (launch_step(ctx, sh, io, st)) return -1;
         // state advance + history column + scene verdict in one launch (unless the solve kernel did them: tiny launches)
         if (!ctx->post_fused)
         hipLaunchKernelGGL(post_step_kernel, dim3((unsigned)S), dim3(N_cmd >= 256 ? 256 : 128), 0, st, N_cmd, K_T_max, k, error_tol,
@@ -1585,12 +1129,10 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
 // development options of a context handed to a context it creates for itself (further parts of a split batch, the second group)
 static void copy_debug_options(dmpc_ctx *dst, const dmpc_ctx *src)
 {
-    static const char *names[] = {"no_fuse", "no_persist", "force_persist", "no_cull", "order_slices", "cull_min", "no_lpt", "crash_min", "crash_any", "no_fast_exit",
-                                  "pivot_explore", "iter_cap", "tier1_qcap", "static_queue", "queue_chunk", "no_split_t", "ext_cap", "nbr_grid", "f32_dep_exp", "grid_min", "no_level_check", "order_hint", "lds_pad_kb", "reduced_solver", "rsolve_cap", "no_level_skip", "prep_fuse"};
-    int dmpc_ctx::*fields[] = {&dmpc_ctx::no_fuse, &dmpc_ctx::no_persist, &dmpc_ctx::force_persist, &dmpc_ctx::no_cull, &dmpc_ctx::order_slices, &dmpc_ctx::cull_min,
-                               &dmpc_ctx::no_lpt, &dmpc_ctx::crash_min, &dmpc_ctx::crash_any, &dmpc_ctx::no_fast_exit, &dmpc_ctx::pivot_explore, &dmpc_ctx::iter_cap,
-                               &dmpc_ctx::tier1_env, &dmpc_ctx::static_queue, &dmpc_ctx::queue_chunk, &dmpc_ctx::no_split_t, &dmpc_ctx::ext_cap, &dmpc_ctx::nbr_grid, &dmpc_ctx::f32_dep_exp, &dmpc_ctx::grid_min, &dmpc_ctx::no_level_check, &dmpc_ctx::order_hint, &dmpc_ctx::lds_pad_kb, &dmpc_ctx::reduced_solver, &dmpc_ctx::rsolve_cap, &dmpc_ctx::no_level_skip, &dmpc_ctx::prep_fuse};
-    for (size_t i = 0; i < sizeof(names) / sizeof(names[0]); ++i) (void)dmpc_debug_option(dst, names[i], src->*(fields[i]));
+    for (const DevOptionEntry &t : dev_options)
+        if (t.inherited) dst->opt.*(t.member) = src->opt.*(t.member);   // (each member as its own value: grid_min_part too)
+    for (dmpc_ctx *pc : dst->peers) copy_debug_options(pc, src);
+    for (dmpc_ctx *ch : dst->children) copy_debug_options(ch, src);
 }
 
 // Batched transitions are bound, MPC step by MPC step, by the slowest agent of the whole batch while most of the GPU
@@ -1607,7 +1149,7 @@ static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
         // Batches of 64 or more scenes run as TWO groups side by side (a second set of rank contexts, threads and streams on the same
         // GPUs): scenes are independent, so while one half's ranks exchange their predictions (peer copies, barrier, events) the
         // other half's solve kernels keep the GPUs busy -- the per-step exchange is off the critical path.
-        const int gparts = ctx->no_split ? 1 : (ctx->split_parts > 0 ? (ctx->split_parts > 2 ? 2 : ctx->split_parts) : (S >= 64 ? 2 : 1));
+        const int gparts = ctx->opt.no_split ? 1 : (ctx->opt.split_parts > 0 ? (ctx->opt.split_parts > 2 ? 2 : ctx->opt.split_parts) : (S >= 64 ? 2 : 1));
         // fewer agents than twice the GPUs (the reference's small swarms on an 8-GPU node): the first GPU alone, as dmpc_step_batch does --
         // sharding N = 4 agents over 8 GPUs is impossible and over 2-3 of them nothing but barriers and peer copies
         if (N < 2 * ctx->grp->G) return transition_one(ctx, S, N, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
@@ -1618,8 +1160,8 @@ static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
             dmpc_ctx *other = dmpc_create(&ctx->prm, DMPC_DEVICE_ALL, ctx->precision);
             g_emulate_devices.store(keep);
             if (!other || !other->grp || other->grp->G != ctx->grp->G) { if (other) dmpc_destroy(other); FAIL(ctx, "dmpc_transition: second group: " + g_err); }
-            copy_debug_options(other, ctx);   // (and, through dmpc_debug_option, to its rank contexts)
-            other->no_split = 1;
+            copy_debug_options(other, ctx);   // (and to its rank contexts)
+            other->opt.no_split = 1;
             ctx->children.push_back(other);
         }
         dmpc_ctx *other = ctx->children[0];
@@ -1642,15 +1184,15 @@ static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
     }
     // parts: every part runs its own MPC loop on its own stream; launches of fewer than ~2000 agents are one-agent workgroups, which the
     // hardware interleaves across streams freely (persistent launches hold a CU's whole LDS), so many small parts overlap best
-    int parts = ctx->split_parts > 0 ? ctx->split_parts : (S >= 128 ? 4 : (S >= 32 ? 2 : 1));
+    int parts = ctx->opt.split_parts > 0 ? ctx->opt.split_parts : (S >= 128 ? 4 : (S >= 32 ? 2 : 1));
     if (parts > S) parts = S;
-    if (parts < 2 || ctx->no_split || ctx->grp || N < 1 || N_cmd < 1 || N_cmd > N || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status)
+    if (parts < 2 || ctx->opt.no_split || ctx->grp || N < 1 || N_cmd < 1 || N_cmd > N || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status)
         return transition_one(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
     while ((int)ctx->children.size() < parts - 1) {
         dmpc_ctx *ch = dmpc_create(&ctx->prm, ctx->device, ctx->precision);
         if (!ch) FAIL(ctx, "dmpc_transition: further context: " + g_err);
         copy_debug_options(ch, ctx);
-        ch->no_split = 1;
+        ch->opt.no_split = 1;
         ctx->children.push_back(ch);
     }
     for (int i = 0; i < parts - 1; ++i)

@@ -267,9 +267,12 @@ extern "C" int dmpc_step_sharded_device(dmpc_ctx *ctx, int S, int N, const doubl
     // mixed precision: the caller's tables are fp64 (and so is the payload of this entry point); the scan reads an fp32 copy
     const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;
     if (mixed && table_f32(ctx, lT, ctx->lTf, (size_t)G * chunk, st)) return -1;
-    if (launch_step(ctx, S, G, cmax, rank, 0, cnt, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out, ctx->sendbuf.as<double>(), status, info, st,
-                    nullptr, rem ? rem : 0, mixed ? ctx->lTf.as<float>() : nullptr))
-        return -1;
+    StepIO io;
+    io.lT = lT; io.x_p = x_p; io.x_v = x_v; io.x_a = x_a; io.pf = pf;
+    io.p_out = p_out; io.v_out = v_out; io.a_out = a_out; io.lT_next = ctx->sendbuf.as<double>(); io.status = status; io.info = info;
+    io.short_from = rem; io.lTf = mixed ? ctx->lTf.as<float>() : nullptr;
+    const StepShape sh{S, G, /*C*/ cmax, /*g_local*/ rank, /*c_first*/ 0, /*c_count*/ cnt};
+    if (launch_step(ctx, sh, io, st)) return -1;
     return exchange(ctx, ctx->sendbuf.p, lT_next, chunk, 8, nullptr, nullptr, 0, st);
 }
 
@@ -430,9 +433,13 @@ static int transition_sharded_impl(dmpc_ctx *ctx, int S, int N, const double *po
     int ndone = 0;
     const int chunk_steps = 8;   // the host looks at the per-step verdicts every 8 MPC steps
     for (int k = 1; k < K_T_max && ndone < S; ++k) {
-        if (launch_step(ctx, S, G, cmax, rank, 0, cnt, cur, xp, xv, xa, own_pf, ctx->pout.as<double>(), ctx->vout.as<double>(),
-                        ctx->aout.as<double>(), ctx->sendbuf.as<double>(), ctx->status.as<int32_t>(), nullptr, st, ctx->scene_done.as<int>(), rem,
-                        mixed ? curf : nullptr, nullptr, mixed ? own_cur : nullptr)) {
+        StepIO io;
+        io.lT = cur; io.x_p = xp; io.x_v = xv; io.x_a = xa; io.pf = own_pf;
+        io.p_out = ctx->pout.as<double>(); io.v_out = ctx->vout.as<double>(); io.a_out = ctx->aout.as<double>(); io.lT_next = ctx->sendbuf.as<double>();
+        io.status = ctx->status.as<int32_t>();
+        io.scene_done = ctx->scene_done.as<int>(); io.short_from = rem; io.lTf = mixed ? curf : nullptr; io.own_prev = mixed ? own_cur : nullptr;
+        const StepShape sh{S, G, /*C*/ cmax, /*g_local*/ rank, /*c_first*/ 0, /*c_count*/ cnt};
+        if (launch_step(ctx, sh, io, st)) {
             // a rank that cannot take its step must not leave the others waiting in the exchange: the group's barriers are released by
             // the abort flag, an RCCL communicator is aborted (the peers' collectives then return an error instead of hanging)
             if (ctx->grp) ctx->grp->abort.store(1);
@@ -568,9 +575,13 @@ static int group_step_batch(dmpc_ctx *root, int S, int N, const double *l, const
             HIPCHK(c, hipMemcpy2DAsync(dst[u], (size_t)cnt * 24, src[u] + (size_t)lo * 3, (size_t)N * 24, (size_t)cnt * 24, (size_t)S, hipMemcpyHostToDevice, st));
         const bool mixed = (c->precision & DMPC_PREC_MIXED) != 0;
         if (mixed && table_f32(c, c->lT.as<double>(), c->lTf, tab, st)) return -1;
-        if (launch_step(c, S, G, cmax, r, 0, cnt, c->lT.as<double>(), dst[0], dst[1], dst[2], dst[3], c->pout.as<double>(), c->vout.as<double>(),
-                        c->aout.as<double>(), nullptr, c->status.as<int32_t>(), c->info.as<int32_t>(), st, nullptr, rem, mixed ? c->lTf.as<float>() : nullptr))
-            return -1;
+        StepIO io;
+        io.lT = c->lT.as<double>(); io.x_p = dst[0]; io.x_v = dst[1]; io.x_a = dst[2]; io.pf = dst[3];
+        io.p_out = c->pout.as<double>(); io.v_out = c->vout.as<double>(); io.a_out = c->aout.as<double>();
+        io.status = c->status.as<int32_t>(); io.info = c->info.as<int32_t>();
+        io.short_from = rem; io.lTf = mixed ? c->lTf.as<float>() : nullptr;
+        const StepShape sh{S, G, /*C*/ cmax, /*g_local*/ r, /*c_first*/ 0, /*c_count*/ cnt};
+        if (launch_step(c, sh, io, st)) return -1;
         double *out[3] = {p_out, v_out, a_out};
         const double *dev[3] = {c->pout.as<double>(), c->vout.as<double>(), c->aout.as<double>()};
         for (int u = 0; u < 3; ++u)

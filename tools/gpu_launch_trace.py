@@ -1,0 +1,52 @@
+"""development: the launch sequence of one MPC step per case of tests/test_gpu_launch_plan.py, for a comparison of two builds of the library.
+
+  rocprofv3 --kernel-trace --output-format csv -d DIR_A -- python tools/gpu_launch_trace.py                                   (this build)
+  rocprofv3 --kernel-trace --output-format csv -d DIR_B -- python tools/with_lib.py OTHER.so tools/gpu_launch_trace.py        (another build)
+  python tools/gpu_launch_trace.py --compare DIR_A DIR_B
+
+The comparison is of the ordered lists of (kernel name, grid size, workgroup size, LDS bytes) per dispatch; it prints the first difference or
+"identical" and exits 0 / 1.  Every case is a host-pointer step of one context (dmpc_step_batch): no child context, no second group."""
+import csv
+import glob
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def dispatches(directory):
+    files = sorted(glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True))
+    if len(files) != 1:
+        sys.exit(f"{directory}: expected one *kernel_trace.csv, found {files}")
+    with open(files[0], newline="") as f:
+        rows = list(csv.DictReader(f))
+    rows.sort(key=lambda r: int(r["Dispatch_Id"]))
+    return [(r["Kernel_Name"], tuple(int(r[f"Grid_Size_{a}"]) for a in "XYZ") if "Grid_Size_X" in r else int(r["Grid_Size"]),
+             tuple(int(r[f"Workgroup_Size_{a}"]) for a in "XYZ") if "Workgroup_Size_X" in r else int(r["Workgroup_Size"]),
+             int(r["LDS_Block_Size"])) for r in rows]
+
+
+def compare(dir_a, dir_b):
+    a, b = dispatches(dir_a), dispatches(dir_b)
+    for i, (x, y) in enumerate(zip(a, b)):
+        if x != y:
+            print(f"dispatch {i} differs:\n  {dir_a}: {x}\n  {dir_b}: {y}")
+            return 1
+    if len(a) != len(b):
+        print(f"{len(a)} against {len(b)} dispatches; the first {min(len(a), len(b))} are equal")
+        return 1
+    print(f"identical: {len(a)} dispatches, {len(set(d[0] for d in a))} kernels")
+    return 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    import test_gpu_launch_plan as plan
+    c = plan.ncu()
+    for cid, variant, precision, shape, opts, _ in plan.CASES:
+        S, N = shape(c)
+        name, _ = plan.run_case(variant, precision, S, N, opts)
+        print(f"{cid}: S={S} N={N} {name}", flush=True)
