@@ -302,6 +302,38 @@ DMPC_API int dmpc_transition(dmpc_ctx *ctx, int S, int N, const double *po, cons
 DMPC_API int dmpc_transition_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
                         double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used, int32_t *scene_status);
 
+/* Scripted vehicles: uncommanded vehicles that MOVE along a path the caller knows (a piloted craft, a vehicle run by another planner).
+ * NO REFERENCE COUNTERPART: DMPC::solveParallelDMPCv2 freezes uncommanded vehicles at their start (dmpc/cpp/dmpc.cpp:1633-1649, what
+ * dmpc_transition_cmd does).  What the reference does define is one MPC step of a commanded agent against a table of N rows (cluster_solvev2,
+ * :1792-1841); the three entries below are that step applied to a table whose uncommanded rows are rewritten before every step -- the loop a
+ * caller of dmpc_step_batch_cmd could write on the host -- with everything dmpc_transition_cmd keeps on the device.  Additive: the ABI
+ * revision stays 8.
+ *   scene     N_cmd >= 1 commanded agents first, M >= 1 scripted vehicles behind them; the table has N = N_cmd + M columns.
+ *   path      [S][M][P][3], P >= 1: sample t of a vehicle is its position at history column t (column 0 = the start, the initDMPC column);
+ *             sample(j, t) = path[j][min(t, P-1)] -- a vehicle whose path has ended stays at its last sample.
+ *   alignment at the MPC step that produces history column k (k = 1 .. K_T_max-1), horizon entry kk = 0 .. K-1 of scripted vehicle j is
+ *             sample(j, k-1+kk): the window covers columns k-1 .. k+K-2, NOT k .. k+K-1.  A commanded neighbour's row has the same alignment
+ *             (it is the output of step k-1, whose first column is history column k-1; the first table starts at po, column 0), and the scan
+ *             compares the agent's own previous horizon with these rows column by column.
+ * Scripted vehicles are never solved, have no status and do not enter ReachedGoal or the scene verdict.
+ *
+ * dmpc_transition_scripted: dmpc_transition_cmd with moving uncommanded vehicles.  Host pointers.  po, pf: [S][N_cmd][3]; pk, vk, ak:
+ * [S][N_cmd][K_T_max][3] or all three NULL.  The path is uploaded once per call; before EVERY step (the first included) one launch writes the
+ * scripted columns of the current table from it (in mixed precision before the fp32 copy of the table is made).  Stopping rule, K_T_used,
+ * scene_status, histories, verdict read-back, batch split (each part gets its scenes' paths) and resident histories as for
+ * dmpc_transition_cmd; on a DMPC_DEVICE_ALL context the call runs on the first GPU (the rule for N_cmd < N); there is no RCCL form.
+ * With P == 1 the result is dmpc_transition_cmd on po = [po; path[:, :, 0]], byte for byte.
+ * M < 1, P < 1, N_cmd < 1, a NULL path or only some of pk / vk / ak: -1 and a message that starts with the entry's name, nothing launched. */
+DMPC_API int dmpc_transition_scripted(dmpc_ctx *ctx, int S, int N_cmd, int M, int P, const double *po, const double *pf, const double *path,
+                             int K_T_max, double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
+                             int32_t *scene_status);
+
+/* The same fill for device-resident callers that loop over dmpc_step_device_cmd: writes columns N_cmd .. N-1 of lT[S][3K][N] for MPC step
+ * k >= 1 (the step that produces history column k) from path_dev [S][N - N_cmd][P][3]; lTf non-NULL: also the same columns of an fp32 table
+ * of the same layout.  Device pointers, asynchronous on `stream`.  Call it on the table a step is about to READ, before that step. */
+DMPC_API int dmpc_scripted_cols_device(dmpc_ctx *ctx, int S, int N, int N_cmd, int P, const double *path_dev, int k, double *lT, float *lTf,
+                              void *stream);
+
 /* Multi-GPU: the agents of every scene sharded over the GPUs of one node, ONE PROCESS (rank) PER GPU, each with its own
  * context.  Replaces the thread clusters of DMPC::solveParallelDMPCv2 (dmpc/cpp/dmpc.cpp:1570-1686): contiguous agent ranges,
  * N/G each, the first N mod G one more (:1600-1625; dmpc_partition), every cluster reading the previous predictions of all
@@ -381,6 +413,21 @@ DMPC_API int dmpc_postcheck_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, int KT_a
                        double vmax, double amax, double Ts, double *r_factor, double *h_scaled, int32_t *n_samples,
                        double *min_dist, int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
                        double *min_dist_static, int32_t *violation_static);
+
+/* dmpc_postcheck after dmpc_transition_scripted (no reference counterpart, see there): the arguments of dmpc_postcheck_cmd with po_static
+ * replaced by path [S][N - N_cmd][P][3] and P, and the two static outputs by min_dist_scripted[S] / violation_scripted[S]; p_scripted
+ * (optional): [S][N - N_cmd][ns_alloc][3], the interpolated positions of the scripted vehicles (samples >= n_samples[s] are zero).
+ * All commanded-only outputs are dmpc_postcheck on the N_cmd histories, bit for bit.  A scripted vehicle's position at a 100 Hz sample is
+ * the same not-a-knot spline the commanded agents get, on THEIR knots: t_i = i h_scaled, i = 0 .. K_T_used-1, with values sample(j, i) --
+ * the path is a path over step indices and is rescaled in time with the fleet; short histories (K_T_used < 4) degenerate as the commanded
+ * spline does.  min_dist_scripted = the smallest |E1 (p_i(t) - q_j(t))| over commanded agents i, scripted vehicles j and samples t (the fp64
+ * expression of the static check), violation_scripted = min_dist_scripted < rmin - 0.05.  Scripted-scripted pairs are not examined.
+ * Requires 1 <= N_cmd < N, P >= 1 and a path; masked scenes report NaN / 0; any output may be NULL. */
+DMPC_API int dmpc_postcheck_scripted(dmpc_ctx *ctx, int S, int N, int N_cmd, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                            const double *pk, const double *vk, const double *ak, const double *pf, const double *path, int P,
+                            double vmax, double amax, double Ts, double *r_factor, double *h_scaled, int32_t *n_samples,
+                            double *min_dist, int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
+                            double *min_dist_scripted, int32_t *violation_scripted, double *p_scripted);
 
 /* f-3: dense collision rows behind the CollConstr / AddCollConstr helpers named in the north star.  All of them
  * compute, per neighbour j (E1 = diag(1,1,1/c), E2 = E1^order; the ORDER is the context's, dmpc_params.order: 2, or 4 on a context of an

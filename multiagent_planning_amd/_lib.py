@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "dmpc_transition_sharded", "dmpc_transition_sharded_gather", "dmpc_group_size", "dmpc_comm_size", "dmpc_abi_version", "dmpc_last_solve_kernel",
     "dmpc_max_deviation",
     "dmpc_step_batch_cmd", "dmpc_step_device_cmd", "dmpc_transition_cmd", "dmpc_postcheck_cmd",
+    "dmpc_transition_scripted", "dmpc_scripted_cols_device", "dmpc_postcheck_scripted",
 ]
 
 
@@ -122,6 +123,11 @@ def load():
     L.dmpc_transition_cmd.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, C.c_double, dp, dp, dp, ip, ip]
     L.dmpc_postcheck_cmd.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_double,
                                      dp, dp, ip, dp, ip, dp, dp, dp, C.c_int, dp, ip]
+    # scripted vehicles: uncommanded vehicles that follow a path (additive, still revision 8)
+    L.dmpc_transition_scripted.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, dp, C.c_int, C.c_double, dp, dp, dp, ip, ip]
+    L.dmpc_scripted_cols_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.dmpc_postcheck_scripted.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, dp, dp, C.c_int, C.c_double, C.c_double,
+                                          C.c_double, dp, dp, ip, dp, ip, dp, dp, dp, C.c_int, dp, ip, dp]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -191,6 +197,18 @@ def _n_cmd(lead_table, cmd, what):
     if n_cmd < 1 or n_cmd > N:
         raise DmpcError(f"{what}: pf has {n_cmd} agents, the table {N}: the commanded agents are the FIRST N_cmd <= N vehicles")
     return int(S), int(N), int(n_cmd), tuple(lead_cmd)
+
+
+def _path(path, lead_cmd, what):
+    """path [S,M,P,3] (or [M,P,3] next to unbatched po / pf) of the scripted vehicles -> (contiguous array, M, P); lead_cmd: leading shape
+    ([N_cmd] or [S,N_cmd]) of the commanded-sized arrays"""
+    path = _f(path)
+    if path.ndim != len(lead_cmd) + 2 or path.shape[-1] != 3 or tuple(path.shape[:-3]) != tuple(lead_cmd[:-1]):
+        raise DmpcError(f"{what}: path {tuple(path.shape)} does not batch like the commanded agents {tuple(lead_cmd)}: [S,M,P,3] (or [M,P,3])")
+    M, P = path.shape[-3], path.shape[-2]
+    if M < 1 or P < 1:
+        raise DmpcError(f"{what}: path {tuple(path.shape)} needs at least one vehicle and one sample")
+    return path, int(M), int(P)
 
 
 def model_matrices(h, K=K_HOR):
@@ -324,11 +342,28 @@ class Dmpc:
         k = min(int(nr[0]), max_rows)
         return dict(xi=xi[:k], rhs=rhs[:k], slack_coef=sc[:k], kc=kc[:k], nrows=int(nr[0]), viol_k=int(vk[0]), status=int(st[0]))
 
-    def transition(self, po, pf, K_T_max, error_tol=0.01, histories=True):
+    def transition(self, po, pf, K_T_max, error_tol=0.01, histories=True, path=None):
         """histories=False: pk/vk/ak are not downloaded (they stay on the device for postcheck()).
         pf with FEWER agents than po (N_cmd = pf's agents < N = po's, the reference's _pf.cols() / _po.cols(); dmpc_transition_cmd): the vehicles
-        behind the first N_cmd are not commanded and stay at po as static obstacles; histories, K_T_used and scene_status cover the commanded ones."""
+        behind the first N_cmd are not commanded and stay at po as static obstacles; histories, K_T_used and scene_status cover the commanded ones.
+        path [S,M,P,3] (or [M,P,3]; dmpc_transition_scripted): M scripted vehicles behind the commanded agents of po / pf (same agent count in
+        both), sample t of a path = the vehicle's position at history column t, held at its last sample once the path has ended."""
         po, pf = _f(po), _f(pf)
+        if path is not None:
+            if po.shape != pf.shape or po.ndim not in (2, 3) or po.shape[-1] != 3:
+                raise DmpcError(f"transition: with path, po {tuple(po.shape)} and pf {tuple(pf.shape)} must cover the same commanded agents")
+            shp = po.shape[:-1]
+            path, M, P = _path(path, shp, "transition")
+            S, n_cmd = (1, shp[0]) if len(shp) == 1 else shp
+            used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+            nul = C.POINTER(C.c_double)()
+            pk = vk = ak = None
+            if histories:
+                pk, vk, ak = (np.zeros(shp + (K_T_max, 3)) for _ in range(3))
+            self._chk(self._L.dmpc_transition_scripted(self._ctx, S, n_cmd, M, P, _dp(po), _dp(pf), _dp(path), int(K_T_max), float(error_tol),
+                                                       _dp(pk) if histories else nul, _dp(vk) if histories else nul, _dp(ak) if histories else nul,
+                                                       _ip(used), _ip(sst)))
+            return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst)
         S, N, n_cmd, shp = _n_cmd(po.shape[:-1], pf, "transition")
         used = np.zeros(S, dtype=np.int32)
         sst = np.zeros(S, dtype=np.int32)
@@ -390,11 +425,15 @@ class Dmpc:
         return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, lo=lo, count=cnt)
 
     def postcheck(self, K_T_used, pf, pk=None, vk=None, ak=None, KT_alloc=None, vmax=2.0, amax=1.0, Ts=0.01, interp=False,
-                  mask=None, po_static=None):
+                  mask=None, po_static=None, path=None):
         """failure_rate.m:136-195 for S scenes.  pk/vk/ak [S,N,KT_alloc,3] (or [N,KT,3]); None: use the histories the
         last transition() left on the device (then KT_alloc = its K_T_max).
         po_static [S,M,3] (or [M,3]): positions of M uncommanded vehicles (dmpc_postcheck_cmd; pf and the histories are the commanded
-        agents'): the result gains min_dist_static / violation_static, the commanded-against-static check; everything else is unchanged."""
+        agents'): the result gains min_dist_static / violation_static, the commanded-against-static check; everything else is unchanged.
+        path [S,M,P,3] (or [M,P,3]; dmpc_postcheck_scripted, not together with po_static): M scripted vehicles, splined on the commanded agents'
+        knots; the result gains min_dist_scripted / violation_scripted and, with interp, p_scripted [S,M,ns,3]."""
+        if path is not None and po_static is not None:
+            raise DmpcError("postcheck: path and po_static exclude each other (scripted vehicles move, static ones rest)")
         pf = _f(pf)
         shp = pf.shape[:-1]
         S, N = (1, shp[0]) if len(shp) == 1 else shp
@@ -412,6 +451,20 @@ class Dmpc:
             p_i = np.zeros((S, N, ns_alloc, 3))
         nul = C.POINTER(C.c_double)()
         msk = None if mask is None else np.ascontiguousarray(np.atleast_1d(mask), dtype=np.int32)
+        if path is not None:
+            path, M, P = _path(path, shp, "postcheck")
+            out["min_dist_scripted"], out["violation_scripted"] = np.zeros(S), np.zeros(S, dtype=np.int32)
+            p_s = np.zeros((S, M, ns_alloc, 3)) if p_i is not None else None
+            self._chk(self._L.dmpc_postcheck_scripted(self._ctx, S, N + M, N, int(KT_alloc), _ip(used),
+                                                      _ip(msk) if msk is not None else C.POINTER(C.c_int32)(), _dp(pk) if pk is not None else nul,
+                                                      _dp(vk) if pk is not None else nul, _dp(ak) if pk is not None else nul, _dp(pf), _dp(path), P,
+                                                      float(vmax), float(amax), float(Ts), _dp(out["r_factor"]), _dp(out["h_scaled"]),
+                                                      _ip(out["n_samples"]), _dp(out["min_dist"]), _ip(out["violation"]), _dp(out["totdist"]),
+                                                      _dp(out["traj_time"]), _dp(p_i) if p_i is not None else nul, ns_alloc,
+                                                      _dp(out["min_dist_scripted"]), _ip(out["violation_scripted"]), _dp(p_s) if p_s is not None else nul))
+            if p_i is not None:
+                out["p"], out["p_scripted"] = p_i, p_s
+            return out
         if po_static is not None:
             pos = _f(po_static)
             if pos.shape[:-2] != shp[:-1] or pos.shape[-1] != 3:
@@ -532,6 +585,11 @@ class Dmpc:
         """dmpc_step_device_cmd: the first n_cmd agents of a one-chunk table lT [S,45,N]; only columns < n_cmd of lT_next are written"""
         self._chk(self._L.dmpc_step_device_cmd(self._ctx, S, N, n_cmd, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out,
                                                lT_next or None, status, info or None, stream or None))
+
+    def scripted_cols_device(self, S, N, n_cmd, P, path, k, lT, lTf=0, stream=0):
+        """dmpc_scripted_cols_device: columns n_cmd .. N-1 of lT [S,45,N] (and of the fp32 table lTf, if given) for MPC step k >= 1 from the
+        device-resident path [S,N-n_cmd,P,3]: horizon entry kk of a vehicle = its sample min(k-1+kk, P-1)"""
+        self._chk(self._L.dmpc_scripted_cols_device(self._ctx, S, N, n_cmd, P, path, int(k), lT, lTf or None, stream or None))
 
     def step_device(self, S, G, Cn, g_local, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out, lT_next, status, info, stream=0):
         self._chk(self._L.dmpc_step_device(self._ctx, S, G, Cn, g_local, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out,

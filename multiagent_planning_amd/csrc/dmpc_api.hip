@@ -149,6 +149,8 @@ struct dmpc_ctx {
     DevBuf grid;             // cell grid of the neighbour lists (counts, starts, entries)
     DevBuf pc_p, pc_v, pc_a, pc_M, pc_w, pc_scene, pc_agent, pc_interp;   // post-check work buffers
     DevBuf pc_static;                                                      // post-check: positions of the uncommanded vehicles + their per-scene minimum
+    DevBuf path;                                                           // dmpc_transition_scripted: the scripted vehicles' paths [S][M][P][3], resident for the call
+    DevBuf pc_sc_path, pc_sc_y, pc_sc_M, pc_sc_w, pc_sc_pts, pc_sc_interp; // dmpc_postcheck_scripted: paths, knots, second derivatives, scratch, sample batch, p_scripted
     DevBuf pc_pts, pc_cell, pc_fill, pc_start, pc_sorted, pc_on;           // post-check, large scenes: cell grid of a batch of samples
     // multi-GPU (dmpc_multigpu.hip): RCCL communicator of this rank, exchange buffers
     void *comm = nullptr;
@@ -998,13 +1000,16 @@ extern "C" int dmpc_init_batch(dmpc_ctx *ctx, int S, int N, const double *po, co
 // the whole `for k = 1:K_T` loop on the device (dmpc_soft_bound.m:115-148, failure_rate.m:99-127) for the N_cmd commanded agents of N vehicles
 // (DMPC::solveParallelDMPCv2, dmpc.cpp:1570-1730: N = _po.cols(), N_cmd = _pf.cols()).  State, goals, outputs, histories, status and the
 // scene verdict are sized and strided by N_cmd (A agents); the tables and neighbour structures by N (T columns).  N_cmd == N: dmpc_transition.
+// path != null (dmpc_transition_scripted): the N - N_cmd vehicles behind the commanded ones follow path[S][N - N_cmd][P][3]; po is then
+// [S][N_cmd][3], and one launch before every step writes their columns of the current table (scripted_cols_kernel).
 static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
                           double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                          int32_t *scene_status)
+                          int32_t *scene_status, const double *path = nullptr, int P = 0)
 {
     if (!ctx) { g_err = "dmpc_transition: ctx is NULL"; return -1; }
     if (S < 1 || N < 1 || N_cmd < 1 || N_cmd > N || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status || ((pk || vk || ak) && !(pk && vk && ak)))
         FAIL(ctx, "dmpc_transition: bad arguments");
+    if (path && (P < 1 || N_cmd >= N)) FAIL(ctx, "dmpc_transition_scripted: bad arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t A = (size_t)S * N_cmd, T = (size_t)S * N;
     if (ensure_step_scratch(ctx, T, A)) return -1;
@@ -1014,7 +1019,12 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
         FAIL(ctx, "device allocation failed");
     hipStream_t st = ctx->stream;
     double *xp = ctx->xp.as<double>(), *xv = ctx->xv.as<double>(), *xa = ctx->xa.as<double>();
-    HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, po, T * 24, hipMemcpyHostToDevice, st));
+    const size_t path_bytes = path ? (T - A) * (size_t)P * 24 : 0;
+    if (path) {   // the paths go up once per call
+        if (ctx->path.ensure(path_bytes)) FAIL(ctx, "device allocation failed");
+        HIPCHK(ctx, hipMemcpyAsync(ctx->path.p, path, path_bytes, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, po, (path ? A : T) * 24, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, pf, A * 24, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemsetAsync(ctx->flags.p, 0, (size_t)K_T_max * S * 8, st));
     HIPCHK(ctx, hipMemsetAsync(ctx->scene_done.p, 0, (size_t)S * 4, st));
@@ -1022,7 +1032,7 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
     HIPCHK(ctx, hipMemsetAsync(ctx->hist_v.p, 0, hist, st));
     HIPCHK(ctx, hipMemsetAsync(ctx->hist_a.p, 0, hist, st));
     // k = 1: initDMPC (dmpc_soft_bound.m:117-121): state = (po, 0, 0), table = straight lines
-    if (N_cmd == N) HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
+    if (N_cmd == N || path) HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
     else HIPCHK(ctx, hipMemcpy2DAsync(xp, (size_t)N_cmd * 24, ctx->po.p, (size_t)N * 24, (size_t)N_cmd * 24, (size_t)S, hipMemcpyDeviceToDevice, st));   // the commanded agents' starts, packed
     HIPCHK(ctx, hipMemsetAsync(xv, 0, A * 24, st));
     HIPCHK(ctx, hipMemsetAsync(xa, 0, A * 24, st));
@@ -1036,8 +1046,10 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
         const size_t nc = A * N3, ns = (T - A) * N3;
         hipLaunchKernelGGL(cmd_cols_from_rows_kernel, dim3((unsigned)((nc + 255) / 256 > 4096 ? 4096 : (nc + 255) / 256)), dim3(256), 0, st, S, N, N_cmd,
                            (const double *)ctx->rows.as<double>(), ctx->lT.as<double>());
-        hipLaunchKernelGGL(static_cols_kernel, dim3((unsigned)((ns + 255) / 256 > 4096 ? 4096 : (ns + 255) / 256)), dim3(256), 0, st, S, N, N_cmd,
-                           (const double *)ctx->po.as<double>(), ctx->lT.as<double>(), ctx->lT2.as<double>());
+        if (!path) {   // (scripted vehicles: their columns are written before every step, the first included -- window k = 1 of the first table)
+            hipLaunchKernelGGL(static_cols_kernel, dim3((unsigned)((ns + 255) / 256 > 4096 ? 4096 : (ns + 255) / 256)), dim3(256), 0, st, S, N, N_cmd,
+                               (const double *)ctx->po.as<double>(), ctx->lT.as<double>(), ctx->lT2.as<double>());
+        }
     }
     const unsigned rb = (unsigned)((A * 3 + 255) / 256);
     hipLaunchKernelGGL(record_kernel, dim3(rb), dim3(256), 0, st, S, N_cmd, K_T_max, 0, xp, xv, xa, ctx->hist_p.as<double>(),
@@ -1085,7 +1097,12 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
         pend_k0 = -1;
         return 0;
     };
+    const size_t n_scr = (T - A) * N3;
+    const unsigned scr_blocks = (unsigned)((n_scr + 255) / 256 > 4096 ? 4096 : (n_scr + 255) / 256);
     for (int k = 1; k < K_T_max && ndone < S; ++k) {
+        if (path)   // the scripted columns of the current table: window k-1 .. k+K-2 of every path (before the fp32 copy, which then covers them)
+            hipLaunchKernelGGL(scripted_cols_kernel, dim3(scr_blocks), dim3(256), 0, st, S, N, N_cmd, P, k, (const double *)ctx->path.as<double>(), cur,
+                               (float *)nullptr);
         if (mixed && table_f32(ctx, cur, ctx->lTf, T * N3, st)) return -1;   // (all N columns, the static ones included)
         const PostStep post{K_T_max, k, error_tol, xp, xv, xa, ctx->hist_p.as<double>(), ctx->hist_v.as<double>(), ctx->hist_a.as<double>(),
                             ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>()};
@@ -1140,7 +1157,7 @@ static void copy_debug_options(dmpc_ctx *dst, const dmpc_ctx *src)
 // threads): the tail of one half overlaps the bulk of the other (512 transitions of 100 agents: 103 -> 60 ms).
 static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
                           double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                          int32_t *scene_status)
+                          int32_t *scene_status, const double *path = nullptr, int P = 0)
 {
     ctx->split_at.clear();
     // uncommanded vehicles on a DMPC_DEVICE_ALL context: the first GPU alone (the rule for N < 2 G below); the batch split further down applies unchanged
@@ -1187,7 +1204,7 @@ static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
     int parts = ctx->opt.split_parts > 0 ? ctx->opt.split_parts : (S >= 128 ? 4 : (S >= 32 ? 2 : 1));
     if (parts > S) parts = S;
     if (parts < 2 || ctx->opt.no_split || ctx->grp || N < 1 || N_cmd < 1 || N_cmd > N || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status)
-        return transition_one(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
+        return transition_one(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, P);
     while ((int)ctx->children.size() < parts - 1) {
         dmpc_ctx *ch = dmpc_create(&ctx->prm, ctx->device, ctx->precision);
         if (!ch) FAIL(ctx, "dmpc_transition: further context: " + g_err);
@@ -1204,9 +1221,10 @@ static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
     auto run = [&](int i) {
         dmpc_ctx *c = i ? ctx->children[(size_t)i - 1] : ctx;
         const int s0 = at[(size_t)i], sn = at[(size_t)i + 1] - s0;
-        const size_t t0 = (size_t)s0 * N, a0 = (size_t)s0 * N_cmd, h0 = a0 * (size_t)K_T_max * 3;   // po is strided by N, everything else by N_cmd
+        const size_t a0 = (size_t)s0 * N_cmd, h0 = a0 * (size_t)K_T_max * 3;   // po is strided by N, everything else by N_cmd ...
+        const size_t t0 = path ? a0 : (size_t)s0 * N;                          // ... (scripted vehicles: po covers the commanded agents, and each part gets its scenes' paths)
         rc[(size_t)i] = transition_one(c, sn, N, N_cmd, po + t0 * 3, pf + a0 * 3, K_T_max, error_tol, pk ? pk + h0 : nullptr, vk ? vk + h0 : nullptr,
-                                       ak ? ak + h0 : nullptr, K_T_used + s0, scene_status + s0);
+                                       ak ? ak + h0 : nullptr, K_T_used + s0, scene_status + s0, path ? path + (size_t)s0 * (N - N_cmd) * P * 3 : nullptr, P);
     };
     std::vector<std::thread> th;
     for (int i = 1; i < parts; ++i) th.emplace_back(run, i);
@@ -1239,6 +1257,49 @@ extern "C" int dmpc_transition_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, const
     return transition_any(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
 }
 
+// Scripted vehicles: the uncommanded vehicles of dmpc_transition_cmd MOVE along paths the caller knows.  No reference counterpart
+// (DMPC::solveParallelDMPCv2 freezes uncommanded vehicles, dmpc.cpp:1633-1649); a commanded agent sees such a column as it sees any neighbour.
+static int check_scripted(dmpc_ctx *ctx, const char *entry, int S, int N_cmd, int M, int P)
+{
+    if (S < 1) FAIL(ctx, std::string(entry) + ": S must be >= 1");
+    if (N_cmd < 1) FAIL(ctx, std::string(entry) + ": N_cmd must be >= 1 (commanded agents first, scripted vehicles behind them)");
+    if (M < 1) FAIL(ctx, std::string(entry) + ": M must be >= 1 (no scripted vehicle: use the entry without them)");
+    if (P < 1) FAIL(ctx, std::string(entry) + ": P must be >= 1 (every path has at least its start)");
+    if ((long)N_cmd + M > 0x7fffffffL) FAIL(ctx, std::string(entry) + ": N_cmd + M overflows");
+    return 0;
+}
+
+extern "C" int dmpc_transition_scripted(dmpc_ctx *ctx, int S, int N_cmd, int M, int P, const double *po, const double *pf, const double *path,
+                                        int K_T_max, double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
+                                        int32_t *scene_status)
+{
+    if (!ctx) { g_err = "dmpc_transition_scripted: ctx is NULL"; return -1; }
+    if (check_scripted(ctx, "dmpc_transition_scripted", S, N_cmd, M, P)) return -1;
+    if (!path) FAIL(ctx, "dmpc_transition_scripted: path is NULL");
+    if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, "dmpc_transition_scripted: pk, vk, ak must be all given or all NULL");
+    if (K_T_max < 2 || !po || !pf || !K_T_used || !scene_status) FAIL(ctx, "dmpc_transition_scripted: bad arguments");
+    // (a DMPC_DEVICE_ALL context: N_cmd < N, its first GPU)
+    return transition_any(ctx, S, N_cmd + M, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, P);
+}
+
+// the fill of dmpc_transition_scripted for callers that loop over dmpc_step_device_cmd themselves
+extern "C" int dmpc_scripted_cols_device(dmpc_ctx *ctx, int S, int N, int N_cmd, int P, const double *path_dev, int k, double *lT, float *lTf,
+                                         void *stream)
+{
+    if (!ctx) { g_err = "dmpc_scripted_cols_device: ctx is NULL"; return -1; }
+    if (check_cmd(ctx, "dmpc_scripted_cols_device", S, N, N_cmd)) return -1;
+    if (check_scripted(ctx, "dmpc_scripted_cols_device", S, N_cmd, N - N_cmd, P)) return -1;
+    if (k < 1) FAIL(ctx, "dmpc_scripted_cols_device: k must be >= 1 (the MPC step that produces history column k)");
+    if (!path_dev || !lT) FAIL(ctx, "dmpc_scripted_cols_device: NULL pointer");
+    if (ctx->grp) FAIL(ctx, "dmpc_scripted_cols_device: device pointers belong to ONE GPU; a DMPC_DEVICE_ALL context drives several (use the host-pointer entry points)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)S * (N - N_cmd) * N3;
+    hipLaunchKernelGGL(scripted_cols_kernel, dim3((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, S, N,
+                       N_cmd, P, k, path_dev, lT, lTf);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
 // post-checks of S finished transitions (failure_rate.m:136-195): rescale, 100 Hz not-a-knot spline, pairwise
 // ellipsoidal collision check, path length, trajectory time.  pk == NULL: use the histories dmpc_transition left
 // resident on the device (no PCIe round trip).
@@ -1247,7 +1308,10 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
                          double *r_factor, double *h_scaled, int32_t *n_samples, double *min_dist,
                          int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
                          int M = 0 /* uncommanded vehicles per scene */, const double *po_static = nullptr /* [S][M][3] */,
-                         double *min_dist_static = nullptr, int32_t *violation_static = nullptr)
+                         double *min_dist_static = nullptr, int32_t *violation_static = nullptr,
+                         // scripted vehicles (dmpc_postcheck_scripted): the M vehicles follow path[S][M][P][3] instead of resting at po_static; the two
+                         // outputs above are then the commanded-against-scripted ones, p_scripted [S][M][ns_alloc][3] the vehicles' interpolated positions
+                         const double *path = nullptr, int P = 0, double *p_scripted = nullptr)
 {
     if (!ctx) { g_err = "dmpc_postcheck: ctx is NULL"; return -1; }
     if (S < 1 || N < 1 || KT_alloc < 2 || !K_T_used || !pf || !(vmax > 0) || !(amax > 0) || !(Ts > 0))
@@ -1374,8 +1438,47 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
     hipLaunchKernelGGL(pc::pairdist_kernel, dim3((unsigned)((ns_max + PC_SAMPLES_PER_BLOCK - 1) / PC_SAMPLES_PER_BLOCK), (unsigned)S),
                        dim3(256), (size_t)N * 24, st, N, KT_alloc, (const int *)d_kt, (const double *)d_hs, (const int *)d_ns, Ts,
                        1.0 / ctx->prm.c, (const double *)dp, (const double *)ctx->pc_M.as<double>(), d_min, d_interp, ns_alloc);
+    // scripted vehicles: their splines on the commanded agents' knots, then every (commanded agent, scripted vehicle) pair per sample
+    const bool with_scripted = path && M > 0 && (min_dist_static || violation_static || p_scripted);
+    double *d_sc_interp = nullptr;
+    std::vector<double> mdsc(S, 0.0);
+    if (with_scripted) {
+        const size_t V = (size_t)S * M, knots = V * (size_t)KT_alloc * 24;
+        if (p_scripted && ns_alloc < 1) FAIL(ctx, "dmpc_postcheck_scripted: ns_alloc must be positive with p_scripted");
+        // samples per pass: at most 256 MB of scripted positions at a time
+        int SBs = (int)std::floor(256.0 * 1048576.0 / ((double)V * 24.0));
+        SBs = SBs < 1 ? 1 : (SBs > 4096 ? 4096 : SBs);
+        if (SBs > ns_max) SBs = ns_max > 0 ? ns_max : 1;
+        if (ctx->pc_sc_path.ensure(V * (size_t)P * 24 + (size_t)S * 8) || ctx->pc_sc_y.ensure(knots) || ctx->pc_sc_M.ensure(knots) || ctx->pc_sc_w.ensure(knots) ||
+            ctx->pc_sc_pts.ensure(V * (size_t)SBs * 24) || (p_scripted && ctx->pc_sc_interp.ensure(V * (size_t)ns_alloc * 24)))
+            FAIL(ctx, "device allocation failed (post-check, scripted vehicles)");
+        unsigned long long *d_min_sc = (unsigned long long *)(ctx->pc_sc_path.as<char>() + V * (size_t)P * 24);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_sc_path.p, path, V * (size_t)P * 24, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemsetAsync(d_min_sc, 0x7f, (size_t)S * 8, st));
+        if (p_scripted) {
+            d_sc_interp = ctx->pc_sc_interp.as<double>();
+            HIPCHK(ctx, hipMemsetAsync(d_sc_interp, 0, V * (size_t)ns_alloc * 24, st));
+        }
+        double *yk = ctx->pc_sc_y.as<double>(), *Mk = ctx->pc_sc_M.as<double>();
+        const size_t nk = V * (size_t)KT_alloc * 3;
+        hipLaunchKernelGGL(pc::scripted_knots_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, P, (const int *)d_kt,
+                           (const double *)ctx->pc_sc_path.as<double>(), yk);
+        hipLaunchKernelGGL(pc::spline_kernel, dim3((unsigned)((V * 3 + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, (const int *)d_kt, (const double *)d_hs,
+                           (const double *)yk, Mk, ctx->pc_sc_w.as<double>());
+        for (int smp0 = 0; smp0 < ns_max; smp0 += SBs) {
+            const int nb = ns_max - smp0 < SBs ? ns_max - smp0 : SBs;
+            hipLaunchKernelGGL(pc::scripted_eval_kernel, dim3((unsigned)((V * (size_t)SBs + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, (const int *)d_kt,
+                               (const double *)d_hs, (const int *)d_ns, Ts, smp0, SBs, (const double *)yk, (const double *)Mk, ctx->pc_sc_pts.as<double>(),
+                               d_sc_interp, ns_alloc);
+            hipLaunchKernelGGL(pc::scripted_pairs_kernel, dim3((unsigned)nb, (unsigned)S), dim3(256), 0, st, N, M, KT_alloc, (const int *)d_kt,
+                               (const double *)d_hs, (const int *)d_ns, Ts, smp0, SBs, 1.0 / ctx->prm.c, (const double *)dp,
+                               (const double *)ctx->pc_M.as<double>(), (const double *)ctx->pc_sc_pts.as<double>(), d_min_sc);
+        }
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(mdsc.data(), d_min_sc, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+    }
     // uncommanded vehicles: every (commanded agent, sample) against every static vehicle (all pairs, exact)
-    const bool with_static = M > 0 && (min_dist_static || violation_static);
+    const bool with_static = !path && M > 0 && (min_dist_static || violation_static);
     unsigned long long *d_min_st = nullptr;
     std::vector<double> mds(S, 0.0);
     if (with_static) {
@@ -1416,6 +1519,7 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
     HIPCHK(ctx, hipMemcpyAsync(tot.data(), d_tot, (size_t)S * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(tt.data(), d_tt, (size_t)S * 8, hipMemcpyDeviceToHost, st));
     if (p_interp) HIPCHK(ctx, hipMemcpyAsync(p_interp, d_interp, A * (size_t)ns_alloc * 24, hipMemcpyDeviceToHost, st));
+    if (d_sc_interp) HIPCHK(ctx, hipMemcpyAsync(p_scripted, d_sc_interp, (size_t)S * M * (size_t)ns_alloc * 24, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     for (int s = 0; s < S; ++s) {
         if (!kt[s]) {
@@ -1430,7 +1534,7 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
             if (violation_static) violation_static[s] = 0;
             continue;
         }
-        const double ds = with_static ? std::sqrt(mds[s]) : INFINITY;
+        const double ds = with_scripted ? std::sqrt(mdsc[s]) : with_static ? std::sqrt(mds[s]) : INFINITY;
         if (min_dist_static) min_dist_static[s] = ds;
         if (violation_static) violation_static[s] = ds < ctx->prm.rmin - 0.05;
         const double d = (N > 1) ? std::sqrt(md[s]) : INFINITY;
@@ -1450,12 +1554,13 @@ static int postcheck_any(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
                          const double *pk, const double *vk, const double *ak, const double *pf, double vmax, double amax, double Ts,
                          double *r_factor, double *h_scaled, int32_t *n_samples, double *min_dist,
                          int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
-                         int M, const double *po_static, double *min_dist_static, int32_t *violation_static)
+                         int M, const double *po_static, double *min_dist_static, int32_t *violation_static,
+                         const double *path = nullptr, int P = 0, double *p_scripted = nullptr)
 {
     const int parts = (int)ctx->split_at.size() - 1;
     if (pk || parts < 2 || ctx->split_at.back() != S || ctx->hist_S != S || (int)ctx->children.size() < parts - 1 || !K_T_used || !pf)
         return postcheck_one(ctx, S, N, KT_alloc, K_T_used, scene_mask, pk, vk, ak, pf, vmax, amax, Ts, r_factor, h_scaled, n_samples,
-                             min_dist, violation, totdist, traj_time, p_interp, ns_alloc, M, po_static, min_dist_static, violation_static);
+                             min_dist, violation, totdist, traj_time, p_interp, ns_alloc, M, po_static, min_dist_static, violation_static, path, P, p_scripted);
     // histories left resident by a split dmpc_transition: each part is checked where it lives, concurrently
     auto off = [&](auto *ptr, size_t o) { return ptr ? ptr + o : ptr; };
     std::vector<int> rc((size_t)parts, 0);
@@ -1469,7 +1574,8 @@ static int postcheck_any(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
                                       off(r_factor, (size_t)s0), off(h_scaled, (size_t)s0), off(n_samples, (size_t)s0), off(min_dist, (size_t)s0),
                                       off(violation, (size_t)s0), off(totdist, (size_t)s0), off(traj_time, (size_t)s0),
                                       off(p_interp, a0 * (size_t)ns_alloc * 3), ns_alloc, M, off(po_static, (size_t)s0 * M * 3),
-                                      off(min_dist_static, (size_t)s0), off(violation_static, (size_t)s0));
+                                      off(min_dist_static, (size_t)s0), off(violation_static, (size_t)s0), off(path, (size_t)s0 * M * P * 3), P,
+                                      off(p_scripted, (size_t)s0 * M * (size_t)ns_alloc * 3));
         c->hist_S = keep;
     };
     std::vector<std::thread> th;
@@ -1504,6 +1610,23 @@ extern "C" int dmpc_postcheck_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, int KT
     if (N_cmd < N && !po_static) FAIL(ctx, "dmpc_postcheck_cmd: po_static is NULL with N_cmd < N");
     return postcheck_any(ctx, S, N_cmd, KT_alloc, K_T_used, scene_mask, pk, vk, ak, pf, vmax, amax, Ts, r_factor, h_scaled, n_samples, min_dist,
                          violation, totdist, traj_time, p_interp, ns_alloc, N - N_cmd, po_static, min_dist_static, violation_static);
+}
+
+// the post-checks after dmpc_transition_scripted: the commanded-only outputs are dmpc_postcheck's; the scripted vehicles are splined on the
+// commanded agents' knots and every (commanded agent, scripted vehicle) pair is examined at every 100 Hz sample
+extern "C" int dmpc_postcheck_scripted(dmpc_ctx *ctx, int S, int N, int N_cmd, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                                       const double *pk, const double *vk, const double *ak, const double *pf, const double *path, int P,
+                                       double vmax, double amax, double Ts, double *r_factor, double *h_scaled, int32_t *n_samples,
+                                       double *min_dist, int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
+                                       double *min_dist_scripted, int32_t *violation_scripted, double *p_scripted)
+{
+    if (!ctx) { g_err = "dmpc_postcheck_scripted: ctx is NULL"; return -1; }
+    if (check_cmd(ctx, "dmpc_postcheck_scripted", S, N, N_cmd)) return -1;
+    if (check_scripted(ctx, "dmpc_postcheck_scripted", S, N_cmd, N - N_cmd, P)) return -1;
+    if (!path) FAIL(ctx, "dmpc_postcheck_scripted: path is NULL");
+    if (p_scripted && ns_alloc < 1) FAIL(ctx, "dmpc_postcheck_scripted: ns_alloc must be positive with p_scripted");
+    return postcheck_any(ctx, S, N_cmd, KT_alloc, K_T_used, scene_mask, pk, vk, ak, pf, vmax, amax, Ts, r_factor, h_scaled, n_samples, min_dist,
+                         violation, totdist, traj_time, p_interp, ns_alloc, N - N_cmd, nullptr, min_dist_scripted, violation_scripted, path, P, p_scripted);
 }
 
 

@@ -1880,6 +1880,29 @@ __global__ void static_cols_kernel(int S, int N, int N_cmd, const double *__rest
     }
 }
 
+// Scripted vehicles (columns N_cmd .. N-1 of a one-chunk table lT[S][3K][N]) for the MPC step that produces history column k (k >= 1):
+// horizon entry kk of vehicle j is sample(j, k-1+kk) = path[j][min(k-1+kk, P-1)] -- the window STARTS at column k-1, like a commanded
+// neighbour's row (the output of step k-1, whose first column is history column k-1); a path that has ended stays at its last sample.
+// Written into the CURRENT table before every step (the solve kernels only ever write the columns of the agents they solved); lTf
+// non-null: the same columns of the table's fp32 copy.  path: [S][M][P][3], M = N - N_cmd
+__global__ void scripted_cols_kernel(int S, int N, int N_cmd, int P, int k, const double *__restrict__ path, double *__restrict__ lT,
+                                     float *__restrict__ lTf)
+{
+    const int M = N - N_cmd;
+    const size_t total = (size_t)S * N3 * M;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const int m = (int)(t % M);   // t enumerates the destination: [s][j][c - N_cmd]
+        const size_t u = t / M;
+        const int j = (int)(u % N3), s = (int)(u / N3);
+        const long col = (long)k - 1 + j / 3;
+        const size_t smp = (size_t)(col < (long)P - 1 ? col : (long)P - 1);
+        const double v = path[(((size_t)s * M + m) * P + smp) * 3 + j % 3];
+        const size_t o = ((size_t)s * N3 + j) * N + N_cmd + m;
+        lT[o] = v;
+        if (lTf) lTf[o] = (float)v;
+    }
+}
+
 // rows[S][N_cmd][3K] of the commanded agents -> columns 0 .. N_cmd-1 of the one-chunk table lT[S][3K][N]
 __global__ void cmd_cols_from_rows_kernel(int S, int N, int N_cmd, const double *__restrict__ rows, double *__restrict__ lT)
 {

@@ -359,6 +359,78 @@ __global__ void static_pairs_kernel(int N, int M, int KTa, const int *__restrict
     if (threadIdx.x == 0 && m < INFINITY) atomicMin(&mind2[s], (unsigned long long)__double_as_longlong(m));
 }
 
+// Scripted vehicles (dmpc_postcheck_scripted): a vehicle that follows a path over step indices gets the spline the commanded agents get, on
+// their time base -- knots t_i = i h_scaled, i = 0 .. K_T_used-1, values sample(j, i) = path[j][min(i, P-1)] (spline_kernel above makes the
+// second derivatives of these knots, short histories included).  thread per knot component; yk: [S][M][KTa][3]; path: [S][M][P][3]
+__global__ void scripted_knots_kernel(int S, int M, int KTa, int P, const int *__restrict__ kt_used, const double *__restrict__ path,
+                                      double *__restrict__ yk)
+{
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (size_t)S * M * KTa * 3) return;
+    const int ax = (int)(g % 3);
+    const int i = (int)((g / 3) % KTa);
+    const size_t sj = g / ((size_t)3 * KTa);
+    const int s = (int)(sj / M);
+    yk[g] = i < kt_used[s] ? path[(sj * P + (i < P - 1 ? i : P - 1)) * 3 + ax] : 0.0;
+}
+
+// thread per (scene, sample of the batch, scripted vehicle): q(t) of the batch's samples smp0 .. smp0+SB-1 -> pts[S][SB][M][3] (what the pair
+// search below reads) and, optionally, p_scripted[S][M][ns_alloc][3]
+__global__ void scripted_eval_kernel(int S, int M, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs,
+                                     const int *__restrict__ ns, double Ts, int smp0, int SB, const double *__restrict__ yk,
+                                     const double *__restrict__ Mk, double *__restrict__ pts, double *__restrict__ p_scripted, int ns_alloc)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)S * SB * M) return;
+    const int j = (int)(t % M);
+    const int b = (int)((t / M) % SB), s = (int)(t / ((size_t)M * SB));
+    const int smp = smp0 + b;
+    if (smp >= ns[s]) return;
+    const int n = kt_used[s];
+    const double h = hs[s], tt = smp * Ts;
+    const size_t o = ((size_t)s * M + j) * (size_t)KTa * 3;
+    const double x = spline_eval2(yk, Mk, o, n, h, tt), yv = spline_eval2(yk, Mk, o + 1, n, h, tt), z = spline_eval2(yk, Mk, o + 2, n, h, tt);
+    pts[3 * t] = x; pts[3 * t + 1] = yv; pts[3 * t + 2] = z;
+    if (p_scripted && smp < ns_alloc) {
+        double *d = p_scripted + (((size_t)s * M + j) * ns_alloc + smp) * 3;
+        d[0] = x; d[1] = yv; d[2] = z;
+    }
+}
+
+// every commanded agent against every scripted vehicle at one sample, all pairs, exact: block = (sample of the batch, scene).  The commanded
+// agents' spline positions at the sample are staged in LDS in tiles of 256 (evaluated once each); the pairs (agent of the tile, vehicle) are
+// strided over the threads with the vehicle index fastest, so the reads of pts are coalesced.  The distance is pair_d2, the expression of
+// static_pairs_kernel, commanded agent first.
+__global__ void scripted_pairs_kernel(int N, int M, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs,
+                                      const int *__restrict__ ns, double Ts, int smp0, int SB, double cinv, const double *__restrict__ y,
+                                      const double *__restrict__ Msp, const double *__restrict__ pts, unsigned long long *__restrict__ mind2)
+{
+    __shared__ double tile[256 * 3];
+    __shared__ double sh[256];
+    const int s = blockIdx.y, b = blockIdx.x, n = kt_used[s], smp = smp0 + b;
+    if (n < 2 || smp >= ns[s]) return;   // masked scene, or a sample beyond the end of this scene's transition (uniform per block)
+    const double h = hs[s], t = smp * Ts;
+    const double *q = pts + ((size_t)s * SB + b) * (size_t)M * 3;
+    double m = INFINITY;
+    for (int i0 = 0; i0 < N; i0 += 256) {
+        const int cnti = N - i0 < 256 ? N - i0 : 256;
+        __syncthreads();
+        if ((int)threadIdx.x < cnti) {
+            const size_t o = ((size_t)s * N + i0 + threadIdx.x) * (size_t)KTa * 3;
+            tile[3 * threadIdx.x] = spline_eval2(y, Msp, o, n, h, t);
+            tile[3 * threadIdx.x + 1] = spline_eval2(y, Msp, o + 1, n, h, t);
+            tile[3 * threadIdx.x + 2] = spline_eval2(y, Msp, o + 2, n, h, t);
+        }
+        __syncthreads();
+        for (size_t e = threadIdx.x; e < (size_t)cnti * M; e += 256) {
+            const int ii = (int)(e / M), j = (int)(e - (size_t)ii * M);
+            m = fmin(m, pair_d2(tile[3 * ii], tile[3 * ii + 1], tile[3 * ii + 2], q[3 * j], q[3 * j + 1], q[3 * j + 2], cinv));
+        }
+    }
+    m = block_min(m, sh);
+    if (threadIdx.x == 0 && m < INFINITY) atomicMin(&mind2[s], (unsigned long long)__double_as_longlong(m));
+}
+
 // per agent: path length sum |p(t_{s+1}) - p(t_s)| (failure_rate.m:183) and the 1-based index after the last
 // sample farther than 5 cm from the goal (failure_rate.m:186-193)
 __global__ void path_kernel(int S, int N, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs,

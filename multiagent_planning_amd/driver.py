@@ -56,27 +56,34 @@ def chunked_to_rows(lT, N=None):
     return np.ascontiguousarray(np.concatenate([lT[g, :, :, :hi - lo].transpose(0, 2, 1) for g, (lo, hi) in enumerate(partition(N, G))], axis=1))
 
 
-def run_transition(dmpc, po, pf, K_T_max, error_tol=0.01):
+def run_transition(dmpc, po, pf, K_T_max, error_tol=0.01, path=None):
     """Whole transitions of S scenes on one device. Returns dict(pk,vk,ak,K_T_used,scene_status).
-    pf with fewer agents than po: the vehicles behind the first N_cmd are uncommanded static obstacles (Dmpc.transition)."""
-    return dmpc.transition(po, pf, K_T_max, error_tol)
+    pf with fewer agents than po: the vehicles behind the first N_cmd are uncommanded static obstacles (Dmpc.transition).
+    path [S,M,P,3]: M scripted vehicles that follow their paths behind the commanded agents of po / pf (dmpc_transition_scripted)."""
+    return dmpc.transition(po, pf, K_T_max, error_tol, path=path)
 
 
-def run_trial(dmpc, po, pf, K_T_max, error_tol=0.01, vmax=2.0, amax=1.0, Ts=0.01, histories=True):
+def run_trial(dmpc, po, pf, K_T_max, error_tol=0.01, vmax=2.0, amax=1.0, Ts=0.01, histories=True, path=None):
     """One trial of the reference's test scripts for S scenes (test/failure_rate.m:99-197): the transition loop,
     then -- for scenes that stayed feasible and reached their goals -- the post-checks, which read the histories
     the transition left on the device.  `success` is failure_rate.m:196
-    (`feasible && ~failed_goal && ~violation`); t/totdist/traj_time are NaN for failed scenes (:197-201)."""
-    tr = dmpc.transition(po, pf, K_T_max, error_tol, histories=histories)   # histories=False: outcomes only, nothing big comes back
+    (`feasible && ~failed_goal && ~violation`); t/totdist/traj_time are NaN for failed scenes (:197-201).
+    path [S,M,P,3]: scripted vehicles (Dmpc.transition); the result gains min_dist_scripted / violation_scripted of the post-check (NaN / 0 for
+    scenes that were not checked) -- `success` stays the reference's, over the commanded agents."""
+    tr = dmpc.transition(po, pf, K_T_max, error_tol, histories=histories, path=path)   # histories=False: outcomes only, nothing big comes back
     S = tr["K_T_used"].shape[0]
     st = tr["scene_status"]
     feasible = (st & ~ST_REACHED) == ST_SOLVED                 # no agent failed before the scene stopped
     reached = feasible & ((st & ST_REACHED) != 0)              # ReachedGoal.m, evaluated on the device every step
     out = dict(tr, feasible=feasible, failed_goal=feasible & ~reached, violation=np.zeros(S, dtype=np.int32),
                totdist=np.full(S, np.nan), traj_time=np.full(S, np.nan), r_factor=np.full(S, np.nan))
+    keys = ("violation", "totdist", "traj_time", "r_factor")
+    if path is not None:
+        out.update(min_dist_scripted=np.full(S, np.nan), violation_scripted=np.zeros(S, dtype=np.int32))
+        keys += ("min_dist_scripted", "violation_scripted")
     if reached.any():
-        pc = dmpc.postcheck(tr["K_T_used"], pf, KT_alloc=K_T_max, vmax=vmax, amax=amax, Ts=Ts, mask=reached)
-        for k in ("violation", "totdist", "traj_time", "r_factor"):
+        pc = dmpc.postcheck(tr["K_T_used"], pf, KT_alloc=K_T_max, vmax=vmax, amax=amax, Ts=Ts, mask=reached, path=path)
+        for k in keys:
             out[k] = pc[k]
     out["success"] = feasible & reached & (out["violation"] == 0)
     return out
