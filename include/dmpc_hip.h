@@ -429,6 +429,32 @@ DMPC_API int dmpc_postcheck_scripted(dmpc_ctx *ctx, int S, int N, int N_cmd, int
                             double *min_dist, int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
                             double *min_dist_scripted, int32_t *violation_scripted, double *p_scripted);
 
+/* Clearance report (no reference counterpart; additive, the ABI revision stays 8): WHICH agent came closest to WHICH vehicle, and WHEN -- what
+ * min_dist / violation of the three post-checks above reduce to one number per scene.  Same rescale, same not-a-knot spline, same 100 Hz samples
+ * and the same fp64 distance expression; the scripted vehicles of `path` are splined as dmpc_postcheck_scripted does.  Every commanded agent
+ * i < N_cmd gets two slots:
+ *   slot 0  its nearest commanded partner j != i, j < N_cmd
+ *   slot 1  its nearest uncommanded vehicle N_cmd <= j < N: at rest at po_static [S][N-N_cmd][3], or scripted along path [S][N-N_cmd][P][3]
+ *           (one of the two, never both; both may be NULL when N_cmd == N)
+ * and per slot, in arrays [S][N_cmd][2] (any of them may be NULL):
+ *   clear_dist     the smallest |E1 (p_i(t) - p_j(t))| over all samples t < n_samples[s] and all j of the slot's kind
+ *   clear_partner  that j, 0-based in the numbering of the table (0 .. N-1)
+ *   clear_sample   the 0-based sample; the time is clear_sample * Ts
+ * Ties go to the smallest sample, then the smallest partner; the result does not depend on the batch size S, the launch geometry or the order
+ * in which the device visits pairs.  Hence min_i clear_dist[s][i][0] == min_dist[s] of dmpc_postcheck, and min_i clear_dist[s][i][1] ==
+ * min_dist_static[s] / min_dist_scripted[s], bit for bit.
+ * reach (> 0, +inf allowed): a distance in the metric of the check that bounds the search.  A slot whose distance is < reach is exact; a slot
+ * with nothing inside reach reports +inf / -1 / -1 (so does slot 1 when N_cmd == N, and slot 0 of an only agent).  With reach = +inf every
+ * slot is exact and tables of more than 256 vehicles are searched all-pairs; a finite reach lets them use the cell grid of dmpc_postcheck with
+ * cells at least reach wide.  Masked scenes report NaN / -1 / -1 in both slots, whatever N_cmd is.
+ * pk, vk, ak: [S][N_cmd][KT_alloc][3] or all three NULL (the resident histories, with dmpc_postcheck's rule on a DMPC_DEVICE_ALL context).
+ * po_static together with path, N_cmd < N with neither, reach <= 0 or NaN, only some of pk / vk / ak, P < 1 with a path: -1 and a message
+ * that starts with the entry's name, nothing launched.  Static-static and scripted-scripted pairs are not examined. */
+DMPC_API int dmpc_postcheck_clearance(dmpc_ctx *ctx, int S, int N, int N_cmd, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                             const double *pk, const double *vk, const double *ak, const double *po_static, const double *path, int P,
+                             double vmax, double amax, double Ts, double reach, double *clear_dist, int32_t *clear_partner,
+                             int32_t *clear_sample);
+
 /* f-3: dense collision rows behind the CollConstr / AddCollConstr helpers named in the north star.  All of them
  * compute, per neighbour j (E1 = diag(1,1,1/c), E2 = E1^order; the ORDER is the context's, dmpc_params.order: 2, or 4 on a context of an
  * all-neighbour variant -- the helpers are generic in it, CollConstrSoftDMPC.m:16-21, and test/comp_test_ellipconstr.m:158 sets 4):

@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "dmpc_max_deviation",
     "dmpc_step_batch_cmd", "dmpc_step_device_cmd", "dmpc_transition_cmd", "dmpc_postcheck_cmd",
     "dmpc_transition_scripted", "dmpc_scripted_cols_device", "dmpc_postcheck_scripted",
+    "dmpc_postcheck_clearance",
 ]
 
 
@@ -128,6 +129,9 @@ def load():
     L.dmpc_scripted_cols_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
     L.dmpc_postcheck_scripted.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, dp, dp, C.c_int, C.c_double, C.c_double,
                                           C.c_double, dp, dp, ip, dp, ip, dp, dp, dp, C.c_int, dp, ip, dp]
+    # clearance report: nearest vehicle, and when, per agent (additive, still revision 8)
+    L.dmpc_postcheck_clearance.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, dp, dp, C.c_int, C.c_double, C.c_double,
+                                           C.c_double, C.c_double, dp, ip, ip]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -490,6 +494,40 @@ class Dmpc:
         if p_i is not None:
             out["p"] = p_i
         return out
+
+    def clearance(self, K_T_used, pf, pk=None, vk=None, ak=None, KT_alloc=None, vmax=2.0, amax=1.0, Ts=0.01, mask=None, po_static=None,
+                  path=None, reach=np.inf):
+        """dmpc_postcheck_clearance: per commanded agent the nearest commanded partner (slot 0) and the nearest uncommanded vehicle (slot 1) over
+        the 100 Hz samples of postcheck(), and when.  The leading arguments are postcheck()'s (pf gives the shape only).  Returns
+        dict(dist [S,N_cmd,2], partner (0-based in the table: commanded agents first), sample, time = sample * Ts, NaN where there is no sample).
+        reach: slots with a distance < reach are exact, the others report inf / -1 / -1 (inf: all exact); masked scenes NaN / -1 / -1."""
+        if path is not None and po_static is not None:
+            raise DmpcError("clearance: path and po_static exclude each other (scripted vehicles move, static ones rest)")
+        shp = np.shape(pf)[:-1]
+        S, N = (1, shp[0]) if len(shp) == 1 else shp
+        used = np.ascontiguousarray(np.atleast_1d(K_T_used), dtype=np.int32)
+        if pk is not None:
+            pk, vk, ak = _f(pk), _f(vk), _f(ak)
+            KT_alloc = pk.shape[-2]
+        assert KT_alloc is not None
+        nul = C.POINTER(C.c_double)()
+        msk = None if mask is None else np.ascontiguousarray(np.atleast_1d(mask), dtype=np.int32)
+        M, P, pos = 0, 0, None
+        if path is not None:
+            path, M, P = _path(path, shp, "clearance")
+        elif po_static is not None:
+            pos = _f(po_static)
+            if pos.shape[:-2] != tuple(shp[:-1]) or pos.shape[-1] != 3:
+                raise DmpcError(f"clearance: po_static {pos.shape} does not batch like pf {np.shape(pf)}")
+            M = pos.shape[-2]
+        dist = np.zeros((S, N, 2))
+        partner, sample = np.zeros((S, N, 2), dtype=np.int32), np.zeros((S, N, 2), dtype=np.int32)
+        self._chk(self._L.dmpc_postcheck_clearance(self._ctx, S, N + M, N, int(KT_alloc), _ip(used),
+                                                   _ip(msk) if msk is not None else C.POINTER(C.c_int32)(), _dp(pk) if pk is not None else nul,
+                                                   _dp(vk) if pk is not None else nul, _dp(ak) if pk is not None else nul,
+                                                   _dp(pos) if pos is not None and M else nul, _dp(path) if path is not None else nul, P,
+                                                   float(vmax), float(amax), float(Ts), float(reach), _dp(dist), _ip(partner), _ip(sample)))
+        return dict(dist=dist, partner=partner, sample=sample, time=np.where(sample >= 0, sample * float(Ts), np.nan))
 
     # ---- standalone small helpers (propStatedmpc.m, propState.m, is_inbounds.m, ReachedGoal.m) -----------
     def prop_state(self, A_p, A_v, a, A_initp=None, po=None, vo=None, off_p=None, off_v=None):

@@ -112,6 +112,7 @@ struct DevOptions {
     int ext_cap = 0;         // development option ext_cap (tests): at most this many T extensions per workgroup (1: every agent that needs one waits for the same slot)
     int queue_chunk = 0;     // development option queue_chunk: positions per ticket of the persistent queue's light bulk (0: chosen per launch)
     int static_queue = 0;    // development option static_queue: persistent waves take queue positions round-robin instead of by ticket
+    int clear_chunk = 8;     // development option clear_chunk: 100 Hz samples per workgroup of the clearance searches (dmpc_postcheck_clearance; tests)
 };
 
 struct dmpc_ctx {
@@ -152,6 +153,7 @@ struct dmpc_ctx {
     DevBuf path;                                                           // dmpc_transition_scripted: the scripted vehicles' paths [S][M][P][3], resident for the call
     DevBuf pc_sc_path, pc_sc_y, pc_sc_M, pc_sc_w, pc_sc_pts, pc_sc_interp; // dmpc_postcheck_scripted: paths, knots, second derivatives, scratch, sample batch, p_scripted
     DevBuf pc_pts, pc_cell, pc_fill, pc_start, pc_sorted, pc_on;           // post-check, large scenes: cell grid of a batch of samples
+    DevBuf pc_cl_part, pc_cl_run, pc_cl_out;                               // dmpc_postcheck_clearance: partials of a sample batch, running best, report
     // multi-GPU (dmpc_multigpu.hip): RCCL communicator of this rank, exchange buffers
     void *comm = nullptr;
     int nranks = 1, rank = 0;
@@ -429,7 +431,7 @@ static const DevOptionEntry dev_options[] = {
     {"no_level_skip", &DevOptions::no_level_skip, true}, {"prep_fuse", &DevOptions::prep_fuse, true}, {"static_queue", &DevOptions::static_queue, true}, {"queue_chunk", &DevOptions::queue_chunk, true},
     {"no_split_t", &DevOptions::no_split_t, true}, {"ext_cap", &DevOptions::ext_cap, true}, {"nbr_grid", &DevOptions::nbr_grid, true}, {"f32_dep_exp", &DevOptions::f32_dep_exp, true},
     {"grid_min", &DevOptions::grid_min, true}, {"grid_min_part", &DevOptions::grid_min_part, true}, {"no_level_check", &DevOptions::no_level_check, true}, {"lds_pad_kb", &DevOptions::lds_pad_kb, true},
-    {"reduced_solver", &DevOptions::reduced_solver, true}, {"rsolve_cap", &DevOptions::rsolve_cap, true}};
+    {"reduced_solver", &DevOptions::reduced_solver, true}, {"rsolve_cap", &DevOptions::rsolve_cap, true}, {"clear_chunk", &DevOptions::clear_chunk, true}};
 
 extern "C" int dmpc_debug_option(dmpc_ctx *ctx, const char *name, int value)
 {
@@ -1300,6 +1302,103 @@ extern "C" int dmpc_scripted_cols_device(dmpc_ctx *ctx, int S, int N, int N_cmd,
     return 0;
 }
 
+// What every post-check starts with (failure_rate.m:136-162): the histories on the device (uploaded, or the resident ones copied), r_factor,
+// h_scaled and the sample count of every scene, the rescaled knots and their spline.  `who`: the entry's name in the messages; pf may be NULL.
+struct PcPrep {
+    std::vector<int32_t> kt, ns;     // K_T_used (0: masked scene), number of 100 Hz samples
+    std::vector<double> rf, hs;      // r_factor, h_scaled
+    int ns_max = 0;
+    // per-scene scalars on the device: kt_used(int) | rf | hs | ns(int) | mind2(u64) | totdist | traj_time
+    int *d_kt = nullptr, *d_ns = nullptr;
+    double *d_rf = nullptr, *d_hs = nullptr, *d_tot = nullptr, *d_tt = nullptr;
+    unsigned long long *d_min = nullptr;
+    double *dp = nullptr, *dv = nullptr, *da = nullptr;   // rescaled histories (dp: the knots of the spline, ctx->pc_M its second derivatives)
+};
+static int pc_prepare(dmpc_ctx *ctx, const std::string &who, int S, int N, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                      const double *pk, const double *vk, const double *ak, const double *pf, double vmax, double amax, double Ts, PcPrep &q)
+{
+    if (S < 1 || N < 1 || KT_alloc < 2 || !K_T_used || !(vmax > 0) || !(amax > 0) || !(Ts > 0))
+        FAIL(ctx, who + ": bad arguments");
+    std::vector<int32_t> &kt = q.kt;
+    kt.assign((size_t)S, 0);
+    for (int s = 0; s < S; ++s) {
+        const bool on = !scene_mask || scene_mask[s];
+        if (on && (K_T_used[s] < 2 || K_T_used[s] > KT_alloc)) FAIL(ctx, who + ": K_T_used out of range");
+        kt[s] = on ? K_T_used[s] : 0;   // masked scenes (aborted trials, failure_rate.m:136) are skipped by every kernel
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t A = (size_t)S * N, hist = A * (size_t)KT_alloc * 24;
+    if (ctx->pc_p.ensure(hist) || ctx->pc_v.ensure(hist) || ctx->pc_a.ensure(hist) || ctx->pc_M.ensure(hist) ||
+        ctx->pc_w.ensure(hist) || ctx->pc_scene.ensure((size_t)S * 64) || ctx->pc_agent.ensure(A * 16) || ctx->pf.ensure(A * 24))
+        FAIL(ctx, "device allocation failed");
+    if (pk) {
+        if (!vk || !ak) FAIL(ctx, who + ": vk/ak missing");
+        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_p.p, pk, hist, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_v.p, vk, hist, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_a.p, ak, hist, hipMemcpyHostToDevice, st));
+    } else {
+        if (ctx->hist_S != S || ctx->hist_N != N || ctx->hist_KT != KT_alloc)
+            FAIL(ctx, who + ": no resident histories of this shape (run dmpc_transition first or pass pk/vk/ak)");
+        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_p.p, ctx->hist_p.p, hist, hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_v.p, ctx->hist_v.p, hist, hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_a.p, ctx->hist_a.p, hist, hipMemcpyDeviceToDevice, st));
+    }
+    if (pf) HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, pf, A * 24, hipMemcpyHostToDevice, st));
+    char *sc = ctx->pc_scene.as<char>();
+    q.d_kt = (int *)sc;
+    q.d_rf = (double *)(sc + (size_t)S * 8); q.d_hs = (double *)(sc + (size_t)S * 16);
+    q.d_ns = (int *)(sc + (size_t)S * 24);
+    q.d_min = (unsigned long long *)(sc + (size_t)S * 32);
+    q.d_tot = (double *)(sc + (size_t)S * 40); q.d_tt = (double *)(sc + (size_t)S * 48);
+    HIPCHK(ctx, hipMemcpyAsync(q.d_kt, kt.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(q.d_min, 0x7f, (size_t)S * 8, st));   // 0x7f7f... = a huge finite double
+    q.dp = ctx->pc_p.as<double>(); q.dv = ctx->pc_v.as<double>(); q.da = ctx->pc_a.as<double>();
+    hipLaunchKernelGGL(pc::rfactor_kernel, dim3((unsigned)S), dim3(256), 0, st, N, KT_alloc, (const int *)q.d_kt, (const double *)q.dv,
+                       (const double *)q.da, vmax, amax, q.d_rf);
+    std::vector<double> &rf = q.rf, &hs = q.hs;
+    std::vector<int32_t> &ns = q.ns;
+    rf.assign((size_t)S, 0.0); hs.assign((size_t)S, 0.0); ns.assign((size_t)S, 0);
+    HIPCHK(ctx, hipMemcpyAsync(rf.data(), q.d_rf, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    q.ns_max = 0;
+    for (int s = 0; s < S; ++s) {
+        if (!kt[s]) { rf[s] = hs[s] = NAN; ns[s] = 0; continue; }
+        if (!(std::isfinite(rf[s]) && rf[s] > 0))   // MATLAB: h_scaled = 0, tk = 0:0:T is empty and spline() errors
+            FAIL(ctx, who + ": degenerate r_factor (all-zero or non-finite histories)");
+        hs[s] = ctx->prm.h / std::sqrt(rf[s]);                                   // failure_rate.m:146
+        const double T = (kt[s] - 1) * hs[s];                              // :149
+        ns[s] = (std::isfinite(T) && T / Ts < 5e7) ? (int)std::floor(T / Ts + 1e-10) + 1 : -1;   // :152
+        if (ns[s] < 1) FAIL(ctx, who + ": degenerate r_factor (all-zero or non-finite histories)");
+        q.ns_max = std::max(q.ns_max, (int)ns[s]);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(q.d_hs, hs.data(), (size_t)S * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(q.d_ns, ns.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
+    const unsigned b3 = (unsigned)((A * 3 + 255) / 256);
+    hipLaunchKernelGGL(pc::rescale_kernel, dim3(b3), dim3(256), 0, st, S, N, KT_alloc, (const int *)q.d_kt, (const double *)q.d_rf,
+                       (const double *)q.d_hs, q.dp, q.dv, q.da);
+    hipLaunchKernelGGL(pc::spline_kernel, dim3(b3), dim3(256), 0, st, S, N, KT_alloc, (const int *)q.d_kt, (const double *)q.d_hs,
+                       (const double *)q.dp, ctx->pc_M.as<double>(), ctx->pc_w.as<double>());
+    return 0;
+}
+
+// the cell grid of the post-checks over the workspace: cells `edge` wide in the metric of the check (z: edge * c) plus a margin of one cell
+// per side, at most 32768 of them (`edge` grows until they fit)
+static pc::Grid pc_make_grid(const dmpc_params &pr, double &edge)
+{
+    pc::Grid g{};
+    for (;;) {
+        g.nx = (int)std::ceil((pr.pmax[0] - pr.pmin[0]) / edge) + 2;
+        g.ny = (int)std::ceil((pr.pmax[1] - pr.pmin[1]) / edge) + 2;
+        g.nz = (int)std::ceil((pr.pmax[2] - pr.pmin[2]) / (edge * pr.c)) + 2;
+        if ((double)g.nx * g.ny * g.nz <= 32768.0) break;
+        edge *= 1.25;
+    }
+    g.x0 = pr.pmin[0] - edge; g.y0 = pr.pmin[1] - edge; g.z0 = pr.pmin[2] - edge * pr.c;
+    g.inv_e = 1.0 / edge; g.inv_ez = 1.0 / (edge * pr.c);
+    return g;
+}
+
 // post-checks of S finished transitions (failure_rate.m:136-195): rescale, 100 Hz not-a-knot spline, pairwise
 // ellipsoidal collision check, path length, trajectory time.  pk == NULL: use the histories dmpc_transition left
 // resident on the device (no PCIe round trip).
@@ -1314,67 +1413,18 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
                          const double *path = nullptr, int P = 0, double *p_scripted = nullptr)
 {
     if (!ctx) { g_err = "dmpc_postcheck: ctx is NULL"; return -1; }
-    if (S < 1 || N < 1 || KT_alloc < 2 || !K_T_used || !pf || !(vmax > 0) || !(amax > 0) || !(Ts > 0))
-        FAIL(ctx, "dmpc_postcheck: bad arguments");
-    std::vector<int32_t> kt(S);
-    for (int s = 0; s < S; ++s) {
-        const bool on = !scene_mask || scene_mask[s];
-        if (on && (K_T_used[s] < 2 || K_T_used[s] > KT_alloc)) FAIL(ctx, "dmpc_postcheck: K_T_used out of range");
-        kt[s] = on ? K_T_used[s] : 0;   // masked scenes (aborted trials, failure_rate.m:136) are skipped by every kernel
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!pf) FAIL(ctx, "dmpc_postcheck: bad arguments");
+    PcPrep q;
+    if (pc_prepare(ctx, "dmpc_postcheck", S, N, KT_alloc, K_T_used, scene_mask, pk, vk, ak, pf, vmax, amax, Ts, q)) return -1;
     hipStream_t st = ctx->stream;
-    const size_t A = (size_t)S * N, hist = A * (size_t)KT_alloc * 24;
-    if (ctx->pc_p.ensure(hist) || ctx->pc_v.ensure(hist) || ctx->pc_a.ensure(hist) || ctx->pc_M.ensure(hist) ||
-        ctx->pc_w.ensure(hist) || ctx->pc_scene.ensure((size_t)S * 64) || ctx->pc_agent.ensure(A * 16) || ctx->pf.ensure(A * 24))
-        FAIL(ctx, "device allocation failed");
-    if (pk) {
-        if (!vk || !ak) FAIL(ctx, "dmpc_postcheck: vk/ak missing");
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_p.p, pk, hist, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_v.p, vk, hist, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_a.p, ak, hist, hipMemcpyHostToDevice, st));
-    } else {
-        if (ctx->hist_S != S || ctx->hist_N != N || ctx->hist_KT != KT_alloc)
-            FAIL(ctx, "dmpc_postcheck: no resident histories of this shape (run dmpc_transition first or pass pk/vk/ak)");
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_p.p, ctx->hist_p.p, hist, hipMemcpyDeviceToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_v.p, ctx->hist_v.p, hist, hipMemcpyDeviceToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_a.p, ctx->hist_a.p, hist, hipMemcpyDeviceToDevice, st));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, pf, A * 24, hipMemcpyHostToDevice, st));
-    // per-scene scalars: [0] kt_used(int) [1] rf [2] hs [3] ns(int) [4] mind2(u64) [5] totdist [6] traj_time
-    char *sc = ctx->pc_scene.as<char>();
-    int *d_kt = (int *)sc;
-    double *d_rf = (double *)(sc + (size_t)S * 8), *d_hs = (double *)(sc + (size_t)S * 16);
-    int *d_ns = (int *)(sc + (size_t)S * 24);
-    unsigned long long *d_min = (unsigned long long *)(sc + (size_t)S * 32);
-    double *d_tot = (double *)(sc + (size_t)S * 40), *d_tt = (double *)(sc + (size_t)S * 48);
-    HIPCHK(ctx, hipMemcpyAsync(d_kt, kt.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(d_min, 0x7f, (size_t)S * 8, st));   // 0x7f7f... = a huge finite double
-    double *dp = ctx->pc_p.as<double>(), *dv = ctx->pc_v.as<double>(), *da = ctx->pc_a.as<double>();
-    hipLaunchKernelGGL(pc::rfactor_kernel, dim3((unsigned)S), dim3(256), 0, st, N, KT_alloc, (const int *)d_kt, (const double *)dv,
-                       (const double *)da, vmax, amax, d_rf);
-    std::vector<double> rf(S), hs(S), md(S), tot(S), tt(S);
-    std::vector<int32_t> ns(S);
-    HIPCHK(ctx, hipMemcpyAsync(rf.data(), d_rf, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    int ns_max = 0;
-    for (int s = 0; s < S; ++s) {
-        if (!kt[s]) { rf[s] = hs[s] = NAN; ns[s] = 0; continue; }
-        if (!(std::isfinite(rf[s]) && rf[s] > 0))   // MATLAB: h_scaled = 0, tk = 0:0:T is empty and spline() errors
-            FAIL(ctx, "dmpc_postcheck: degenerate r_factor (all-zero or non-finite histories)");
-        hs[s] = ctx->prm.h / std::sqrt(rf[s]);                                   // failure_rate.m:146
-        const double T = (kt[s] - 1) * hs[s];                              // :149
-        ns[s] = (std::isfinite(T) && T / Ts < 5e7) ? (int)std::floor(T / Ts + 1e-10) + 1 : -1;   // :152
-        if (ns[s] < 1) FAIL(ctx, "dmpc_postcheck: degenerate r_factor (all-zero or non-finite histories)");
-        ns_max = std::max(ns_max, (int)ns[s]);
-    }
-    HIPCHK(ctx, hipMemcpyAsync(d_hs, hs.data(), (size_t)S * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(d_ns, ns.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
-    const unsigned b3 = (unsigned)((A * 3 + 255) / 256);
-    hipLaunchKernelGGL(pc::rescale_kernel, dim3(b3), dim3(256), 0, st, S, N, KT_alloc, (const int *)d_kt, (const double *)d_rf,
-                       (const double *)d_hs, dp, dv, da);
-    hipLaunchKernelGGL(pc::spline_kernel, dim3(b3), dim3(256), 0, st, S, N, KT_alloc, (const int *)d_kt, (const double *)d_hs,
-                       (const double *)dp, ctx->pc_M.as<double>(), ctx->pc_w.as<double>());
+    const size_t A = (size_t)S * N;
+    const std::vector<int32_t> &kt = q.kt, &ns = q.ns;
+    const std::vector<double> &rf = q.rf, &hs = q.hs;
+    const int ns_max = q.ns_max;
+    int *d_kt = q.d_kt, *d_ns = q.d_ns;
+    double *d_hs = q.d_hs, *d_tot = q.d_tot, *d_tt = q.d_tt, *dp = q.dp;
+    unsigned long long *d_min = q.d_min;
+    std::vector<double> md(S), tot(S), tt(S);
     double *d_interp = nullptr;
     if (p_interp) {
         if (ns_alloc < 1) FAIL(ctx, "dmpc_postcheck: ns_alloc must be positive with p_interp");
@@ -1389,16 +1439,7 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
     double edge = 2.0 * ctx->prm.rmin;
     int SB = 1, ncell = 1;
     if (use_grid) {
-        const dmpc_params &pr = ctx->prm;
-        for (;;) {   // cells of `edge` (z: edge * c) over the workspace + 2 cells of margin, at most 32768 of them
-            g.nx = (int)std::ceil((pr.pmax[0] - pr.pmin[0]) / edge) + 2;
-            g.ny = (int)std::ceil((pr.pmax[1] - pr.pmin[1]) / edge) + 2;
-            g.nz = (int)std::ceil((pr.pmax[2] - pr.pmin[2]) / (edge * pr.c)) + 2;
-            if ((double)g.nx * g.ny * g.nz <= 32768.0) break;
-            edge *= 1.25;
-        }
-        g.x0 = pr.pmin[0] - edge; g.y0 = pr.pmin[1] - edge; g.z0 = pr.pmin[2] - edge * pr.c;
-        g.inv_e = 1.0 / edge; g.inv_ez = 1.0 / (edge * pr.c);
+        g = pc_make_grid(ctx->prm, edge);
         ncell = g.nx * g.ny * g.nz;
         const double per_sample = (double)S * ((double)N * 36.0 + (double)ncell * 8.0 + 4.0);
         SB = (int)std::floor(256.0 * 1048576.0 / per_sample);
@@ -1629,6 +1670,133 @@ extern "C" int dmpc_postcheck_scripted(dmpc_ctx *ctx, int S, int N, int N_cmd, i
                          violation, totdist, traj_time, p_interp, ns_alloc, N - N_cmd, nullptr, min_dist_scripted, violation_scripted, path, P, p_scripted);
 }
 
+
+// The clearance report of dmpc_postcheck_clearance for the scenes of ONE context: the preamble of every post-check over the Nc commanded
+// agents, then per batch of samples one point set of all N vehicles, one search and the fold of its partials (dmpc_postcheck.hip).
+static int clearance_one(dmpc_ctx *ctx, int S, int N, int Nc, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                         const double *pk, const double *vk, const double *ak, const double *po_static, const double *path, int P,
+                         double vmax, double amax, double Ts, double reach, double *clear_dist, int32_t *clear_partner, int32_t *clear_sample)
+{
+    PcPrep q;
+    if (pc_prepare(ctx, "dmpc_postcheck_clearance", S, Nc, KT_alloc, K_T_used, scene_mask, pk, vk, ak, nullptr, vmax, amax, Ts, q)) return -1;
+    hipStream_t st = ctx->stream;
+    const int M = N - Nc, ns_max = q.ns_max;
+    const double *d_static = nullptr, *d_yk = nullptr, *d_Mk = nullptr;
+    if (M > 0 && path) {   // scripted vehicles: their splines on the commanded agents' knots (as dmpc_postcheck_scripted makes them)
+        const size_t V = (size_t)S * M, knots = V * (size_t)KT_alloc * 24;
+        if (ctx->pc_sc_path.ensure(V * (size_t)P * 24 + (size_t)S * 8) || ctx->pc_sc_y.ensure(knots) || ctx->pc_sc_M.ensure(knots) || ctx->pc_sc_w.ensure(knots))
+            FAIL(ctx, "device allocation failed (clearance, scripted vehicles)");
+        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_sc_path.p, path, V * (size_t)P * 24, hipMemcpyHostToDevice, st));
+        const size_t nk = V * (size_t)KT_alloc * 3;
+        hipLaunchKernelGGL(pc::scripted_knots_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, P, (const int *)q.d_kt,
+                           (const double *)ctx->pc_sc_path.as<double>(), ctx->pc_sc_y.as<double>());
+        hipLaunchKernelGGL(pc::spline_kernel, dim3((unsigned)((V * 3 + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, (const int *)q.d_kt,
+                           (const double *)q.d_hs, (const double *)ctx->pc_sc_y.as<double>(), ctx->pc_sc_M.as<double>(), ctx->pc_sc_w.as<double>());
+        d_yk = ctx->pc_sc_y.as<double>(); d_Mk = ctx->pc_sc_M.as<double>();
+    } else if (M > 0) {
+        if (ctx->pc_static.ensure((size_t)S * M * 24 + (size_t)S * 8)) FAIL(ctx, "device allocation failed (clearance, static vehicles)");
+        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_static.p, po_static, (size_t)S * M * 24, hipMemcpyHostToDevice, st));
+        d_static = ctx->pc_static.as<double>();
+    }
+    // The search.  Cell grid: cells at least `reach` wide, so every pair closer than `reach` lies in adjacent cells and is evaluated -- a slot
+    // whose best is < reach is exact, any other is reported empty.  Tiled all-pairs: small tables, no bound on the distance, or a bound so
+    // wide that the workspace is one cell.
+    double edge = 2.0 * ctx->prm.rmin;
+    pc::Grid g = pc_make_grid(ctx->prm, edge);   // (the edge dmpc_postcheck chooses)
+    bool use_grid = N > PC_BRUTE_MAX && std::isfinite(reach);
+    if (use_grid && reach > edge) { edge = reach; g = pc_make_grid(ctx->prm, edge); }
+    if (g.nx <= 3 && g.ny <= 3 && g.nz <= 3) use_grid = false;   // (one cell and its margin)
+    const int ncell = g.nx * g.ny * g.nz;
+    // samples per chunk (= per workgroup) and per batch: at most 256 MB of positions, grid and partials at a time
+    int CH = ctx->opt.clear_chunk > 0 ? ctx->opt.clear_chunk : 8;
+    const double per_sample = (double)S * ((double)N * 24.0 + (use_grid ? (double)N * 8.0 + (double)ncell * 8.0 + 4.0 : 0.0) + (double)Nc * 32.0 / CH);
+    int SB = (int)std::floor(256.0 * 1048576.0 / per_sample);
+    SB = SB < 1 ? 1 : (SB > 256 ? 256 : SB);
+    if (SB > ns_max) SB = ns_max > 0 ? ns_max : 1;
+    if (CH > SB) CH = SB;
+    const int nchunk = (SB + CH - 1) / CH;
+    const size_t sbn = (size_t)S * SB, tot = sbn * N, slots = (size_t)S * Nc * 2;
+    if (ctx->pc_pts.ensure(tot * 24) || ctx->pc_cl_part.ensure((size_t)nchunk * slots * 16) || ctx->pc_cl_run.ensure(slots * 16) || ctx->pc_cl_out.ensure(slots * 16) ||
+        (use_grid && (ctx->pc_cell.ensure(tot * 4) || ctx->pc_sorted.ensure(tot * 4) || ctx->pc_fill.ensure(sbn * ncell * 4) ||
+                      ctx->pc_start.ensure(sbn * ((size_t)ncell + 1) * 4))))
+        FAIL(ctx, "device allocation failed (clearance)");
+    double *part_d2 = ctx->pc_cl_part.as<double>(), *run_d2 = ctx->pc_cl_run.as<double>(), *o_dist = ctx->pc_cl_out.as<double>();
+    int *part_smp = (int *)(part_d2 + (size_t)nchunk * slots), *part_j = part_smp + (size_t)nchunk * slots;
+    int *run_smp = (int *)(run_d2 + slots), *run_j = run_smp + slots;
+    int *o_partner = (int *)(o_dist + slots), *o_sample = o_partner + slots;
+    const double cinv = 1.0 / ctx->prm.c;
+    const dim3 search((unsigned)((Nc + 255) / 256), (unsigned)nchunk, (unsigned)S);
+    auto finish = [&](int chunks, int first, int last) {
+        hipLaunchKernelGGL(pc::clear_finish_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, slots, Nc, chunks, first, last, (const int *)q.d_kt,
+                           reach, (const double *)part_d2, (const int *)part_smp, (const int *)part_j, run_d2, run_smp, run_j, o_dist, o_partner, o_sample);
+    };
+    if (use_grid) HIPCHK(ctx, hipMemsetAsync(ctx->pc_fill.p, 0, sbn * ncell * 4, st));
+    if (ns_max < 1) finish(0, 1, 1);   // (every scene masked)
+    for (int smp0 = 0; smp0 < ns_max; smp0 += SB) {
+        hipLaunchKernelGGL(pc::clear_eval_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, S, N, Nc, KT_alloc, (const int *)q.d_kt,
+                           (const double *)q.d_hs, (const int *)q.d_ns, Ts, smp0, SB, (const double *)q.dp, (const double *)ctx->pc_M.as<double>(), d_static,
+                           d_yk, d_Mk, use_grid ? 1 : 0, g, ctx->pc_pts.as<double>(), ctx->pc_cell.as<int>(), ctx->pc_fill.as<int>());
+        if (use_grid) {
+            hipLaunchKernelGGL(pc::grid_scan_kernel, dim3((unsigned)sbn), dim3(1024), 0, st, ncell, ctx->pc_fill.as<int>(), ctx->pc_start.as<int>());
+            hipLaunchKernelGGL(pc::grid_scatter_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, tot, N, ncell,
+                               (const int *)ctx->pc_cell.as<int>(), (const int *)ctx->pc_start.as<int>(), ctx->pc_fill.as<int>(), ctx->pc_sorted.as<int>());
+            HIPCHK(ctx, hipMemsetAsync(ctx->pc_fill.p, 0, sbn * ncell * 4, st));
+            hipLaunchKernelGGL(pc::clear_grid_kernel, search, dim3(256), 0, st, S, N, Nc, SB, CH, smp0, (const int *)q.d_ns, g, cinv,
+                               (const double *)ctx->pc_pts.as<double>(), (const int *)ctx->pc_cell.as<int>(), (const int *)ctx->pc_start.as<int>(),
+                               (const int *)ctx->pc_sorted.as<int>(), part_d2, part_smp, part_j);
+        } else {
+            hipLaunchKernelGGL(pc::clear_brute_kernel, search, dim3(256), 0, st, S, N, Nc, SB, CH, smp0, (const int *)q.d_ns, cinv,
+                               (const double *)ctx->pc_pts.as<double>(), part_d2, part_smp, part_j);
+        }
+        finish(nchunk, smp0 == 0, smp0 + SB >= ns_max);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if (clear_dist) HIPCHK(ctx, hipMemcpyAsync(clear_dist, o_dist, slots * 8, hipMemcpyDeviceToHost, st));
+    if (clear_partner) HIPCHK(ctx, hipMemcpyAsync(clear_partner, o_partner, slots * 4, hipMemcpyDeviceToHost, st));
+    if (clear_sample) HIPCHK(ctx, hipMemcpyAsync(clear_sample, o_sample, slots * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int dmpc_postcheck_clearance(dmpc_ctx *ctx, int S, int N, int N_cmd, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                                        const double *pk, const double *vk, const double *ak, const double *po_static, const double *path, int P,
+                                        double vmax, double amax, double Ts, double reach, double *clear_dist, int32_t *clear_partner,
+                                        int32_t *clear_sample)
+{
+    if (!ctx) { g_err = "dmpc_postcheck_clearance: ctx is NULL"; return -1; }
+    if (check_cmd(ctx, "dmpc_postcheck_clearance", S, N, N_cmd)) return -1;
+    if (po_static && path) FAIL(ctx, "dmpc_postcheck_clearance: po_static and path exclude each other (static vehicles rest, scripted ones move)");
+    if (N_cmd < N && !po_static && !path) FAIL(ctx, "dmpc_postcheck_clearance: N_cmd < N needs po_static or path");
+    if (!(reach > 0)) FAIL(ctx, "dmpc_postcheck_clearance: reach must be > 0 (+inf: every slot exact)");
+    if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, "dmpc_postcheck_clearance: pk, vk, ak must be all given or all NULL");
+    if (path && P < 1) FAIL(ctx, "dmpc_postcheck_clearance: P must be >= 1 (every path has at least its start)");
+    const int M = N - N_cmd, parts = (int)ctx->split_at.size() - 1;
+    if (pk || parts < 2 || ctx->split_at.back() != S || ctx->hist_S != S || (int)ctx->children.size() < parts - 1 || !K_T_used)
+        return clearance_one(ctx, S, N, N_cmd, KT_alloc, K_T_used, scene_mask, pk, vk, ak, po_static, path, P, vmax, amax, Ts, reach, clear_dist,
+                             clear_partner, clear_sample);
+    // resident histories of a split dmpc_transition: each part is searched where it lives, concurrently (as postcheck_any does)
+    auto off = [&](auto *ptr, size_t o) { return ptr ? ptr + o : ptr; };
+    std::vector<int> rc((size_t)parts, 0);
+    auto run = [&](int i) {
+        dmpc_ctx *c = i ? ctx->children[(size_t)i - 1] : ctx;
+        const int s0 = ctx->split_at[(size_t)i], sn = ctx->split_at[(size_t)i + 1] - s0;
+        const size_t a0 = (size_t)s0 * N_cmd * 2;
+        const int keep = c->hist_S;
+        c->hist_S = sn;
+        rc[(size_t)i] = clearance_one(c, sn, N, N_cmd, KT_alloc, K_T_used + s0, off(scene_mask, (size_t)s0), nullptr, nullptr, nullptr,
+                                      off(po_static, (size_t)s0 * M * 3), off(path, (size_t)s0 * M * P * 3), P, vmax, amax, Ts, reach, off(clear_dist, a0),
+                                      off(clear_partner, a0), off(clear_sample, a0));
+        c->hist_S = keep;
+    };
+    std::vector<std::thread> th;
+    for (int i = 1; i < parts; ++i) th.emplace_back(run, i);
+    run(0);
+    for (auto &t : th) t.join();
+    for (int i = 1; i < parts; ++i)
+        if (rc[(size_t)i]) FAIL(ctx, ctx->children[(size_t)i - 1]->err);
+    return rc[0];
+}
 
 // ---------------------------------------------------------------------------------------------
 // dense collision-row builders (dec-iSCP/CollConstr.m, dmpc/matlab/CollConstr*DMPC.m, cup-SCP/AddCollConstr.m)

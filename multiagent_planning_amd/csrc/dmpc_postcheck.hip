@@ -477,4 +477,174 @@ __global__ void finish_kernel(int N, const double *__restrict__ dist, const int 
     if (t == 0) { totdist[s] = sd[0]; traj_time[s] = si[0] * Ts; }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Clearance report (dmpc_postcheck_clearance): per commanded agent i the nearest commanded partner (slot 0) and the nearest uncommanded
+// vehicle (slot 1) over all 100 Hz samples, with the sample at which it happens.  The searches above reduce the same distances to one number
+// per scene; here every thread owns one agent and keeps (d2, sample, partner) per slot in registers.  Ties go to the smallest sample, then the
+// smallest partner: samples are walked in ascending order and a later one replaces the best only when it is strictly smaller; within a sample
+// the tiled search walks the partners in ascending order (strict <), the cell-grid search, whose order inside a cell is arbitrary, compares
+// (d2, partner).  A batch of SB samples is cut into chunks of CH; a block = (tile of 256 agents, chunk, scene) writes its agents' bests of the
+// chunk as partials [chunk][S][Nc][2], and clear_finish_kernel folds them, in chunk order, into the running best of the whole transition.
+
+// thread per (scene, sample of the batch, vehicle of the table): pts[S][SB][N][3] -- columns < Nc the commanded agents' spline (the evaluation
+// of grid_eval_kernel), the others the static positions po_static[S][N-Nc][3] or the scripted vehicles' spline (the evaluation of
+// scripted_eval_kernel on the knots yk / Mk [S][N-Nc][KTa][3]); with_grid: the vehicle's cell -> cell_of, count -> fill (as grid_eval_kernel)
+__global__ void clear_eval_kernel(int S, int N, int Nc, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs,
+                                  const int *__restrict__ ns, double Ts, int smp0, int SB, const double *__restrict__ y,
+                                  const double *__restrict__ M, const double *__restrict__ po_static, const double *__restrict__ yk,
+                                  const double *__restrict__ Mk, int with_grid, Grid g, double *__restrict__ pts, int *__restrict__ cell_of,
+                                  int *__restrict__ fill)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)S * SB * N) return;
+    const int j = (int)(t % N);
+    const int b = (int)((t / N) % SB), s = (int)(t / ((size_t)N * SB));
+    const int smp = smp0 + b;
+    if (smp >= ns[s]) { if (with_grid) cell_of[t] = -1; return; }
+    const int n = kt_used[s];
+    const double h = hs[s], tt = smp * Ts;
+    double x, yv, z;
+    if (j < Nc) {
+        const size_t o = ((size_t)s * Nc + j) * (size_t)KTa * 3;
+        x = spline_eval2(y, M, o, n, h, tt); yv = spline_eval2(y, M, o + 1, n, h, tt); z = spline_eval2(y, M, o + 2, n, h, tt);
+    } else if (yk) {
+        const size_t o = ((size_t)s * (N - Nc) + (j - Nc)) * (size_t)KTa * 3;
+        x = spline_eval2(yk, Mk, o, n, h, tt); yv = spline_eval2(yk, Mk, o + 1, n, h, tt); z = spline_eval2(yk, Mk, o + 2, n, h, tt);
+    } else {
+        const double *q = po_static + ((size_t)s * (N - Nc) + (j - Nc)) * 3;
+        x = q[0]; yv = q[1]; z = q[2];
+    }
+    pts[3 * t] = x; pts[3 * t + 1] = yv; pts[3 * t + 2] = z;
+    if (!with_grid) return;
+    int ix = (int)floor((x - g.x0) * g.inv_e), iy = (int)floor((yv - g.y0) * g.inv_e), iz = (int)floor((z - g.z0) * g.inv_ez);
+    ix = ix < 0 ? 0 : (ix >= g.nx ? g.nx - 1 : ix);
+    iy = iy < 0 ? 0 : (iy >= g.ny ? g.ny - 1 : iy);
+    iz = iz < 0 ? 0 : (iz >= g.nz ? g.nz - 1 : iz);
+    const int c = ix + g.nx * (iy + g.ny * iz);
+    cell_of[t] = c;
+    atomicAdd(&fill[((size_t)s * SB + b) * ((size_t)g.nx * g.ny * g.nz) + c], 1);
+}
+
+// agent i against the vehicles lo .. hi-1 of one sample, streamed through LDS in tiles of 256, in ascending order (every thread of the block
+// takes part in the staging; `vi`: the thread owns an agent)
+__device__ __forceinline__ void clear_scan_tiles(const double *__restrict__ pp, int lo, int hi, int i, bool vi, double xi, double yi, double zi,
+                                                 double cinv, int smp, double *tile, double &bd, int &bs, int &bj)
+{
+    for (int j0 = lo; j0 < hi; j0 += 256) {
+        const int cntj = hi - j0 < 256 ? hi - j0 : 256;
+        __syncthreads();
+        for (int e = threadIdx.x; e < cntj * 3; e += 256) tile[e] = pp[3 * (size_t)j0 + e];
+        __syncthreads();
+        if (vi)
+            for (int jj = 0; jj < cntj; ++jj) {
+                const double d = pair_d2(xi, yi, zi, tile[3 * jj], tile[3 * jj + 1], tile[3 * jj + 2], cinv);
+                if (d < bd && j0 + jj != i) { bd = d; bs = smp; bj = j0 + jj; }
+            }
+    }
+}
+// the partials of one (chunk, scene, agent): part_d2 [chunk][S][Nc][2], part_smp and part_j alike
+__device__ __forceinline__ void clear_store(int S, int Nc, int chunk, int s, int i, double *__restrict__ part_d2, int *__restrict__ part_smp,
+                                            int *__restrict__ part_j, double d0, int s0, int j0, double d1, int s1, int j1)
+{
+    const size_t o = (((size_t)chunk * S + s) * Nc + i) * 2;
+    part_d2[o] = d0; part_smp[o] = s0; part_j[o] = j0;
+    part_d2[o + 1] = d1; part_smp[o + 1] = s1; part_j[o + 1] = j1;
+}
+
+// tiled all-pairs: block = (tile of 256 commanded agents i, chunk of CH samples, scene); exact for every agent
+__global__ void clear_brute_kernel(int S, int N, int Nc, int SB, int CH, int smp0, const int *__restrict__ ns, double cinv,
+                                   const double *__restrict__ pts, double *__restrict__ part_d2, int *__restrict__ part_smp,
+                                   int *__restrict__ part_j)
+{
+    __shared__ double tile[256 * 3];
+    const int s = blockIdx.z, chunk = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const bool vi = i < Nc;
+    const int nsamp = ns[s];
+    double d0 = INFINITY, d1 = INFINITY;
+    int s0 = -1, s1 = -1, j0 = -1, j1 = -1;
+    for (int q = 0; q < CH; ++q) {
+        const int b = chunk * CH + q, smp = smp0 + b;
+        if (b >= SB || smp >= nsamp) break;   // (uniform per block)
+        const double *pp = pts + ((size_t)s * SB + b) * (size_t)N * 3;
+        const double xi = vi ? pp[3 * i] : 0.0, yi = vi ? pp[3 * i + 1] : 0.0, zi = vi ? pp[3 * i + 2] : 0.0;
+        clear_scan_tiles(pp, 0, Nc, i, vi, xi, yi, zi, cinv, smp, tile, d0, s0, j0);
+        clear_scan_tiles(pp, Nc, N, i, vi, xi, yi, zi, cinv, smp, tile, d1, s1, j1);
+    }
+    if (vi) clear_store(S, Nc, chunk, s, i, part_d2, part_smp, part_j, d0, s0, j0, d1, s1, j1);
+}
+
+// (d2, sample, partner) lexicographically; the samples of a thread ascend, so an equal distance wins only at the same sample with a smaller partner
+__device__ __forceinline__ void clear_take(double d, int smp, int j, double &bd, int &bs, int &bj)
+{
+    if (d < bd || (d == bd && bs == smp && j < bj)) { bd = d; bs = smp; bj = j; }
+}
+// cell grid: block = (tile of 256 commanded agents i, chunk of CH samples, scene); every vehicle of the 27 cells around i's (grid_pairs_kernel's
+// walk over a grid that holds all N vehicles).  Finds every pair closer than the cell edge; what lies farther is for the caller to discard.
+__global__ void clear_grid_kernel(int S, int N, int Nc, int SB, int CH, int smp0, const int *__restrict__ ns, Grid g, double cinv,
+                                  const double *__restrict__ pts, const int *__restrict__ cell_of, const int *__restrict__ start,
+                                  const int *__restrict__ sorted, double *__restrict__ part_d2, int *__restrict__ part_smp,
+                                  int *__restrict__ part_j)
+{
+    const int s = blockIdx.z, chunk = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= Nc) return;
+    const int nsamp = ns[s], ncell = g.nx * g.ny * g.nz;
+    double d0 = INFINITY, d1 = INFINITY;
+    int s0 = -1, s1 = -1, j0 = -1, j1 = -1;
+    for (int q = 0; q < CH; ++q) {
+        const int b = chunk * CH + q, smp = smp0 + b;
+        if (b >= SB || smp >= nsamp) break;
+        const size_t sb = (size_t)s * SB + b, t = sb * N + i;
+        const int c = cell_of[t];
+        if (c < 0) break;
+        const int ix = c % g.nx, iy = (c / g.nx) % g.ny, iz = c / (g.nx * g.ny);
+        const double xi = pts[3 * t], yi = pts[3 * t + 1], zi = pts[3 * t + 2];
+        const int *st = start + sb * (ncell + 1), *so = sorted + sb * N;
+        const double *pp = pts + sb * (size_t)N * 3;
+        const int x_lo = ix > 0 ? ix - 1 : 0, x_hi = ix + 1 < g.nx ? ix + 1 : g.nx - 1;
+        for (int dz = -1; dz <= 1; ++dz) {
+            const int z = iz + dz;
+            if (z < 0 || z >= g.nz) continue;
+            for (int dy = -1; dy <= 1; ++dy) {
+                const int yy = iy + dy;
+                if (yy < 0 || yy >= g.ny) continue;
+                const int base = g.nx * (yy + g.ny * z);
+                const int e0 = st[base + x_lo], e1 = st[base + x_hi + 1];   // x is the fastest cell index: three cells = one run
+                for (int e = e0; e < e1; ++e) {
+                    const int j = so[e];
+                    if (j == i) continue;
+                    const double d = pair_d2(xi, yi, zi, pp[3 * j], pp[3 * j + 1], pp[3 * j + 2], cinv);
+                    if (j < Nc) clear_take(d, smp, j, d0, s0, j0);
+                    else clear_take(d, smp, j, d1, s1, j1);
+                }
+            }
+        }
+    }
+    clear_store(S, Nc, chunk, s, i, part_d2, part_smp, part_j, d0, s0, j0, d1, s1, j1);
+}
+
+// thread per (scene, agent, slot): the batch's partials, in chunk order, into the running best run_* [S][Nc][2] (`first`: the batch opens the
+// transition), which only its owner touches; `last`: the report -- dist = sqrt(d2), a slot without anything closer than `reach` +inf / -1 / -1,
+// a masked scene NaN / -1 / -1
+__global__ void clear_finish_kernel(size_t total, int Nc, int nchunk, int first, int last, const int *__restrict__ kt_used, double reach,
+                                    const double *__restrict__ part_d2, const int *__restrict__ part_smp, const int *__restrict__ part_j,
+                                    double *__restrict__ run_d2, int *__restrict__ run_smp, int *__restrict__ run_j,
+                                    double *__restrict__ dist, int *__restrict__ partner, int *__restrict__ sample)
+{
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    double bd = first ? INFINITY : run_d2[e];
+    int bs = first ? -1 : run_smp[e], bj = first ? -1 : run_j[e];
+    for (int c = 0; c < nchunk; ++c) {
+        const size_t o = (size_t)c * total + e;
+        if (part_d2[o] < bd) { bd = part_d2[o]; bs = part_smp[o]; bj = part_j[o]; }
+    }
+    run_d2[e] = bd; run_smp[e] = bs; run_j[e] = bj;
+    if (!last) return;
+    const double d = sqrt(bd);
+    const bool masked = !kt_used[e / ((size_t)Nc * 2)], found = d < reach;
+    dist[e] = masked ? NAN : (found ? d : INFINITY);
+    partner[e] = !masked && found ? bj : -1;
+    sample[e] = !masked && found ? bs : -1;
+}
+
 }   // namespace pc

@@ -9,6 +9,7 @@
 //   [P,V,A,status,info] = dmpc_mex('step_batch', params, l, x_p, x_v, x_a, pf)          states / pf 3 x N_cmd, N_cmd <= N: see below
 //   [r_factor,h_scaled,violation,totdist,traj_time,p] = dmpc_mex('postcheck', params, pk, vk, ak, pf, vmax, amax, Ts)
 //   [r_factor,h_scaled,violation,totdist,traj_time,p,violation_static,min_dist_static] = dmpc_mex('postcheck', ..., Ts, po_static)
+//   [dist,partner,time] = dmpc_mex('clearance', params, pk, vk, ak, pf, vmax, amax, Ts[, po_static|[][, reach]])   2 x N each; partner 1-based, 0 = none
 //   [Lambda,Av,A0,Delta] = dmpc_mex('model_matrices', params)
 //   [Ain,bin,dist] = dmpc_mex('coll_rows', params, l, sel0, k_cmp0, k_blk0, p, a0, rmin, c, A)     (0-based indices)
 //   [Ain,bin]      = dmpc_mex('add_coll_constr', params, p, po, rmin, c, A)
@@ -34,6 +35,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "dmpc_hip.h"
 
@@ -201,6 +203,33 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
             if (dmpc_postcheck(ctx, 1, N, KT, &kt, nullptr, mxGetPr(prhs[2]), mxGetPr(prhs[3]), mxGetPr(prhs[4]), mxGetPr(prhs[5]),
                                vmax, amax, Ts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mxGetPr(plhs[5]), ns))
                 mexErrMsgIdAndTxt("dmpc:postcheck", "%s", dmpc_last_error(ctx));
+        }
+        return;
+    }
+    if (!std::strcmp(cmd, "clearance")) {   // dmpc_postcheck_clearance for one trial: nearest commanded partner (row 1) / uncommanded vehicle (row 2) per agent
+        need(nrhs >= 9 && nrhs <= 11, "clearance: (cmd, params, pk, vk, ak, pf, vmax, amax, Ts[, po_static[, reach]])");
+        const mwSize *dh = mxGetDimensions(prhs[2]);
+        need(mxGetNumberOfDimensions(prhs[2]) == 3 && dh[0] == 3, "pk must be 3 x KT x N");
+        const int KT = (int)dh[1], N = (int)dh[2];
+        for (int i = 3; i < 5; ++i) need(mxGetNumberOfElements(prhs[i]) == (size_t)3 * KT * N, "vk, ak must match pk");
+        need(mxGetNumberOfElements(prhs[5]) == (size_t)3 * N, "pf must be 1 x 3 x N");
+        const double vmax = mxGetScalar(prhs[6]), amax = mxGetScalar(prhs[7]), Ts = mxGetScalar(prhs[8]);
+        const int M = nrhs >= 10 ? (int)(mxGetNumberOfElements(prhs[9]) / 3) : 0;
+        if (nrhs >= 10) need(mxGetNumberOfElements(prhs[9]) == (size_t)3 * M, "po_static must be 3 x M (or [])");
+        const double reach = nrhs == 11 ? mxGetScalar(prhs[10]) : (double)INFINITY;
+        int32_t kt = KT;
+        std::vector<int32_t> partner((size_t)2 * N), sample((size_t)2 * N);
+        plhs[0] = mxCreateDoubleMatrix(2, N, mxREAL);   // MATLAB (2, N) column-major IS the [N][2] slot layout
+        if (dmpc_postcheck_clearance(ctx, 1, N + M, N, KT, &kt, nullptr, mxGetPr(prhs[2]), mxGetPr(prhs[3]), mxGetPr(prhs[4]), M > 0 ? mxGetPr(prhs[9]) : nullptr,
+                                     nullptr, 0, vmax, amax, Ts, reach, mxGetPr(plhs[0]), partner.data(), sample.data()))
+            mexErrMsgIdAndTxt("dmpc:clearance", "%s", dmpc_last_error(ctx));
+        if (nlhs > 1) {   // 1-based vehicle of the table (commanded agents first); 0: nothing inside reach
+            plhs[1] = mxCreateDoubleMatrix(2, N, mxREAL);
+            for (size_t e = 0; e < (size_t)2 * N; ++e) mxGetPr(plhs[1])[e] = (double)(partner[e] + 1);
+        }
+        if (nlhs > 2) {   // seconds from the start of the rescaled transition; NaN: nothing inside reach
+            plhs[2] = mxCreateDoubleMatrix(2, N, mxREAL);
+            for (size_t e = 0; e < (size_t)2 * N; ++e) mxGetPr(plhs[2])[e] = sample[e] >= 0 ? sample[e] * Ts : (double)NAN;
         }
         return;
     }
