@@ -112,6 +112,8 @@ struct DevOptions {
     int ext_cap = 0;         // development option ext_cap (tests): at most this many T extensions per workgroup (1: every agent that needs one waits for the same slot)
     int queue_chunk = 0;     // development option queue_chunk: positions per ticket of the persistent queue's light bulk (0: chosen per launch)
     int static_queue = 0;    // development option static_queue: persistent waves take queue positions round-robin instead of by ticket
+    int close_pairs = 1;     // development option close_pairs: 0 = the scan walks its neighbour list for the pairs inside rmin instead of taking them from the grid query (A/B runs, tests)
+    int close_cap = 64;      // development option close_cap: (neighbour, step) pairs the query records per agent; an agent with more falls back to the walk (tests)
     int clear_chunk = 8;     // development option clear_chunk: 100 Hz samples per workgroup of the clearance searches (dmpc_postcheck_clearance; tests)
 };
 
@@ -129,6 +131,7 @@ struct dmpc_ctx {
     // scratch for the host-pointer entry points
     DevBuf post_acc; int post_acc_S = 0, post_fused = 0;
     DevBuf rowbuf, rowkc, hdr, order, bbox, bbox_nm, nbr_list, nbr_cnt, lrow, counter, flag_list, scene_done;
+    DevBuf close_list, close_cnt;   // the query's close pairs (StepParams::close_list)
     int num_cu = 0;
     DevOptions opt;          // development options (dmpc_debug_option)
     int max_lds_persist = 0;
@@ -431,7 +434,8 @@ static const DevOptionEntry dev_options[] = {
     {"no_level_skip", &DevOptions::no_level_skip, true}, {"prep_fuse", &DevOptions::prep_fuse, true}, {"static_queue", &DevOptions::static_queue, true}, {"queue_chunk", &DevOptions::queue_chunk, true},
     {"no_split_t", &DevOptions::no_split_t, true}, {"ext_cap", &DevOptions::ext_cap, true}, {"nbr_grid", &DevOptions::nbr_grid, true}, {"f32_dep_exp", &DevOptions::f32_dep_exp, true},
     {"grid_min", &DevOptions::grid_min, true}, {"grid_min_part", &DevOptions::grid_min_part, true}, {"no_level_check", &DevOptions::no_level_check, true}, {"lds_pad_kb", &DevOptions::lds_pad_kb, true},
-    {"reduced_solver", &DevOptions::reduced_solver, true}, {"rsolve_cap", &DevOptions::rsolve_cap, true}, {"clear_chunk", &DevOptions::clear_chunk, true}};
+    {"reduced_solver", &DevOptions::reduced_solver, true}, {"rsolve_cap", &DevOptions::rsolve_cap, true}, {"clear_chunk", &DevOptions::clear_chunk, true},
+    {"close_pairs", &DevOptions::close_pairs, true}, {"close_cap", &DevOptions::close_cap, true}};
 
 extern "C" int dmpc_debug_option(dmpc_ctx *ctx, const char *name, int value)
 {

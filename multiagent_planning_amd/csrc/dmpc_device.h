@@ -93,6 +93,11 @@ struct StepParams {
                             // certified infeasible is solved: A/B runs of the extrapolation's margin, tests/test_gpu_reduced.py)
     int rsolve_cap;         // reduced solver (dmpc_rsolve.hip): equality-constrained solves per ladder level before an agent is handed to the general solver (0: REQP_MAX; development option rsolve_cap)
     int iter_cap;           // active-set iteration cap per try (ITER_CAP; development runs lower it to measure the per-iteration cost)
+    // close pairs (grid_query_kernel -> scan): the (neighbour code, horizon step) pairs whose fp32 squared distance is below rmin^2 * 1.001 --
+    // the pairs the scan's list walk would select for its exact test; null: the scan walks the list itself
+    const int *close_list;  // [S*c_count][close_cap] records of two ints {neighbour code, step}, in no particular order
+    const int *close_cnt;   // [S*c_count] records of each agent; -1: more than close_cap (the scan walks the list)
+    int close_cap;
 };
 
 constexpr int SCAN_CAND_CAP = 1024;   // (neighbour, step) candidates buffered per flush of the hard-row scan

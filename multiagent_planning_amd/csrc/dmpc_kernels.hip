@@ -676,6 +676,32 @@ __device__ __forceinline__ void scan_body(const StepParams &P, const int lane, c
             // of 4 lanes never straddle a row).  The fp32 distance only SELECTS (threshold widened by 1e-3, a hundred times the
             // rounding of a workspace-sized coordinate); the decision dist < rmin is made on the table itself, with the
             // arithmetic of the other walk, for the few (step, neighbour) pairs that pass.
+            // Close pairs (grid_query_kernel): the query's distance test has just formed these fp32 distances from the same rows and left the
+            // (neighbour, step) pairs below the same threshold, rmin^2 * 1.001: lanes = pairs, one round of exact tests, no walk.  The bits
+            // cannot change: the fp32 test only SELECTS, and with the threshold widened by 1e-3 -- a hundred times the fp32 rounding of a
+            // workspace-sized coordinate -- the query's selection and the walk's are both supersets of the pairs with exact dist < rmin (they
+            // may differ from each other at the threshold's edge: another summation order).  anyb is an OR over the exact decisions, made
+            // here with the walk's expression and operand order; mind0 is read only when some neighbour is inside rmin at k = 0, and the
+            // minimising pair is then in every superset.  Count -1 (more pairs than the list holds) or no close list: the walk below.
+            const int ncl = (!SCP && P.close_cnt) ? __builtin_amdgcn_readfirstlane(P.close_cnt[gid]) : -1;
+            if (ncl >= 0) {
+                typedef int i2_t __attribute__((ext_vector_type(2)));
+                const i2_t *cl = (const i2_t *)P.close_list + (size_t)gid * P.close_cap;
+                for (int e0 = 0; e0 < ncl; e0 += 64) {
+                    const bool have = e0 + lane < ncl;
+                    const i2_t rec = cl[have ? e0 + lane : e0];
+                    const int code = rec.x, kq = rec.y, k3 = 3 * kq;
+                    const real *nb = tab + ((size_t)((code >> 20) * S + scene) * N3 + k3) * C + (code & 0xfffff);
+                    if (have) {
+                        const real dx = own_s[k3] - nb[0], dy = own_s[k3 + 1] - nb[(size_t)C], dz = own_s[k3 + 2] - nb[2 * (size_t)C];
+                        const real ez = dz * e1z;
+                        const real d2 = dx * dx + dy * dy + ez * ez;
+                        const real dist = sqrt(d2);
+                        if (dist < rmin) anyb |= (1u << kq);       // CheckCollSoftDMPC.m:11
+                        if (kq == 0) mind0 = fmin(mind0, d2);       // (only ever used when some neighbour is inside rmin at k = 0)
+                    }
+                }
+            } else {
             const float *rt = (const float *)P.lrow;
             const float *rt1 = rt + (size_t)scene * C * 64;
             constexpr int TW = 8;
@@ -726,6 +752,7 @@ __device__ __forceinline__ void scan_body(const StepParams &P, const int lane, c
             }
             };
             if (G == 1) walk(std::true_type{}); else walk(std::false_type{});
+            }
         } else {
             for (int e0 = 0; e0 < n_entries; e0 += 64) {
                 int r, jc;
@@ -1585,12 +1612,21 @@ __global__ __launch_bounds__(256) void grid_fill2_kernel(int total, int C, int n
 // 28 wave slots), and ends with the last agents' whole chains otherwise.
 constexpr int GQ_WAVES = NSEG;
 constexpr int GQ_STAGE = 128;      // staging list of box-test survivors per wave (a full wave is taken off it as soon as there is one)
-inline size_t grid_query_lds(int nagents) { return (((size_t)((nagents + 31) / 32) * 4 + GQ_WAVES * GQ_STAGE * 4 + 15) & ~(size_t)15) + 16 * 16; }
+// Close pairs (close_cap > 0): the distance test has every per-step squared distance of a candidate in a register; the (neighbour, step) pairs
+// below thr_close = rmin^2 * 1.001 -- the pairs the scan's list walk selected for its exact test by loading every listed neighbour's row
+// AGAIN and forming the same distances -- are appended to a per-agent list behind a counter in LDS (the three waves share it) and written out
+// coalesced: close_list[agent][close_cap] records {code, step}, close_cnt[agent] (-1: more than close_cap, the scan walks the list as before).
+// A neighbour is an entry of ONE cell per segment and a step belongs to one segment: no pair is recorded twice.
+inline size_t grid_query_lds(int nagents, int close_cap = 0)
+{
+    return (((size_t)((nagents + 31) / 32) * 4 + GQ_WAVES * GQ_STAGE * 4 + 15) & ~(size_t)15) + 16 * 16 + (close_cap > 0 ? 16 + (size_t)close_cap * 8 : 0);
+}
 typedef float f2_t __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G, int C, int g_local, int c_first, int c_count, GridGeom gg, float R, float Rz, float e1z, float thr2,
                                                                    const float *__restrict__ bbox_nm, const float *__restrict__ lrow, const int *__restrict__ start,
                                                                    const f4_t *__restrict__ ent, const int *__restrict__ maxhalf, int cap, int cell_order,
-                                                                   int *__restrict__ list, int *__restrict__ cnt_out)
+                                                                   int *__restrict__ list, int *__restrict__ cnt_out,
+                                                                   float thr_close, int close_cap, int *__restrict__ close_list, int *__restrict__ close_cnt)
 {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
     const int gid = (int)blockIdx.x;
@@ -1606,7 +1642,9 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
     unsigned *bits = (unsigned *)dmpc_smem;
     int *stage = (int *)(dmpc_smem + (size_t)nwords * 4) + wave * GQ_STAGE;
     f4_t *ownrow = (f4_t *)(dmpc_smem + (((size_t)nwords * 4 + GQ_WAVES * GQ_STAGE * 4 + 15) & ~(size_t)15));
+    int *ccnt = (int *)(ownrow + 16), *crec = ccnt + 4;   // close pairs: counter (16 bytes), close_cap records of two ints (only there when close_cap > 0)
     for (int i = (int)threadIdx.x; i < nwords; i += 64 * GQ_WAVES) bits[i] = 0u;
+    if (close_cap > 0 && threadIdx.x == 0) *ccnt = 0;
     const size_t self_i = (size_t)(g_local * S + scene) * C + cl;
     if (threadIdx.x < 16) ownrow[lane] = ((const f4_t *)lrow)[self_i * 16 + lane];   // the own horizon: 15 x (x, y, z, 0) + 4 zeros
     // own boxes (wave-uniform: scalar loads)
@@ -1650,19 +1688,31 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
             const int code = stage[have ? lane : 0];
             const int r = code >> 20, jc = code & 0xfffff;
             const f4_t *row = (const f4_t *)lrow + ((size_t)(r * S + scene) * C + jc) * 16 + SEG_STEPS * sg;
-            f4_t v[SEG_STEPS];
-#pragma unroll
-            for (int u = 0; u < SEG_STEPS; ++u) v[u] = row[u];
             bool pass = false;
-#pragma unroll
+            int cmask = 0;   // steps of the segment closer than thr_close (close pairs; thr_close < thr2: a subset of the passes; never with close_cap = 0, thr_close < 0)
+            // (one step at a time, not unrolled: with one test per step the compiler made this a chain of early exits, a row quarter loaded per
+            // step, 56 registers; a second test per step on the unrolled form keeps all five quarters in registers -- 85, five waves per SIMD
+            // instead of eight.  This form is the same chain of five loads at 60 registers.)
+#pragma unroll 1
             for (int u = 0; u < SEG_STEPS; ++u) {
-                const f4_t o = ownrow[SEG_STEPS * sg + u];
-                const float dx = o.x - v[u].x, dy = o.y - v[u].y, dz = (o.z - v[u].z) * e1z;
-                pass = pass || (dx * dx + dy * dy + dz * dz < thr2);
+                const f4_t o = ownrow[SEG_STEPS * sg + u], w = row[u];
+                const float dx = o.x - w.x, dy = o.y - w.y, dz = (o.z - w.z) * e1z;
+                const float d2 = dx * dx + dy * dy + dz * dz;
+                pass = pass || (d2 < thr2);
+                cmask |= (d2 < thr_close) ? (1 << u) : 0;
             }
             if (have && pass) {
                 const int idx = r * C + jc;
                 atomicOr(bits + (idx >> 5), 1u << (idx & 31));
+                if (cmask != 0) {   // rare; a lane claims its records with one LDS atomic of its own: no wave collective in this lane-dependent branch
+                    int pos = atomicAdd(ccnt, __popc(cmask));
+                    while (cmask) {
+                        const int u = __ffs(cmask) - 1;
+                        cmask &= cmask - 1;
+                        if (pos < close_cap) { crec[2 * pos] = code; crec[2 * pos + 1] = SEG_STEPS * sg + u; }
+                        ++pos;
+                    }
+                }
             }
         };
         // The candidates: per (y, z) cell row one RUN of entries (the cells of a run along x are contiguous), ~50 entries each at N = 10^4.
@@ -1743,6 +1793,12 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
         if (nst > 0) traj_test(nst);
     }
     __syncthreads();
+    if (wave == 1 && close_cap > 0) {   // the close pairs, next to wave 0's list: whole records, coalesced (the count went past close_cap: none, the scan walks the list)
+        const int n = *ccnt;
+        int *dst = close_list + (size_t)oid * 2 * close_cap;
+        if (n <= close_cap) for (int i = lane; i < 2 * n; i += 64) dst[i] = crec[i];
+        if (lane == 0) close_cnt[oid] = n > close_cap ? -1 : n;
+    }
     if (wave != 0) return;
     // the list = the bitmap in order (increasing neighbour index), one contiguous run per agent
     int *out = list + (size_t)oid * cap;

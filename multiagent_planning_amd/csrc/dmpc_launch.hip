@@ -199,6 +199,8 @@ struct ListPlan {
     long cap = 0;            // entries per agent
     double R = 0, Rsel = 0;  // radius of the boxes' test / of the scan's selection
     size_t gq_lds = 0;
+    bool close = false;      // the query also leaves the (neighbour, step) pairs inside rmin: the scan tests those instead of walking its list
+    int close_cap = 0;       // records per agent
     GridGeom gg{};
     int ncell = 1;
     size_t n_cnt = 0, n_mh = 0, n_st = 0, n_hd = 0;   // the grid buffer's partition (ints): counts, largest half extents, starts, header in all
@@ -287,7 +289,10 @@ static ListPlan plan_lists(const dmpc_ctx *ctx, const StepPlan &pl)
     L.R = L.Rsel * 1.0001 + 1e-4;   // a little more than the scan's radius: conservative in fp32 too
     // round 4: lists from a cell grid, filtered by the fp32 distance test (grid_query_kernel); the all-pairs box test of round 3 stays
     // behind option nbr_grid = 0 (A/B runs, tests) and for scenes whose bitmap would not fit a wave's LDS
-    L.gq_lds = grid_query_lds(sh.G * sh.C);
+    // (with the close pairs' staging list, when the variant's scan walks its list for them and the option is on)
+    const bool close_want = p.variant != DMPC_VAR_HARD && o.close_pairs && o.close_cap > 0;
+    L.close_cap = close_want ? (o.close_cap > 4096 ? 4096 : o.close_cap) : 0;
+    L.gq_lds = grid_query_lds(sh.G * sh.C, L.close_cap);
     // (from grid_min agents per scene on: in a scene of a few hundred agents the reach of a query covers most of the workspace and the
     // all-pairs test with the neighbours' boxes as scalar operands is the cheaper pass -- tools/gpu_grid_min_ab.py, 102 400 agents, scan
     // side all-pairs / grid: hard rows 400 agents per scene 0.81 / 0.81 ms, 800: 1.07 / 0.91, 1 600: 1.42 / 1.06, 3 200: 1.92 / 1.24;
@@ -298,6 +303,8 @@ static ListPlan plan_lists(const dmpc_ctx *ctx, const StepPlan &pl)
     const int grid_from = (sh.c_count == sh.G * sh.C || (sh.G == 1 && 2L * sh.c_count >= (long)sh.C)) ? o.grid_min : o.grid_min_part;
     L.use_grid = o.nbr_grid && sh.G * sh.C >= grid_from && L.gq_lds <= 64 * 1024;
     L.nbr_major = p.variant != DMPC_VAR_HARD || L.use_grid;
+    L.close = L.use_grid && close_want;
+    if (!L.close) L.close_cap = 0;
     if (!L.use_grid) return L;
     // cells: R along x (the cells of a run along x are contiguous in the entry array: their granularity is free), 1.5 R along y
     // and 1.5 R c along z (the metric's z scale), at most 32 per axis
@@ -514,11 +521,14 @@ static int build_neighbour_lists(dmpc_ctx *ctx, const StepPlan &pl, const StepIO
         hipLaunchKernelGGL(grid_scan_kernel, dim3((unsigned)(S * NSEG)), dim3(L.ncell > 512 ? 1024 : 256), 0, st, L.ncell, g_cnt, g_st);
         hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, S, C, L.ncell, (float)(1.0 / p.c), (const int *)g_cell, g_cnt, (const int *)g_st, (const float *)ctx->lrow.as<float>(), g_ent);
     }
+    if (L.close && (ctx->close_list.ensure(agents * (size_t)L.close_cap * 8) || ctx->close_cnt.ensure(agents * 4))) FAIL(ctx, "device allocation failed (close pairs)");
     if (L.use_grid) {
         hipLaunchKernelGGL(grid_query_kernel, dim3((unsigned)pl.total), dim3(64 * GQ_WAVES), L.gq_lds, st, S, G, C, g_local, c_first, c_count, L.gg,
                            (float)L.R, (float)(L.R * p.c), (float)(1.0 / p.c), (float)(L.Rsel * L.Rsel * 1.002), (const float *)ctx->bbox_nm.as<float>(), (const float *)ctx->lrow.as<float>(),
                            (const int *)g_st, (const f4_t *)g_ent, (const int *)g_mh, (int)L.cap, (G == 1 && c_first == 0 && c_count == C && !short_from) ? 1 : 0,
-                           ctx->nbr_list.as<int>(), ctx->nbr_cnt.as<int>());
+                           ctx->nbr_list.as<int>(), ctx->nbr_cnt.as<int>(),
+                           L.close ? (float)(p.rmin * p.rmin) * 1.001f : -1.f, L.close_cap, L.close ? ctx->close_list.as<int>() : nullptr, L.close ? ctx->close_cnt.as<int>() : nullptr);
+        if (L.close) { P.close_list = ctx->close_list.as<int>(); P.close_cnt = ctx->close_cnt.as<int>(); P.close_cap = L.close_cap; }
     } else {
         const int nblk = (c_count + 63) / 64;
         hipLaunchKernelGGL(nbr_kernel, dim3((unsigned)(S * nblk * NBR_PARTS)), dim3(64), 0, st, S, G, C, g_local, c_first, c_count, short_from, (float)L.R, (float)(L.R * p.c),

@@ -1,0 +1,149 @@
+"""GPU: close pairs -- the grid query hands the scan the (neighbour, horizon step) pairs inside rmin, the scan makes one round of exact tests on
+them instead of walking its neighbour list (development options close_pairs, close_cap).
+
+The query's fp32 test only selects: the decision dist < rmin is made with the walk's own arithmetic on the table, and both selections are
+supersets of the pairs that pass it.  So every output word must equal the walk's (close_pairs = 0) and the whole-table walk's (no_cull = 1):
+with the default capacity, with a capacity of ONE record (agents with two or more pairs fall back to the walk), on a sub-range of a table
+and on one chunk of a two-chunk table."""
+import ctypes as C
+import functools
+import os
+import re
+
+import numpy as np
+import pytest
+
+import multiagent_planning_amd as mp
+from multiagent_planning_amd import _lib, workload as wl
+from helpers import ROOT
+import obstacles as ob
+import test_gpu_paths as paths
+import test_gpu_obstacles as obstacle_tests
+import test_gpu_multigpu as multigpu_tests
+
+pytestmark = pytest.mark.gpu
+
+KEYS = ("status", "info", "p", "v", "a")
+N_AGENTS = 700      # >= cull_min agents per scene: lists on; not a multiple of 64 (ragged last tile); grid_min = 256 forces the cell grid
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(S):
+    cfg = wl.CONFIGS["C4"]
+    kw = wl.solver_kwargs(cfg, N_AGENTS)
+    po, pf = wl.make_scenes(cfg, S, N_AGENTS, wl.SEED0 + 31)
+    return cfg, kw, po, pf
+
+
+@functools.lru_cache(maxsize=None)
+def _leg(variant, precision, S, opts):
+    """three closed-loop steps of one leg (computed once, shared by the tests, never modified)"""
+    _, kw, po, pf = _scene(S)
+    return paths._steps(variant, kw, po, pf, 3, precision, **dict(opts))
+
+
+def _same(a, b, what):
+    for x, y in zip(a, b):
+        for k in KEYS:
+            assert np.array_equal(x[k], y[k]), (what, k)
+
+
+def default_close_cap():
+    """the context default as the library's source states it"""
+    src = open(os.path.join(ROOT, "multiagent_planning_amd", "csrc", "dmpc_api.hip")).read()
+    return int(re.search(r"\bint close_cap = (\d+);", src).group(1))
+
+
+CASES = [("bound", "f64"), ("bound2", "f64"), ("all3", "f64"), ("ondemand", "f64"), ("cpp", "f64"), ("bound", "mixed")]
+
+
+@pytest.mark.parametrize("S", [2, 1])       # five-kernel grid of a batch; fused grid of one scene with the cell-ordered query
+@pytest.mark.parametrize("variant,precision", CASES)
+def test_close_pairs_do_not_change_a_bit(variant, precision, S):
+    on = _leg(variant, precision, S, (("grid_min", 256), ("close_pairs", 1)))
+    off = _leg(variant, precision, S, (("grid_min", 256), ("close_pairs", 0)))
+    plain = _leg(variant, precision, S, (("no_cull", 1),))
+    _same(on, off, (variant, precision, S, "close_pairs=0"))
+    _same(on, plain, (variant, precision, S, "no_cull"))
+    assert (on[-1]["info"][..., 1] > 0).any()      # some agents did build collision rows
+
+
+def _pairs_inside_rmin(po, pf, kw, h):
+    """per agent of one scene the (step, neighbour) pairs with dist < rmin on the initDMPC lines, fp64"""
+    t = np.arange(15) * h / 10
+    line = po[None, :, :] + t[:, None, None] * (pf - po)[None, :, :]            # [15, N, 3]
+    d = line[:, :, None, :] - line[:, None, :, :]
+    d[..., 2] /= kw["c"]
+    dist = np.sqrt((d * d).sum(-1))
+    idx = np.arange(po.shape[0])
+    dist[:, idx, idx] = np.inf
+    return (dist < kw["rmin"]).sum(axis=(0, 2))
+
+
+@pytest.mark.parametrize("S", [2, 1])
+def test_close_list_overflow_falls_back_to_the_walk(S):
+    """close_cap = 1: an agent with two or more pairs inside rmin overflows its close list and must take the list walk.  That the overflow
+    happens, and that the default capacity holds the first step without one, is shown from the CPU side."""
+    cfg, kw, po, pf = _scene(S)
+    cap = default_close_cap()
+    for s in range(S):
+        n = _pairs_inside_rmin(po[s], pf[s], kw, cfg["h"])
+        print(f"scene {s}: {(n > 0).sum()} of {len(n)} agents have a pair, {(n >= 2).sum()} have >= 2, maximum {n.max()}")
+        assert (n >= 2).any() and n.max() <= cap
+    one = _leg("bound", "f64", S, (("grid_min", 256), ("close_cap", 1)))
+    _same(one, _leg("bound", "f64", S, (("no_cull", 1),)), (S, "close_cap=1"))
+    assert (one[-1]["info"][..., 1] > 0).any()
+
+
+@pytest.mark.parametrize("regime", ["grid5", "grid2"])
+def test_close_pairs_on_a_sub_range_of_the_table(regime):
+    """c_count < C on a one-chunk table (uncommanded vehicles behind the commanded agents): batch of scenes and one scene"""
+    S, N, nc = obstacle_tests.REGIMES[regime]
+    kw, l, xp, xv, xa, pf = obstacle_tests._regime_inputs(regime)
+    outs = []
+    for close in (1, 0):
+        for precision in ("f64", "mixed"):
+            d = mp.Dmpc("bound", precision=precision, **kw).debug_option("close_pairs", close)
+            rc, o = ob.raw_step_batch_cmd(d, l, xp[:, :nc], xv[:, :nc], xa[:, :nc], pf[:, :nc], nc)
+            assert rc == 0, d._L.dmpc_last_error(d._ctx)
+            outs.append(o)
+    for a, b in zip(outs[:2], outs[2:]):
+        obstacle_tests._same_bytes(a, b, regime)
+        assert (a["info"][..., 1] > 0).any()
+
+
+def test_close_pairs_on_one_chunk_of_a_two_chunk_table():
+    """the ranks of a two-rank job in turn (unequal clusters: the second chunk's last column is padding), each against the rank-major table"""
+    import torch
+    N, G, S = 701, 2, 2
+    cfg, kw, po, pf = multigpu_tests._scenes(N, S, wl.SEED0 + 31)
+    l, _, _ = mp.Dmpc("bound", **kw).init_batch(po, pf)
+    z = np.zeros_like(po)
+    dev = torch.device("cuda", 0)
+    parts = [_lib.partition(N, G, r) for r in range(G)]
+    cmax = parts[0][2]
+    lT = np.zeros((G, S, 45, cmax))
+    for r, (lo, cnt, _) in enumerate(parts):
+        lT[r, :, :, :cnt] = l[:, lo:lo + cnt].transpose(0, 2, 1)
+    lT_d = torch.from_numpy(lT).to(dev)
+    L = _lib.load()
+    L.dmpc_debug_set_rank.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    rows = 0
+    for r, (lo, cnt, _) in enumerate(parts):
+        res = []
+        for close in (1, 0):
+            d = mp.Dmpc("bound", **kw).debug_option("grid_min", 256).debug_option("close_pairs", close)
+            assert L.dmpc_debug_set_rank(d._ctx, G, r) == 0
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a[:, lo:lo + cnt])).to(dev)
+            xp, xv, xa, gf = t(po), t(z), t(z), t(pf)
+            p = torch.zeros((S, cnt, 45), dtype=torch.float64, device=dev); v, a = torch.zeros_like(p), torch.zeros_like(p)
+            st = torch.zeros((S, cnt), dtype=torch.int32, device=dev); inf = torch.zeros((S, cnt, 8), dtype=torch.int32, device=dev)
+            nxt = torch.zeros_like(lT_d)
+            d.step_sharded_device(S, N, lT_d.data_ptr(), xp.data_ptr(), xv.data_ptr(), xa.data_ptr(), gf.data_ptr(), p.data_ptr(), v.data_ptr(),
+                                  a.data_ptr(), nxt.data_ptr(), st.data_ptr(), inf.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            res.append(dict(status=st.cpu().numpy(), info=inf.cpu().numpy(), p=p.cpu().numpy(), v=v.cpu().numpy(), a=a.cpu().numpy(),
+                            nxt=nxt[r].cpu().numpy()))
+        obstacle_tests._same_bytes(res[0], res[1], f"rank {r}")
+        rows += int((res[0]["info"][..., 1] > 0).sum())
+    assert rows > 0
