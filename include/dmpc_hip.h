@@ -334,6 +334,35 @@ DMPC_API int dmpc_transition_scripted(dmpc_ctx *ctx, int S, int N_cmd, int M, in
 DMPC_API int dmpc_scripted_cols_device(dmpc_ctx *ctx, int S, int N, int N_cmd, int P, const double *path_dev, int k, double *lT, float *lTf,
                               void *stream);
 
+/* Missions: one transition through a SEQUENCE of goal sets (formations A -> B -> C flown as one trajectory, a retarget at a known time, a
+ * formation that is only passed through).  NO REFERENCE COUNTERPART: the reference flies one leg (one pf, every agent at rest at the start,
+ * the trial over when pf is reached).  What it defines is the MPC step; this entry is that step in the loop a caller of
+ * dmpc_step_batch[_cmd] could write on the host, with the rule below applied between two steps -- on the device, so that the verdicts
+ * are still read one window behind the steps.  Additive: the ABI revision stays 8.
+ *   goals     [S][Q][N_cmd][3], Q >= 1 stages per scene; deadline [S][Q] (int32) or NULL = none: 0 = none, negative values are refused,
+ *             the last stage's entry must be 0.
+ *   stage 0   starts at history column 0, the initDMPC column: its straight lines run from po to goals[s][0], as in dmpc_transition.
+ *   a stage q < Q-1 ENDS AT THE FIRST COLUMN k at which (a) ReachedGoal holds on column k against goals[s][q] (max_i |p_i - pf_i| < error_tol,
+ *             the verdict of that column as dmpc_transition computes it) or (b) deadline[s][q] > 0 and k - k_start(q) >= deadline[s][q].
+ *             Then stage_col[s][q] = k, k_start(q+1) = k, and the step that produces column k+1 is the first one solved with goals[s][q+1].
+ *             THE TABLE IS NOT REWRITTEN: for that one step the neighbours see the plans made for the old goals, as a host loop's would.
+ *             AT MOST ONE STAGE ENDS PER COLUMN: stage q+1 is first examined on column k+1, also when its goals are stage q's (or are met
+ *             already) -- two stages with the same goals end on consecutive columns.
+ *   stage Q-1 reached on column k ends the trial: DMPC_ST_SOLVED | DMPC_ST_REACHED, K_T_used = k+1, stage_col[s][Q-1] = k (dmpc_transition's
+ *             rules).  Reaching an earlier stage never ends the trial and never sets DMPC_ST_REACHED.
+ *   failure   an agent whose status is not exactly DMPC_ST_SOLVED stops the scene as in dmpc_transition, in whatever stage; no stage ends on
+ *             that column.  stage_col of a stage that never ended is -1.
+ * K_T_max counts the columns of the whole mission.  pk, vk, ak: ONE [S][N_cmd][K_T_max][3] array each (or all three NULL), resident afterwards:
+ * dmpc_postcheck*, dmpc_postcheck_clearance with pf = goals[:, Q-1] work on them unchanged.  stage_col: [S][Q] or NULL.
+ * po: [S][N][3] without a path (N_cmd < N: static vehicles, as dmpc_transition_cmd); with path [S][N-N_cmd][P][3]: [S][N_cmd][3] and scripted
+ * vehicles, as dmpc_transition_scripted.  Q == 1 without deadline is dmpc_transition / _cmd / _scripted byte for byte.  Batch split as
+ * dmpc_transition (each part gets its scenes' goals, deadlines and stage_col); a DMPC_DEVICE_ALL context runs the call on its first GPU;
+ * there is no RCCL form.  Q < 1, a NULL goals, a negative deadline, a non-zero last deadline, or what the entries above refuse: -1 and a
+ * message that starts with the entry's name, nothing launched. */
+DMPC_API int dmpc_transition_mission(dmpc_ctx *ctx, int S, int N, int N_cmd, int Q, const double *po, const double *goals, const int32_t *deadline,
+                            const double *path, int P, int K_T_max, double error_tol, double *pk, double *vk, double *ak,
+                            int32_t *K_T_used, int32_t *scene_status, int32_t *stage_col);
+
 /* Multi-GPU: the agents of every scene sharded over the GPUs of one node, ONE PROCESS (rank) PER GPU, each with its own
  * context.  Replaces the thread clusters of DMPC::solveParallelDMPCv2 (dmpc/cpp/dmpc.cpp:1570-1686): contiguous agent ranges,
  * N/G each, the first N mod G one more (:1600-1625; dmpc_partition), every cluster reading the previous predictions of all

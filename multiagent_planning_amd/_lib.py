@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "dmpc_step_batch_cmd", "dmpc_step_device_cmd", "dmpc_transition_cmd", "dmpc_postcheck_cmd",
     "dmpc_transition_scripted", "dmpc_scripted_cols_device", "dmpc_postcheck_scripted",
     "dmpc_postcheck_clearance",
+    "dmpc_transition_mission",
 ]
 
 
@@ -132,6 +133,8 @@ def load():
     # clearance report: nearest vehicle, and when, per agent (additive, still revision 8)
     L.dmpc_postcheck_clearance.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, dp, dp, C.c_int, C.c_double, C.c_double,
                                            C.c_double, C.c_double, dp, ip, ip]
+    # missions: a transition through a sequence of goal sets (additive, still revision 8)
+    L.dmpc_transition_mission.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, ip, dp, C.c_int, C.c_int, C.c_double, dp, dp, dp, ip, ip, ip]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -385,6 +388,39 @@ class Dmpc:
             self._chk(self._L.dmpc_transition_cmd(self._ctx, S, N, n_cmd, _dp(po), _dp(pf), int(K_T_max), float(error_tol), hp[0], hp[1], hp[2],
                                                   _ip(used), _ip(sst)))
         return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst)
+
+    def mission(self, po, goals, K_T_max, error_tol=0.01, histories=True, deadline=None, path=None):
+        """dmpc_transition_mission: one transition through the Q goal sets goals [Q,N_cmd,3] (next to an unbatched po) or [S,Q,N_cmd,3].  A stage
+        ends at the first column where its goals are reached or -- deadline [Q] / [S,Q], 0 = none, the last 0 -- its deadline has passed; the
+        next step is solved with the next goal set, the last stage ends the trial.  po with MORE vehicles than the goals: static vehicles, as
+        transition(); path [S,M,P,3]: scripted vehicles, po then covers the commanded agents.  Returns what transition() returns, and stage_col
+        [S,Q]: the column each stage ended on (-1: it never did)."""
+        po, goals = _f(po), _f(goals)
+        if po.ndim not in (2, 3) or goals.ndim != po.ndim + 1 or po.shape[-1] != 3 or goals.shape[-1] != 3 or goals.shape[:-3] != po.shape[:-2]:
+            raise DmpcError(f"mission: goals {tuple(goals.shape)} must be [Q,N_cmd,3] next to po [N,3], or [S,Q,N_cmd,3] next to po [S,N,3]: po is {tuple(po.shape)}")
+        S = 1 if po.ndim == 2 else po.shape[0]
+        Q, n_cmd, N = goals.shape[-3], goals.shape[-2], po.shape[-2]
+        lead = po.shape[:-2] + (n_cmd,)
+        M = P = 0
+        if path is not None:
+            if N != n_cmd:
+                raise DmpcError(f"mission: with path, po {tuple(po.shape)} and goals {tuple(goals.shape)} must cover the same commanded agents")
+            path, M, P = _path(path, lead, "mission")
+        elif n_cmd < 1 or n_cmd > N:
+            raise DmpcError(f"mission: goals have {n_cmd} agents, po {N}: the commanded agents are the FIRST N_cmd <= N vehicles")
+        nul, inul = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
+        if deadline is not None:
+            deadline = np.ascontiguousarray(np.broadcast_to(np.asarray(deadline, dtype=np.int32), (S, Q)))
+        used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+        stage_col = np.zeros((S, Q), dtype=np.int32)
+        pk = vk = ak = None
+        if histories:
+            pk, vk, ak = (np.zeros(lead + (K_T_max, 3)) for _ in range(3))
+        self._chk(self._L.dmpc_transition_mission(self._ctx, S, N + M, n_cmd, Q, _dp(po), _dp(goals), _ip(deadline) if deadline is not None else inul,
+                                                  _dp(path) if path is not None else nul, P, int(K_T_max), float(error_tol),
+                                                  _dp(pk) if histories else nul, _dp(vk) if histories else nul, _dp(ak) if histories else nul,
+                                                  _ip(used), _ip(sst), _ip(stage_col)))
+        return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, stage_col=stage_col)
 
     # ---- multi-GPU (one process per GPU): dmpc_multigpu.hip ----
     @staticmethod

@@ -154,6 +154,7 @@ struct dmpc_ctx {
     DevBuf pc_p, pc_v, pc_a, pc_M, pc_w, pc_scene, pc_agent, pc_interp;   // post-check work buffers
     DevBuf pc_static;                                                      // post-check: positions of the uncommanded vehicles + their per-scene minimum
     DevBuf path;                                                           // dmpc_transition_scripted: the scripted vehicles' paths [S][M][P][3], resident for the call
+    DevBuf mis_goals, mis_state;                                           // dmpc_transition_mission: goal sets [S][Q][N_cmd][3]; ints: stage [S], k_start [S], stage_col [S][Q], deadline [S][Q]
     DevBuf pc_sc_path, pc_sc_y, pc_sc_M, pc_sc_w, pc_sc_pts, pc_sc_interp; // dmpc_postcheck_scripted: paths, knots, second derivatives, scratch, sample batch, p_scripted
     DevBuf pc_pts, pc_cell, pc_fill, pc_start, pc_sorted, pc_on;           // post-check, large scenes: cell grid of a batch of samples
     DevBuf pc_cl_part, pc_cl_run, pc_cl_out;                               // dmpc_postcheck_clearance: partials of a sample batch, running best, report
@@ -1008,10 +1009,19 @@ extern "C" int dmpc_init_batch(dmpc_ctx *ctx, int S, int N, const double *po, co
 // scene verdict are sized and strided by N_cmd (A agents); the tables and neighbour structures by N (T columns).  N_cmd == N: dmpc_transition.
 // path != null (dmpc_transition_scripted): the N - N_cmd vehicles behind the commanded ones follow path[S][N - N_cmd][P][3]; po is then
 // [S][N_cmd][3], and one launch before every step writes their columns of the current table (scripted_cols_kernel).
+// mission != null (dmpc_transition_mission): pf is ignored, the goal sets are mission->goals [S][Q][N_cmd][3], resident for the call; stage 0's go
+// into ctx->pf, and one launch after the verdict of every column (mission_stage_kernel) applies the stage rule there.
+struct Mission {
+    int Q;
+    const double *goals;       // [S][Q][N_cmd][3]
+    const int32_t *deadline;   // [S][Q] or null
+    int32_t *stage_col;        // [S][Q] or null
+};
 static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
                           double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                          int32_t *scene_status, const double *path = nullptr, int P = 0)
+                          int32_t *scene_status, const double *path = nullptr, int P = 0, const Mission *mission = nullptr)
 {
+    if (mission) pf = mission->goals;
     if (!ctx) { g_err = "dmpc_transition: ctx is NULL"; return -1; }
     if (S < 1 || N < 1 || N_cmd < 1 || N_cmd > N || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status || ((pk || vk || ak) && !(pk && vk && ak)))
         FAIL(ctx, "dmpc_transition: bad arguments");
@@ -1031,6 +1041,18 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
         HIPCHK(ctx, hipMemcpyAsync(ctx->path.p, path, path_bytes, hipMemcpyHostToDevice, st));
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, po, (path ? A : T) * 24, hipMemcpyHostToDevice, st));
+    const int Q = mission ? mission->Q : 1;
+    int *mis_stage = nullptr, *mis_k0 = nullptr, *mis_col = nullptr, *mis_dl = nullptr;
+    if (mission) {   // the goal sets and the deadlines go up once per call; stage = k_start = 0, stage_col = -1
+        const size_t SQ = (size_t)S * Q;
+        if (ctx->pf.ensure(A * 24) || ctx->mis_goals.ensure(SQ * N_cmd * 24) || ctx->mis_state.ensure((2 * (size_t)S + 2 * SQ) * 4)) FAIL(ctx, "device allocation failed");
+        mis_stage = ctx->mis_state.as<int>(); mis_k0 = mis_stage + S; mis_col = mis_k0 + S; mis_dl = mission->deadline ? mis_col + SQ : nullptr;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->mis_goals.p, mission->goals, SQ * N_cmd * 24, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpy2DAsync(ctx->pf.p, (size_t)N_cmd * 24, ctx->mis_goals.p, (size_t)Q * N_cmd * 24, (size_t)N_cmd * 24, (size_t)S, hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemsetAsync(mis_stage, 0, 2 * (size_t)S * 4, st));
+        HIPCHK(ctx, hipMemsetAsync(mis_col, 0xff, SQ * 4, st));
+        if (mis_dl) HIPCHK(ctx, hipMemcpyAsync(mis_dl, mission->deadline, SQ * 4, hipMemcpyHostToDevice, st));
+    } else
     HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, pf, A * 24, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemsetAsync(ctx->flags.p, 0, (size_t)K_T_max * S * 8, st));
     HIPCHK(ctx, hipMemsetAsync(ctx->scene_done.p, 0, (size_t)S * 4, st));
@@ -1064,6 +1086,10 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
     HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->status.p, DMPC_ST_SOLVED, A, st));
     hipLaunchKernelGGL(scene_reduce_kernel, dim3((unsigned)S), dim3(256), 0, st, N_cmd, error_tol, xp, ctx->pf.as<double>(),
                        (const int *)ctx->status.as<int32_t>(), ctx->flags.as<int>(), ctx->scene_done.as<int>());
+    const unsigned mis_threads = N_cmd * 3 >= 256 ? 256 : 64;
+    if (mission)   // a first stage that is reached on the initDMPC column ends there
+        hipLaunchKernelGGL(mission_stage_kernel, dim3((unsigned)S), dim3(mis_threads), 0, st, N_cmd, Q, 0, (const double *)ctx->mis_goals.as<double>(),
+                           (const int *)mis_dl, ctx->flags.as<int>(), ctx->scene_done.as<int>(), mis_stage, mis_k0, mis_col, ctx->pf.as<double>());
     double *cur = ctx->lT.as<double>(), *nxt = ctx->lT2.as<double>();
     ctx->post_acc_S = 0;   // the scene accumulators of the fused post-step start from zero in every transition
     const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;   // the scan of every step reads an fp32 copy of the current table
@@ -1126,6 +1152,10 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
                            (const int *)ctx->status.as<int32_t>(), xp, xv, xa, (const double *)ctx->pf.as<double>(), ctx->hist_p.as<double>(),
                            ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>(),
                            (const int *)ctx->scene_done.as<int>());
+        if (mission)   // the stage rule on column k, behind its verdict (post_step_kernel above, or the fused post step of the solve launch)
+            hipLaunchKernelGGL(mission_stage_kernel, dim3((unsigned)S), dim3(mis_threads), 0, st, N_cmd, Q, k, (const double *)ctx->mis_goals.as<double>(),
+                               (const int *)mis_dl, ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>(), mis_stage, mis_k0, mis_col,
+                               ctx->pf.as<double>());
         HIPCHK(ctx, hipGetLastError());
         std::swap(cur, nxt);   // l = new_l (dmpc_soft_bound.m:146)
         if (k % chunk == 0 || k == K_T_max - 1) {
@@ -1144,6 +1174,7 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
         HIPCHK(ctx, hipMemcpyAsync(vk, ctx->hist_v.p, hist, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipMemcpyAsync(ak, ctx->hist_a.p, hist, hipMemcpyDeviceToHost, st));
     }
+    if (mission && mission->stage_col) HIPCHK(ctx, hipMemcpyAsync(mission->stage_col, mis_col, (size_t)S * Q * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     ctx->hist_S = S; ctx->hist_N = N_cmd; ctx->hist_KT = K_T_max;   // (the resident histories are the commanded agents')
     return 0;
@@ -1163,11 +1194,12 @@ static void copy_debug_options(dmpc_ctx *dst, const dmpc_ctx *src)
 // threads): the tail of one half overlaps the bulk of the other (512 transitions of 100 agents: 103 -> 60 ms).
 static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
                           double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                          int32_t *scene_status, const double *path = nullptr, int P = 0)
+                          int32_t *scene_status, const double *path = nullptr, int P = 0, const Mission *mission = nullptr)
 {
     ctx->split_at.clear();
     // uncommanded vehicles on a DMPC_DEVICE_ALL context: the first GPU alone (the rule for N < 2 G below); the batch split further down applies unchanged
-    if (ctx->grp && N_cmd == N) {   // every visible GPU: the agents of each scene sharded over them (dmpc_multigpu.hip)
+    // (a mission too: its first GPU, whether or not every vehicle is commanded)
+    if (ctx->grp && N_cmd == N && !mission) {   // every visible GPU: the agents of each scene sharded over them (dmpc_multigpu.hip)
         if (S < 1 || N < 1 || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status || ((pk || vk || ak) && !(pk && vk && ak))) FAIL(ctx, "dmpc_transition: bad arguments");
         // Batches of 64 or more scenes run as TWO groups side by side (a second set of rank contexts, threads and streams on the same
         // GPUs): scenes are independent, so while one half's ranks exchange their predictions (peer copies, barrier, events) the
@@ -1210,7 +1242,7 @@ static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
     int parts = ctx->opt.split_parts > 0 ? ctx->opt.split_parts : (S >= 128 ? 4 : (S >= 32 ? 2 : 1));
     if (parts > S) parts = S;
     if (parts < 2 || ctx->opt.no_split || ctx->grp || N < 1 || N_cmd < 1 || N_cmd > N || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status)
-        return transition_one(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, P);
+        return transition_one(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, P, mission);
     while ((int)ctx->children.size() < parts - 1) {
         dmpc_ctx *ch = dmpc_create(&ctx->prm, ctx->device, ctx->precision);
         if (!ch) FAIL(ctx, "dmpc_transition: further context: " + g_err);
@@ -1229,8 +1261,15 @@ static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
         const int s0 = at[(size_t)i], sn = at[(size_t)i + 1] - s0;
         const size_t a0 = (size_t)s0 * N_cmd, h0 = a0 * (size_t)K_T_max * 3;   // po is strided by N, everything else by N_cmd ...
         const size_t t0 = path ? a0 : (size_t)s0 * N;                          // ... (scripted vehicles: po covers the commanded agents, and each part gets its scenes' paths)
+        Mission part{};   // a mission: the part's scenes' slices of the goal sets, the deadlines and stage_col
+        if (mission) {
+            const size_t q0 = (size_t)s0 * mission->Q;
+            part = Mission{mission->Q, mission->goals + q0 * N_cmd * 3, mission->deadline ? mission->deadline + q0 : nullptr,
+                           mission->stage_col ? mission->stage_col + q0 : nullptr};
+        }
         rc[(size_t)i] = transition_one(c, sn, N, N_cmd, po + t0 * 3, pf + a0 * 3, K_T_max, error_tol, pk ? pk + h0 : nullptr, vk ? vk + h0 : nullptr,
-                                       ak ? ak + h0 : nullptr, K_T_used + s0, scene_status + s0, path ? path + (size_t)s0 * (N - N_cmd) * P * 3 : nullptr, P);
+                                       ak ? ak + h0 : nullptr, K_T_used + s0, scene_status + s0, path ? path + (size_t)s0 * (N - N_cmd) * P * 3 : nullptr, P,
+                                       mission ? &part : nullptr);
     };
     std::vector<std::thread> th;
     for (int i = 1; i < parts; ++i) th.emplace_back(run, i);
@@ -1286,6 +1325,32 @@ extern "C" int dmpc_transition_scripted(dmpc_ctx *ctx, int S, int N_cmd, int M, 
     if (K_T_max < 2 || !po || !pf || !K_T_used || !scene_status) FAIL(ctx, "dmpc_transition_scripted: bad arguments");
     // (a DMPC_DEVICE_ALL context: N_cmd < N, its first GPU)
     return transition_any(ctx, S, N_cmd + M, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, P);
+}
+
+// Missions: a transition through a sequence of goal sets.  No reference counterpart (the reference flies one leg); the step is the
+// reference's, the stage rule the loop a caller of dmpc_step_batch[_cmd] could write on the host -- applied on the device after the verdict of
+// every column (mission_stage_kernel), so that the host keeps reading the verdicts one window behind.
+extern "C" int dmpc_transition_mission(dmpc_ctx *ctx, int S, int N, int N_cmd, int Q, const double *po, const double *goals, const int32_t *deadline,
+                                       const double *path, int P, int K_T_max, double error_tol, double *pk, double *vk, double *ak,
+                                       int32_t *K_T_used, int32_t *scene_status, int32_t *stage_col)
+{
+    if (!ctx) { g_err = "dmpc_transition_mission: ctx is NULL"; return -1; }
+    if (check_cmd(ctx, "dmpc_transition_mission", S, N, N_cmd)) return -1;
+    if (Q < 1) FAIL(ctx, "dmpc_transition_mission: Q must be >= 1 (a mission has at least one stage)");
+    if (!goals) FAIL(ctx, "dmpc_transition_mission: goals is NULL");
+    if (path && check_scripted(ctx, "dmpc_transition_mission", S, N_cmd, N - N_cmd, P)) return -1;
+    if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, "dmpc_transition_mission: pk, vk, ak must be all given or all NULL");
+    if (K_T_max < 2 || !po || !K_T_used || !scene_status) FAIL(ctx, "dmpc_transition_mission: bad arguments");
+    if ((size_t)S * (size_t)Q > 0x7fffffffu) FAIL(ctx, "dmpc_transition_mission: S * Q overflows");
+    if (deadline)
+        for (int s = 0; s < S; ++s) {
+            for (int q = 0; q < Q; ++q)
+                if (deadline[(size_t)s * Q + q] < 0) FAIL(ctx, "dmpc_transition_mission: a deadline is negative (0: none)");
+            if (deadline[(size_t)s * Q + Q - 1] != 0) FAIL(ctx, "dmpc_transition_mission: the last stage's deadline must be 0 (the last stage ends the trial when it is reached)");
+        }
+    const Mission mission{Q, goals, deadline, stage_col};
+    // (a DMPC_DEVICE_ALL context: its first GPU)
+    return transition_any(ctx, S, N, N_cmd, po, goals, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, path ? P : 0, &mission);
 }
 
 // the fill of dmpc_transition_scripted for callers that loop over dmpc_step_device_cmd themselves

@@ -2086,4 +2086,45 @@ __global__ void scene_reduce_kernel(int N, double tol, const double *__restrict_
     }
 }
 
+// Missions (dmpc_transition_mission): the stage rule of one scene after the post step of history column k, one block per scene.  Launched in
+// stream order behind whatever wrote flags[s] = (reached, OR of status bits) and scene_done[s] for column k: scene_reduce_kernel (k = 0),
+// post_step_kernel, or the fused post step of a tiny launch.  The fused post step's per-scene accumulators (post_max / post_or / post_cnt) need
+// nothing from here: the wave that counts a scene's last agent of a step exchanges the maximum and the OR for zero and stores zero to the
+// count before it writes the verdict, and a scene that is skipped never touches them, so they are zero for every scene when that solve launch
+// has ended -- before this kernel starts, whether the scene goes on or not.
+//   goals [S][Q][N][3], deadline [S][Q] or null, flags: column k's [S][2], stage / k_start / stage_col: [S], [S], [S][Q]
+// stage[s] == Q: the mission of the scene is over (last stage reached, or an agent failed).  Every value the branches test is the same for all
+// threads of a block, and the barrier stands in front of them.
+__global__ void mission_stage_kernel(int N, int Q, int k, const double *__restrict__ goals, const int *__restrict__ deadline, int *flags,
+                                     int *scene_done, int *stage, int *k_start, int *stage_col, double *pf)
+{
+    const int s = blockIdx.x;
+    const int q = stage[s];
+    const int reached = flags[(size_t)s * 2], bits = flags[(size_t)s * 2 + 1];
+    const int k0 = k_start[s];
+    const int dl = (deadline && q < Q) ? deadline[(size_t)s * Q + q] : 0;
+    __syncthreads();   // every thread has read the scene's words before thread 0 rewrites them
+    if (q >= Q || bits == 0) return;   // over, or column k was never written (the scene had stopped before)
+    if (bits & ~ST_SOLVED) {           // a failed agent stops the scene as in dmpc_transition: scene_done stays set, no stage ends
+        if (threadIdx.x == 0) stage[s] = Q;
+        return;
+    }
+    if (q == Q - 1) {                  // the last stage ends the trial when it is reached (the verdict stands as the post step wrote it)
+        if (reached && threadIdx.x == 0) { stage_col[(size_t)s * Q + q] = k; stage[s] = Q; }
+        return;
+    }
+    if (!(reached || (dl > 0 && k - k0 >= dl))) return;
+    // stage q ends on column k: the step that produces column k + 1 is solved with the next goal set; the table is left as it is
+    const double *src = goals + ((size_t)s * Q + q + 1) * (size_t)N * 3;
+    double *dst = pf + (size_t)s * N * 3;
+    for (int i = threadIdx.x; i < N * 3; i += blockDim.x) dst[i] = src[i];
+    if (threadIdx.x == 0) {
+        stage_col[(size_t)s * Q + q] = k;
+        stage[s] = q + 1;
+        k_start[s] = k;
+        flags[(size_t)s * 2] = 0;      // the host must not read "reached" for an intermediate stage
+        scene_done[s] = 0;             // (the status word is clean here: a failed scene returned above and stays done)
+    }
+}
+
 }  // namespace dmpc

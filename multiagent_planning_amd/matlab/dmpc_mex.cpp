@@ -19,6 +19,7 @@
 //   [xi,rhs,dist,kc,viol_k,coll] = dmpc_mex('rows_one', params, l, n, po, vo)           CheckCollSoftDMPC + CollConstr*DMPC rows
 //   Ain            = dmpc_mex('rows_dense', params, xi, kc, A)                          -diff_mat*A of structured rows
 //   [pk,vk,ak,K_T_used,scene_status] = dmpc_mex('transition', params, po, pf, K_T_max, error_tol)   the whole k-loop on the GPU
+//   [pk,vk,ak,K_T_used,scene_status,stage_col] = dmpc_mex('mission', params, po, goals, K_T_max, error_tol[, deadline])   goals 3 x N_cmd x Q: see below
 //   inbounds       = dmpc_mex('is_inbounds', params, p, pmin, pmax)                    is_inbounds.m
 //   pass           = dmpc_mex('reached_goal', params, p, pf, error_tol)                ReachedGoal.m
 //   tol            = dmpc_mex('max_deviation', params, p, prev_p)                      maxDeviation.m (p, prev_p: 3 x K)
@@ -27,6 +28,9 @@
 // Uncommanded vehicles (DMPC::solveParallelDMPCv2, dmpc/cpp/dmpc.cpp:1572-1573: N = _po.cols(), N_cmd = _pf.cols()): 'transition' and
 // 'step_batch' take pf (and the states) with FEWER columns than po / l -- the first N_cmd vehicles are commanded, the others stay at po as
 // static obstacles, and the outputs cover the commanded ones; 'postcheck' takes po_static (3 x M) behind Ts.
+// Missions (dmpc_transition_mission, no reference counterpart): 'mission' is 'transition' through the Q goal sets goals(:,:,q) one after the
+// other -- a stage ends at the first column where its goals are reached or its deadline (1 x Q, 0 = none, the last 0) has passed; stage_col
+// (1 x Q) holds the 0-based history column each stage ended on, -1 for a stage that never did.  N_cmd < N: static vehicles, as 'transition'.
 // `params` is a struct with the fields of dmpc_params (variant as the DMPC_VAR_* integer).
 // The signature-preserving wrappers (solveSoftDMPCbound.m, ...) in this directory call 'solve_one'
 // and convert status bits into the reference's [] + flag conventions.
@@ -381,6 +385,34 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
         if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);
         if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
+        return;
+    }
+    if (!std::strcmp(cmd, "mission")) {   // one trial through a sequence of goal sets (dmpc_transition_mission)
+        need(nrhs == 6 || nrhs == 7, "mission: (cmd, params, po, goals, K_T_max, error_tol[, deadline])");
+        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3), KT = (int)mxGetScalar(prhs[4]);
+        const mwSize *gd = mxGetDimensions(prhs[3]);
+        const int Nc = mxGetNumberOfDimensions(prhs[3]) >= 2 ? (int)gd[1] : 0;
+        const int Q = Nc >= 1 ? (int)(mxGetNumberOfElements(prhs[3]) / ((size_t)3 * Nc)) : 0;
+        need(N >= 1 && Nc >= 1 && Nc <= N && Q >= 1 && gd[0] == 3 && mxGetNumberOfElements(prhs[3]) == (size_t)3 * Nc * Q && KT >= 2,
+             "po must be 3 x N, goals 3 x N_cmd x Q (N_cmd <= N, Q >= 1), K_T_max >= 2");
+        const bool with_dl = nrhs == 7 && mxGetNumberOfElements(prhs[6]) > 0;
+        need(!with_dl || mxGetNumberOfElements(prhs[6]) == (size_t)Q, "deadline must have Q elements (or be empty)");
+        std::vector<int32_t> dl((size_t)Q, 0), col((size_t)Q, -1);
+        for (int q = 0; with_dl && q < Q; ++q) dl[(size_t)q] = (int32_t)mxGetPr(prhs[6])[q];
+        const mwSize d3[3] = {3, (mwSize)KT, (mwSize)Nc};
+        plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        mxArray *v = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), *a = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        int32_t used = 0, sst = 0;
+        if (dmpc_transition_mission(ctx, 1, N, Nc, Q, mxGetPr(prhs[2]), mxGetPr(prhs[3]), with_dl ? dl.data() : nullptr, nullptr, 0, KT,
+                                    mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v), mxGetPr(a), &used, &sst, col.data()))
+            mexErrMsgIdAndTxt("dmpc:mission", "%s", dmpc_last_error(ctx));
+        if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);
+        if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
+        if (nlhs > 5) {
+            plhs[5] = mxCreateDoubleMatrix(1, (mwSize)Q, mxREAL);
+            for (int q = 0; q < Q; ++q) mxGetPr(plhs[5])[q] = (double)col[(size_t)q];
+        }
         return;
     }
     if (!std::strcmp(cmd, "random_test") || !std::strcmp(cmd, "random_exchange")) {   // randomTest.m / randomExchange.m
