@@ -15,11 +15,12 @@ from multiagent_planning_amd import workload as wl
 pytestmark = pytest.mark.gpu
 
 
-def _steps(variant, kw, po, pf, nsteps, precision="f64", **opts):
+def _steps(variant, kw, po, pf, nsteps, precision="f64", table=None, **opts):
+    """closed-loop steps from rest at po; table: the first step's prediction table instead of initDMPC's straight lines"""
     d = mp.Dmpc(variant, precision=precision, **kw)
     for k_, v_ in opts.items():
         d.debug_option(k_, v_)
-    l, _, _ = d.init_batch(po, pf)
+    l = d.init_batch(po, pf)[0] if table is None else table
     xp, xv, xa = po.copy(), np.zeros_like(po), np.zeros_like(po)
     outs = []
     for _ in range(nsteps):
@@ -137,8 +138,6 @@ def test_crash_start_reaches_the_same_minimiser(variant, monkeypatch):
     a = new[0]
     # the crash start did run: fewer full iterations are impossible to see from outside, but the working sets are large
     assert a["info"][..., 7].max() >= 20
-    if variant != "repair":
-        assert (a["info"][..., 2] > 1).any() or True
 
 
 @pytest.mark.parametrize("variant,N,S,opts", [("bound", 100, 40, {}), ("bound", 100, 40, {"force_persist": 1}), ("bound2", 60, 8, {}), ("ondemand", 100, 24, {}),
