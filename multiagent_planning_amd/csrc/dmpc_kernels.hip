@@ -42,6 +42,10 @@ __device__ __forceinline__ double readlane_d(double v, int l /*uniform*/)
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ int readlane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+// wave-uniform by construction, not by what the compiler can see (a value read from LDS or global memory at a uniform address, the result
+// of an out-of-line function): say so -- everything derived from it is then scalar, branches on it are scalar branches
+#define UNI(x_) __builtin_amdgcn_readfirstlane(x_)
+__device__ __forceinline__ bool uni_b(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
 
 // Wave-wide reductions on the VALU with DPP row shifts / row broadcasts (gfx9 scan idiom): six
 // steps, no LDS crossbar traffic (a ds_bpermute butterfly costs ~10x more here).  Lane 63 ends up
@@ -197,6 +201,171 @@ __device__ __forceinline__ KargPtr kernarg_params()
     asm volatile("" : "+s"(p));
     return p;
 }
+typedef const double __attribute__((address_space(4))) *ConstD;
+
+// ---- the agent prologue, output stage and record of the three kernels that can finish an agent: the scan's unconstrained exit, the general
+// ---- solver (dmpc_solve.hip) and the reduced solver (dmpc_rsolve.hip).  One definition each: the outputs are the same words whichever finishes it.
+// which agent a wave works for: index vb of the launch -> scene, column ci of the launch, column cl of chunk g_local, index gid into the launch's arrays
+struct AgentId { int scene, ci, cl, gid; };
+__device__ __forceinline__ AgentId agent_id(const StepParams &P, const int vb)
+{
+    AgentId I;
+    I.scene = vb / P.c_count; I.ci = vb - I.scene * P.c_count;
+    I.cl = P.c_first + I.ci;
+    I.gid = I.scene * P.c_count + I.ci;
+    return I;
+}
+// ... and what the scan handed over about it: the eight-int header, and the branch record unpacked from it.  (Wave-uniform integers only: the
+// agent's state vectors stay plain local arrays of the callers -- a struct the compiler sends to scratch must not make them addressable.)
+struct Handoff : AgentId {
+    int hdr[8];
+    int nr, status, nrows_built, viol_k;
+    bool violation, rows_exist, coll0;   // coll0 (cpp): collision noticed at the first step, solution still returned
+};
+// (readfirstlane: the header is read with vector loads -- the scan wrote it in this launch's lifetime, no scalar load -- and everything
+// derived from it, the row count, the status word, the ladder start, would be compiled as lane-dependent: masked loops, vector compares)
+__device__ __forceinline__ Handoff agent_handoff(const StepParams &P, const int vb)
+{
+    Handoff I;
+    static_cast<AgentId &>(I) = agent_id(P, vb);
+    const int *hdr = P.hdr + (size_t)I.gid * 8;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) I.hdr[i] = UNI(hdr[i]);
+    I.nr = I.hdr[0]; I.nrows_built = I.hdr[1]; I.viol_k = I.hdr[2]; I.status = I.hdr[3];
+    I.violation = (I.hdr[4] & 1) != 0; I.coll0 = (I.hdr[4] & 4) != 0; I.rows_exist = I.hdr[5] != 0;
+    return I;
+}
+
+// Closed loops, tiny launches: the work of post_step_kernel for one agent (dmpc_soft_bound.m:132-134, the history column,
+// ReachedGoal.m:3-11), done by the wave that produced the agent's step; p_out, v_out, a_out: lanes 0..2 hold the first horizon column.
+// The scene's maximum / OR / count are order-independent, so which wave finishes last changes nothing.
+__device__ __forceinline__ void post_step_part(const KargPtr Qp, const int lane, const int gid, const int scene, const bool solved,
+                                               const int status, const double p_out, const double v_out, const double a_out)
+{
+    double xn = 0.0, vn = 0.0, an = 0.0, e2 = 0.0;
+    if (lane < 3) {
+        const size_t b = (size_t)gid * 3 + lane;
+        xn = solved ? p_out : Qp->post_xp[b]; vn = solved ? v_out : Qp->post_xv[b]; an = solved ? a_out : Qp->post_xa[b];
+        if (solved) { Qp->post_xp[b] = xn; Qp->post_xv[b] = vn; Qp->post_xa[b] = an; }
+        const size_t ho = ((size_t)gid * Qp->post_KT + Qp->post_k) * 3 + lane;
+        Qp->post_pk[ho] = xn; Qp->post_vk[ho] = vn; Qp->post_ak[ho] = an;
+        const double dd = xn - Qp->pf[b];
+        e2 = dd * dd;
+    }
+    const double dx2 = readlane_d(e2, 0), dy2 = readlane_d(e2, 1), dz2 = readlane_d(e2, 2);
+    if (lane == 0) {
+        const double dist = sqrt(dx2 + dy2 + dz2);
+        atomicMax(Qp->post_max + scene, (unsigned long long)__double_as_longlong(dist));
+        atomicOr(Qp->post_or + scene, status);
+        __threadfence();
+        if (atomicAdd(Qp->post_cnt + scene, 1) == Qp->c_count - 1) {   // the scene's last agent of this step
+            const unsigned long long mb = atomicExch(Qp->post_max + scene, 0ull);
+            const int orv = atomicExch(Qp->post_or + scene, 0);
+            Qp->post_cnt[scene] = 0;
+            const int reached = __longlong_as_double((long long)mb) < Qp->post_tol ? 1 : 0;
+            Qp->post_flags[(size_t)scene * 2] = reached; Qp->post_flags[(size_t)scene * 2 + 1] = orv;
+            if (Qp->post_done && (reached || (orv & ~ST_SOLVED))) Qp->post_done[scene] = 1;
+        }
+    }
+}
+
+// Nothing to do for this agent in a solve launch: its scene already stopped, or the scan finished it (unconstrained exit) -- a fused
+// post-step still takes its outputs then.  Returns whether the caller returns.
+__device__ __forceinline__ bool agent_skip(const StepParams &P, const int lane, const Handoff &I)
+{
+    if (I.hdr[4] & 8) return true;
+    if (I.hdr[4] & 16) {
+        if (P.post_on) {
+            const KargPtr Qp = kernarg_params();
+            const int st_done = Qp->status[I.gid];
+            double p1 = 0.0, v1 = 0.0, a1 = 0.0;
+            if (lane < 3) { p1 = Qp->p_out[(size_t)I.gid * N3 + lane]; v1 = Qp->v_out[(size_t)I.gid * N3 + lane]; a1 = Qp->a_out[(size_t)I.gid * N3 + lane]; }
+            post_step_part(Qp, lane, I.gid, I.scene, (st_done & ST_SOLVED) != 0, st_done, p1, v1, a1);
+        }
+        return true;
+    }
+    return false;
+}
+
+// solveQPv2 / solveQP / solveSoftDMPC[_c] / solveDMPC have no in-bounds test behind the solve
+// (the reduced solver only ever sees bound, bound2, cpp and cpp2: there this is !cppv)
+__device__ __forceinline__ bool has_inbounds_test(const int var)
+{
+    return !(var == VAR_ELLIP || var == VAR_SOFTALL || var == VAR_SOFTALL_C || var == VAR_SCP || var == VAR_CPP1 || var == VAR_CPP || var == VAR_CPP2);
+}
+
+// The agent's position and velocity on axis `ax`, read AGAIN behind the solver loop -- six SCALAR loads through constant-address-space
+// pointers (the values are wave-uniform) -- instead of living in registers across it
+__device__ __forceinline__ void state_again(const KargPtr Qp, const int gid, const int ax, double &po_l, double &vo_l)
+{
+    const ConstD sp = (ConstD)(unsigned long long)(Qp->x_p + 3 * (size_t)gid), sv_ = (ConstD)(unsigned long long)(Qp->x_v + 3 * (size_t)gid);
+    const double po0 = sp[0], po1 = sp[1], po2 = sp[2], vo0 = sv_[0], vo1 = sv_[1], vo2 = sv_[2];
+    vo_l = ax == 0 ? vo0 : (ax == 1 ? vo1 : vo2);
+    po_l = ax == 0 ? po0 : (ax == 1 ? po1 : po2);
+}
+
+// a9/a10, the output stage: propagate, in-bounds test, outputs + next table chunk, fused post-step.  `oc`: this lane holds output component
+// (k, ax) = lane 3 k + ax of the stacked vectors, `w` and `a` its position offset and acceleration, `a_s` the stacked accelerations in LDS;
+// `post`: a fused post-step is this kernel's to do (the solvers; the scan leaves it to the solve launch: agent_skip); `status` comes in
+// with everything but ST_OUTBOUND and goes out complete.
+__device__ __forceinline__ int agent_outputs(const KargPtr Qp, const int lane, const AgentId &I, const bool oc, const int k, const int ax,
+                                             const bool solved, const double w, const double a, const double *a_s,
+                                             const bool inbounds_test, const bool post, int status)
+{
+    const int gid = I.gid;
+    double p_out = 0.0, v_out = 0.0, a_out = 0.0;
+    if (solved && oc) {   // p = A_p a + A_initp [po;vo] ; v = A_v a + vo   (propStatedmpc.m:3-4)
+        double po_l, vo_l;
+        state_again(Qp, gid, ax, po_l, vo_l);
+        p_out = w + init_pos(k, Qp->h, vo_l, po_l);
+        v_out = vel_out(a_s, k, ax, Qp->h, vo_l);
+        a_out = a;
+    }
+    if (solved && inbounds_test) {   // is_inbounds.m:2-5 on p(:,1)
+        const double tolb = 50e-3;
+        bool bad = false;
+        const double hi3 = lane == 0 ? Qp->pmax[0] : (lane == 1 ? Qp->pmax[1] : Qp->pmax[2]), lo3 = lane == 0 ? Qp->pmin[0] : (lane == 1 ? Qp->pmin[1] : Qp->pmin[2]);
+        if (lane < 3) bad = !(p_out < hi3 + tolb) || !(p_out > lo3 - tolb);
+        if (__any(bad)) status |= ST_OUTBOUND;
+    }
+    if (oc) {
+        Qp->p_out[(size_t)gid * N3 + lane] = p_out;
+        Qp->v_out[(size_t)gid * N3 + lane] = v_out;
+        Qp->a_out[(size_t)gid * N3 + lane] = a_out;
+        if (Qp->lT_next) {
+            // next table chunk [S][3K][C]: uniform 64-bit base, 32-bit per-lane offset; unsolved agents keep their old prediction
+            const int Cq = Qp->C;
+            // (mixed precision: Qp->lT is the fp32 table of the scan; the fp64 predictions of this chunk are in Qp->own_prev)
+            const double *own = Qp->own_prev ? Qp->own_prev + (size_t)I.scene * N3 * Cq + I.cl : Qp->lT + ((size_t)(Qp->g_local * Qp->S + I.scene) * N3) * Cq + I.cl;
+            Qp->lT_next[(size_t)I.scene * N3 * Cq + I.cl + (size_t)(unsigned)(lane * Cq)] = solved ? p_out : own[(size_t)(unsigned)(lane * Cq)];
+        }
+    }
+    if (post && Qp->post_on) post_step_part(Qp, lane, gid, I.scene, solved, status, p_out, v_out, a_out);
+    return status;
+}
+
+// lane 0 of a solver: the agent's status word, work estimate and branch record
+__device__ __forceinline__ void agent_record(const KargPtr Qp, const Handoff &I, const int status, const int cost, const bool solved, const int tries,
+                                             const int ccase, const int iters, const int nslack, const int q, const int maxq)
+{
+    Qp->status[I.gid] = status;
+    if (Qp->cost_out) Qp->cost_out[I.gid] = cost;
+    if (Qp->info) {
+        int *inf = Qp->info + (size_t)I.gid * 8;
+        inf[0] = I.viol_k; inf[1] = I.nrows_built; inf[2] = tries; inf[3] = (!solved && (status & ST_COLL)) ? 0 : ccase;   // (`coll` return: no QP, no cost case)
+        inf[4] = iters; inf[5] = nslack; inf[6] = solved ? q : 0; inf[7] = maxq;
+    }
+}
+
+// Persistent forms: the wave's NEXT queue ticket is claimed (lane 0, result left in flight in `ticket`) when the agent is as good as done
+// -- the first violation scan that finds nothing, or the start of the output stage -- so that the atomic's latency hides behind the
+// output stage and nothing is claimed ahead of a solve: a position claimed before a 300-500 us infeasibility proof waited behind
+// it, and such parked agents were the last to end the launch (round 3: the waves ended 779-878 us, busy fraction 0.90).
+template <bool PERSIST>
+__device__ __forceinline__ void claim_next(const int lane, const bool want_ticket, int &ticket, bool &claimed)
+{
+    if (PERSIST && want_ticket && !claimed) { claimed = true; if (lane == 0) ticket = atomicAdd(kernarg_params()->counter, 1); }
+}
 
 // Retry-ladder certificate (bounded-slack variants).  The rows of one horizon step k constrain only w_k = (Lambda a)_k,
 // and with |a| <= alim the reachable set of w_k is EXACTLY the box |w_k| <= alim ((k+1) h)^2 / 2 per axis (cut by the
@@ -336,9 +505,8 @@ __device__ __forceinline__ void scan_body(const StepParams &P, const int lane, c
                                           const double *scp_prev = nullptr, unsigned *scp_mask = nullptr)
 {
     const int S = P.S, G = P.G, C = P.C, nrmax = P.nrmax;
-    const int scene = vb / P.c_count, ci = vb - scene * P.c_count;
-    const int cl = P.c_first + ci;                                     // agent inside chunk g_local
-    const int gid = scene * P.c_count + ci;                            // index into the launch's arrays
+    const AgentId I = agent_id(P, vb);
+    const int scene = I.scene, cl = I.cl, gid = I.gid;
     const int var = P.variant;
     constexpr bool soft = SOFT;   // slack-carrying variants (bound, bound2, all3, softall, repair) vs hard rows (hard, ondemand, ellip)
 
@@ -886,7 +1054,6 @@ __device__ __forceinline__ void scan_body(const StepParams &P, const int lane, c
             // instead of staying live in SGPRs across the neighbour walk and the row builder: the slack variants' scan spilled 190
             // scalar registers to VGPR lanes (a fifth of its instructions were v_readlane / v_writelane and the s_nop around them).
             const KargPtr Qp = kernarg_params();
-            typedef const double __attribute__((address_space(4))) *ConstD;
             Agent B_;
             {
                 const ConstD sp = (ConstD)(unsigned long long)(Qp->x_p + 3 * (size_t)gid), sv = (ConstD)(unsigned long long)(Qp->x_v + 3 * (size_t)gid);
@@ -900,18 +1067,17 @@ __device__ __forceinline__ void scan_body(const StepParams &P, const int lane, c
             const bool comp = lane < N3;
             const int k_l = comp ? lane / 3 : 0, ax_l = comp ? lane - 3 * k_l : 0;
             const double *tb = Qp->tables + (size_t)ccase * TAB_CASE_DOUBLES;
-            double a_unc = 0.0, w_unc = 0.0, p0_l = 0.0, vo_l = 0.0;
+            double a_unc = 0.0, w_unc = 0.0;
             bool viol = false;
             const double tol = 1e-10;
             if (comp) {
-                const double gax = goal_gap(sel3(B_.pf, ax_l), sel3(B_.po, ax_l), sel3(B_.vo, ax_l), Qp->h);
+                const double po_l = sel3(B_.po, ax_l), vo_l = sel3(B_.vo, ax_l);   // (picked once: with a sel3 per use the compiler kept B_.po addressable, 32 bytes of scratch)
+                const double gax = goal_gap(sel3(B_.pf, ax_l), po_l, vo_l, Qp->h);
                 const double ao_l = sel3(B_.ao, ax_l);
                 a_unc = unc_entry(qw, sw, gax, ao_l, tb[k_l * 30 + 15 + (K - 1)], tb[k_l * 30]);
                 w_unc = unc_entry(qw, sw, gax, ao_l, tb[(15 + k_l) * 30 + 15 + (K - 1)], tb[(15 + k_l) * 30]);
-                vo_l = sel3(B_.vo, ax_l);
                 const double sh = (double)(k_l + 1) * Qp->h * vo_l;
-                const double whi = (ax_l == 0 ? Qp->pmax[0] : (ax_l == 1 ? Qp->pmax[1] : Qp->pmax[2])) - sel3(B_.po, ax_l) - sh, wlo = (ax_l == 0 ? Qp->pmin[0] : (ax_l == 1 ? Qp->pmin[1] : Qp->pmin[2])) - sel3(B_.po, ax_l) - sh;
-                p0_l = init_pos(k_l, Qp->h, vo_l, sel3(B_.po, ax_l));
+                const double whi = (ax_l == 0 ? Qp->pmax[0] : (ax_l == 1 ? Qp->pmax[1] : Qp->pmax[2])) - po_l - sh, wlo = (ax_l == 0 ? Qp->pmin[0] : (ax_l == 1 ? Qp->pmin[1] : Qp->pmin[2])) - po_l - sh;
                 viol = (fabs(a_unc) - Qp->alim > tol) || (fmax(w_unc - whi, wlo - w_unc) > tol);
             }
             bool trivial = ls == 0 && !__any(viol);
@@ -956,28 +1122,13 @@ __device__ __forceinline__ void scan_body(const StepParams &P, const int lane, c
                 trivial = !__any(rv);
             }
             if (trivial) {
-                int st = ST_SOLVED | (coll_flag ? ST_COLL : 0);
-                const double p_out = w_unc + p0_l;
-                double v_out = 0.0;
-                if (comp) v_out = vel_out(a_s, k_l, ax_l, Qp->h, vo_l);
-                const bool ob_check = !(var == VAR_ELLIP || var == VAR_SOFTALL || var == VAR_SOFTALL_C || var == VAR_SCP || var == VAR_CPP1 || cppv);   // (as the solver's output stage)
-                if (ob_check) {
-                    const double tolb = 50e-3;
-                    bool bad = false;
-                    if (lane < 3) bad = !(p_out < (lane == 0 ? Qp->pmax[0] : (lane == 1 ? Qp->pmax[1] : Qp->pmax[2])) + tolb) || !(p_out > (lane == 0 ? Qp->pmin[0] : (lane == 1 ? Qp->pmin[1] : Qp->pmin[2])) - tolb);
-                    if (__any(bad)) st |= ST_OUTBOUND;
-                }
-                if (comp) {
-                    Qp->p_out[(size_t)gid * N3 + lane] = p_out;
-                    Qp->v_out[(size_t)gid * N3 + lane] = v_out;
-                    Qp->a_out[(size_t)gid * N3 + lane] = a_unc;
-                    if (Qp->lT_next) Qp->lT_next[(size_t)scene * N3 * C + cl + (size_t)(unsigned)(lane * C)] = p_out;
-                }
+                // (the solvers' output stage; a fused post-step of this agent is left to the solve launch: agent_skip)
+                const int st = agent_outputs(Qp, lane, I, comp, k_l, ax_l, true, w_unc, a_unc, a_s, has_inbounds_test(var), false, ST_SOLVED | (coll_flag ? ST_COLL : 0));
                 if (lane == 0) {
                     Qp->status[gid] = st;
                     hdr[4] = (violation ? 1 : 0) | (coll_flag ? 4 : 0) | 16;
                     hdr[7] = 256;   // (the order kernel reads this word only)
-                    if (Qp->info) {
+                    if (Qp->info) {   // (the solvers' agent_record with its constants: one try, no iteration, no work estimate)
                         int *inf = Qp->info + (size_t)gid * 8;
                         inf[0] = viol_k; inf[1] = nrows_ref; inf[2] = 1; inf[3] = ccase;
                         inf[4] = 0; inf[5] = 0; inf[6] = 0; inf[7] = 0;
@@ -1163,7 +1314,7 @@ __global__ __launch_bounds__(SOFT ? 512 : DMPC_HARD_PW * 64, 1) void dmpc_solve_
     //     where the launch ends (the last #waves positions: a fine-grained tail), and for QUEUE_CHUNK adjacent positions in
     //     between (the light bulk): fewer atomics, at most one light chunk of imbalance -- and a pre-claimed chunk waits behind
     //     its wave's current agent, which is why the chunk is short;
-    //   * the next ticket is claimed when the current agent is as good as solved (solve_body: CLAIM_NEXT) and read after its output
+    //   * the next ticket is claimed when the current agent is as good as solved (claim_next) and read after its output
     //     stage: most of the latency hides there, and no position waits behind a solve that turns out long.
     const int nw = (int)(gridDim.x * (blockDim.x >> 6));
     const int rest = total > nw ? total - nw : 0;

@@ -11,18 +11,20 @@
 //   * a slack at one of its bounds is a fixed variable too: its row is then a HARD row (three at most are independent: they only see the
 //     3-vector w_kc); a row with a free slack is a SOFT row and enters as the rank-1 penalty 2/sd^2 xi xi' on w_kc -- any number of
 //     them cost nine wave reductions;
-//   * what is left as "general constraints" -- hard rows, workspace walls, the entering constraint -- is a system of at most five
-//     unknowns, solved from scratch in uniform registers with the entering constraint LAST (its pivot is the dependence test).
+//   * what is left as "general constraints" -- hard rows, workspace walls (up to R_NW = 3: a corner), the entering constraint -- is a small
+//     system of at most R_NH = 8 constraints, one per lane, solved from scratch by Gauss-Jordan with the entering constraint LAST (its pivot
+//     is the dependence test).
 // Every equality-constrained QP of the iteration is solved FROM SCRATCH: nothing is updated, nothing drifts, no verification pass; a
-// partial step interpolates multipliers (and the primal) between two such solutions.  No LDS beyond 96 doubles per wave for the output
-// stage, so the launch is bound by registers, not by the 19 KB per wave of the inverse factor (dmpc_solve.hip: 1.75 waves per SIMD).
-// CPU prototype of exactly this algorithm, validated against the oracle on 27 000 agent-steps: tools/proto/rqp_proto.c.
+// partial step interpolates multipliers (and the primal) between two such solutions.  The acceleration bounds also move in blocks (see
+// RBLOCK_UNDO below), and a ladder level that takes long is put to the ladder certificate (ladder_level_infeasible, dmpc_kernels.hip).
+// LDS: 280 doubles per wave (the certificate's planes; the stacked vectors of the output stage), so the launch is bound by registers, not
+// by the 19 KB per wave of the inverse factor.  CPU prototype of the first version, validated on 27 000 agent-steps: tools/proto/rqp_proto.c.
 //
 // Lane layout: component (axis x, step k) lives in lane 16 x + k (k < 15): the tridiagonal neighbours are row_shr:1 / row_shl:1, sums over
 // an axis are sums over a DPP row; collision row j lives in lane j (at most 64 rows: more -> the general kernel).  Agents this kernel does
-// not take (more than 64 rows, rows on several steps, more than two active walls, more than five hard constraints, an iteration cap) are
-// flagged ST_QOVER and solved by the general kernel (dmpc_solve.hip) in the tier-2 launch: none in the 27 000 agent-steps of the prototype's
-// campaign but for a third wall (1).
+// not take (more than 64 rows, rows on several steps, a fourth active wall, more than R_NH hard constraints, a dependent or degenerate
+// working set, the caps on scans and equality solves per level) are flagged ST_QOVER and solved by the general kernel (dmpc_solve.hip) in
+// the tier-2 launch.  Prologue, output stage and record are the shared ones of dmpc_kernels.hip: the same words whichever kernel finishes an agent.
 
 // #define RSOLVE_TRACE 1
 template <int N> __device__ __forceinline__ double rshr(double v) { return dpp0_d<0x110 + N>(v); }   // lane i <- lane i-N of its row (0 off the row)
@@ -123,42 +125,26 @@ __device__ __forceinline__ void rsolve_body(const StepParams &P, const int lane,
 #else
 #define RPH(i_) do { } while (0)
 #endif
-#define RCLAIM_NEXT() do { if (want_ticket && !claimed) { claimed = true; if (lane == 0) ticket = atomicAdd(kernarg_params()->counter, 1); } } while (0)
     // (fields of the parameter block that are picked by a run-time index -- pmin / pmax by axis, the weights by cost case -- are read through the
     // kernel-argument segment: a select between fields of the by-value struct is compiled as a select of ADDRESSES and sends the whole block to scratch)
     const KargPtr Qk = kernarg_params();
 #define PMAXQ(x_) ((x_) == 0 ? Qk->pmax[0] : ((x_) == 1 ? Qk->pmax[1] : Qk->pmax[2]))
 #define PMINQ(x_) ((x_) == 0 ? Qk->pmin[0] : ((x_) == 1 ? Qk->pmin[1] : Qk->pmin[2]))
     const int nrmax = P.nrmax, var = P.variant;
-    const int scene = vb / P.c_count, ci = vb - scene * P.c_count;
-    const int cl = P.c_first + ci;
-    const int gid = scene * P.c_count + ci;
+    const Handoff I = agent_handoff(P, vb);
+    const int gid = I.gid;
     double *B = (double *)__builtin_assume_aligned(smem, 16);
     const size_t per = (size_t)nrmax * 7;
     const double *g_rows = P.rowbuf + (size_t)gid * per;
     const double *r_xi = g_rows, *r_b = g_rows + 3 * (size_t)nrmax, *r_sd = r_b + nrmax, *r_st = r_b + 2 * (size_t)nrmax, *r_slb = r_b + 3 * (size_t)nrmax;
     const int *r_kc = P.rowkc + (size_t)gid * nrmax;
-    const int *hdr = P.hdr + (size_t)gid * 8;
-    struct { int x, y, z, w; } h0, h1;
-    h0.x = UNI(hdr[0]); h0.y = UNI(hdr[1]); h0.z = UNI(hdr[2]); h0.w = UNI(hdr[3]); h1.x = UNI(hdr[4]); h1.y = UNI(hdr[5]); h1.z = UNI(hdr[6]); h1.w = UNI(hdr[7]);
     double po[3], vo[3], ao[3], pf[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) { po[d] = P.x_p[3 * gid + d]; vo[d] = P.x_v[3 * gid + d]; ao[d] = P.x_a[3 * gid + d]; pf[d] = P.pf[3 * gid + d]; }
-    if (h1.x & 8) return;                              // agent of a scene that already stopped
-    if (h1.x & 16) {                                   // finished by the scan (unconstrained exit)
-        if (P.post_on) {
-            const KargPtr Qp = kernarg_params();
-            const int st_done = Qp->status[gid];
-            double p1 = 0.0, v1 = 0.0, a1 = 0.0;
-            if (lane < 3) { p1 = Qp->p_out[(size_t)gid * N3 + lane]; v1 = Qp->v_out[(size_t)gid * N3 + lane]; a1 = Qp->a_out[(size_t)gid * N3 + lane]; }
-            post_step_part(Qp, lane, gid, scene, (st_done & ST_SOLVED) != 0, st_done, p1, v1, a1);
-        }
-        return;
-    }
-    const int nr = h0.x;
-    int status = h0.w;
-    const int nrows_built = h0.y, viol_k = h0.z;
-    const bool violation = (h1.x & 1) != 0, rows_exist = h1.y != 0;
+    if (agent_skip(P, lane, I)) return;
+    const int nr = I.nr;
+    int status = I.status;
+    const bool violation = I.violation, rows_exist = I.rows_exist;
     const bool cppv = (var == VAR_CPP || var == VAR_CPP2);
 
     // ---------------------------------------------------------------- rows: lane = row
@@ -202,7 +188,6 @@ __device__ __forceinline__ void rsolve_body(const StepParams &P, const int lane,
     }
     // the scales of the bounds and walls, H1^-1(k,k) and (L H1^-1 L')(k,k), are read where an entering bound / wall needs one: a SCALAR load from the table
     // (constant address space: the index is wave-uniform) issued a section ahead of its use -- kept per lane they were four registers of a kernel that spills
-    typedef const double __attribute__((address_space(4))) *ConstD;
     const ConstD Gts = (ConstD)(unsigned long long)Gt;
     const double sc_row = Gt[(15 + kc) * 31];   // n'H^-1 n of the UNREDUCED Hessian: the scale of the dependence test (dmpc_solve.hip: delta <= 1e-13 s_pp)
 
@@ -212,7 +197,7 @@ __device__ __forceinline__ void rsolve_body(const StepParams &P, const int lane,
     const bool ladder = (var == VAR_BOUND || var == VAR_BOUND2 || cppv);
     const int max_tries = P.max_tries > 0 ? P.max_tries : (cppv ? 21 : 30);
     const double tol = 1e-10;
-    int tries = h1.z, iters_total = 0, maxq = 0, qfinal = 0, cost = 0;
+    int tries = I.hdr[6], iters_total = 0, maxq = 0, qfinal = 0, cost = 0;
     double lev_f = 1.0;   // the rows' slack bound and penalty carry this factor (a power of two) on the current ladder level
     bool solved = false;
     double a = 0.0, lam = 0.0;
@@ -297,7 +282,7 @@ __device__ __forceinline__ void rsolve_body(const StepParams &P, const int lane,
 #undef RCAND
                     const float smax = wave_max_f(bests);
                     const unsigned long long wm = __ballot(bestc >= 0 && bests == smax);
-                    if (wm == 0ull) { RCLAIM_NEXT(); rc = 0; break; }   // optimal
+                    if (wm == 0ull) { claim_next<true>(lane, want_ticket, ticket, claimed); rc = 0; break; }   // optimal
                     if (++iters > P.iter_cap || iters > 400) { rc = 2; why = 3; break; }
                     // the level is looked at by the ladder certificate once (3-variable polytope emptiness over the rows of the step with every slack at its
                     // bound): an infeasible level costs the dual method tens of steps to prove
@@ -831,9 +816,9 @@ __device__ __forceinline__ void rsolve_body(const StepParams &P, const int lane,
 #endif
     (void)why;
     const KargPtr Qp = kernarg_params();
-    RCLAIM_NEXT();
+    claim_next<true>(lane, want_ticket, ticket, claimed);
     if (giveup) {   // the general kernel takes this agent (tier-2 launch over the flagged list)
-        status = h0.w | ST_QOVER;
+        status = I.status | ST_QOVER;
         if (lane == 0) {
             Qp->status[gid] = status;
             if (Qp->flag_list) Qp->flag_list[atomicAdd(Qp->flag_count, 1)] = gid;
@@ -844,7 +829,7 @@ __device__ __forceinline__ void rsolve_body(const StepParams &P, const int lane,
     int nslack = 0;
     const bool no_set = solved && __ballot((comp && fx != 0) || (rv && (rfl & RB_IN))) == 0ull && nw == 0;
     if (solved) {
-        status |= ST_SOLVED;
+        status |= ST_SOLVED | (I.coll0 ? ST_COLL : 0);
         const bool in_ = rv && (rfl & RB_IN);
         const double eps = !in_ ? 0.0 : ((rfl & RB_PINL) ? slb : ((rfl & RB_PIN0) ? 0.0 : -0.5 * fma(rsd, lam, st)));
         nslack = __popcll(__ballot(eps < -1e-12));
@@ -856,57 +841,21 @@ __device__ __forceinline__ void rsolve_body(const StepParams &P, const int lane,
         if (comp) { B[3 * k_l + ax_l] = a; B[48 + 3 * k_l + ax_l] = w; }
         LSYNC();
     }
-    double p_out = 0.0, v_out = 0.0, a_out = 0.0;
     const bool oc = lane < N3;
     const int ko = oc ? lane / 3 : 0, axo = oc ? lane - 3 * ko : 0;
+    double w = 0.0, a_o = 0.0;
     if (solved && oc) {
-        typedef const double __attribute__((address_space(4))) *ConstD;
-        const ConstD sp = (ConstD)(unsigned long long)(Qp->x_p + 3 * (size_t)gid), sv_ = (ConstD)(unsigned long long)(Qp->x_v + 3 * (size_t)gid);
-        const double po0 = sp[0], po1 = sp[1], po2 = sp[2], vo0 = sv_[0], vo1 = sv_[1], vo2 = sv_[2];
-        const double vo_o = axo == 0 ? vo0 : (axo == 1 ? vo1 : vo2);
-        const double p0_o = init_pos(ko, Qp->h, vo_o, axo == 0 ? po0 : (axo == 1 ? po1 : po2));
-        double w = B[48 + lane];
+        w = B[48 + lane]; a_o = B[lane];
         if (no_set) {   // the unconstrained minimiser: its positions from the Gram table, bit for bit what the scan's unconstrained exit writes
-            const double gx = goal_gap(axo == 0 ? Qp->pf[3 * (size_t)gid] : (axo == 1 ? Qp->pf[3 * (size_t)gid + 1] : Qp->pf[3 * (size_t)gid + 2]), axo == 0 ? po0 : (axo == 1 ? po1 : po2), vo_o, Qp->h);
+            double po_o, vo_o;
+            state_again(Qp, gid, axo, po_o, vo_o);
+            const double gx = goal_gap(axo == 0 ? Qp->pf[3 * (size_t)gid] : (axo == 1 ? Qp->pf[3 * (size_t)gid + 1] : Qp->pf[3 * (size_t)gid + 2]), po_o, vo_o, Qp->h);
             const double aoo = Qp->x_a[3 * (size_t)gid + axo];
             w = unc_entry(qw, sw, gx, aoo, Gt[(15 + ko) * 30 + 15 + (K - 1)], Gt[(15 + ko) * 30]);
         }
-        p_out = w + p0_o;
-        v_out = vel_out(B, ko, axo, Qp->h, vo_o);
-        a_out = B[lane];
     }
-    if (solved) {
-        const bool ob_check = !cppv;
-        if (h1.x & 4) status |= ST_COLL;
-        if (ob_check) {
-            const double tolb = 50e-3;
-            bool bad = false;
-            const double hi3 = lane == 0 ? Qp->pmax[0] : (lane == 1 ? Qp->pmax[1] : Qp->pmax[2]), lo3 = lane == 0 ? Qp->pmin[0] : (lane == 1 ? Qp->pmin[1] : Qp->pmin[2]);
-            if (lane < 3) bad = !(p_out < hi3 + tolb) || !(p_out > lo3 - tolb);
-            if (__any(bad)) status |= ST_OUTBOUND;
-        }
-    }
-    if (oc) {
-        Qp->p_out[(size_t)gid * N3 + lane] = p_out;
-        Qp->v_out[(size_t)gid * N3 + lane] = v_out;
-        Qp->a_out[(size_t)gid * N3 + lane] = a_out;
-        if (Qp->lT_next) {
-            const int Cq = Qp->C;
-            const double *own = Qp->own_prev ? Qp->own_prev + (size_t)scene * N3 * Cq + cl : Qp->lT + ((size_t)(Qp->g_local * Qp->S + scene) * N3) * Cq + cl;
-            Qp->lT_next[(size_t)scene * N3 * Cq + cl + (size_t)(unsigned)(lane * Cq)] = solved ? p_out : own[(size_t)(unsigned)(lane * Cq)];
-        }
-    }
-    if (Qp->post_on) post_step_part(Qp, lane, gid, scene, solved, status, p_out, v_out, a_out);
-    if (lane == 0) {
-        Qp->status[gid] = status;
-        if (Qp->cost_out) Qp->cost_out[gid] = cost;
-        if (Qp->info) {
-            int *inf = Qp->info + (size_t)gid * 8;
-            inf[0] = viol_k; inf[1] = nrows_built; inf[2] = tries; inf[3] = (!solved && (status & ST_COLL)) ? 0 : ccase;
-            inf[4] = iters_total; inf[5] = nslack; inf[6] = solved ? qfinal : 0; inf[7] = maxq;
-        }
-    }
-#undef RCLAIM_NEXT
+    status = agent_outputs(Qp, lane, I, oc, ko, axo, solved, w, a_o, B, has_inbounds_test(var), true, status);
+    if (lane == 0) agent_record(Qp, I, status, cost, solved, tries, ccase, iters_total, nslack, qfinal, maxq);
 #undef RBLOCK_UNDO
 #undef PMAXQ
 #undef PMINQ

@@ -137,11 +137,6 @@ __device__ __forceinline__ double wave_max0(double v)   // v >= 0 on every lane
     return readlane_d(v, 63);
 }
 
-// wave-uniform by construction, not by what the compiler can see (a value read from LDS or global memory at a uniform address, the result
-// of an out-of-line function): say so -- everything derived from it is then scalar, branches on it are scalar branches
-#define UNI(x_) __builtin_amdgcn_readfirstlane(x_)
-__device__ __forceinline__ bool uni_b(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
-
 // uniform description of one constraint
 struct Cd {
     int ty, idx, gi, si;     // type, index (component or row), Gram index (space, step), slack row (-1: none)
@@ -504,41 +499,6 @@ __device__ __attribute__((noinline)) CrashRes crash_append(LdsD *Bl, const LdsD 
     return res;
 }
 
-// Closed loops, tiny launches: the work of post_step_kernel for one agent (dmpc_soft_bound.m:132-134, the history column,
-// ReachedGoal.m:3-11), done by the wave that produced the agent's step; p_out, v_out, a_out: lanes 0..2 hold the first horizon column.
-// The scene's maximum / OR / count are order-independent, so which wave finishes last changes nothing.
-__device__ __forceinline__ void post_step_part(const KargPtr Qp, const int lane, const int gid, const int scene, const bool solved,
-                                               const int status, const double p_out, const double v_out, const double a_out)
-{
-    {
-        double xn = 0.0, vn = 0.0, an = 0.0, e2 = 0.0;
-        if (lane < 3) {
-            const size_t b = (size_t)gid * 3 + lane;
-            xn = solved ? p_out : Qp->post_xp[b]; vn = solved ? v_out : Qp->post_xv[b]; an = solved ? a_out : Qp->post_xa[b];
-            if (solved) { Qp->post_xp[b] = xn; Qp->post_xv[b] = vn; Qp->post_xa[b] = an; }
-            const size_t ho = ((size_t)gid * Qp->post_KT + Qp->post_k) * 3 + lane;
-            Qp->post_pk[ho] = xn; Qp->post_vk[ho] = vn; Qp->post_ak[ho] = an;
-            const double dd = xn - Qp->pf[b];
-            e2 = dd * dd;
-        }
-        const double dx2 = readlane_d(e2, 0), dy2 = readlane_d(e2, 1), dz2 = readlane_d(e2, 2);
-        if (lane == 0) {
-            const double dist = sqrt(dx2 + dy2 + dz2);
-            atomicMax(Qp->post_max + scene, (unsigned long long)__double_as_longlong(dist));
-            atomicOr(Qp->post_or + scene, status);
-            __threadfence();
-            if (atomicAdd(Qp->post_cnt + scene, 1) == Qp->c_count - 1) {   // the scene's last agent of this step
-                const unsigned long long mb = atomicExch(Qp->post_max + scene, 0ull);
-                const int orv = atomicExch(Qp->post_or + scene, 0);
-                Qp->post_cnt[scene] = 0;
-                const int reached = __longlong_as_double((long long)mb) < Qp->post_tol ? 1 : 0;
-                Qp->post_flags[(size_t)scene * 2] = reached; Qp->post_flags[(size_t)scene * 2 + 1] = orv;
-                if (Qp->post_done && (reached || (orv & ~ST_SOLVED))) Qp->post_done[scene] = 1;
-            }
-        }
-    }
-}
-
 // `bidx`: the workgroup's index (one-agent-per-workgroup launches, renumbered XCD-aware and sent through the launch order
 // here) or -- persistent form -- the AGENT the wave is about to solve (the queue position already resolved through the order
 // by the persistent loop); `smem`: this wave's LDS; `shtab`: the workgroup-shared tables (persistent
@@ -548,12 +508,6 @@ __device__ __forceinline__ void solve_body(const StepParams &P, const int lane, 
                                            unsigned char *smem, const double *shtab, const bool want_ticket, int &ticket, bool &claimed,
                                            const int ext0 = 0 /* split T: doubles from this wave's block to extension 0 of the workgroup's pool */)
 {
-    // Persistent form: the wave's NEXT queue ticket is claimed (lane 0, result left in flight in `ticket`) when the agent is as good as done
-    // -- the first violation scan that finds nothing, or the start of the output stage -- so that the atomic's latency hides behind the
-    // output stage and nothing is claimed ahead of a solve: a position claimed before a 300-500 us infeasibility proof waited behind
-    // it, and such parked agents were the last to end the launch (round 3: the waves ended 779-878 us, busy fraction 0.90).
-#define CLAIM_NEXT() do { if (PERSIST && want_ticket && !claimed) { claimed = true; \
-        if (lane == 0) ticket = atomicAdd(kernarg_params()->counter, 1); } } while (0)
     using SL = SolveLds<SOFT, QCAP, PERSIST, TS, TF>;
     constexpr bool soft = SOFT;
     constexpr bool F32T = sizeof(TF) == 4;
@@ -590,9 +544,8 @@ __device__ __forceinline__ void solve_body(const StepParams &P, const int lane, 
         vb = off + y;
         if (P.order) vb = P.order[bidx];   // heaviest agents first (order_kernel) / tier-2 list
     }
-    const int scene = vb / P.c_count, ci = vb - scene * P.c_count;
-    const int cl = P.c_first + ci;
-    const int gid = scene * P.c_count + ci;
+    const Handoff I = agent_handoff(P, vb);   // (the first of the set-up's two rounds of global loads, below)
+    const int gid = I.gid;
 
     double *B = (double *)__builtin_assume_aligned(smem, 16);
     double *r_eps = B + SL::VAR;                                                   // soft variants: nrmax doubles
@@ -615,16 +568,11 @@ __device__ __forceinline__ void solve_body(const StepParams &P, const int lane, 
     double *r_xi = g_rows, *r_b = g_rows + 3 * (size_t)nrmax;
     double *r_sd = soft ? r_b + nrmax : nullptr, *r_st = soft ? r_b + 2 * (size_t)nrmax : nullptr, *r_slb = soft ? r_b + 3 * (size_t)nrmax : nullptr;
     int *r_kc = P.rowkc + (size_t)gid * nrmax;
-    int *hdr = P.hdr + (size_t)gid * 8;
 
     // ---------------------------------------------------------------- the global loads of the set-up in two rounds
     // (hand-off header + agent state, then the register-cached rows, which need the row count: two memory round trips
     // instead of a chain of four -- header flag, state, row count, rows.  Rows addressed without the count, i.e. reads of
     // scratch the scan never wrote, were measured slower: those lines come cold from HBM and the whole set-up waits for them.)
-    struct { int x, y, z, w; } h0, h1;   // the scan's hand-off header: 8 ints
-    // (readfirstlane: the header is read with vector loads -- the scan wrote it in this launch's lifetime, no scalar load -- and everything
-    // derived from it, the row count, the status word, the ladder start, would be compiled as lane-dependent: masked loops, vector compares)
-    h0.x = UNI(hdr[0]); h0.y = UNI(hdr[1]); h0.z = UNI(hdr[2]); h0.w = UNI(hdr[3]); h1.x = UNI(hdr[4]); h1.y = UNI(hdr[5]); h1.z = UNI(hdr[6]); h1.w = UNI(hdr[7]);
     const int stq = P.only_flagged ? UNI(P.status[gid]) : ST_QOVER;
     double po[3], vo[3], ao[3], pf[3];
 #pragma unroll
@@ -633,22 +581,11 @@ __device__ __forceinline__ void solve_body(const StepParams &P, const int lane, 
         ao[d] = P.x_a[3 * gid + d]; pf[d] = P.pf[3 * gid + d];
     }
     if (P.only_flagged && !(stq & ST_QOVER)) return;   // tier 2: only agents that overflowed tier 1
-    if (h1.x & 8) return;                              // agent of a scene that already stopped
-    if (h1.x & 16) {   // finished by the scan (unconstrained exit): nothing to solve; a fused post-step still takes its outputs
-        if (P.post_on) {
-            const KargPtr Qp = kernarg_params();
-            const int st_done = Qp->status[gid];
-            double p1 = 0.0, v1 = 0.0, a1 = 0.0;
-            if (lane < 3) { p1 = Qp->p_out[(size_t)gid * N3 + lane]; v1 = Qp->v_out[(size_t)gid * N3 + lane]; a1 = Qp->a_out[(size_t)gid * N3 + lane]; }
-            post_step_part(Qp, lane, gid, scene, (st_done & ST_SOLVED) != 0, st_done, p1, v1, a1);
-        }
-        return;
-    }
+    if (agent_skip(P, lane, I)) return;
 
     // the scan's branch record
-    int nr = h0.x, status = h0.w;
-    const int nrows_built = h0.y, viol_k = h0.z;
-    const bool violation = (h1.x & 1) != 0, rows_exist = h1.y != 0;
+    int nr = I.nr, status = I.status;
+    const bool violation = I.violation, rows_exist = I.rows_exist;
     const bool cppv = (var == VAR_CPP || var == VAR_CPP2);
 #ifndef DMPC_HARD_RC
 #define DMPC_HARD_RC 2
@@ -776,7 +713,7 @@ __device__ __forceinline__ void solve_body(const StepParams &P, const int lane, 
     // A first-tier launch that runs out of working-set slots hands the agent over UNTOUCHED (its row scalings undone, nothing
     // recorded): the second tier repeats the whole solve, on the path an uninterrupted solve takes -- the result of an agent
     // must not depend on how deep the launch was that it ran in.
-    int tries = h1.z, iters_total = 0, maxq = 0, q = 0;
+    int tries = I.hdr[6], iters_total = 0, maxq = 0, q = 0;
     int cost = 0;   // work estimate in quarter microseconds (wave-uniform, scalar registers): the next step's launch-order key (P.cost_out)
     int scale_pow = 0;   // the rows' slack bound and penalty currently carry the factor 2^scale_pow
 #ifdef DMPC_DEV_TRACE
@@ -1150,7 +1087,7 @@ __device__ __forceinline__ void solve_body(const StepParams &P, const int lane, 
                     // the very BEGINNING of a solve -- finds nothing: until round 5 every agent with a crash start claimed its wave's next queue position
                     // there, and that position then waited behind the whole solve: the queue degenerated to an assignment one agent ahead, measured
                     // launch 880 us where list scheduling of the same durations in the same order gives 770)
-                    if (!forced && !crash) CLAIM_NEXT();
+                    if (!forced && !crash) claim_next<PERSIST>(lane, want_ticket, ticket, claimed);
                     if (!crash && !forced && (q == 0 || fresh)) break;   // optimal
                     if (!crash && !soft && !F32T && !forced) {   // (fp32 factor: the incrementally updated iterate drifts by ~1e-7 per step -- always the full verification)
                         // (slack-free variants; the slack variants carry multipliers of 1e5-1e6 and always take the full verification)
@@ -1551,7 +1488,7 @@ __device__ __forceinline__ void solve_body(const StepParams &P, const int lane, 
     // The launch parameters the output stage needs are read again from the kernel-argument segment (scalar loads through an
     // opaque pointer) instead of staying live in SGPRs across the solver loop, where they were spilled to VGPR lanes.
     const KargPtr Qp = kernarg_params();
-    CLAIM_NEXT();
+    claim_next<PERSIST>(lane, want_ticket, ticket, claimed);
     if (TS < QCAP && xo != 0) {   // the extension goes back to the pool, zeroed (every LDS value a wave can read stays finite)
         double *ex = B + xo + tcol(TS);
         for (int i = lane; i < ext_doubles(QCAP, TS); i += 64) ex[i] = 0.0;
@@ -1560,66 +1497,27 @@ __device__ __forceinline__ void solve_body(const StepParams &P, const int lane, 
     }
     int nslack = 0;
     if (solved) {
-        status |= ST_SOLVED;
+        status |= ST_SOLVED | (I.coll0 ? ST_COLL : 0);   // (cpp: a collision noticed at the first step, solution still returned)
         if (soft) {
             int cnt = 0;
             for (int i = lane; i < nr; i += 64) cnt += (r_eps[i] < -1e-12) ? 1 : 0;
             nslack = (int)wave_sum0((double)cnt);
         }
     }
-    double p_out = 0.0, v_out = 0.0, a_out = 0.0;
-    if (solved && comp) {
-        // p = A_p a + A_initp [po;vo] ; v = A_v a + vo   (propStatedmpc.m:3-4).  The agent's state is read again here -- six SCALAR loads
-        // through constant-address-space pointers (the values are wave-uniform) -- instead of living in registers across the solver loop
-        typedef const double __attribute__((address_space(4))) *ConstD;
-        const ConstD sp = (ConstD)(unsigned long long)(Qp->x_p + 3 * (size_t)gid), sv_ = (ConstD)(unsigned long long)(Qp->x_v + 3 * (size_t)gid);
-        const double po0 = sp[0], po1 = sp[1], po2 = sp[2], vo0 = sv_[0], vo1 = sv_[1], vo2 = sv_[2];
-        const double vo_l = ax_l == 0 ? vo0 : (ax_l == 1 ? vo1 : vo2);
-        const double p0_l = init_pos(k_l, Qp->h, vo_l, ax_l == 0 ? po0 : (ax_l == 1 ? po1 : po2));   // A_initp(k,:) [po;vo]
-        p_out = w + p0_l;
-        v_out = vel_out(B + SL::A, k_l, ax_l, Qp->h, vo_l);
-        a_out = a;
-    }
-    if (solved) {
-        const bool ob_check = !(var == VAR_ELLIP || var == VAR_SOFTALL || var == VAR_SOFTALL_C || var == VAR_SCP || var == VAR_CPP1 || cppv);   // solveQPv2 / solveQP / solveSoftDMPC[_c] / solveDMPC have no in-bounds test
-        if (h1.x & 4) status |= ST_COLL;   // cpp: collision noticed at the first step, solution still returned
-        if (ob_check) {   // is_inbounds.m:2-5 on p(:,1)
-            const double tolb = 50e-3;
-            bool bad = false;
-            const double hi3 = lane == 0 ? Qp->pmax[0] : (lane == 1 ? Qp->pmax[1] : Qp->pmax[2]), lo3 = lane == 0 ? Qp->pmin[0] : (lane == 1 ? Qp->pmin[1] : Qp->pmin[2]);
-            if (lane < 3) bad = !(p_out < hi3 + tolb) || !(p_out > lo3 - tolb);
-            if (__any(bad)) status |= ST_OUTBOUND;
-        }
-    }
-    if (comp) {
-        Qp->p_out[(size_t)gid * N3 + lane] = p_out;
-        Qp->v_out[(size_t)gid * N3 + lane] = v_out;
-        Qp->a_out[(size_t)gid * N3 + lane] = a_out;
-        if (Qp->lT_next) {
-            // next table chunk [S][3K][C]: uniform 64-bit base, 32-bit per-lane offset; unsolved agents keep their old prediction
-            const int Cq = Qp->C;
-            // (mixed precision: Qp->lT is the fp32 table of the scan; the fp64 predictions of this chunk are in Qp->own_prev)
-            const double *own = Qp->own_prev ? Qp->own_prev + (size_t)scene * N3 * Cq + cl : Qp->lT + ((size_t)(Qp->g_local * Qp->S + scene) * N3) * Cq + cl;
-            Qp->lT_next[(size_t)scene * N3 * Cq + cl + (size_t)(unsigned)(lane * Cq)] = solved ? p_out : own[(size_t)(unsigned)(lane * Cq)];
-        }
-    }
-    if (Qp->post_on) post_step_part(Qp, lane, gid, scene, solved, status, p_out, v_out, a_out);
+    status = agent_outputs(Qp, lane, I, comp, k_l, ax_l, solved, w, a, B + SL::A, has_inbounds_test(var), true, status);
     if (lane == 0) {
-        Qp->status[gid] = status;
-        if (Qp->cost_out) Qp->cost_out[gid] = cost;
+        agent_record(Qp, I, status, cost, solved, tries, ccase, iters_total, nslack, q, maxq);
+#ifdef DMPC_DEV_TRACE
         if (Qp->info) {
             int *inf = Qp->info + (size_t)gid * 8;
-            inf[0] = viol_k; inf[1] = nrows_built; inf[2] = tries; inf[3] = (!solved && (status & ST_COLL)) ? 0 : ccase;   // (`coll` return: no QP, no cost case)
-            inf[4] = iters_total; inf[5] = nslack; inf[6] = solved ? q : 0; inf[7] = maxq;
-#ifdef DMPC_DEV_TRACE
             if (ph_on && Qp->dbg_cap >= 4) {
                 PH(9 > 8 ? 4 : 4);
                 double *d = Qp->dbg + (size_t)(Qp->dbg_cap - 3) * 8;
                 for (int u = 0; u < 20; ++u) d[u] = (double)phv[u];
             }
-            if (Qp->dbg_agent == -6) { inf[5] = h1.w; inf[3] = cost; }   // development: the scan's key word (with the feature bits of the DEV_TRACE scan) and the work estimate
+            if (Qp->dbg_agent == -6) { inf[5] = I.hdr[7]; inf[3] = cost; }   // development: the scan's key word (with the feature bits of the DEV_TRACE scan) and the work estimate
             if (Qp->dbg_agent == -4) { inf[0] = dev_nfast; inf[1] = dev_rounds; inf[3] = dev_negdrops; inf[5] = dev_tbl; inf[6] = dev_gen; }   // development: crash statistics in place of the branch record
-#endif
         }
+#endif
     }
 }
