@@ -484,6 +484,37 @@ DMPC_API int dmpc_postcheck_clearance(dmpc_ctx *ctx, int S, int N, int N_cmd, in
                              double vmax, double amax, double Ts, double reach, double *clear_dist, int32_t *clear_partner,
                              int32_t *clear_sample);
 
+/* Flight setpoints and limits report (additive, the ABI revision stays 8): position, velocity AND acceleration of the N commanded agents at the
+ * 100 Hz samples of the post-check -- what DMPC::interp_trajectory (dmpc/cpp/dmpc.cpp:1938-2050) returns as pos / vel / acc, what
+ * dmpc_soft_bound.m:165-169 computes as spline(tk,pk,t), spline(tk,vk,t), spline(tk,ak,t) and what dmpc_trajectories2file takes -- and, per
+ * agent, the largest |v| and |a| over the whole transition with the sample at which it happens.
+ * The preamble is dmpc_postcheck's: r_factor, h_scaled, n_samples, the rescaled histories and the position spline are the same bits.  v and a
+ * are the same not-a-knot spline on the same knots i * h_scaled through the velocity and acceleration histories AS THE RESCALE LEAVES THEM --
+ * including the last acceleration column, which the reference's loop `for k = 1:K-1` (failure_rate.m:156-162) never multiplies by r_factor.
+ * v is deliberately NOT the derivative of the position spline (nor a of the velocity spline): the reference interpolates three series
+ * independently, and on a recorded transition (tests/golden/postcheck_comp_kctr_2.npz) the two velocities differ by up to 5.3e-2 m/s.
+ * Histories with K_T_used < 4 degenerate as the position spline does (parabola / line through the points).
+ * pk, vk, ak: [S][N][KT_alloc][3], un-rescaled, or all three NULL (the resident histories under dmpc_postcheck's rules: a split batch is
+ * handled part by part where the histories live; a DMPC_DEVICE_ALL context holds the scene-wide ones).  Inputs are never modified.
+ * Setpoints: p_sp, v_sp, a_sp [S][N][ns_alloc][3], any of them NULL.  Global sample j (t = j * Ts) with smp0 <= j < min(smp0 + ns_alloc,
+ * n_samples[s]) goes to index j - smp0; every other slot is zero.  p_sp with smp0 = 0 is p_interp of dmpc_postcheck byte for byte, and any
+ * window is a slice of the full call byte for byte.  Windows that would need more than 256 MB of device memory are produced in several
+ * passes.  ns_alloc = 0 with all three NULL is the report alone: no setpoint is stored anywhere and 4 S N numbers come back.
+ * Report, arrays [S][N], any of them NULL:
+ *   v_peak         max_j |v_i(t_j)| over ALL samples j < n_samples[s] (the window does not restrict it); |x| = sqrt(fma(z, z, fma(y, y, x * x)))
+ *   v_peak_sample  the 0-based sample of that maximum; ties go to the smallest sample
+ *   a_peak, a_peak_sample   the same for the acceleration
+ * The report does not depend on S, the window, the passes, the launch geometry or which outputs are NULL.  The rescale enforces vmax / amax
+ * at the knots only; the spline may exceed them in between (on the recorded transition above a_peak of one agent is 1.0044 at amax = 1).
+ * Comparing the peaks with the limits is the caller's job.  Masked scenes report NaN / -1 and zero setpoints.
+ * -1 with a message that starts with the entry's name and nothing launched: what dmpc_postcheck refuses of the common arguments, smp0 < 0,
+ * ns_alloc < 0, a setpoint array with ns_alloc = 0, ns_alloc > 0 without one, only some of pk / vk / ak. */
+DMPC_API int dmpc_postcheck_setpoints(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                             const double *pk, const double *vk, const double *ak, double vmax, double amax, double Ts,
+                             int smp0, int ns_alloc, double *p_sp, double *v_sp, double *a_sp,
+                             double *v_peak, int32_t *v_peak_sample, double *a_peak, int32_t *a_peak_sample,
+                             double *r_factor, double *h_scaled, int32_t *n_samples);
+
 /* f-3: dense collision rows behind the CollConstr / AddCollConstr helpers named in the north star.  All of them
  * compute, per neighbour j (E1 = diag(1,1,1/c), E2 = E1^order; the ORDER is the context's, dmpc_params.order: 2, or 4 on a context of an
  * all-neighbour variant -- the helpers are generic in it, CollConstrSoftDMPC.m:16-21, and test/comp_test_ellipconstr.m:158 sets 4):

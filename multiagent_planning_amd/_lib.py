@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "dmpc_transition_scripted", "dmpc_scripted_cols_device", "dmpc_postcheck_scripted",
     "dmpc_postcheck_clearance",
     "dmpc_transition_mission",
+    "dmpc_postcheck_setpoints",
 ]
 
 
@@ -135,6 +136,9 @@ def load():
                                            C.c_double, C.c_double, dp, ip, ip]
     # missions: a transition through a sequence of goal sets (additive, still revision 8)
     L.dmpc_transition_mission.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, ip, dp, C.c_int, C.c_int, C.c_double, dp, dp, dp, ip, ip, ip]
+    # flight setpoints p, v, a at 100 Hz and the limits report (additive, still revision 8)
+    L.dmpc_postcheck_setpoints.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                           dp, dp, dp, dp, ip, dp, ip, dp, dp, ip]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -564,6 +568,39 @@ class Dmpc:
                                                    _dp(pos) if pos is not None and M else nul, _dp(path) if path is not None else nul, P,
                                                    float(vmax), float(amax), float(Ts), float(reach), _dp(dist), _ip(partner), _ip(sample)))
         return dict(dist=dist, partner=partner, sample=sample, time=np.where(sample >= 0, sample * float(Ts), np.nan))
+
+    def setpoints(self, K_T_used, N=None, pk=None, vk=None, ak=None, KT_alloc=None, vmax=2.0, amax=1.0, Ts=0.01, mask=None, first=0, count=None,
+                  report_only=False):
+        """dmpc_postcheck_setpoints: the 100 Hz setpoints p, v, a [S,N,count,3] of the commanded agents (samples first .. first+count-1, zero
+        from n_samples on) and the limits report v_peak, v_peak_sample, a_peak, a_peak_sample [S,N] over ALL samples, next to r_factor,
+        h_scaled, n_samples [S] of postcheck().  pk/vk/ak [S,N,KT_alloc,3] (or [N,KT,3]); None: the resident histories of the last transition
+        (then N and KT_alloc say their shape).  count=None: the window runs from `first` to the largest n_samples (sized by a report-only
+        call, as postcheck(interp=True) sizes p).  report_only: no p, v, a."""
+        used = np.ascontiguousarray(np.atleast_1d(K_T_used), dtype=np.int32)
+        S = used.size
+        if pk is not None:
+            pk, vk, ak = (None if x is None else _f(x) for x in (pk, vk, ak))
+            N, KT_alloc = pk.shape[-3], pk.shape[-2]
+        assert N is not None and KT_alloc is not None
+        nul, inul = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
+        msk = None if mask is None else np.ascontiguousarray(np.atleast_1d(mask), dtype=np.int32)
+        if report_only:
+            count = 0
+        elif count is None:
+            pre = self.setpoints(used, N, pk, vk, ak, KT_alloc, vmax, amax, Ts, mask, report_only=True)
+            count = max(int(pre["n_samples"].max()) - int(first), 1)
+        count = int(count)
+        out = dict(v_peak=np.zeros((S, N)), v_peak_sample=np.zeros((S, N), dtype=np.int32), a_peak=np.zeros((S, N)),
+                   a_peak_sample=np.zeros((S, N), dtype=np.int32), r_factor=np.zeros(S), h_scaled=np.zeros(S), n_samples=np.zeros(S, dtype=np.int32))
+        sp = None if report_only else [np.zeros((S, N, count, 3)) for _ in range(3)]
+        opt = lambda x: _dp(x) if x is not None else nul
+        self._chk(self._L.dmpc_postcheck_setpoints(self._ctx, S, int(N), int(KT_alloc), _ip(used), _ip(msk) if msk is not None else inul, opt(pk), opt(vk),
+                                                   opt(ak), float(vmax), float(amax), float(Ts), int(first), count, *(3 * [nul] if sp is None else map(_dp, sp)),
+                                                   _dp(out["v_peak"]), _ip(out["v_peak_sample"]), _dp(out["a_peak"]), _ip(out["a_peak_sample"]),
+                                                   _dp(out["r_factor"]), _dp(out["h_scaled"]), _ip(out["n_samples"])))
+        if sp is not None:
+            out["p"], out["v"], out["a"] = sp
+        return out
 
     # ---- standalone small helpers (propStatedmpc.m, propState.m, is_inbounds.m, ReachedGoal.m) -----------
     def prop_state(self, A_p, A_v, a, A_initp=None, po=None, vo=None, off_p=None, off_v=None):

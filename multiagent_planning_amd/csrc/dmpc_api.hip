@@ -115,6 +115,7 @@ struct DevOptions {
     int close_pairs = 1;     // development option close_pairs: 0 = the scan walks its neighbour list for the pairs inside rmin instead of taking them from the grid query (A/B runs, tests)
     int close_cap = 64;      // development option close_cap: (neighbour, step) pairs the query records per agent; an agent with more falls back to the walk (tests)
     int clear_chunk = 8;     // development option clear_chunk: 100 Hz samples per workgroup of the clearance searches (dmpc_postcheck_clearance; tests)
+    int setpoint_batch = 0;  // development option setpoint_batch: 100 Hz samples per staging pass of dmpc_postcheck_setpoints (0: the 256 MB rule; tests)
 };
 
 struct dmpc_ctx {
@@ -158,6 +159,7 @@ struct dmpc_ctx {
     DevBuf pc_sc_path, pc_sc_y, pc_sc_M, pc_sc_w, pc_sc_pts, pc_sc_interp; // dmpc_postcheck_scripted: paths, knots, second derivatives, scratch, sample batch, p_scripted
     DevBuf pc_pts, pc_cell, pc_fill, pc_start, pc_sorted, pc_on;           // post-check, large scenes: cell grid of a batch of samples
     DevBuf pc_cl_part, pc_cl_run, pc_cl_out;                               // dmpc_postcheck_clearance: partials of a sample batch, running best, report
+    DevBuf pc_Mv, pc_Ma, pc_sp_stage, pc_sp_part, pc_sp_run, pc_sp_out;    // dmpc_postcheck_setpoints: second derivatives of the v / a splines, staged setpoints of a pass, peak partials, running peaks, report
     // multi-GPU (dmpc_multigpu.hip): RCCL communicator of this rank, exchange buffers
     void *comm = nullptr;
     int nranks = 1, rank = 0;
@@ -436,6 +438,7 @@ static const DevOptionEntry dev_options[] = {
     {"no_split_t", &DevOptions::no_split_t, true}, {"ext_cap", &DevOptions::ext_cap, true}, {"nbr_grid", &DevOptions::nbr_grid, true}, {"f32_dep_exp", &DevOptions::f32_dep_exp, true},
     {"grid_min", &DevOptions::grid_min, true}, {"grid_min_part", &DevOptions::grid_min_part, true}, {"no_level_check", &DevOptions::no_level_check, true}, {"lds_pad_kb", &DevOptions::lds_pad_kb, true},
     {"reduced_solver", &DevOptions::reduced_solver, true}, {"rsolve_cap", &DevOptions::rsolve_cap, true}, {"clear_chunk", &DevOptions::clear_chunk, true},
+    {"setpoint_batch", &DevOptions::setpoint_batch, true},
     {"close_pairs", &DevOptions::close_pairs, true}, {"close_cap", &DevOptions::close_cap, true}};
 
 extern "C" int dmpc_debug_option(dmpc_ctx *ctx, const char *name, int value)
@@ -1856,6 +1859,137 @@ extern "C" int dmpc_postcheck_clearance(dmpc_ctx *ctx, int S, int N, int N_cmd, 
         rc[(size_t)i] = clearance_one(c, sn, N, N_cmd, KT_alloc, K_T_used + s0, off(scene_mask, (size_t)s0), nullptr, nullptr, nullptr,
                                       off(po_static, (size_t)s0 * M * 3), off(path, (size_t)s0 * M * P * 3), P, vmax, amax, Ts, reach, off(clear_dist, a0),
                                       off(clear_partner, a0), off(clear_sample, a0));
+        c->hist_S = keep;
+    };
+    std::vector<std::thread> th;
+    for (int i = 1; i < parts; ++i) th.emplace_back(run, i);
+    run(0);
+    for (auto &t : th) t.join();
+    for (int i = 1; i < parts; ++i)
+        if (rc[(size_t)i]) FAIL(ctx, ctx->children[(size_t)i - 1]->err);
+    return rc[0];
+}
+
+// The setpoints and the limits report of dmpc_postcheck_setpoints for the scenes of ONE context: the preamble of every post-check, the splines
+// of the rescaled velocity and acceleration histories next to the position one, then the samples in ascending runs -- what lies in front of
+// the window and behind it in one launch each without stores, the window in passes of SB samples that are staged on the device and copied
+// out before the next (dmpc_postcheck.hip).
+static int setpoints_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask, const double *pk,
+                         const double *vk, const double *ak, double vmax, double amax, double Ts, int smp0, int ns_alloc, double *p_sp,
+                         double *v_sp, double *a_sp, double *v_peak, int32_t *v_peak_sample, double *a_peak, int32_t *a_peak_sample,
+                         double *r_factor, double *h_scaled, int32_t *n_samples)
+{
+    PcPrep q;
+    if (pc_prepare(ctx, "dmpc_postcheck_setpoints", S, N, KT_alloc, K_T_used, scene_mask, pk, vk, ak, nullptr, vmax, amax, Ts, q)) return -1;
+    hipStream_t st = ctx->stream;
+    const size_t A = (size_t)S * N, hist = A * (size_t)KT_alloc * 24;
+    const int ns_max = q.ns_max;
+    if (ctx->pc_Mv.ensure(hist) || ctx->pc_Ma.ensure(hist)) FAIL(ctx, "device allocation failed (setpoints)");
+    const unsigned b3 = (unsigned)((A * 3 + 255) / 256);
+    hipLaunchKernelGGL(pc::spline_kernel, dim3(b3), dim3(256), 0, st, S, N, KT_alloc, (const int *)q.d_kt, (const double *)q.d_hs,
+                       (const double *)q.dv, ctx->pc_Mv.as<double>(), ctx->pc_w.as<double>());
+    hipLaunchKernelGGL(pc::spline_kernel, dim3(b3), dim3(256), 0, st, S, N, KT_alloc, (const int *)q.d_kt, (const double *)q.d_hs,
+                       (const double *)q.da, ctx->pc_Ma.as<double>(), ctx->pc_w.as<double>());
+    // samples per pass over the window: at most 256 MB of staged setpoints at a time
+    const int n_arr = (p_sp ? 1 : 0) + (v_sp ? 1 : 0) + (a_sp ? 1 : 0);
+    int SB = 0;
+    if (n_arr) {
+        SB = (int)std::min(std::floor(256.0 * 1048576.0 / ((double)A * 24.0 * n_arr)), (double)ns_alloc);
+        if (ctx->opt.setpoint_batch > 0) SB = std::min(ctx->opt.setpoint_batch, ns_alloc);
+        SB = SB < 1 ? 1 : SB;
+    }
+    // the runs: [lo, hi) and whether the run is staged
+    struct Run { int lo, hi; bool staged; };
+    std::vector<Run> runs;
+    const long long w_end = (long long)smp0 + ns_alloc;
+    if (!n_arr) { if (ns_max > 0) runs.push_back({0, ns_max, false}); }
+    else {
+        if (std::min(smp0, ns_max) > 0) runs.push_back({0, std::min(smp0, ns_max), false});
+        for (long long lo = smp0; lo < w_end; lo += SB) runs.push_back({(int)lo, (int)std::min(lo + SB, w_end), true});
+        if (w_end < ns_max) runs.push_back({(int)w_end, ns_max, false});
+    }
+    int max_chunks = 1;
+    for (const Run &r : runs) max_chunks = std::max(max_chunks, (r.hi - r.lo + SP_CHUNK - 1) / SP_CHUNK);
+    const size_t stage = A * (size_t)SB * 24;
+    if ((n_arr && ctx->pc_sp_stage.ensure(stage * n_arr)) || ctx->pc_sp_part.ensure((size_t)max_chunks * A * 24) || ctx->pc_sp_run.ensure(A * 24) ||
+        ctx->pc_sp_out.ensure(A * 24))
+        FAIL(ctx, "device allocation failed (setpoints)");
+    double *d_stage[3] = {nullptr, nullptr, nullptr};
+    double *host[3] = {p_sp, v_sp, a_sp};
+    for (int a = 0, u = 0; a < 3; ++a)
+        if (host[a]) d_stage[a] = ctx->pc_sp_stage.as<double>() + (size_t)(u++) * A * (size_t)SB * 3;
+    // partials [chunk][S][N], running peaks and report [S][N]: values of v, values of a, samples of v, samples of a
+    double *part_v = ctx->pc_sp_part.as<double>(), *part_a = part_v + (size_t)max_chunks * A;
+    int *part_vs = (int *)(part_a + (size_t)max_chunks * A), *part_as = part_vs + (size_t)max_chunks * A;
+    double *run_v = ctx->pc_sp_run.as<double>(), *run_a = run_v + A, *o_v = ctx->pc_sp_out.as<double>(), *o_a = o_v + A;
+    int *run_vs = (int *)(run_a + A), *run_as = run_vs + A, *o_vs = (int *)(o_a + A), *o_as = o_vs + A;
+    auto finish = [&](int chunks, int first, int last) {
+        hipLaunchKernelGGL(pc::setpoint_finish_kernel, dim3((unsigned)((A + 255) / 256)), dim3(256), 0, st, A, N, chunks, first, last, (const int *)q.d_kt,
+                           (const double *)part_v, (const int *)part_vs, (const double *)part_a, (const int *)part_as, run_v, run_vs, run_a, run_as, o_v,
+                           o_vs, o_a, o_as);
+    };
+    if (runs.empty()) finish(0, 1, 1);   // (every scene masked, no window)
+    for (size_t r = 0; r < runs.size(); ++r) {
+        const Run &run = runs[r];
+        const int len = run.hi - run.lo, chunks = (len + SP_CHUNK - 1) / SP_CHUNK;
+        hipLaunchKernelGGL(pc::setpoint_kernel, dim3((unsigned)((N + SP_TILE - 1) / SP_TILE), (unsigned)chunks, (unsigned)S), dim3(SP_CHUNK), 0, st, S, N,
+                           KT_alloc, (const int *)q.d_kt, (const double *)q.d_hs, (const int *)q.d_ns, Ts, run.lo, run.hi, (const double *)q.dp,
+                           (const double *)ctx->pc_M.as<double>(), (const double *)q.dv, (const double *)ctx->pc_Mv.as<double>(), (const double *)q.da,
+                           (const double *)ctx->pc_Ma.as<double>(), run.staged ? d_stage[0] : nullptr, run.staged ? d_stage[1] : nullptr,
+                           run.staged ? d_stage[2] : nullptr, SB, part_v, part_vs, part_a, part_as);
+        finish(chunks, r == 0, r + 1 == runs.size());
+        HIPCHK(ctx, hipGetLastError());
+        if (!run.staged) continue;
+        for (int a = 0; a < 3; ++a)   // rows of `len` samples out of the staging rows of SB, to their place in the rows of ns_alloc
+            if (host[a] && len == ns_alloc && SB == ns_alloc)   // (the whole window in one pass: one contiguous block)
+                HIPCHK(ctx, hipMemcpyAsync(host[a], d_stage[a], A * (size_t)ns_alloc * 24, hipMemcpyDeviceToHost, st));
+            else if (host[a])
+                HIPCHK(ctx, hipMemcpy2DAsync(host[a] + (size_t)(run.lo - smp0) * 3, (size_t)ns_alloc * 24, d_stage[a], (size_t)SB * 24, (size_t)len * 24, A,
+                                             hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));   // (the next pass overwrites the staging arrays)
+    }
+    HIPCHK(ctx, hipGetLastError());
+    if (v_peak) HIPCHK(ctx, hipMemcpyAsync(v_peak, o_v, A * 8, hipMemcpyDeviceToHost, st));
+    if (a_peak) HIPCHK(ctx, hipMemcpyAsync(a_peak, o_a, A * 8, hipMemcpyDeviceToHost, st));
+    if (v_peak_sample) HIPCHK(ctx, hipMemcpyAsync(v_peak_sample, o_vs, A * 4, hipMemcpyDeviceToHost, st));
+    if (a_peak_sample) HIPCHK(ctx, hipMemcpyAsync(a_peak_sample, o_as, A * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    for (int s = 0; s < S; ++s) {   // (what dmpc_postcheck reports: NaN / NaN / 0 for a masked scene)
+        if (r_factor) r_factor[s] = q.rf[s];
+        if (h_scaled) h_scaled[s] = q.hs[s];
+        if (n_samples) n_samples[s] = q.ns[s];
+    }
+    return 0;
+}
+
+extern "C" int dmpc_postcheck_setpoints(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                                        const double *pk, const double *vk, const double *ak, double vmax, double amax, double Ts, int smp0,
+                                        int ns_alloc, double *p_sp, double *v_sp, double *a_sp, double *v_peak, int32_t *v_peak_sample,
+                                        double *a_peak, int32_t *a_peak_sample, double *r_factor, double *h_scaled, int32_t *n_samples)
+{
+    if (!ctx) { g_err = "dmpc_postcheck_setpoints: ctx is NULL"; return -1; }
+    if (smp0 < 0) FAIL(ctx, "dmpc_postcheck_setpoints: smp0 must be >= 0 (the first sample of the window)");
+    if (ns_alloc < 0) FAIL(ctx, "dmpc_postcheck_setpoints: ns_alloc must be >= 0");
+    if (ns_alloc == 0 && (p_sp || v_sp || a_sp)) FAIL(ctx, "dmpc_postcheck_setpoints: a setpoint array needs ns_alloc > 0");
+    if (ns_alloc > 0 && !p_sp && !v_sp && !a_sp) FAIL(ctx, "dmpc_postcheck_setpoints: ns_alloc > 0 needs p_sp, v_sp or a_sp (the report alone: ns_alloc = 0)");
+    if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, "dmpc_postcheck_setpoints: pk, vk, ak must be all given or all NULL");
+    if ((long long)smp0 + ns_alloc > 0x7fff0000LL) FAIL(ctx, "dmpc_postcheck_setpoints: smp0 + ns_alloc overflows the sample index");
+    const int parts = (int)ctx->split_at.size() - 1;
+    if (pk || parts < 2 || ctx->split_at.back() != S || ctx->hist_S != S || (int)ctx->children.size() < parts - 1 || !K_T_used)
+        return setpoints_one(ctx, S, N, KT_alloc, K_T_used, scene_mask, pk, vk, ak, vmax, amax, Ts, smp0, ns_alloc, p_sp, v_sp, a_sp, v_peak,
+                             v_peak_sample, a_peak, a_peak_sample, r_factor, h_scaled, n_samples);
+    // resident histories of a split dmpc_transition: each part is evaluated where it lives, concurrently (as postcheck_any does)
+    auto off = [&](auto *ptr, size_t o) { return ptr ? ptr + o : ptr; };
+    std::vector<int> rc((size_t)parts, 0);
+    auto run = [&](int i) {
+        dmpc_ctx *c = i ? ctx->children[(size_t)i - 1] : ctx;
+        const int s0 = ctx->split_at[(size_t)i], sn = ctx->split_at[(size_t)i + 1] - s0;
+        const size_t a0 = (size_t)s0 * N, w0 = a0 * (size_t)ns_alloc * 3;
+        const int keep = c->hist_S;
+        c->hist_S = sn;
+        rc[(size_t)i] = setpoints_one(c, sn, N, KT_alloc, K_T_used + s0, off(scene_mask, (size_t)s0), nullptr, nullptr, nullptr, vmax, amax, Ts, smp0,
+                                      ns_alloc, off(p_sp, w0), off(v_sp, w0), off(a_sp, w0), off(v_peak, a0), off(v_peak_sample, a0), off(a_peak, a0),
+                                      off(a_peak_sample, a0), off(r_factor, (size_t)s0), off(h_scaled, (size_t)s0), off(n_samples, (size_t)s0));
         c->hist_S = keep;
     };
     std::vector<std::thread> th;

@@ -647,4 +647,126 @@ __global__ void clear_finish_kernel(size_t total, int Nc, int nchunk, int first,
     sample[e] = !masked && found ? bs : -1;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Flight setpoints (dmpc_postcheck_setpoints): position, velocity and acceleration of every commanded agent at the 100 Hz samples, and per agent
+// the largest |v| and |a| over ALL samples with the sample at which it happens.  The reference splines the three histories independently
+// (dmpc_soft_bound.m:165-169), so three splines on the same knots are evaluated: y = the rescaled pk / vk / ak as rescale_kernel leaves them,
+// M = their second derivatives (spline_kernel).  Sample j has t = j * Ts, the expression of path_kernel / grid_eval_kernel.
+// A workgroup = (tile of SP_TILE agents, chunk of SP_CHUNK samples, scene): thread t owns sample lo + chunk * SP_CHUNK + t and walks the agents
+// of the tile, so the lanes of a wave hold consecutive samples of ONE agent -- the stores into [..][SB][3] are one contiguous run per wave and
+// the ~h_scaled / Ts lanes of a spline interval read the same knots.  Peaks: (value, sample) pairs ordered by larger value, then smaller sample
+// -- a total order, so the maximum does not depend on how the samples are grouped: per wave by cross-lane exchange, per workgroup through LDS
+// in wave order, partials [chunk][S][N], folded in chunk order by setpoint_finish_kernel.
+#define SP_TILE 64
+#define SP_CHUNK 256
+
+// the norm of every peak, on every path
+__device__ __forceinline__ double norm3(double x, double y, double z)
+{
+    return sqrt(fma(z, z, fma(y, y, x * x)));
+}
+// (value, sample) lexicographically: the larger value, then the smaller sample; (-1, -1) is "no sample" (norms are >= 0)
+__device__ __forceinline__ void peak_take(double v, int smp, double &bv, int &bs)
+{
+    if (v > bv || (v == bv && smp < bs)) { bv = v; bs = smp; }
+}
+__device__ __forceinline__ void peak_wave(double &bv, int &bs)
+{
+    for (int d = 32; d > 0; d >>= 1) {
+        const double ov = __shfl_xor(bv, d, 64);
+        const int os = __shfl_xor(bs, d, 64);
+        peak_take(ov, os, bv, bs);
+    }
+}
+
+// samples lo .. hi-1 of the transition.  sp / sv / sa: staging arrays [S][N][SB][3] of the samples lo .. lo+SB-1 (hi - lo <= SB) or null; every slot
+// below hi is written, zero from the scene's n_samples on.  part_*: [gridDim.y][S][N].
+__global__ void __launch_bounds__(SP_CHUNK)
+setpoint_kernel(int S, int N, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs, const int *__restrict__ ns, double Ts,
+                int lo, int hi, const double *__restrict__ yp, const double *__restrict__ Mp, const double *__restrict__ yv,
+                const double *__restrict__ Mv, const double *__restrict__ ya, const double *__restrict__ Ma, double *__restrict__ sp,
+                double *__restrict__ sv, double *__restrict__ sa, int SB, double *__restrict__ part_v, int *__restrict__ part_vs,
+                double *__restrict__ part_a, int *__restrict__ part_as)
+{
+    __shared__ double sh_v[SP_TILE][SP_CHUNK / 64], sh_a[SP_TILE][SP_CHUNK / 64];
+    __shared__ int sh_vs[SP_TILE][SP_CHUNK / 64], sh_as[SP_TILE][SP_CHUNK / 64];
+    const int s = blockIdx.z, chunk = blockIdx.y, i0 = blockIdx.x * SP_TILE;
+    const int cnt = N - i0 < SP_TILE ? N - i0 : SP_TILE;
+    const int j0 = lo + chunk * SP_CHUNK, j = j0 + (int)threadIdx.x;
+    const int n = kt_used[s], nsamp = ns[s];
+    const bool slot = j < hi, live = slot && j < nsamp;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const size_t a0 = (size_t)s * N + i0;
+    if (j0 >= nsamp) {   // (uniform per workgroup) nothing to evaluate: zero slots, empty partials
+        if (slot)
+            for (int a = 0; a < cnt; ++a) {
+                const size_t q = ((a0 + a) * (size_t)SB + (size_t)(j - lo)) * 3;
+                if (sp) { sp[q] = 0.0; sp[q + 1] = 0.0; sp[q + 2] = 0.0; }
+                if (sv) { sv[q] = 0.0; sv[q + 1] = 0.0; sv[q + 2] = 0.0; }
+                if (sa) { sa[q] = 0.0; sa[q + 1] = 0.0; sa[q + 2] = 0.0; }
+            }
+        if ((int)threadIdx.x < cnt) {
+            const size_t e = ((size_t)chunk * S + s) * N + i0 + threadIdx.x;
+            part_v[e] = -1.0; part_vs[e] = -1; part_a[e] = -1.0; part_as[e] = -1;
+        }
+        return;
+    }
+    const double h = hs[s], t = j * Ts;
+    for (int a = 0; a < cnt; ++a) {
+        const size_t o = (a0 + a) * (size_t)KTa * 3;
+        double px = 0.0, py = 0.0, pz = 0.0, vx = 0.0, vy = 0.0, vz = 0.0, ax = 0.0, ay = 0.0, az = 0.0;
+        double bv = -1.0, ba = -1.0;
+        int bvs = -1, bas = -1;
+        if (live) {
+            px = spline_eval2(yp, Mp, o, n, h, t); py = spline_eval2(yp, Mp, o + 1, n, h, t); pz = spline_eval2(yp, Mp, o + 2, n, h, t);
+            vx = spline_eval2(yv, Mv, o, n, h, t); vy = spline_eval2(yv, Mv, o + 1, n, h, t); vz = spline_eval2(yv, Mv, o + 2, n, h, t);
+            ax = spline_eval2(ya, Ma, o, n, h, t); ay = spline_eval2(ya, Ma, o + 1, n, h, t); az = spline_eval2(ya, Ma, o + 2, n, h, t);
+            bv = norm3(vx, vy, vz); bvs = j;
+            ba = norm3(ax, ay, az); bas = j;
+        }
+        if (slot) {
+            const size_t q = ((a0 + a) * (size_t)SB + (size_t)(j - lo)) * 3;
+            if (sp) { sp[q] = px; sp[q + 1] = py; sp[q + 2] = pz; }
+            if (sv) { sv[q] = vx; sv[q + 1] = vy; sv[q + 2] = vz; }
+            if (sa) { sa[q] = ax; sa[q + 1] = ay; sa[q + 2] = az; }
+        }
+        peak_wave(bv, bvs);
+        peak_wave(ba, bas);
+        if (lane == 0) { sh_v[a][wave] = bv; sh_vs[a][wave] = bvs; sh_a[a][wave] = ba; sh_as[a][wave] = bas; }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+        const int a = threadIdx.x;
+        double bv = sh_v[a][0], ba = sh_a[a][0];
+        int bvs = sh_vs[a][0], bas = sh_as[a][0];
+        for (int w = 1; w < SP_CHUNK / 64; ++w) { peak_take(sh_v[a][w], sh_vs[a][w], bv, bvs); peak_take(sh_a[a][w], sh_as[a][w], ba, bas); }
+        const size_t e = ((size_t)chunk * S + s) * N + i0 + a;
+        part_v[e] = bv; part_vs[e] = bvs; part_a[e] = ba; part_as[e] = bas;
+    }
+}
+
+// thread per (scene, agent): the partials of one launch, in chunk order, into the running peaks run_* [S][N] (`first`: the launch opens the
+// transition); `last`: the report, a masked scene NaN / -1
+__global__ void setpoint_finish_kernel(size_t total, int N, int nchunk, int first, int last, const int *__restrict__ kt_used,
+                                       const double *__restrict__ part_v, const int *__restrict__ part_vs, const double *__restrict__ part_a,
+                                       const int *__restrict__ part_as, double *__restrict__ run_v, int *__restrict__ run_vs,
+                                       double *__restrict__ run_a, int *__restrict__ run_as, double *__restrict__ o_v, int *__restrict__ o_vs,
+                                       double *__restrict__ o_a, int *__restrict__ o_as)
+{
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    double bv = first ? -1.0 : run_v[e], ba = first ? -1.0 : run_a[e];
+    int bvs = first ? -1 : run_vs[e], bas = first ? -1 : run_as[e];
+    for (int c = 0; c < nchunk; ++c) {
+        const size_t o = (size_t)c * total + e;
+        peak_take(part_v[o], part_vs[o], bv, bvs);
+        peak_take(part_a[o], part_as[o], ba, bas);
+    }
+    run_v[e] = bv; run_vs[e] = bvs; run_a[e] = ba; run_as[e] = bas;
+    if (!last) return;
+    const bool masked = !kt_used[e / (size_t)N];
+    o_v[e] = masked ? NAN : bv; o_vs[e] = masked ? -1 : bvs;
+    o_a[e] = masked ? NAN : ba; o_as[e] = masked ? -1 : bas;
+}
+
 }   // namespace pc

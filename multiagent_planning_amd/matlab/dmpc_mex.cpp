@@ -10,6 +10,8 @@
 //   [r_factor,h_scaled,violation,totdist,traj_time,p] = dmpc_mex('postcheck', params, pk, vk, ak, pf, vmax, amax, Ts)
 //   [r_factor,h_scaled,violation,totdist,traj_time,p,violation_static,min_dist_static] = dmpc_mex('postcheck', ..., Ts, po_static)
 //   [dist,partner,time] = dmpc_mex('clearance', params, pk, vk, ak, pf, vmax, amax, Ts[, po_static|[][, reach]])   2 x N each; partner 1-based, 0 = none
+//   [p,v,a,peaks] = dmpc_mex('setpoints', params, pk, vk, ak, vmax, amax, Ts[, first[, count]])   100 Hz setpoints 3 x count x N from sample `first` (1-based) on;
+//                                                                                    peaks 4 x N: v_peak; its sample (1-based); a_peak; its sample
 //   [Lambda,Av,A0,Delta] = dmpc_mex('model_matrices', params)
 //   [Ain,bin,dist] = dmpc_mex('coll_rows', params, l, sel0, k_cmp0, k_blk0, p, a0, rmin, c, A)     (0-based indices)
 //   [Ain,bin]      = dmpc_mex('add_coll_constr', params, p, po, rmin, c, A)
@@ -234,6 +236,46 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 2) {   // seconds from the start of the rescaled transition; NaN: nothing inside reach
             plhs[2] = mxCreateDoubleMatrix(2, N, mxREAL);
             for (size_t e = 0; e < (size_t)2 * N; ++e) mxGetPr(plhs[2])[e] = sample[e] >= 0 ? sample[e] * Ts : (double)NAN;
+        }
+        return;
+    }
+    if (!std::strcmp(cmd, "setpoints")) {   // dmpc_postcheck_setpoints for one trial: spline(tk,pk,t), spline(tk,vk,t), spline(tk,ak,t) (dmpc_soft_bound.m:165-169) and the peaks of |v|, |a|
+        need(nrhs >= 8 && nrhs <= 10, "setpoints: (cmd, params, pk, vk, ak, vmax, amax, Ts[, first[, count]])");
+        const mwSize *dh = mxGetDimensions(prhs[2]);
+        need(mxGetNumberOfDimensions(prhs[2]) == 3 && dh[0] == 3, "pk must be 3 x KT x N");
+        const int KT = (int)dh[1], N = (int)dh[2];
+        for (int i = 3; i < 5; ++i) need(mxGetNumberOfElements(prhs[i]) == (size_t)3 * KT * N, "vk, ak must match pk");
+        const double vmax = mxGetScalar(prhs[5]), amax = mxGetScalar(prhs[6]), Ts = mxGetScalar(prhs[7]);
+        const double first = nrhs >= 9 ? mxGetScalar(prhs[8]) : 1.0;
+        need(first >= 1 && first == std::floor(first) && first < 2147483647.0, "first must be a sample number >= 1");
+        const int smp0 = (int)first - 1;
+        int32_t kt = KT, ns = 0;
+        int count = 0;
+        if (nrhs == 10) {
+            const double c = mxGetScalar(prhs[9]);
+            need(c >= 1 && c == std::floor(c) && c < 2147483647.0, "count must be an integer >= 1");
+            count = (int)c;
+        } else {   // from `first` to the end of the trajectory: the report alone says how long it is
+            if (dmpc_postcheck_setpoints(ctx, 1, N, KT, &kt, nullptr, mxGetPr(prhs[2]), mxGetPr(prhs[3]), mxGetPr(prhs[4]), vmax, amax, Ts, 0, 0, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ns))
+                mexErrMsgIdAndTxt("dmpc:setpoints", "%s", dmpc_last_error(ctx));
+            count = ns - smp0 > 1 ? ns - smp0 : 1;
+        }
+        const mwSize d3[3] = {3, (mwSize)count, (mwSize)N};   // MATLAB (3, count, N) column-major IS the [N][count][3] layout
+        plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        mxArray *v = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), *a = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        std::vector<double> vp((size_t)N), ap((size_t)N);
+        std::vector<int32_t> vs((size_t)N), as((size_t)N);
+        if (dmpc_postcheck_setpoints(ctx, 1, N, KT, &kt, nullptr, mxGetPr(prhs[2]), mxGetPr(prhs[3]), mxGetPr(prhs[4]), vmax, amax, Ts, smp0, count,
+                                     mxGetPr(plhs[0]), mxGetPr(v), mxGetPr(a), vp.data(), vs.data(), ap.data(), as.data(), nullptr, nullptr, nullptr))
+            mexErrMsgIdAndTxt("dmpc:setpoints", "%s", dmpc_last_error(ctx));
+        if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
+        if (nlhs > 3) {   // rows: v_peak, its 1-based sample, a_peak, its 1-based sample
+            plhs[3] = mxCreateDoubleMatrix(4, N, mxREAL);
+            for (int i = 0; i < N; ++i) {
+                double *col = mxGetPr(plhs[3]) + (size_t)4 * i;
+                col[0] = vp[(size_t)i]; col[1] = (double)(vs[(size_t)i] + 1); col[2] = ap[(size_t)i]; col[3] = (double)(as[(size_t)i] + 1);
+            }
         }
         return;
     }
