@@ -104,6 +104,8 @@ struct DevOptions {
     int grid_min = 768;      // development option grid_min: cell-grid neighbour lists from this many agents per scene on (below: nbr_kernel) ...
     int grid_min_part = 2048; // ... and when the query covers only a PART of the scene's agents (a rank's chunk: the grid is still built over all of them)
     int prep_fuse = 1;       // development option prep_fuse: 0 = the cell grid of a single scene by the five kernels of round 4 instead of grid_prep_kernel + grid_fill2_kernel
+    int grid_cells = -1;     // development option grid_cells: row of plan_lists' cell geometries (0 = the cells of rounds 4-6: R x 1.5 R x 1.5 R c, at most 32 per axis; 1, 2, 3 finer; other values: the default row)
+    int list_cap = 0;        // development option list_cap (tests): at most this many entries per neighbour list, in multiples of 64 (0: the built-in rule -- which never goes below the scene's agent count, so a full list needs this option)
     int nbr_grid = 1;        // development option nbr_grid: 0 = neighbour lists of large scenes from the all-pairs box test of round 3 (nbr_kernel) instead of the cell grid + distance filter
     int no_level_skip = 0;   // development option no_level_skip (see StepParams)
     int no_level_check = 0;  // development option no_level_check (see StepParams)
@@ -136,6 +138,7 @@ struct dmpc_ctx {
     int num_cu = 0;
     DevOptions opt;          // development options (dmpc_debug_option)
     int max_lds_persist = 0;
+    int max_lds_fill2 = 0;   // dynamic-LDS limit grid_fill2_kernel was last raised to (build_neighbour_lists)
     DevBuf prev_cost;        // [S * c_count] work estimates of the previous step (solve kernel -> order kernel)
     long prev_cost_shape = -1;
     int single_tier = 0;         // 1: solve with the full working-set capacity in one launch
@@ -439,7 +442,7 @@ static const DevOptionEntry dev_options[] = {
     {"grid_min", &DevOptions::grid_min, true}, {"grid_min_part", &DevOptions::grid_min_part, true}, {"no_level_check", &DevOptions::no_level_check, true}, {"lds_pad_kb", &DevOptions::lds_pad_kb, true},
     {"reduced_solver", &DevOptions::reduced_solver, true}, {"rsolve_cap", &DevOptions::rsolve_cap, true}, {"clear_chunk", &DevOptions::clear_chunk, true},
     {"setpoint_batch", &DevOptions::setpoint_batch, true},
-    {"close_pairs", &DevOptions::close_pairs, true}, {"close_cap", &DevOptions::close_cap, true}};
+    {"close_pairs", &DevOptions::close_pairs, true}, {"close_cap", &DevOptions::close_cap, true}, {"grid_cells", &DevOptions::grid_cells, true}, {"list_cap", &DevOptions::list_cap, true}};
 
 extern "C" int dmpc_debug_option(dmpc_ctx *ctx, const char *name, int value)
 {

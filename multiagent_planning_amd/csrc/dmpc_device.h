@@ -60,6 +60,7 @@ struct StepParams {
     int *nbr_list;          // [S*c_count][nbr_cap] neighbours that can come close, in increasing index order (nbr_kernel), or null
     const void *lrow;       // neighbour-major copy of the table the scan reads (table_nbrmajor_kernel), with the lists; or null
     const int *nbr_cnt;     // [S*c_count][NBR_PARTS] entries of each piece of a list; -1: did not fit (the scan walks the whole table)
+    int nbr_parts;          // pieces the list builder left a list in: NBR_PARTS (nbr_kernel), or 1 (grid_query_kernel: one contiguous run, its count in slot 0 -- the other slots are not written)
     // closed loops, tiny launches: the step after the solve (state advance, history column, scene verdict: post_step_kernel) done by
     // the solve kernel itself -- each wave for its agent, the last wave of a scene (a counter) for the verdict; post_on = 0: off
     int post_on, post_KT, post_k;

@@ -581,8 +581,13 @@ __device__ __forceinline__ void scan_body(const StepParams &P, const int lane, c
     // row builders below walk the list instead of all N neighbours.  Conservative: results are unchanged.
     // nnbr < 0: no list (small scenes, variants that take every neighbour, or more survivors than the list holds).
     int nnbr = -1;
-    if (P.nbr_cnt) {
-        // the pre-pass leaves the list in NBR_PARTS pieces (one per quarter of the scene, each in increasing neighbour order): close the gaps
+    if (P.nbr_cnt && P.nbr_parts == 1) {
+        // the grid query leaves the list in ONE piece: one count, nothing to close (sixteen counts read one after the other were fifteen
+        // serialised round trips for a zero at the head of every scan wave)
+        const int n = __builtin_amdgcn_readfirstlane(P.nbr_cnt[(size_t)gid * NBR_PARTS]);
+        if (n >= 0) { nnbr = n; scan_nbr = P.nbr_list + (size_t)gid * P.nbr_cap; }
+    } else if (P.nbr_cnt) {
+        // nbr_kernel leaves the list in NBR_PARTS pieces (one per part of the scene, each in increasing neighbour order): close the gaps
         int *lst = P.nbr_list + (size_t)gid * P.nbr_cap;
         const int pcap = P.nbr_cap / NBR_PARTS;
         int tot = 0;
@@ -1693,26 +1698,34 @@ __global__ __launch_bounds__(256) void grid_prep_kernel(int total, int C, int sh
     __syncthreads();
     if (threadIdx.x < NSEG * 3) { const int v = mh[threadIdx.x]; if (v > *(volatile int *)(maxhalf + threadIdx.x)) atomicMax(maxhalf + threadIdx.x, v); }
 }
-// grid_fill2_kernel: every block forms the exclusive prefix of the three segments' cell counts in its LDS (1 560 cells each at N = 10^4: cheaper
-// than a launch of its own and a trip through memory), block 0 also writes it out for the query; then the entry records as grid_fill_kernel,
-// at start[cell] + the position grid_prep_kernel drew.  Dynamic LDS: NSEG * (ncell + 1) ints.
+// grid_fill2_kernel: every block forms the exclusive prefix of the three segments' cell counts in its LDS (8 200 cells each at N = 10^4: cheaper
+// than a launch of its own and a trip through memory) and writes its slice of it out for the query; then the entry records as grid_fill_kernel,
+// at start[cell] + the position grid_prep_kernel drew.  Dynamic LDS: NSEG * (ncell + 1) ints (plan_lists: up to 128 KB, the limit raised by the launcher).
 __global__ __launch_bounds__(256) void grid_fill2_kernel(int total, int C, int ncell, float e1z, const int *__restrict__ cellof, const int *__restrict__ posof,
                                                          const int *__restrict__ cnt, int *__restrict__ start, const float *__restrict__ lrow, f4_t *__restrict__ ent)
 {
     int *st = (int *)dmpc_smem;   // [NSEG][ncell + 1]
     __shared__ int wtot[NSEG][4];
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int chunk = (ncell + 255) / 256;
+    // the counts come into LDS coalesced and become their prefix in place (a thread that read its chunk from memory did so at a stride of
+    // the chunk, twice: 33 cells at the 8 200 cells of a fine grid); an ODD chunk keeps the threads of a wave on different banks
+    const int chunk = ((ncell + 255) / 256) | 1;
     const int lo = t * chunk, hi = lo + chunk < ncell ? lo + chunk : ncell;
+    // (the three segments side by side in every loop: three independent chains of loads / LDS round trips instead of one after the other)
+#pragma unroll 4
+    for (int j = t; j < ncell; j += 256)
+#pragma unroll
+        for (int sg = 0; sg < NSEG; ++sg) st[sg * (ncell + 1) + j] = cnt[(size_t)sg * ncell + j];
+    __syncthreads();
     // the three segments' prefixes together: a thread sums its chunk of each, one scan inside the wave (shuffles), the four waves' totals through LDS
     int sum[NSEG], inc[NSEG];
 #pragma unroll
-    for (int sg = 0; sg < NSEG; ++sg) {
-        const int *c = cnt + (size_t)sg * ncell;
-        int v = 0;
-        for (int j = lo; j < hi; ++j) v += c[j];
-        sum[sg] = v; inc[sg] = v;
-    }
+    for (int sg = 0; sg < NSEG; ++sg) sum[sg] = 0;
+    for (int j = lo; j < hi; ++j)
+#pragma unroll
+        for (int sg = 0; sg < NSEG; ++sg) sum[sg] += st[sg * (ncell + 1) + j];
+#pragma unroll
+    for (int sg = 0; sg < NSEG; ++sg) inc[sg] = sum[sg];
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1)
 #pragma unroll
@@ -1721,16 +1734,22 @@ __global__ __launch_bounds__(256) void grid_fill2_kernel(int total, int C, int n
 #pragma unroll
         for (int sg = 0; sg < NSEG; ++sg) wtot[sg][wave] = inc[sg];
     __syncthreads();
+    int run[NSEG];
 #pragma unroll
     for (int sg = 0; sg < NSEG; ++sg) {
-        const int *c = cnt + (size_t)sg * ncell;
-        int run = inc[sg] - sum[sg];   // exclusive inside the wave
-        for (int w = 0; w < wave; ++w) run += wtot[sg][w];
-        for (int j = lo; j < hi; ++j) { st[sg * (ncell + 1) + j] = run; run += c[j]; }
+        run[sg] = inc[sg] - sum[sg];   // exclusive inside the wave
+        for (int w = 0; w < wave; ++w) run[sg] += wtot[sg][w];
         if (t == 255) st[sg * (ncell + 1) + ncell] = wtot[sg][0] + wtot[sg][1] + wtot[sg][2] + wtot[sg][3];
     }
+    for (int j = lo; j < hi; ++j)   // (a thread's own chunk: nobody else reads or writes it)
+#pragma unroll
+        for (int sg = 0; sg < NSEG; ++sg) { int *c = st + sg * (ncell + 1) + j; const int n = *c; *c = run[sg]; run[sg] += n; }
     __syncthreads();
-    if (blockIdx.x == 0) for (int j = t; j < NSEG * (ncell + 1); j += 256) start[j] = st[j];
+    {   // the prefix for the query: every block holds all of it and writes its own slice (block 0 alone wrote 96 rounds at 8 200 cells)
+        const int all = NSEG * (ncell + 1), slice = (all + (int)gridDim.x - 1) / (int)gridDim.x;
+        const int j0 = (int)blockIdx.x * slice, j1 = j0 + slice < all ? j0 + slice : all;
+        for (int j = j0 + t; j < j1; j += 256) start[j] = st[j];
+    }
     const int i = (int)blockIdx.x * 256 + t;
     if (i >= total) return;
     const int code = ((i / C) << 20) | (i % C);   // (chunk << 20) | column
@@ -1806,7 +1825,12 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
     const int self_code = (g_local << 20) | cl;
     {
         const int sg = wave;
-        // this segment's own box, inflated by the selection radius; the cells its neighbours' centres can lie in
+        // this segment's own box, inflated by the selection radius; the cells its neighbours' centres can lie in.  Why the range is a superset
+        // whatever the cell size and however many cells an axis has (plan_lists: up to 64): a neighbour that comes within R of this agent at a
+        // step of the segment has, per axis, a point of its segment box within R of the own box, and its box centre lies within its half
+        // extent <= maxhalf of that point: centre in [lo - reach, hi + reach].  grid_coord is monotone (floor, then the clamp to [0, n - 1]), so
+        // the centre's cell lies between the cells of the two ends -- for any org, inv and n; binning and query use the same function and
+        // the same GridGeom.
         int c_lo[3], c_hi[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -1973,7 +1997,7 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
         }
         total += wave_total;
     }
-    if (lane < NBR_PARTS) cnt_out[(size_t)oid * NBR_PARTS + lane] = lane == 0 ? (total > cap ? -1 : total) : 0;
+    if (lane == 0) cnt_out[(size_t)oid * NBR_PARTS] = total > cap ? -1 : total;   // one piece, one count (StepParams::nbr_parts = 1: the scan reads slot 0 alone)
 }
 
 // calibration of the HBM-side counters (profiles/: FETCH_SIZE is documented for 16-byte-per-lane streams only): a streaming read of a known

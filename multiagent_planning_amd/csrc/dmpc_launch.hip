@@ -191,6 +191,8 @@ struct TierPlan {
 };
 
 // the neighbour lists of large scenes
+constexpr int GRID_CELLS_DEFAULT = 2;                 // row of plan_lists' cell geometries taken when option grid_cells names none
+constexpr size_t GRID_FILL2_LDS_MAX = 128 * 1024;     // dynamic LDS of a grid_fill2_kernel block up to which one scene's grid is built in two launches
 struct ListPlan {
     bool build = false;      // lists at all
     bool use_grid = false;   // from the cell grid + distance filter (grid_query_kernel); else the all-pairs box test (nbr_kernel)
@@ -285,6 +287,7 @@ static ListPlan plan_lists(const dmpc_ctx *ctx, const StepPlan &pl)
     L.cap = ((long)sh.G * sh.C + 63) & ~63L;
     if (L.cap > 4096) L.cap = 4096;
     while (L.cap > 256 && agents * (size_t)L.cap * 4 > ((size_t)1 << 30)) L.cap >>= 1;
+    if (o.list_cap > 0 && (((long)o.list_cap + 63) & ~63L) < L.cap) L.cap = ((long)o.list_cap + 63) & ~63L;
     L.Rsel = (p.variant == DMPC_VAR_HARD) ? 1.0 : 3.0 * p.rmin;
     L.R = L.Rsel * 1.0001 + 1e-4;   // a little more than the scan's radius: conservative in fp32 too
     // round 4: lists from a cell grid, filtered by the fp32 distance test (grid_query_kernel); the all-pairs box test of round 3 stays
@@ -306,22 +309,41 @@ static ListPlan plan_lists(const dmpc_ctx *ctx, const StepPlan &pl)
     L.close = L.use_grid && close_want;
     if (!L.close) L.close_cap = 0;
     if (!L.use_grid) return L;
-    // cells: R along x (the cells of a run along x are contiguous in the entry array: their granularity is free), 1.5 R along y
-    // and 1.5 R c along z (the metric's z scale), at most 32 per axis
-    const double cell[3] = {L.R, 1.5 * L.R, 1.5 * L.R * p.c};
-    for (int a = 0; a < 3; ++a) {
-        const double span = p.pmax[a] - p.pmin[a];
-        int n = (int)(span / cell[a]);
-        n = n < 1 ? 1 : (n > 32 ? 32 : n);
-        L.gg.n[a] = n; L.gg.org[a] = (float)p.pmin[a]; L.gg.inv[a] = (float)(n / (span > 0 ? span : 1.0));
-        L.ncell *= n;
-    }
+    // Cells, in units of (R, R, R c) -- c: the metric's z scale -- and the most cells an axis gets: decided here alone, the kernels take
+    // whatever GridGeom says.  The cells of a run along x are contiguous in the entry array, so fine x cells cost the query nothing; every
+    // (y, z) cell row in reach is one run of its candidate sequence, and since round 5 the runs of a query are one sequence (64 run bounds
+    // per batch, one fetch), so finer y and z cells cost a few more run bounds and save the candidates of the cells' rounding: per agent and
+    // MPC step 2 / 6 / 10 of the 10^4-agent scene 1 115 / 1 855 / 2 621 candidates in geometry 0, 810 / 1 432 / 2 074 in geometry 2
+    // (DESIGN.md section 7 has the measured table).  Option grid_cells selects the row; the default is the one that measured best.
+    // A finer grid is taken only while it has no more cells than geometry 0 can have (32^3): no buffer, no prefix pass over the cells
+    // grows beyond what it could be before.
+    static const struct { double f[3]; int cap; } geoms[] = {
+        {{1.0, 1.5, 1.5}, 32},    // 0: rounds 4-6
+        {{0.5, 1.5, 1.5}, 64},    // 1: finer along x only
+        {{0.5, 1.0, 1.0}, 64},    // 2
+        {{0.5, 1.0, 0.5}, 64}};   // 3: finer in z (above the fused build's limit at N = 10^4)
+    constexpr int n_geoms = (int)(sizeof(geoms) / sizeof(geoms[0]));
+    auto cells = [&](int which) {
+        L.ncell = 1;
+        for (int a = 0; a < 3; ++a) {
+            const double span = p.pmax[a] - p.pmin[a];
+            const double cell = geoms[which].f[a] * L.R * (a == 2 ? p.c : 1.0);
+            int n = (int)(span / cell);
+            n = n < 1 ? 1 : (n > geoms[which].cap ? geoms[which].cap : n);
+            L.gg.n[a] = n; L.gg.org[a] = (float)p.pmin[a]; L.gg.inv[a] = (float)(n / (span > 0 ? span : 1.0));
+            L.ncell *= n;
+        }
+    };
+    cells((o.grid_cells >= 0 && o.grid_cells < n_geoms) ? o.grid_cells : GRID_CELLS_DEFAULT);
+    if (L.ncell > 32 * 32 * 32) cells(0);
     // one grid per third of the horizon (keyed by the centre of that segment's box: a third of the extent of the whole horizon's).  One
     // buffer: [S][3][ncell] counts, [S][3][3] largest half extents (zeroed together), [S][3][ncell + 1] starts, [3][G S C] cells, [S][3][G C] entries
     L.n_cnt = (size_t)sh.S * NSEG * L.ncell; L.n_mh = (size_t)sh.S * NSEG * 3; L.n_st = (size_t)sh.S * NSEG * (L.ncell + 1);
     L.n_hd = (L.n_cnt + L.n_mh + L.n_st + 2 * (size_t)NSEG * total + 7) & ~(size_t)7;   // (the entry records behind it are 32-byte aligned)
     L.n_zero = L.n_cnt + L.n_mh;
-    L.fused = sh.S == 1 && o.prep_fuse && (size_t)NSEG * (L.ncell + 1) * 4 <= 48 * 1024;
+    // (every block of grid_fill2_kernel keeps the prefix of all NSEG x (ncell + 1) counts in its LDS: up to GRID_FILL2_LDS_MAX = 128 KB of a
+    // CU's 160 -- 10 921 cells; the 8 200 of geometry 2 at N = 10^4 take 96 KB, one block per CU, 40 blocks -- above it the five kernels)
+    L.fused = sh.S == 1 && o.prep_fuse && (size_t)NSEG * (L.ncell + 1) * 4 <= GRID_FILL2_LDS_MAX;
     return L;
 }
 
@@ -507,7 +529,8 @@ static int build_neighbour_lists(dmpc_ctx *ctx, const StepPlan &pl, const StepIO
     }
     if (L.fused) {
         // the counters are zero when the last scan launch left them so (for this buffer and size); a memset otherwise (first step, another batch shape in between)
-        const unsigned long long key = (unsigned long long)(size_t)g_cnt ^ ((unsigned long long)L.n_zero << 48) ^ ((unsigned long long)total << 20);
+        // (n_zero follows the cell count: up to 3 x 32^3 + 9, seventeen bits -- multiplied through the word, not shifted out of it)
+        const unsigned long long key = (unsigned long long)(size_t)g_cnt ^ ((unsigned long long)L.n_zero * 0x9E3779B97F4A7C15ull) ^ ((unsigned long long)total << 20);
         if (!ctx->grid_clean || ctx->grid_clean_key != key) HIPCHK(ctx, hipMemsetAsync(g_cnt, 0, L.n_zero * 4, st));
         ctx->grid_clean = false; ctx->grid_clean_key = key;
         P.gzero = g_cnt; P.gzero_n = (int)L.n_zero;
@@ -515,7 +538,12 @@ static int build_neighbour_lists(dmpc_ctx *ctx, const StepPlan &pl, const StepIO
         ctx->grid_clean = false;
     launch_list_inputs(ctx, total, C, short_from, L.fused, L.nbr_major, L.gg, L.n_zero, io.lT, io.lTf, g_cnt, g_mh, g_cell, g_pos, st);
     if (L.fused) {
-        hipLaunchKernelGGL(grid_fill2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), (size_t)NSEG * (L.ncell + 1) * 4, st, total, C, L.ncell, (float)(1.0 / p.c), (const int *)g_cell, (const int *)g_pos, (const int *)g_cnt, g_st, (const float *)ctx->lrow.as<float>(), g_ent);
+        const size_t lds_fill = (size_t)NSEG * (L.ncell + 1) * 4;
+        if ((int)lds_fill > ctx->max_lds_fill2) {   // (the limit of a kernel's dynamic LDS is 64 KB until it is raised)
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)grid_fill2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fill));
+            ctx->max_lds_fill2 = (int)lds_fill;
+        }
+        hipLaunchKernelGGL(grid_fill2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), lds_fill, st, total, C, L.ncell, (float)(1.0 / p.c), (const int *)g_cell, (const int *)g_pos, (const int *)g_cnt, g_st, (const float *)ctx->lrow.as<float>(), g_ent);
     } else if (L.use_grid) {
         hipLaunchKernelGGL(grid_bin_kernel, dim3((unsigned)((total + 255) / 256), NSEG), dim3(256), 0, st, total, S, C, short_from, L.gg, (const float *)ctx->bbox_nm.as<float>(), g_cell, g_cnt, g_mh);
         hipLaunchKernelGGL(grid_scan_kernel, dim3((unsigned)(S * NSEG)), dim3(L.ncell > 512 ? 1024 : 256), 0, st, L.ncell, g_cnt, g_st);
@@ -535,6 +563,7 @@ static int build_neighbour_lists(dmpc_ctx *ctx, const StepPlan &pl, const StepIO
                            (const float *)ctx->bbox.as<float>(), (const float *)ctx->bbox_nm.as<float>(), (int)L.cap, ctx->nbr_list.as<int>(), ctx->nbr_cnt.as<int>());
     }
     P.nbr_cap = (int)L.cap; P.nbr_list = ctx->nbr_list.as<int>(); P.nbr_cnt = ctx->nbr_cnt.as<int>();
+    P.nbr_parts = L.use_grid ? 1 : NBR_PARTS;   // (the query writes a list as one run; nbr_cnt keeps NBR_PARTS slots per agent either way)
     return 0;
 }
 
