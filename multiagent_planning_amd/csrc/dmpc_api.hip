@@ -1474,6 +1474,46 @@ static pc::Grid pc_make_grid(const dmpc_params &pr, double &edge)
     return g;
 }
 
+// samples per pass: at most 256 MB at a time, between 1 and `cap`, and no more than there are (ns_max; 1 when there is none)
+static int pc_pass_size(double bytes_per_sample, int cap, int ns_max)
+{
+    const int n = (int)std::min(std::max(std::floor(256.0 * 1048576.0 / bytes_per_sample), 1.0), (double)cap);
+    return n > ns_max ? std::max(ns_max, 1) : n;
+}
+
+// the buffers of the sample cell grid: `sbn` (scene, sample) pairs of a pass with `tot` points in `ncell` cells each
+static bool pc_grid_ensure(dmpc_ctx *ctx, size_t sbn, size_t tot, int ncell)
+{
+    return ctx->pc_pts.ensure(tot * 24) || ctx->pc_cell.ensure(tot * 4) || ctx->pc_sorted.ensure(tot * 4) || ctx->pc_fill.ensure(sbn * ncell * 4) ||
+           ctx->pc_start.ensure(sbn * ((size_t)ncell + 1) * 4);
+}
+// the grid of one pass from the cells and counts the table kernel left: scan, scatter, counts back to zero for the next pass
+static int pc_grid_build(dmpc_ctx *ctx, size_t sbn, size_t tot, int N, int ncell)
+{
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(pc::grid_scan_kernel, dim3((unsigned)sbn), dim3(1024), 0, st, ncell, ctx->pc_fill.as<int>(), ctx->pc_start.as<int>());
+    hipLaunchKernelGGL(pc::grid_scatter_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, tot, N, ncell,
+                       (const int *)ctx->pc_cell.as<int>(), (const int *)ctx->pc_start.as<int>(), ctx->pc_fill.as<int>(), ctx->pc_sorted.as<int>());
+    HIPCHK(ctx, hipMemsetAsync(ctx->pc_fill.p, 0, sbn * ncell * 4, st));
+    return 0;
+}
+
+// the scripted vehicles' splines on the commanded agents' knots: path[S][M][P][3] to the device (with room for S u64 behind it), the knots
+// pc_sc_y and their second derivatives pc_sc_M
+static int pc_scripted_splines(dmpc_ctx *ctx, const std::string &what, int S, int M, int KT_alloc, int P, const double *path, const PcPrep &q)
+{
+    hipStream_t st = ctx->stream;
+    const size_t V = (size_t)S * M, knots = V * (size_t)KT_alloc * 24, nk = V * (size_t)KT_alloc * 3;
+    if (ctx->pc_sc_path.ensure(V * (size_t)P * 24 + (size_t)S * 8) || ctx->pc_sc_y.ensure(knots) || ctx->pc_sc_M.ensure(knots) || ctx->pc_sc_w.ensure(knots))
+        FAIL(ctx, "device allocation failed (" + what + ", scripted vehicles)");
+    HIPCHK(ctx, hipMemcpyAsync(ctx->pc_sc_path.p, path, V * (size_t)P * 24, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(pc::scripted_knots_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, P, (const int *)q.d_kt,
+                       (const double *)ctx->pc_sc_path.as<double>(), ctx->pc_sc_y.as<double>());
+    hipLaunchKernelGGL(pc::spline_kernel, dim3((unsigned)((V * 3 + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, (const int *)q.d_kt,
+                       (const double *)q.d_hs, (const double *)ctx->pc_sc_y.as<double>(), ctx->pc_sc_M.as<double>(), ctx->pc_sc_w.as<double>());
+    return 0;
+}
+
 // post-checks of S finished transitions (failure_rate.m:136-195): rescale, 100 Hz not-a-knot spline, pairwise
 // ellipsoidal collision check, path length, trajectory time.  pk == NULL: use the histories dmpc_transition left
 // resident on the device (no PCIe round trip).
@@ -1513,30 +1553,22 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
     pc::Grid g{};
     double edge = 2.0 * ctx->prm.rmin;
     int SB = 1, ncell = 1;
-    if (use_grid) {
+    if (use_grid) {   // (ns_max > 0)
         g = pc_make_grid(ctx->prm, edge);
         ncell = g.nx * g.ny * g.nz;
-        const double per_sample = (double)S * ((double)N * 36.0 + (double)ncell * 8.0 + 4.0);
-        SB = (int)std::floor(256.0 * 1048576.0 / per_sample);
-        SB = SB < 1 ? 1 : (SB > 256 ? 256 : SB);
-        if (SB > ns_max) SB = ns_max;
+        SB = pc_pass_size((double)S * ((double)N * 36.0 + (double)ncell * 8.0 + 4.0), 256, ns_max);
         const size_t sbn = (size_t)S * SB;
-        if (ctx->pc_pts.ensure(sbn * N * 24) || ctx->pc_cell.ensure(sbn * N * 4) || ctx->pc_sorted.ensure(sbn * N * 4) ||
-            ctx->pc_fill.ensure(sbn * ncell * 4) || ctx->pc_start.ensure(sbn * ((size_t)ncell + 1) * 4) || ctx->pc_on.ensure((size_t)S * 4))
-            FAIL(ctx, "device allocation failed (post-check cell grid)");
+        if (pc_grid_ensure(ctx, sbn, sbn * N, ncell) || ctx->pc_on.ensure((size_t)S * 4)) FAIL(ctx, "device allocation failed (post-check cell grid)");
         HIPCHK(ctx, hipMemsetAsync(ctx->pc_fill.p, 0, sbn * ncell * 4, st));
     }
     auto grid_pass = [&](const int *scene_on) -> int {
         const size_t sbn = (size_t)S * SB, tot = sbn * N;
         for (int smp0 = 0; smp0 < ns_max; smp0 += SB) {
-            hipLaunchKernelGGL(pc::grid_eval_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, S, N, KT_alloc, (const int *)d_kt,
-                               (const double *)d_hs, (const int *)d_ns, Ts, smp0, SB, (const double *)dp, (const double *)ctx->pc_M.as<double>(), g,
-                               ctx->pc_pts.as<double>(), ctx->pc_cell.as<int>(), ctx->pc_fill.as<int>(), scene_on ? (double *)nullptr : d_interp, ns_alloc);
+            hipLaunchKernelGGL(pc::sample_table_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, S, N, N, KT_alloc, (const int *)d_kt,
+                               (const double *)d_hs, (const int *)d_ns, Ts, smp0, SB, (const double *)dp, (const double *)ctx->pc_M.as<double>(), nullptr, nullptr,
+                               nullptr, 1, g, ctx->pc_pts.as<double>(), ctx->pc_cell.as<int>(), ctx->pc_fill.as<int>(), scene_on ? nullptr : d_interp, nullptr, ns_alloc);
             if (!scene_on) {
-                hipLaunchKernelGGL(pc::grid_scan_kernel, dim3((unsigned)sbn), dim3(1024), 0, st, ncell, ctx->pc_fill.as<int>(), ctx->pc_start.as<int>());
-                hipLaunchKernelGGL(pc::grid_scatter_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, tot, N, ncell,
-                                   (const int *)ctx->pc_cell.as<int>(), (const int *)ctx->pc_start.as<int>(), ctx->pc_fill.as<int>(), ctx->pc_sorted.as<int>());
-                HIPCHK(ctx, hipMemsetAsync(ctx->pc_fill.p, 0, sbn * ncell * 4, st));
+                if (pc_grid_build(ctx, sbn, tot, N, ncell)) return -1;
                 hipLaunchKernelGGL(pc::grid_pairs_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)SB, (unsigned)S), dim3(256), 0, st, N, SB, g,
                                    1.0 / ctx->prm.c, (const double *)ctx->pc_pts.as<double>(), (const int *)ctx->pc_cell.as<int>(),
                                    (const int *)ctx->pc_start.as<int>(), (const int *)ctx->pc_sorted.as<int>(), d_min);
@@ -1559,33 +1591,23 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
     double *d_sc_interp = nullptr;
     std::vector<double> mdsc(S, 0.0);
     if (with_scripted) {
-        const size_t V = (size_t)S * M, knots = V * (size_t)KT_alloc * 24;
+        const size_t V = (size_t)S * M;
         if (p_scripted && ns_alloc < 1) FAIL(ctx, "dmpc_postcheck_scripted: ns_alloc must be positive with p_scripted");
-        // samples per pass: at most 256 MB of scripted positions at a time
-        int SBs = (int)std::floor(256.0 * 1048576.0 / ((double)V * 24.0));
-        SBs = SBs < 1 ? 1 : (SBs > 4096 ? 4096 : SBs);
-        if (SBs > ns_max) SBs = ns_max > 0 ? ns_max : 1;
-        if (ctx->pc_sc_path.ensure(V * (size_t)P * 24 + (size_t)S * 8) || ctx->pc_sc_y.ensure(knots) || ctx->pc_sc_M.ensure(knots) || ctx->pc_sc_w.ensure(knots) ||
-            ctx->pc_sc_pts.ensure(V * (size_t)SBs * 24) || (p_scripted && ctx->pc_sc_interp.ensure(V * (size_t)ns_alloc * 24)))
+        const int SBs = pc_pass_size((double)V * 24.0, 4096, ns_max);   // (scripted positions)
+        if (ctx->pc_sc_pts.ensure(V * (size_t)SBs * 24) || (p_scripted && ctx->pc_sc_interp.ensure(V * (size_t)ns_alloc * 24)))
             FAIL(ctx, "device allocation failed (post-check, scripted vehicles)");
+        if (pc_scripted_splines(ctx, "post-check", S, M, KT_alloc, P, path, q)) return -1;
         unsigned long long *d_min_sc = (unsigned long long *)(ctx->pc_sc_path.as<char>() + V * (size_t)P * 24);
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_sc_path.p, path, V * (size_t)P * 24, hipMemcpyHostToDevice, st));
         HIPCHK(ctx, hipMemsetAsync(d_min_sc, 0x7f, (size_t)S * 8, st));
         if (p_scripted) {
             d_sc_interp = ctx->pc_sc_interp.as<double>();
             HIPCHK(ctx, hipMemsetAsync(d_sc_interp, 0, V * (size_t)ns_alloc * 24, st));
         }
-        double *yk = ctx->pc_sc_y.as<double>(), *Mk = ctx->pc_sc_M.as<double>();
-        const size_t nk = V * (size_t)KT_alloc * 3;
-        hipLaunchKernelGGL(pc::scripted_knots_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, P, (const int *)d_kt,
-                           (const double *)ctx->pc_sc_path.as<double>(), yk);
-        hipLaunchKernelGGL(pc::spline_kernel, dim3((unsigned)((V * 3 + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, (const int *)d_kt, (const double *)d_hs,
-                           (const double *)yk, Mk, ctx->pc_sc_w.as<double>());
         for (int smp0 = 0; smp0 < ns_max; smp0 += SBs) {
             const int nb = ns_max - smp0 < SBs ? ns_max - smp0 : SBs;
-            hipLaunchKernelGGL(pc::scripted_eval_kernel, dim3((unsigned)((V * (size_t)SBs + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, (const int *)d_kt,
-                               (const double *)d_hs, (const int *)d_ns, Ts, smp0, SBs, (const double *)yk, (const double *)Mk, ctx->pc_sc_pts.as<double>(),
-                               d_sc_interp, ns_alloc);
+            hipLaunchKernelGGL(pc::sample_table_kernel, dim3((unsigned)((V * (size_t)SBs + 255) / 256)), dim3(256), 0, st, S, M, 0, KT_alloc, (const int *)d_kt,
+                               (const double *)d_hs, (const int *)d_ns, Ts, smp0, SBs, nullptr, nullptr, nullptr, (const double *)ctx->pc_sc_y.as<double>(),
+                               (const double *)ctx->pc_sc_M.as<double>(), 0, pc::Grid{}, ctx->pc_sc_pts.as<double>(), nullptr, nullptr, nullptr, d_sc_interp, ns_alloc);
             hipLaunchKernelGGL(pc::scripted_pairs_kernel, dim3((unsigned)nb, (unsigned)S), dim3(256), 0, st, N, M, KT_alloc, (const int *)d_kt,
                                (const double *)d_hs, (const int *)d_ns, Ts, smp0, SBs, 1.0 / ctx->prm.c, (const double *)dp,
                                (const double *)ctx->pc_M.as<double>(), (const double *)ctx->pc_sc_pts.as<double>(), d_min_sc);
@@ -1665,33 +1687,26 @@ static int postcheck_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
     return 0;
 }
 
-// N: the agents the histories cover (the commanded ones); M, po_static, min_dist_static, violation_static: the uncommanded vehicles (dmpc_postcheck_cmd) or 0 / null
-static int postcheck_any(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
-                         const double *pk, const double *vk, const double *ak, const double *pf, double vmax, double amax, double Ts,
-                         double *r_factor, double *h_scaled, int32_t *n_samples, double *min_dist,
-                         int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
-                         int M, const double *po_static, double *min_dist_static, int32_t *violation_static,
-                         const double *path = nullptr, int P = 0, double *p_scripted = nullptr)
+// "the histories of this call are the resident ones of a split batch": dmpc_transition ran the scenes in parts on the child contexts and each
+// part's histories stayed where it ran
+static bool pc_split_resident(const dmpc_ctx *ctx, int S, const double *pk)
 {
     const int parts = (int)ctx->split_at.size() - 1;
-    if (pk || parts < 2 || ctx->split_at.back() != S || ctx->hist_S != S || (int)ctx->children.size() < parts - 1 || !K_T_used || !pf)
-        return postcheck_one(ctx, S, N, KT_alloc, K_T_used, scene_mask, pk, vk, ak, pf, vmax, amax, Ts, r_factor, h_scaled, n_samples,
-                             min_dist, violation, totdist, traj_time, p_interp, ns_alloc, M, po_static, min_dist_static, violation_static, path, P, p_scripted);
-    // histories left resident by a split dmpc_transition: each part is checked where it lives, concurrently
-    auto off = [&](auto *ptr, size_t o) { return ptr ? ptr + o : ptr; };
+    return !pk && parts >= 2 && ctx->split_at.back() == S && ctx->hist_S == S && (int)ctx->children.size() >= parts - 1;
+}
+// f(c, s0, sn) for every part of such a batch, concurrently: the scenes s0 .. s0+sn-1 on the context c that holds them (whose hist_S reads sn
+// for the call); part 0 on the calling thread.  The first failed child's message becomes the caller's error.
+template <class F>
+static int pc_run_split(dmpc_ctx *ctx, F f)
+{
+    const int parts = (int)ctx->split_at.size() - 1;
     std::vector<int> rc((size_t)parts, 0);
     auto run = [&](int i) {
         dmpc_ctx *c = i ? ctx->children[(size_t)i - 1] : ctx;
         const int s0 = ctx->split_at[(size_t)i], sn = ctx->split_at[(size_t)i + 1] - s0;
-        const size_t a0 = (size_t)s0 * N;
         const int keep = c->hist_S;
         c->hist_S = sn;
-        rc[(size_t)i] = postcheck_one(c, sn, N, KT_alloc, K_T_used + s0, off(scene_mask, (size_t)s0), nullptr, nullptr, nullptr, pf + a0 * 3, vmax, amax, Ts,
-                                      off(r_factor, (size_t)s0), off(h_scaled, (size_t)s0), off(n_samples, (size_t)s0), off(min_dist, (size_t)s0),
-                                      off(violation, (size_t)s0), off(totdist, (size_t)s0), off(traj_time, (size_t)s0),
-                                      off(p_interp, a0 * (size_t)ns_alloc * 3), ns_alloc, M, off(po_static, (size_t)s0 * M * 3),
-                                      off(min_dist_static, (size_t)s0), off(violation_static, (size_t)s0), off(path, (size_t)s0 * M * P * 3), P,
-                                      off(p_scripted, (size_t)s0 * M * (size_t)ns_alloc * 3));
+        rc[(size_t)i] = f(c, s0, sn);
         c->hist_S = keep;
     };
     std::vector<std::thread> th;
@@ -1701,6 +1716,30 @@ static int postcheck_any(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
     for (int i = 1; i < parts; ++i)
         if (rc[(size_t)i]) FAIL(ctx, ctx->children[(size_t)i - 1]->err);
     return rc[0];
+}
+
+// N: the agents the histories cover (the commanded ones); M, po_static, min_dist_static, violation_static: the uncommanded vehicles (dmpc_postcheck_cmd) or 0 / null
+static int postcheck_any(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
+                         const double *pk, const double *vk, const double *ak, const double *pf, double vmax, double amax, double Ts,
+                         double *r_factor, double *h_scaled, int32_t *n_samples, double *min_dist,
+                         int32_t *violation, double *totdist, double *traj_time, double *p_interp, int ns_alloc,
+                         int M, const double *po_static, double *min_dist_static, int32_t *violation_static,
+                         const double *path = nullptr, int P = 0, double *p_scripted = nullptr)
+{
+    if (!pc_split_resident(ctx, S, pk) || !K_T_used || !pf)
+        return postcheck_one(ctx, S, N, KT_alloc, K_T_used, scene_mask, pk, vk, ak, pf, vmax, amax, Ts, r_factor, h_scaled, n_samples,
+                             min_dist, violation, totdist, traj_time, p_interp, ns_alloc, M, po_static, min_dist_static, violation_static, path, P, p_scripted);
+    // each part is checked where it lives
+    auto off = [&](auto *ptr, size_t o) { return ptr ? ptr + o : ptr; };
+    return pc_run_split(ctx, [&](dmpc_ctx *c, int s0, int sn) {
+        const size_t a0 = (size_t)s0 * N;
+        return postcheck_one(c, sn, N, KT_alloc, K_T_used + s0, off(scene_mask, (size_t)s0), nullptr, nullptr, nullptr, pf + a0 * 3, vmax, amax, Ts,
+                             off(r_factor, (size_t)s0), off(h_scaled, (size_t)s0), off(n_samples, (size_t)s0), off(min_dist, (size_t)s0),
+                             off(violation, (size_t)s0), off(totdist, (size_t)s0), off(traj_time, (size_t)s0),
+                             off(p_interp, a0 * (size_t)ns_alloc * 3), ns_alloc, M, off(po_static, (size_t)s0 * M * 3),
+                             off(min_dist_static, (size_t)s0), off(violation_static, (size_t)s0), off(path, (size_t)s0 * M * P * 3), P,
+                             off(p_scripted, (size_t)s0 * M * (size_t)ns_alloc * 3));
+    });
 }
 
 extern "C" int dmpc_postcheck(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_t *K_T_used, const int32_t *scene_mask,
@@ -1758,15 +1797,7 @@ static int clearance_one(dmpc_ctx *ctx, int S, int N, int Nc, int KT_alloc, cons
     const int M = N - Nc, ns_max = q.ns_max;
     const double *d_static = nullptr, *d_yk = nullptr, *d_Mk = nullptr;
     if (M > 0 && path) {   // scripted vehicles: their splines on the commanded agents' knots (as dmpc_postcheck_scripted makes them)
-        const size_t V = (size_t)S * M, knots = V * (size_t)KT_alloc * 24;
-        if (ctx->pc_sc_path.ensure(V * (size_t)P * 24 + (size_t)S * 8) || ctx->pc_sc_y.ensure(knots) || ctx->pc_sc_M.ensure(knots) || ctx->pc_sc_w.ensure(knots))
-            FAIL(ctx, "device allocation failed (clearance, scripted vehicles)");
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pc_sc_path.p, path, V * (size_t)P * 24, hipMemcpyHostToDevice, st));
-        const size_t nk = V * (size_t)KT_alloc * 3;
-        hipLaunchKernelGGL(pc::scripted_knots_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, P, (const int *)q.d_kt,
-                           (const double *)ctx->pc_sc_path.as<double>(), ctx->pc_sc_y.as<double>());
-        hipLaunchKernelGGL(pc::spline_kernel, dim3((unsigned)((V * 3 + 255) / 256)), dim3(256), 0, st, S, M, KT_alloc, (const int *)q.d_kt,
-                           (const double *)q.d_hs, (const double *)ctx->pc_sc_y.as<double>(), ctx->pc_sc_M.as<double>(), ctx->pc_sc_w.as<double>());
+        if (pc_scripted_splines(ctx, "clearance", S, M, KT_alloc, P, path, q)) return -1;
         d_yk = ctx->pc_sc_y.as<double>(); d_Mk = ctx->pc_sc_M.as<double>();
     } else if (M > 0) {
         if (ctx->pc_static.ensure((size_t)S * M * 24 + (size_t)S * 8)) FAIL(ctx, "device allocation failed (clearance, static vehicles)");
@@ -1785,15 +1816,12 @@ static int clearance_one(dmpc_ctx *ctx, int S, int N, int Nc, int KT_alloc, cons
     // samples per chunk (= per workgroup) and per batch: at most 256 MB of positions, grid and partials at a time
     int CH = ctx->opt.clear_chunk > 0 ? ctx->opt.clear_chunk : 8;
     const double per_sample = (double)S * ((double)N * 24.0 + (use_grid ? (double)N * 8.0 + (double)ncell * 8.0 + 4.0 : 0.0) + (double)Nc * 32.0 / CH);
-    int SB = (int)std::floor(256.0 * 1048576.0 / per_sample);
-    SB = SB < 1 ? 1 : (SB > 256 ? 256 : SB);
-    if (SB > ns_max) SB = ns_max > 0 ? ns_max : 1;
+    const int SB = pc_pass_size(per_sample, 256, ns_max);
     if (CH > SB) CH = SB;
     const int nchunk = (SB + CH - 1) / CH;
     const size_t sbn = (size_t)S * SB, tot = sbn * N, slots = (size_t)S * Nc * 2;
     if (ctx->pc_pts.ensure(tot * 24) || ctx->pc_cl_part.ensure((size_t)nchunk * slots * 16) || ctx->pc_cl_run.ensure(slots * 16) || ctx->pc_cl_out.ensure(slots * 16) ||
-        (use_grid && (ctx->pc_cell.ensure(tot * 4) || ctx->pc_sorted.ensure(tot * 4) || ctx->pc_fill.ensure(sbn * ncell * 4) ||
-                      ctx->pc_start.ensure(sbn * ((size_t)ncell + 1) * 4))))
+        (use_grid && pc_grid_ensure(ctx, sbn, tot, ncell)))
         FAIL(ctx, "device allocation failed (clearance)");
     double *part_d2 = ctx->pc_cl_part.as<double>(), *run_d2 = ctx->pc_cl_run.as<double>(), *o_dist = ctx->pc_cl_out.as<double>();
     int *part_smp = (int *)(part_d2 + (size_t)nchunk * slots), *part_j = part_smp + (size_t)nchunk * slots;
@@ -1808,14 +1836,11 @@ static int clearance_one(dmpc_ctx *ctx, int S, int N, int Nc, int KT_alloc, cons
     if (use_grid) HIPCHK(ctx, hipMemsetAsync(ctx->pc_fill.p, 0, sbn * ncell * 4, st));
     if (ns_max < 1) finish(0, 1, 1);   // (every scene masked)
     for (int smp0 = 0; smp0 < ns_max; smp0 += SB) {
-        hipLaunchKernelGGL(pc::clear_eval_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, S, N, Nc, KT_alloc, (const int *)q.d_kt,
+        hipLaunchKernelGGL(pc::sample_table_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, S, N, Nc, KT_alloc, (const int *)q.d_kt,
                            (const double *)q.d_hs, (const int *)q.d_ns, Ts, smp0, SB, (const double *)q.dp, (const double *)ctx->pc_M.as<double>(), d_static,
-                           d_yk, d_Mk, use_grid ? 1 : 0, g, ctx->pc_pts.as<double>(), ctx->pc_cell.as<int>(), ctx->pc_fill.as<int>());
+                           d_yk, d_Mk, use_grid ? 1 : 0, g, ctx->pc_pts.as<double>(), ctx->pc_cell.as<int>(), ctx->pc_fill.as<int>(), nullptr, nullptr, 0);
         if (use_grid) {
-            hipLaunchKernelGGL(pc::grid_scan_kernel, dim3((unsigned)sbn), dim3(1024), 0, st, ncell, ctx->pc_fill.as<int>(), ctx->pc_start.as<int>());
-            hipLaunchKernelGGL(pc::grid_scatter_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, tot, N, ncell,
-                               (const int *)ctx->pc_cell.as<int>(), (const int *)ctx->pc_start.as<int>(), ctx->pc_fill.as<int>(), ctx->pc_sorted.as<int>());
-            HIPCHK(ctx, hipMemsetAsync(ctx->pc_fill.p, 0, sbn * ncell * 4, st));
+            if (pc_grid_build(ctx, sbn, tot, N, ncell)) return -1;
             hipLaunchKernelGGL(pc::clear_grid_kernel, search, dim3(256), 0, st, S, N, Nc, SB, CH, smp0, (const int *)q.d_ns, g, cinv,
                                (const double *)ctx->pc_pts.as<double>(), (const int *)ctx->pc_cell.as<int>(), (const int *)ctx->pc_start.as<int>(),
                                (const int *)ctx->pc_sorted.as<int>(), part_d2, part_smp, part_j);
@@ -1846,31 +1871,18 @@ extern "C" int dmpc_postcheck_clearance(dmpc_ctx *ctx, int S, int N, int N_cmd, 
     if (!(reach > 0)) FAIL(ctx, "dmpc_postcheck_clearance: reach must be > 0 (+inf: every slot exact)");
     if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, "dmpc_postcheck_clearance: pk, vk, ak must be all given or all NULL");
     if (path && P < 1) FAIL(ctx, "dmpc_postcheck_clearance: P must be >= 1 (every path has at least its start)");
-    const int M = N - N_cmd, parts = (int)ctx->split_at.size() - 1;
-    if (pk || parts < 2 || ctx->split_at.back() != S || ctx->hist_S != S || (int)ctx->children.size() < parts - 1 || !K_T_used)
+    const int M = N - N_cmd;
+    if (!pc_split_resident(ctx, S, pk) || !K_T_used)
         return clearance_one(ctx, S, N, N_cmd, KT_alloc, K_T_used, scene_mask, pk, vk, ak, po_static, path, P, vmax, amax, Ts, reach, clear_dist,
                              clear_partner, clear_sample);
-    // resident histories of a split dmpc_transition: each part is searched where it lives, concurrently (as postcheck_any does)
+    // each part is searched where it lives
     auto off = [&](auto *ptr, size_t o) { return ptr ? ptr + o : ptr; };
-    std::vector<int> rc((size_t)parts, 0);
-    auto run = [&](int i) {
-        dmpc_ctx *c = i ? ctx->children[(size_t)i - 1] : ctx;
-        const int s0 = ctx->split_at[(size_t)i], sn = ctx->split_at[(size_t)i + 1] - s0;
+    return pc_run_split(ctx, [&](dmpc_ctx *c, int s0, int sn) {
         const size_t a0 = (size_t)s0 * N_cmd * 2;
-        const int keep = c->hist_S;
-        c->hist_S = sn;
-        rc[(size_t)i] = clearance_one(c, sn, N, N_cmd, KT_alloc, K_T_used + s0, off(scene_mask, (size_t)s0), nullptr, nullptr, nullptr,
-                                      off(po_static, (size_t)s0 * M * 3), off(path, (size_t)s0 * M * P * 3), P, vmax, amax, Ts, reach, off(clear_dist, a0),
-                                      off(clear_partner, a0), off(clear_sample, a0));
-        c->hist_S = keep;
-    };
-    std::vector<std::thread> th;
-    for (int i = 1; i < parts; ++i) th.emplace_back(run, i);
-    run(0);
-    for (auto &t : th) t.join();
-    for (int i = 1; i < parts; ++i)
-        if (rc[(size_t)i]) FAIL(ctx, ctx->children[(size_t)i - 1]->err);
-    return rc[0];
+        return clearance_one(c, sn, N, N_cmd, KT_alloc, K_T_used + s0, off(scene_mask, (size_t)s0), nullptr, nullptr, nullptr,
+                             off(po_static, (size_t)s0 * M * 3), off(path, (size_t)s0 * M * P * 3), P, vmax, amax, Ts, reach, off(clear_dist, a0),
+                             off(clear_partner, a0), off(clear_sample, a0));
+    });
 }
 
 // The setpoints and the limits report of dmpc_postcheck_setpoints for the scenes of ONE context: the preamble of every post-check, the splines
@@ -1897,9 +1909,8 @@ static int setpoints_one(dmpc_ctx *ctx, int S, int N, int KT_alloc, const int32_
     const int n_arr = (p_sp ? 1 : 0) + (v_sp ? 1 : 0) + (a_sp ? 1 : 0);
     int SB = 0;
     if (n_arr) {
-        SB = (int)std::min(std::floor(256.0 * 1048576.0 / ((double)A * 24.0 * n_arr)), (double)ns_alloc);
+        SB = pc_pass_size((double)A * 24.0 * n_arr, ns_alloc, ns_alloc);   // (no cap of its own: the window)
         if (ctx->opt.setpoint_batch > 0) SB = std::min(ctx->opt.setpoint_batch, ns_alloc);
-        SB = SB < 1 ? 1 : SB;
     }
     // the runs: [lo, hi) and whether the run is staged
     struct Run { int lo, hi; bool staged; };
@@ -1977,31 +1988,17 @@ extern "C" int dmpc_postcheck_setpoints(dmpc_ctx *ctx, int S, int N, int KT_allo
     if (ns_alloc > 0 && !p_sp && !v_sp && !a_sp) FAIL(ctx, "dmpc_postcheck_setpoints: ns_alloc > 0 needs p_sp, v_sp or a_sp (the report alone: ns_alloc = 0)");
     if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, "dmpc_postcheck_setpoints: pk, vk, ak must be all given or all NULL");
     if ((long long)smp0 + ns_alloc > 0x7fff0000LL) FAIL(ctx, "dmpc_postcheck_setpoints: smp0 + ns_alloc overflows the sample index");
-    const int parts = (int)ctx->split_at.size() - 1;
-    if (pk || parts < 2 || ctx->split_at.back() != S || ctx->hist_S != S || (int)ctx->children.size() < parts - 1 || !K_T_used)
+    if (!pc_split_resident(ctx, S, pk) || !K_T_used)
         return setpoints_one(ctx, S, N, KT_alloc, K_T_used, scene_mask, pk, vk, ak, vmax, amax, Ts, smp0, ns_alloc, p_sp, v_sp, a_sp, v_peak,
                              v_peak_sample, a_peak, a_peak_sample, r_factor, h_scaled, n_samples);
-    // resident histories of a split dmpc_transition: each part is evaluated where it lives, concurrently (as postcheck_any does)
+    // each part is evaluated where it lives
     auto off = [&](auto *ptr, size_t o) { return ptr ? ptr + o : ptr; };
-    std::vector<int> rc((size_t)parts, 0);
-    auto run = [&](int i) {
-        dmpc_ctx *c = i ? ctx->children[(size_t)i - 1] : ctx;
-        const int s0 = ctx->split_at[(size_t)i], sn = ctx->split_at[(size_t)i + 1] - s0;
+    return pc_run_split(ctx, [&](dmpc_ctx *c, int s0, int sn) {
         const size_t a0 = (size_t)s0 * N, w0 = a0 * (size_t)ns_alloc * 3;
-        const int keep = c->hist_S;
-        c->hist_S = sn;
-        rc[(size_t)i] = setpoints_one(c, sn, N, KT_alloc, K_T_used + s0, off(scene_mask, (size_t)s0), nullptr, nullptr, nullptr, vmax, amax, Ts, smp0,
-                                      ns_alloc, off(p_sp, w0), off(v_sp, w0), off(a_sp, w0), off(v_peak, a0), off(v_peak_sample, a0), off(a_peak, a0),
-                                      off(a_peak_sample, a0), off(r_factor, (size_t)s0), off(h_scaled, (size_t)s0), off(n_samples, (size_t)s0));
-        c->hist_S = keep;
-    };
-    std::vector<std::thread> th;
-    for (int i = 1; i < parts; ++i) th.emplace_back(run, i);
-    run(0);
-    for (auto &t : th) t.join();
-    for (int i = 1; i < parts; ++i)
-        if (rc[(size_t)i]) FAIL(ctx, ctx->children[(size_t)i - 1]->err);
-    return rc[0];
+        return setpoints_one(c, sn, N, KT_alloc, K_T_used + s0, off(scene_mask, (size_t)s0), nullptr, nullptr, nullptr, vmax, amax, Ts, smp0,
+                             ns_alloc, off(p_sp, w0), off(v_sp, w0), off(a_sp, w0), off(v_peak, a0), off(v_peak_sample, a0), off(a_peak, a0),
+                             off(a_peak_sample, a0), off(r_factor, (size_t)s0), off(h_scaled, (size_t)s0), off(n_samples, (size_t)s0));
+    });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -25,6 +25,13 @@ __device__ __forceinline__ double block_min(double v, double *sh)
     __syncthreads();
     return r;
 }
+// the tail of every per-scene minimum of squared distances: the minimum is order independent, so an integer atomicMin on the
+// (non-negative) double's bit pattern is exact
+__device__ __forceinline__ void scene_min(double m, double *sh, unsigned long long *__restrict__ mind2)
+{
+    m = block_min(m, sh);
+    if (threadIdx.x == 0 && m < INFINITY) atomicMin(mind2, (unsigned long long)__double_as_longlong(m));
+}
 
 // r_factor = min over agents and knots of min(amax/|a_k|, vmax/|v_k|)   (failure_rate.m:138-145)
 __global__ void rfactor_kernel(int N, int KTa, const int *__restrict__ kt_used, const double *__restrict__ vk,
@@ -84,55 +91,60 @@ __global__ void spline_kernel(int S, int N, int KTa, const int *__restrict__ kt_
     const int s = (int)(sa / N);
     const int n = kt_used[s];
     const size_t o = sa * (size_t)KTa * 3 + ax;
-#define Y(k) y[o + (size_t)(k) * 3]
-#define MM(k) M[o + (size_t)(k) * 3]
-#define W(k) w[o + (size_t)(k) * 3]
+    const double *Y = y + o;   // knot k of the series: [3 * k]
+    double *MM = M + o, *W = w + o;
     if (n < 4) {   // spline() degenerates to the parabola / line through the points: constant second derivative
         const double h = hs[s];
-        const double m = (n == 3) ? (Y(2) - 2 * Y(1) + Y(0)) / (h * h) : 0.0;
-        for (int k = 0; k < n; ++k) MM(k) = m;
+        const double m = (n == 3) ? (Y[6] - 2 * Y[3] + Y[0]) / (h * h) : 0.0;
+        for (int k = 0; k < n; ++k) MM[3 * k] = m;
         return;
     }
     const double s6 = 6.0 / (hs[s] * hs[s]);
-    const double m1 = (Y(2) - 2 * Y(1) + Y(0)) * s6 / 6.0;
-    const double me = (Y(n - 1) - 2 * Y(n - 2) + Y(n - 3)) * s6 / 6.0;
-    MM(1) = m1;
-    MM(n - 2) = me;
+    const double m1 = (Y[6] - 2 * Y[3] + Y[0]) * s6 / 6.0;
+    const double me = (Y[3 * (n - 1)] - 2 * Y[3 * (n - 2)] + Y[3 * (n - 3)]) * s6 / 6.0;
+    MM[3] = m1;
+    MM[3 * (n - 2)] = me;
     // forward sweep over 2..n-3
     double cp = 0.0, dp = 0.0;
     for (int k = 2; k <= n - 3; ++k) {
-        double d = (Y(k + 1) - 2 * Y(k) + Y(k - 1)) * s6;
+        double d = (Y[3 * (k + 1)] - 2 * Y[3 * k] + Y[3 * (k - 1)]) * s6;
         if (k == 2) d -= m1;
         if (k == n - 3) d -= me;
         const double den = 4.0 - ((k == 2) ? 0.0 : cp);
         cp = 1.0 / den;
         dp = (d - ((k == 2) ? 0.0 : dp)) / den;
-        W(k) = cp;
-        MM(k) = dp;
+        W[3 * k] = cp;
+        MM[3 * k] = dp;
     }
-    for (int k = n - 4; k >= 2; --k) MM(k) = MM(k) - W(k) * MM(k + 1);
-    MM(0) = 2 * MM(1) - MM(2);
-    MM(n - 1) = 2 * MM(n - 2) - MM(n - 3);
-#undef W
+    for (int k = n - 4; k >= 2; --k) MM[3 * k] = MM[3 * k] - W[3 * k] * MM[3 * (k + 1)];
+    MM[0] = 2 * MM[3] - MM[6];
+    MM[3 * (n - 1)] = 2 * MM[3 * (n - 2)] - MM[3 * (n - 3)];
 }
 
-__device__ __forceinline__ double spline_eval(const double *__restrict__ y, const double *__restrict__ M, size_t o, int n,
-                                              double h, double t)
+// The spline of one series at t: the interval k of t (clamped to the knots, so the end intervals extrapolate) and u = t - t_k once, then the
+// cubic of one axis.  `o`: the offset of the series' knot 0, axis included, in y and M.
+__device__ __forceinline__ int spline_interval(int n, double h, double t, double &u)
 {
     int k = (int)floor(t / h);
     k = k < 0 ? 0 : (k > n - 2 ? n - 2 : k);
-    const double u = t - k * h;
-    const double y0 = Y(k), y1 = Y(k + 1), m0 = MM(k), m1 = MM(k + 1);
+    u = t - k * h;
+    return k;
+}
+__device__ __forceinline__ double spline_axis(const double *__restrict__ y, const double *__restrict__ M, size_t o, int k, double h, double u)
+{
+    const size_t q = o + (size_t)k * 3;
+    const double y0 = y[q], y1 = y[q + 3], m0 = M[q], m1 = M[q + 3];
     const double b = (y1 - y0) / h - h * (2 * m0 + m1) / 6.0;
     return y0 + u * (b + u * (m0 / 2 + u * (m1 - m0) / (6.0 * h)));
 }
-// the same evaluation for the kernels below the #undefs
-__device__ __forceinline__ double spline_eval2(const double *__restrict__ y, const double *__restrict__ M, size_t o, int n, double h, double t)
+struct P3 { double x, y, z; };
+// the three axes of one (scene, vehicle) series [KTa][3] that starts at `o`
+__device__ __forceinline__ P3 spline_eval(const double *__restrict__ y, const double *__restrict__ M, size_t o, int n, double h, double t)
 {
-    return spline_eval(y, M, o, n, h, t);
+    double u;
+    const int k = spline_interval(n, h, t, u);
+    return P3{spline_axis(y, M, o, k, h, u), spline_axis(y, M, o + 1, k, h, u), spline_axis(y, M, o + 2, k, h, u)};
 }
-#undef Y
-#undef MM
 
 // squared ellipsoidal distance |E1 (p_i - p_j)|^2 of one pair (failure_rate.m:172): ONE expression with pinned contractions for
 // every kernel that evaluates it, so the brute-force and the cell-grid search return the same bits
@@ -144,8 +156,7 @@ __device__ __forceinline__ double pair_d2(double xi, double yi, double zi, doubl
 
 #define PC_SAMPLES_PER_BLOCK 8
 // pairwise ellipsoidal distance at every 100 Hz sample (failure_rate.m:165-181): block = (sample group, scene);
-// positions of all agents at one sample are staged in LDS, pairs are strided over the threads; the per-scene
-// minimum is order independent so an integer atomicMin on the (non-negative) double's bit pattern is exact.
+// positions of all agents at one sample are staged in LDS, pairs are strided over the threads (thread per component: one axis each).
 __global__ void pairdist_kernel(int N, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs,
                                 const int *__restrict__ ns, double Ts, double cinv, const double *__restrict__ y,
                                 const double *__restrict__ M, unsigned long long *__restrict__ mind2,
@@ -159,10 +170,11 @@ __global__ void pairdist_kernel(int N, int KTa, const int *__restrict__ kt_used,
     for (int q = 0; q < PC_SAMPLES_PER_BLOCK; ++q) {
         const int smp = blockIdx.x * PC_SAMPLES_PER_BLOCK + q;
         if (smp >= nsamp) break;
-        const double t = smp * Ts;
+        double u;
+        const int k = spline_interval(n, h, smp * Ts, u);
         for (int e = threadIdx.x; e < N * 3; e += blockDim.x) {
             const size_t o = ((size_t)s * N + e / 3) * (size_t)KTa * 3 + e % 3;
-            const double v = spline_eval(y, M, o, n, h, t);
+            const double v = spline_axis(y, M, o, k, h, u);
             pos[e] = v;
             if (p_interp && smp < ns_alloc) p_interp[(((size_t)s * N + e / 3) * ns_alloc + smp) * 3 + e % 3] = v;
         }
@@ -174,8 +186,7 @@ __global__ void pairdist_kernel(int N, int KTa, const int *__restrict__ kt_used,
         }
         __syncthreads();
     }
-    m = block_min(m, sh);
-    if (threadIdx.x == 0 && m < INFINITY) atomicMin(&mind2[s], (unsigned long long)__double_as_longlong(m));
+    scene_min(m, sh, &mind2[s]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -196,32 +207,48 @@ struct Grid {
 };
 #define PC_BRUTE_MAX 256
 
-// thread per (scene, sample of the batch, agent): spline position -> pts, cell -> cell_of, count -> fill
-__global__ void grid_eval_kernel(int S, int N, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs,
-                                 const int *__restrict__ ns, double Ts, int smp0, int SB, const double *__restrict__ y,
-                                 const double *__restrict__ M, Grid g, double *__restrict__ pts, int *__restrict__ cell_of,
-                                 int *__restrict__ fill, double *__restrict__ p_interp, int ns_alloc)
+// the cell of a point: floor, clamped to the grid
+__device__ __forceinline__ int grid_cell(const Grid &g, double x, double y, double z)
 {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (size_t)S * SB * N) return;
-    const int i = (int)(t % N);
-    const int b = (int)((t / N) % SB), s = (int)(t / ((size_t)N * SB));
-    const int smp = smp0 + b;
-    if (smp >= ns[s]) { cell_of[t] = -1; return; }
-    const int n = kt_used[s];
-    const double h = hs[s], tt = smp * Ts;
-    const size_t o = ((size_t)s * N + i) * (size_t)KTa * 3;
-    const double x = spline_eval2(y, M, o, n, h, tt), yv = spline_eval2(y, M, o + 1, n, h, tt), z = spline_eval2(y, M, o + 2, n, h, tt);
-    pts[3 * t] = x; pts[3 * t + 1] = yv; pts[3 * t + 2] = z;
-    if (p_interp && smp < ns_alloc) {
-        double *d = p_interp + (((size_t)s * N + i) * ns_alloc + smp) * 3;
-        d[0] = x; d[1] = yv; d[2] = z;
-    }
-    int ix = (int)floor((x - g.x0) * g.inv_e), iy = (int)floor((yv - g.y0) * g.inv_e), iz = (int)floor((z - g.z0) * g.inv_ez);
+    int ix = (int)floor((x - g.x0) * g.inv_e), iy = (int)floor((y - g.y0) * g.inv_e), iz = (int)floor((z - g.z0) * g.inv_ez);
     ix = ix < 0 ? 0 : (ix >= g.nx ? g.nx - 1 : ix);
     iy = iy < 0 ? 0 : (iy >= g.ny ? g.ny - 1 : iy);
     iz = iz < 0 ? 0 : (iz >= g.nz ? g.nz - 1 : iz);
-    const int c = ix + g.nx * (iy + g.ny * iz);
+    return ix + g.nx * (iy + g.ny * iz);
+}
+
+// The table of points of a batch of samples, pts[S][SB][N][3]: thread per (scene, sample smp0 + b of the batch, column).  Columns < Nc are the
+// commanded agents' spline (knots y / M [S][Nc][KTa][3]), the others the static positions po_static[S][N-Nc][3] or, with yk, the scripted
+// vehicles' spline on the knots yk / Mk [S][N-Nc][KTa][3].  Options: with_grid, the point's cell -> cell_of and its count -> fill; p_interp
+// [S][Nc][ns_alloc][3] and p_scripted [S][N-Nc][ns_alloc][3], the interpolated positions of the two kinds of column (null: none).  A sample at or
+// beyond the scene's end writes cell_of = -1 with the grid and nothing else.
+__global__ void sample_table_kernel(int S, int N, int Nc, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs,
+                                    const int *__restrict__ ns, double Ts, int smp0, int SB, const double *__restrict__ y,
+                                    const double *__restrict__ M, const double *__restrict__ po_static, const double *__restrict__ yk,
+                                    const double *__restrict__ Mk, int with_grid, Grid g, double *__restrict__ pts, int *__restrict__ cell_of,
+                                    int *__restrict__ fill, double *__restrict__ p_interp, double *__restrict__ p_scripted, int ns_alloc)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)S * SB * N) return;
+    const int j = (int)(t % N);
+    const int b = (int)((t / N) % SB), s = (int)(t / ((size_t)N * SB));
+    const int smp = smp0 + b;
+    if (smp >= ns[s]) { if (with_grid) cell_of[t] = -1; return; }
+    const int n = kt_used[s];
+    const double h = hs[s], tt = smp * Ts;
+    const size_t v = j < Nc ? (size_t)s * Nc + j : (size_t)s * (N - Nc) + (j - Nc);   // the column's row in its own arrays
+    P3 p;
+    if (j < Nc) p = spline_eval(y, M, v * (size_t)KTa * 3, n, h, tt);
+    else if (yk) p = spline_eval(yk, Mk, v * (size_t)KTa * 3, n, h, tt);
+    else p = P3{po_static[3 * v], po_static[3 * v + 1], po_static[3 * v + 2]};
+    pts[3 * t] = p.x; pts[3 * t + 1] = p.y; pts[3 * t + 2] = p.z;
+    double *out = j < Nc ? p_interp : p_scripted;
+    if (out && smp < ns_alloc) {
+        double *d = out + (v * ns_alloc + smp) * 3;
+        d[0] = p.x; d[1] = p.y; d[2] = p.z;
+    }
+    if (!with_grid) return;
+    const int c = grid_cell(g, p.x, p.y, p.z);
     cell_of[t] = c;
     atomicAdd(&fill[((size_t)s * SB + b) * ((size_t)g.nx * g.ny * g.nz) + c], 1);
 }
@@ -257,6 +284,39 @@ __global__ void grid_scatter_kernel(size_t total, int N, int ncell, const int *_
     const int slot = start[sb * (ncell + 1) + c] + atomicAdd(&fill[sb * ncell + c], 1);
     sorted[sb * N + slot] = (int)(t % N);
 }
+// f(j) for every point j of the 27 cells around cell c, in the order z, y, run of x cells; st / so: `start` and `sorted` of the (scene, sample)
+template <class F>
+__device__ __forceinline__ void grid_walk(const Grid &g, int c, const int *__restrict__ st, const int *__restrict__ so, F f)
+{
+    const int ix = c % g.nx, iy = (c / g.nx) % g.ny, iz = c / (g.nx * g.ny);
+    const int x_lo = ix > 0 ? ix - 1 : 0, x_hi = ix + 1 < g.nx ? ix + 1 : g.nx - 1;
+    for (int dz = -1; dz <= 1; ++dz) {
+        const int z = iz + dz;
+        if (z < 0 || z >= g.nz) continue;
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int yy = iy + dy;
+            if (yy < 0 || yy >= g.ny) continue;
+            const int base = g.nx * (yy + g.ny * z);
+            const int e0 = st[base + x_lo], e1 = st[base + x_hi + 1];   // x is the fastest cell index: three cells = one run
+            for (int e = e0; e < e1; ++e) f(so[e]);
+        }
+    }
+}
+// f(j, x, y, z) for the points lo .. hi-1 of pp[][3], in ascending order, streamed through LDS in tiles of 256.  Every thread of the block
+// takes part in the staging and reaches both barriers; `vi`: the thread owns an agent and f is called for it.
+template <class F>
+__device__ __forceinline__ void tile_stream(const double *__restrict__ pp, int lo, int hi, bool vi, double *tile, F f)
+{
+    for (int j0 = lo; j0 < hi; j0 += 256) {
+        const int cntj = hi - j0 < 256 ? hi - j0 : 256;
+        __syncthreads();
+        for (int e = threadIdx.x; e < cntj * 3; e += 256) tile[e] = pp[3 * (size_t)j0 + e];
+        __syncthreads();
+        if (vi)
+            for (int jj = 0; jj < cntj; ++jj) f(j0 + jj, tile[3 * jj], tile[3 * jj + 1], tile[3 * jj + 2]);
+    }
+}
+
 // block = (tile of 256 agents i, sample, scene): every agent j > i of the 27 cells around i's
 __global__ void grid_pairs_kernel(int N, int SB, Grid g, double cinv, const double *__restrict__ pts, const int *__restrict__ cell_of,
                                   const int *__restrict__ start, const int *__restrict__ sorted, unsigned long long *__restrict__ mind2)
@@ -267,30 +327,13 @@ __global__ void grid_pairs_kernel(int N, int SB, Grid g, double cinv, const doub
     double m = INFINITY;
     const int c = i < N ? cell_of[t] : -1;
     if (c >= 0) {
-        const int ncell = g.nx * g.ny * g.nz;
-        const int ix = c % g.nx, iy = (c / g.nx) % g.ny, iz = c / (g.nx * g.ny);
         const double xi = pts[3 * t], yi = pts[3 * t + 1], zi = pts[3 * t + 2];
-        const int *st = start + sb * (ncell + 1), *so = sorted + sb * N;
         const double *pp = pts + sb * (size_t)N * 3;
-        const int x_lo = ix > 0 ? ix - 1 : 0, x_hi = ix + 1 < g.nx ? ix + 1 : g.nx - 1;
-        for (int dz = -1; dz <= 1; ++dz) {
-            const int z = iz + dz;
-            if (z < 0 || z >= g.nz) continue;
-            for (int dy = -1; dy <= 1; ++dy) {
-                const int yy = iy + dy;
-                if (yy < 0 || yy >= g.ny) continue;
-                const int base = g.nx * (yy + g.ny * z);
-                const int e0 = st[base + x_lo], e1 = st[base + x_hi + 1];   // x is the fastest cell index: three cells = one run
-                for (int e = e0; e < e1; ++e) {
-                    const int j = so[e];
-                    if (j <= i) continue;
-                    m = fmin(m, pair_d2(xi, yi, zi, pp[3 * j], pp[3 * j + 1], pp[3 * j + 2], cinv));
-                }
-            }
-        }
+        grid_walk(g, c, start + sb * ((size_t)g.nx * g.ny * g.nz + 1), sorted + sb * N, [&](int j) {
+            if (j > i) m = fmin(m, pair_d2(xi, yi, zi, pp[3 * j], pp[3 * j + 1], pp[3 * j + 2], cinv));
+        });
     }
-    m = block_min(m, sh);
-    if (threadIdx.x == 0 && m < INFINITY) atomicMin(&mind2[s], (unsigned long long)__double_as_longlong(m));
+    scene_min(m, sh, &mind2[s]);
 }
 // brute force over the positions of a batch (fallback of the grid search: scenes without any pair closer than `edge`):
 // block = (tile of 256 agents i, sample, scene); the tiles of j >= tile(i) stream through LDS
@@ -308,19 +351,10 @@ __global__ void pairs_brute_pts_kernel(int N, int SB, double cinv, const double 
     const bool vi = i < N;
     const double xi = vi ? pp[3 * i] : 0.0, yi = vi ? pp[3 * i + 1] : 0.0, zi = vi ? pp[3 * i + 2] : 0.0;
     double m = INFINITY;
-    for (int jt = it; jt * 256 < N; ++jt) {
-        const int j0 = jt * 256, cntj = N - j0 < 256 ? N - j0 : 256;
-        __syncthreads();
-        for (int e = threadIdx.x; e < cntj * 3; e += 256) tile[e] = pp[3 * (size_t)j0 + e];
-        __syncthreads();
-        if (vi)
-            for (int jj = 0; jj < cntj; ++jj) {
-                if (j0 + jj <= i) continue;
-                m = fmin(m, pair_d2(xi, yi, zi, tile[3 * jj], tile[3 * jj + 1], tile[3 * jj + 2], cinv));
-            }
-    }
-    m = block_min(m, sh);
-    if (threadIdx.x == 0 && m < INFINITY) atomicMin(&mind2[s], (unsigned long long)__double_as_longlong(m));
+    tile_stream(pp, it * 256, N, vi, tile, [&](int j, double xj, double yj, double zj) {
+        if (j > i) m = fmin(m, pair_d2(xi, yi, zi, xj, yj, zj, cinv));
+    });
+    scene_min(m, sh, &mind2[s]);
 }
 
 // Uncommanded vehicles: every (commanded agent, sample) against every static vehicle, all pairs, exact.  block = (tile of 256 (agent, sample)
@@ -338,25 +372,15 @@ __global__ void static_pairs_kernel(int N, int M, int KTa, const int *__restrict
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if ((size_t)blockIdx.x * 256 >= (size_t)N * nsamp) return;   // (uniform per block: the grid is sized for the longest scene)
     const bool vi = e < (size_t)N * nsamp;
-    double xi = 0.0, yi = 0.0, zi = 0.0;
+    P3 p{0.0, 0.0, 0.0};
     if (vi) {
         const int i = (int)(e / nsamp), smp = (int)(e - (size_t)i * nsamp);
-        const double h = hs[s], t = smp * Ts;
-        const size_t o = ((size_t)s * N + i) * (size_t)KTa * 3;
-        xi = spline_eval2(y, Msp, o, n, h, t); yi = spline_eval2(y, Msp, o + 1, n, h, t); zi = spline_eval2(y, Msp, o + 2, n, h, t);
+        p = spline_eval(y, Msp, ((size_t)s * N + i) * (size_t)KTa * 3, n, hs[s], smp * Ts);
     }
-    const double *ps = po_static + (size_t)s * M * 3;
     double m = INFINITY;
-    for (int j0 = 0; j0 < M; j0 += 256) {
-        const int cntj = M - j0 < 256 ? M - j0 : 256;
-        __syncthreads();
-        for (int q = threadIdx.x; q < cntj * 3; q += 256) tile[q] = ps[3 * (size_t)j0 + q];
-        __syncthreads();
-        if (vi)
-            for (int jj = 0; jj < cntj; ++jj) m = fmin(m, pair_d2(xi, yi, zi, tile[3 * jj], tile[3 * jj + 1], tile[3 * jj + 2], cinv));
-    }
-    m = block_min(m, sh);
-    if (threadIdx.x == 0 && m < INFINITY) atomicMin(&mind2[s], (unsigned long long)__double_as_longlong(m));
+    tile_stream(po_static + (size_t)s * M * 3, 0, M, vi, tile,
+                [&](int, double xj, double yj, double zj) { m = fmin(m, pair_d2(p.x, p.y, p.z, xj, yj, zj, cinv)); });
+    scene_min(m, sh, &mind2[s]);
 }
 
 // Scripted vehicles (dmpc_postcheck_scripted): a vehicle that follows a path over step indices gets the spline the commanded agents get, on
@@ -372,29 +396,6 @@ __global__ void scripted_knots_kernel(int S, int M, int KTa, int P, const int *_
     const size_t sj = g / ((size_t)3 * KTa);
     const int s = (int)(sj / M);
     yk[g] = i < kt_used[s] ? path[(sj * P + (i < P - 1 ? i : P - 1)) * 3 + ax] : 0.0;
-}
-
-// thread per (scene, sample of the batch, scripted vehicle): q(t) of the batch's samples smp0 .. smp0+SB-1 -> pts[S][SB][M][3] (what the pair
-// search below reads) and, optionally, p_scripted[S][M][ns_alloc][3]
-__global__ void scripted_eval_kernel(int S, int M, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs,
-                                     const int *__restrict__ ns, double Ts, int smp0, int SB, const double *__restrict__ yk,
-                                     const double *__restrict__ Mk, double *__restrict__ pts, double *__restrict__ p_scripted, int ns_alloc)
-{
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (size_t)S * SB * M) return;
-    const int j = (int)(t % M);
-    const int b = (int)((t / M) % SB), s = (int)(t / ((size_t)M * SB));
-    const int smp = smp0 + b;
-    if (smp >= ns[s]) return;
-    const int n = kt_used[s];
-    const double h = hs[s], tt = smp * Ts;
-    const size_t o = ((size_t)s * M + j) * (size_t)KTa * 3;
-    const double x = spline_eval2(yk, Mk, o, n, h, tt), yv = spline_eval2(yk, Mk, o + 1, n, h, tt), z = spline_eval2(yk, Mk, o + 2, n, h, tt);
-    pts[3 * t] = x; pts[3 * t + 1] = yv; pts[3 * t + 2] = z;
-    if (p_scripted && smp < ns_alloc) {
-        double *d = p_scripted + (((size_t)s * M + j) * ns_alloc + smp) * 3;
-        d[0] = x; d[1] = yv; d[2] = z;
-    }
 }
 
 // every commanded agent against every scripted vehicle at one sample, all pairs, exact: block = (sample of the batch, scene).  The commanded
@@ -416,10 +417,8 @@ __global__ void scripted_pairs_kernel(int N, int M, int KTa, const int *__restri
         const int cnti = N - i0 < 256 ? N - i0 : 256;
         __syncthreads();
         if ((int)threadIdx.x < cnti) {
-            const size_t o = ((size_t)s * N + i0 + threadIdx.x) * (size_t)KTa * 3;
-            tile[3 * threadIdx.x] = spline_eval2(y, Msp, o, n, h, t);
-            tile[3 * threadIdx.x + 1] = spline_eval2(y, Msp, o + 1, n, h, t);
-            tile[3 * threadIdx.x + 2] = spline_eval2(y, Msp, o + 2, n, h, t);
+            const P3 p = spline_eval(y, Msp, ((size_t)s * N + i0 + threadIdx.x) * (size_t)KTa * 3, n, h, t);
+            tile[3 * threadIdx.x] = p.x; tile[3 * threadIdx.x + 1] = p.y; tile[3 * threadIdx.x + 2] = p.z;
         }
         __syncthreads();
         for (size_t e = threadIdx.x; e < (size_t)cnti * M; e += 256) {
@@ -427,8 +426,7 @@ __global__ void scripted_pairs_kernel(int N, int M, int KTa, const int *__restri
             m = fmin(m, pair_d2(tile[3 * ii], tile[3 * ii + 1], tile[3 * ii + 2], q[3 * j], q[3 * j + 1], q[3 * j + 2], cinv));
         }
     }
-    m = block_min(m, sh);
-    if (threadIdx.x == 0 && m < INFINITY) atomicMin(&mind2[s], (unsigned long long)__double_as_longlong(m));
+    scene_min(m, sh, &mind2[s]);
 }
 
 // per agent: path length sum |p(t_{s+1}) - p(t_s)| (failure_rate.m:183) and the 1-based index after the last
@@ -446,9 +444,8 @@ __global__ void path_kernel(int S, int N, int KTa, const int *__restrict__ kt_us
     double px = 0, py = 0, pz = 0, acc = 0;
     int last = 0;
     for (int smp = 0; smp < nsamp; ++smp) {
-        const double t = smp * Ts;
-        const double x = spline_eval(y, M, o, n, h, t), yv = spline_eval(y, M, o + 1, n, h, t),
-                     z = spline_eval(y, M, o + 2, n, h, t);
+        const P3 p = spline_eval(y, M, o, n, h, smp * Ts);
+        const double x = p.x, yv = p.y, z = p.z;
         if (smp) acc += sqrt((x - px) * (x - px) + (yv - py) * (yv - py) + (z - pz) * (z - pz));
         px = x; py = yv; pz = z;
         const double dg = sqrt((x - gx) * (x - gx) + (yv - gy) * (yv - gy) + (z - gz) * (z - gz));
@@ -486,61 +483,14 @@ __global__ void finish_kernel(int N, const double *__restrict__ dist, const int 
 // (d2, partner).  A batch of SB samples is cut into chunks of CH; a block = (tile of 256 agents, chunk, scene) writes its agents' bests of the
 // chunk as partials [chunk][S][Nc][2], and clear_finish_kernel folds them, in chunk order, into the running best of the whole transition.
 
-// thread per (scene, sample of the batch, vehicle of the table): pts[S][SB][N][3] -- columns < Nc the commanded agents' spline (the evaluation
-// of grid_eval_kernel), the others the static positions po_static[S][N-Nc][3] or the scripted vehicles' spline (the evaluation of
-// scripted_eval_kernel on the knots yk / Mk [S][N-Nc][KTa][3]); with_grid: the vehicle's cell -> cell_of, count -> fill (as grid_eval_kernel)
-__global__ void clear_eval_kernel(int S, int N, int Nc, int KTa, const int *__restrict__ kt_used, const double *__restrict__ hs,
-                                  const int *__restrict__ ns, double Ts, int smp0, int SB, const double *__restrict__ y,
-                                  const double *__restrict__ M, const double *__restrict__ po_static, const double *__restrict__ yk,
-                                  const double *__restrict__ Mk, int with_grid, Grid g, double *__restrict__ pts, int *__restrict__ cell_of,
-                                  int *__restrict__ fill)
-{
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (size_t)S * SB * N) return;
-    const int j = (int)(t % N);
-    const int b = (int)((t / N) % SB), s = (int)(t / ((size_t)N * SB));
-    const int smp = smp0 + b;
-    if (smp >= ns[s]) { if (with_grid) cell_of[t] = -1; return; }
-    const int n = kt_used[s];
-    const double h = hs[s], tt = smp * Ts;
-    double x, yv, z;
-    if (j < Nc) {
-        const size_t o = ((size_t)s * Nc + j) * (size_t)KTa * 3;
-        x = spline_eval2(y, M, o, n, h, tt); yv = spline_eval2(y, M, o + 1, n, h, tt); z = spline_eval2(y, M, o + 2, n, h, tt);
-    } else if (yk) {
-        const size_t o = ((size_t)s * (N - Nc) + (j - Nc)) * (size_t)KTa * 3;
-        x = spline_eval2(yk, Mk, o, n, h, tt); yv = spline_eval2(yk, Mk, o + 1, n, h, tt); z = spline_eval2(yk, Mk, o + 2, n, h, tt);
-    } else {
-        const double *q = po_static + ((size_t)s * (N - Nc) + (j - Nc)) * 3;
-        x = q[0]; yv = q[1]; z = q[2];
-    }
-    pts[3 * t] = x; pts[3 * t + 1] = yv; pts[3 * t + 2] = z;
-    if (!with_grid) return;
-    int ix = (int)floor((x - g.x0) * g.inv_e), iy = (int)floor((yv - g.y0) * g.inv_e), iz = (int)floor((z - g.z0) * g.inv_ez);
-    ix = ix < 0 ? 0 : (ix >= g.nx ? g.nx - 1 : ix);
-    iy = iy < 0 ? 0 : (iy >= g.ny ? g.ny - 1 : iy);
-    iz = iz < 0 ? 0 : (iz >= g.nz ? g.nz - 1 : iz);
-    const int c = ix + g.nx * (iy + g.ny * iz);
-    cell_of[t] = c;
-    atomicAdd(&fill[((size_t)s * SB + b) * ((size_t)g.nx * g.ny * g.nz) + c], 1);
-}
-
-// agent i against the vehicles lo .. hi-1 of one sample, streamed through LDS in tiles of 256, in ascending order (every thread of the block
-// takes part in the staging; `vi`: the thread owns an agent)
+// agent i against the vehicles lo .. hi-1 of one sample, in ascending order: with the strict <, ties go to the smallest partner
 __device__ __forceinline__ void clear_scan_tiles(const double *__restrict__ pp, int lo, int hi, int i, bool vi, double xi, double yi, double zi,
                                                  double cinv, int smp, double *tile, double &bd, int &bs, int &bj)
 {
-    for (int j0 = lo; j0 < hi; j0 += 256) {
-        const int cntj = hi - j0 < 256 ? hi - j0 : 256;
-        __syncthreads();
-        for (int e = threadIdx.x; e < cntj * 3; e += 256) tile[e] = pp[3 * (size_t)j0 + e];
-        __syncthreads();
-        if (vi)
-            for (int jj = 0; jj < cntj; ++jj) {
-                const double d = pair_d2(xi, yi, zi, tile[3 * jj], tile[3 * jj + 1], tile[3 * jj + 2], cinv);
-                if (d < bd && j0 + jj != i) { bd = d; bs = smp; bj = j0 + jj; }
-            }
-    }
+    tile_stream(pp, lo, hi, vi, tile, [&](int j, double xj, double yj, double zj) {
+        const double d = pair_d2(xi, yi, zi, xj, yj, zj, cinv);
+        if (d < bd && j != i) { bd = d; bs = smp; bj = j; }
+    });
 }
 // the partials of one (chunk, scene, agent): part_d2 [chunk][S][Nc][2], part_smp and part_j alike
 __device__ __forceinline__ void clear_store(int S, int Nc, int chunk, int s, int i, double *__restrict__ part_d2, int *__restrict__ part_smp,
@@ -578,8 +528,8 @@ __device__ __forceinline__ void clear_take(double d, int smp, int j, double &bd,
 {
     if (d < bd || (d == bd && bs == smp && j < bj)) { bd = d; bs = smp; bj = j; }
 }
-// cell grid: block = (tile of 256 commanded agents i, chunk of CH samples, scene); every vehicle of the 27 cells around i's (grid_pairs_kernel's
-// walk over a grid that holds all N vehicles).  Finds every pair closer than the cell edge; what lies farther is for the caller to discard.
+// cell grid: block = (tile of 256 commanded agents i, chunk of CH samples, scene); every vehicle of the 27 cells around i's (grid_walk
+// over a grid that holds all N vehicles).  Finds every pair closer than the cell edge; what lies farther is for the caller to discard.
 __global__ void clear_grid_kernel(int S, int N, int Nc, int SB, int CH, int smp0, const int *__restrict__ ns, Grid g, double cinv,
                                   const double *__restrict__ pts, const int *__restrict__ cell_of, const int *__restrict__ start,
                                   const int *__restrict__ sorted, double *__restrict__ part_d2, int *__restrict__ part_smp,
@@ -587,39 +537,25 @@ __global__ void clear_grid_kernel(int S, int N, int Nc, int SB, int CH, int smp0
 {
     const int s = blockIdx.z, chunk = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Nc) return;
-    const int nsamp = ns[s], ncell = g.nx * g.ny * g.nz;
-    double d0 = INFINITY, d1 = INFINITY;
-    int s0 = -1, s1 = -1, j0 = -1, j1 = -1;
+    const int nsamp = ns[s];
+    const size_t ncell = (size_t)g.nx * g.ny * g.nz;
+    double bd[2] = {INFINITY, INFINITY};   // slot 0: commanded partners, slot 1: the other vehicles
+    int bs[2] = {-1, -1}, bj[2] = {-1, -1};
     for (int q = 0; q < CH; ++q) {
         const int b = chunk * CH + q, smp = smp0 + b;
         if (b >= SB || smp >= nsamp) break;
         const size_t sb = (size_t)s * SB + b, t = sb * N + i;
         const int c = cell_of[t];
         if (c < 0) break;
-        const int ix = c % g.nx, iy = (c / g.nx) % g.ny, iz = c / (g.nx * g.ny);
         const double xi = pts[3 * t], yi = pts[3 * t + 1], zi = pts[3 * t + 2];
-        const int *st = start + sb * (ncell + 1), *so = sorted + sb * N;
         const double *pp = pts + sb * (size_t)N * 3;
-        const int x_lo = ix > 0 ? ix - 1 : 0, x_hi = ix + 1 < g.nx ? ix + 1 : g.nx - 1;
-        for (int dz = -1; dz <= 1; ++dz) {
-            const int z = iz + dz;
-            if (z < 0 || z >= g.nz) continue;
-            for (int dy = -1; dy <= 1; ++dy) {
-                const int yy = iy + dy;
-                if (yy < 0 || yy >= g.ny) continue;
-                const int base = g.nx * (yy + g.ny * z);
-                const int e0 = st[base + x_lo], e1 = st[base + x_hi + 1];   // x is the fastest cell index: three cells = one run
-                for (int e = e0; e < e1; ++e) {
-                    const int j = so[e];
-                    if (j == i) continue;
-                    const double d = pair_d2(xi, yi, zi, pp[3 * j], pp[3 * j + 1], pp[3 * j + 2], cinv);
-                    if (j < Nc) clear_take(d, smp, j, d0, s0, j0);
-                    else clear_take(d, smp, j, d1, s1, j1);
-                }
-            }
-        }
+        grid_walk(g, c, start + sb * (ncell + 1), sorted + sb * N, [&](int j) {
+            if (j == i) return;
+            const int k = j < Nc ? 0 : 1;
+            clear_take(pair_d2(xi, yi, zi, pp[3 * j], pp[3 * j + 1], pp[3 * j + 2], cinv), smp, j, bd[k], bs[k], bj[k]);
+        });
     }
-    clear_store(S, Nc, chunk, s, i, part_d2, part_smp, part_j, d0, s0, j0, d1, s1, j1);
+    clear_store(S, Nc, chunk, s, i, part_d2, part_smp, part_j, bd[0], bs[0], bj[0], bd[1], bs[1], bj[1]);
 }
 
 // thread per (scene, agent, slot): the batch's partials, in chunk order, into the running best run_* [S][Nc][2] (`first`: the batch opens the
@@ -651,7 +587,7 @@ __global__ void clear_finish_kernel(size_t total, int Nc, int nchunk, int first,
 // Flight setpoints (dmpc_postcheck_setpoints): position, velocity and acceleration of every commanded agent at the 100 Hz samples, and per agent
 // the largest |v| and |a| over ALL samples with the sample at which it happens.  The reference splines the three histories independently
 // (dmpc_soft_bound.m:165-169), so three splines on the same knots are evaluated: y = the rescaled pk / vk / ak as rescale_kernel leaves them,
-// M = their second derivatives (spline_kernel).  Sample j has t = j * Ts, the expression of path_kernel / grid_eval_kernel.
+// M = their second derivatives (spline_kernel).  Sample j has t = j * Ts, the expression of path_kernel / sample_table_kernel.
 // A workgroup = (tile of SP_TILE agents, chunk of SP_CHUNK samples, scene): thread t owns sample lo + chunk * SP_CHUNK + t and walks the agents
 // of the tile, so the lanes of a wave hold consecutive samples of ONE agent -- the stores into [..][SB][3] are one contiguous run per wave and
 // the ~h_scaled / Ts lanes of a spline interval read the same knots.  Peaks: (value, sample) pairs ordered by larger value, then smaller sample
@@ -714,21 +650,19 @@ setpoint_kernel(int S, int N, int KTa, const int *__restrict__ kt_used, const do
     const double h = hs[s], t = j * Ts;
     for (int a = 0; a < cnt; ++a) {
         const size_t o = (a0 + a) * (size_t)KTa * 3;
-        double px = 0.0, py = 0.0, pz = 0.0, vx = 0.0, vy = 0.0, vz = 0.0, ax = 0.0, ay = 0.0, az = 0.0;
+        P3 p{0.0, 0.0, 0.0}, v = p, ac = p;
         double bv = -1.0, ba = -1.0;
         int bvs = -1, bas = -1;
         if (live) {
-            px = spline_eval2(yp, Mp, o, n, h, t); py = spline_eval2(yp, Mp, o + 1, n, h, t); pz = spline_eval2(yp, Mp, o + 2, n, h, t);
-            vx = spline_eval2(yv, Mv, o, n, h, t); vy = spline_eval2(yv, Mv, o + 1, n, h, t); vz = spline_eval2(yv, Mv, o + 2, n, h, t);
-            ax = spline_eval2(ya, Ma, o, n, h, t); ay = spline_eval2(ya, Ma, o + 1, n, h, t); az = spline_eval2(ya, Ma, o + 2, n, h, t);
-            bv = norm3(vx, vy, vz); bvs = j;
-            ba = norm3(ax, ay, az); bas = j;
+            p = spline_eval(yp, Mp, o, n, h, t); v = spline_eval(yv, Mv, o, n, h, t); ac = spline_eval(ya, Ma, o, n, h, t);
+            bv = norm3(v.x, v.y, v.z); bvs = j;
+            ba = norm3(ac.x, ac.y, ac.z); bas = j;
         }
         if (slot) {
             const size_t q = ((a0 + a) * (size_t)SB + (size_t)(j - lo)) * 3;
-            if (sp) { sp[q] = px; sp[q + 1] = py; sp[q + 2] = pz; }
-            if (sv) { sv[q] = vx; sv[q + 1] = vy; sv[q + 2] = vz; }
-            if (sa) { sa[q] = ax; sa[q + 1] = ay; sa[q + 2] = az; }
+            if (sp) { sp[q] = p.x; sp[q + 1] = p.y; sp[q + 2] = p.z; }
+            if (sv) { sv[q] = v.x; sv[q + 1] = v.y; sv[q + 2] = v.z; }
+            if (sa) { sa[q] = ac.x; sa[q + 1] = ac.y; sa[q + 2] = ac.z; }
         }
         peak_wave(bv, bvs);
         peak_wave(ba, bas);

@@ -327,3 +327,80 @@ def test_postcheck_sparse_large_scene_falls_back_to_brute_force():
     ref = PC.postcheck(p, v, a, p[:, -1], kw["h"], kw["rmin"], kw["c"])
     assert ref["min_dist"] > 2 * kw["rmin"] and out["violation"][0] == 0
     assert abs(out["min_dist"][0] - ref["min_dist"]) <= 1e-10
+
+
+def test_postcheck_ragged_batch_on_the_grid_with_vehicles_interp_and_two_sample_passes():
+    """the sample-table kernel where its options meet: a ragged batch on the cell-grid path (N_cmd = 257: one above the brute-force limit,
+    a second agent tile of one agent), static and scripted vehicles, interpolated outputs, and more than one sample pass.  Accelerations up
+    to about 4 amax give r_factor <= 0.25 or so, h_scaled >= 0.4 s or so: scene 0 (9 knots) runs over the grid's pass of 256 samples, scene 1
+    (4 knots) ends inside the first pass, so the second pass meets samples beyond a scene's end; scene 2 is masked.
+    Bars: the files' own -- bytes between the calls and against setpoints(), _check's against the oracle (min_dist by its k-d tree),
+    _check_scripted's numpy checks (1e-10 on the spline, 1e-12 on the distance), tests/clearance.py's restatement for the clearance report."""
+    import clearance as cl
+    from test_gpu_scripted import _check_scripted, _same_bytes
+    S, N, M, KTa, P = 3, 257, 2, 9, 5
+    used, mask = np.array([9, 4, 6], dtype=np.int32), np.array([1, 1, 0], dtype=np.int32)
+    rng = np.random.default_rng(2570)
+    kw = _kw_for(N)
+    pk, vk, ak = (np.zeros((S, N, KTa, 3)) for _ in range(3))
+    for s in range(S):
+        pk[s, :, :used[s]], vk[s, :, :used[s]], ak[s, :, :used[s]] = _swarm_hist(rng, N, used[s], N ** (1.0 / 3.0), speed=2.5)
+    pf = pk[np.arange(S), :, used - 1] + rng.normal(0, 0.02, (S, N, 3))
+    pos = pk[:, [0, 100], 0] + (0.5, 0.0, 0.0)                                             # two vehicles beside the starts of agents 0 and 100
+    path = pk[:, [50, 200], :1] + (0.0, 0.5, 0.0) + np.cumsum(rng.uniform(-0.1, 0.1, (S, M, P, 3)), axis=2)
+    live = [s for s in range(S) if mask[s]]
+    ref = {s: PC.postcheck(pk[s][:, :used[s]], vk[s][:, :used[s]], ak[s][:, :used[s]], pf[s], kw["h"], kw["rmin"], kw["c"], pairs="tree") for s in live}
+    assert ref[0]["n_samples"] > 256 and ref[1]["n_samples"] < 256, (ref[0]["n_samples"], ref[1]["n_samples"])
+    d = mp.Dmpc("bound", **kw)
+    plain = d.postcheck(used, pf, pk, vk, ak, interp=True, mask=mask)
+    static = d.postcheck(used, pf, pk, vk, ak, interp=True, mask=mask, po_static=pos)
+    scripted = d.postcheck(used, pf, pk, vk, ak, interp=True, mask=mask, path=path)
+    _same_bytes({k: static[k] for k in plain}, plain, "commanded-only outputs, static vehicles")
+    _same_bytes({k: scripted[k] for k in plain}, plain, "commanded-only outputs, scripted vehicles")
+    for s in live:
+        print(f"scene {s}: {plain['n_samples'][s]} samples, r_factor {plain['r_factor'][s]:.4f}, min_dist {plain['min_dist'][s]:.6f} oracle {ref[s]['min_dist']:.6f}")
+        assert abs(plain["min_dist"][s] - ref[s]["min_dist"]) <= 1e-10
+        assert plain["n_samples"][s] == ref[s]["n_samples"] and abs(plain["r_factor"][s] - ref[s]["r_factor"]) <= 1e-13 * ref[s]["r_factor"]
+        _check(plain, s, ref[s])
+    sp = d.setpoints(used, pk=pk, vk=vk, ak=ak, mask=mask)
+    assert sp["p"].shape == plain["p"].shape and sp["p"].tobytes() == plain["p"].tobytes()
+    for s in live:
+        assert plain["p"][s][:, :plain["n_samples"][s]].any() and not plain["p"][s][:, plain["n_samples"][s]:].any()
+    # the vehicles: numpy on the returned positions
+    scripted["K_T_used"] = used
+    e1 = np.array([1.0, 1.0, 1.0 / kw["c"]])
+    for s in live:
+        _check_scripted(scripted, s, path[s], kw)
+        n = int(static["n_samples"][s])
+        dd = np.sqrt((((static["p"][s][:, None, :n] - pos[s][None, :, None]) * e1) ** 2).sum(-1))
+        assert abs(static["min_dist_static"][s] - dd.min()) <= 1e-12
+        assert int(static["violation_static"][s]) == int(dd.min() < kw["rmin"] - 0.05)
+    # the clearance report: the tiled search (reach = inf) against numpy, agent by agent, and the cell grid (reach = 1.5) against it -- every
+    # slot whose numpy distance is < reach the same bytes, every other +inf / -1 / -1 (which is what check_scene would ask of the grid's report)
+    near = {s: cl.nearest(plain["p"][s][:, :plain["n_samples"][s]], None, kw["c"])[0] for s in live}
+    for name, extra, pc, key in (("static", dict(po_static=pos), static, "min_dist_static"), ("scripted", dict(path=path), scripted, "min_dist_scripted")):
+        full = d.clearance(used, pf, pk, vk, ak, mask=mask, **extra)
+        grid = d.clearance(used, pf, pk, vk, ak, mask=mask, reach=1.5, **extra)
+        for s in live:
+            n = int(pc["n_samples"][s])
+            p = pc["p"][s][:, :n]
+            q = scripted["p_scripted"][s][:, :n] if name == "scripted" else np.repeat(pos[s][:, None], n, axis=1)
+            filled, empty = cl.check_scene(full["dist"][s], full["partner"][s], full["sample"][s], p, q, kw["c"])
+            assert filled == 2 * N and empty == 0
+            for slot, k in ((0, "min_dist"), (1, key)):
+                assert np.float64(full["dist"][s, :, slot].min()).tobytes() == np.float64(pc[k][s]).tobytes(), (name, s, k)
+            inside = np.stack([near[s], [cl.distances(p[i], q, kw["c"]).min() for i in range(N)]], axis=1) < 1.5
+            print(f"{name} scene {s}: {int(inside[:, 0].sum())} / {int(inside[:, 1].sum())} slots of kind 0 / 1 inside 1.5 m")
+            assert inside[:, 0].any() and inside[:, 1].any() and not inside[:, 1].all()
+            for k in ("dist", "partner", "sample"):
+                assert grid[k][s][inside].tobytes() == full[k][s][inside].tobytes(), (name, s, k)
+            assert np.isposinf(grid["dist"][s][~inside]).all() and (grid["partner"][s][~inside] == -1).all() and (grid["sample"][s][~inside] == -1).all()
+        for rep in (full, grid):
+            assert np.isnan(rep["dist"][2]).all() and (rep["partner"][2] == -1).all() and (rep["sample"][2] == -1).all()
+    # the masked scene: NaN / 0, as the entries document, and all-zero position rows
+    for out in (plain, static, scripted):
+        for k in ("r_factor", "h_scaled", "min_dist", "totdist", "traj_time"):
+            assert np.isnan(out[k][2]), k
+        assert out["n_samples"][2] == 0 and out["violation"][2] == 0 and not out["p"][2].any()
+    assert np.isnan(static["min_dist_static"][2]) and static["violation_static"][2] == 0
+    assert np.isnan(scripted["min_dist_scripted"][2]) and scripted["violation_scripted"][2] == 0 and not scripted["p_scripted"][2].any()
