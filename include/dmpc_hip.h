@@ -84,6 +84,7 @@ enum {
     DMPC_ST_INFEAS = 8,    /* QP infeasible after the retry ladder (solveSoftDMPCbound.m:102-155) */
     DMPC_ST_CAPACITY = 16, /* internal capacity exceeded (rows / active set): result NOT valid   */
     DMPC_ST_ITERCAP = 32,  /* iteration cap hit: result NOT valid                                */
+    DMPC_ST_HELD = 64,     /* dmpc_transition_hold only: the agent flew its previous plan on this column */
     DMPC_ST_REACHED = 256  /* scene_status of dmpc_transition only: all agents reached their goals */
 };
 
@@ -362,6 +363,41 @@ DMPC_API int dmpc_scripted_cols_device(dmpc_ctx *ctx, int S, int N, int N_cmd, i
 DMPC_API int dmpc_transition_mission(dmpc_ctx *ctx, int S, int N, int N_cmd, int Q, const double *po, const double *goals, const int32_t *deadline,
                             const double *path, int P, int K_T_max, double error_tol, double *pk, double *vk, double *ak,
                             int32_t *K_T_used, int32_t *scene_status, int32_t *stage_col);
+
+/* Hold policy: dmpc_transition_mission in which AN AGENT WHOSE SOLVE FAILED FLIES ITS PREVIOUS PLAN WHILE THE SCENE GOES ON.  NO REFERENCE
+ * COUNTERPART: the reference's failure-rate experiment -- and every other closed loop of this header -- stops the whole scene at the first
+ * column on which any agent's status is not exactly DMPC_ST_SOLVED.  Additive: the ABI revision stays 8.  The arguments up to stage_col are
+ * dmpc_transition_mission's, with the same meaning, the same refusals and the same batch split (Q == 1 without a deadline: the one-leg, static
+ * and scripted forms).  The rule, per commanded agent, after the solve of the step that produces history column k:
+ *   fail      the agent's status is not exactly DMPC_ST_SOLVED -- the predicate that stops a scene elsewhere; it includes
+ *             DMPC_ST_SOLVED | DMPC_ST_OUTBOUND and the DMPC_ST_SOLVED | DMPC_ST_COLL of the cpp variants, whose solution is then discarded.
+ *   run       the number of consecutive columns up to and including k on which the agent failed; 0 after a column on which it did not.
+ *   held      fail and run <= max_hold: the agent's plan of this step is its previous plan shifted by one entry,
+ *               p'[kk] = p[kk+1], v'[kk] = v[kk+1], a'[kk] = a[kk+1]   (kk = 0 .. K-2, copies)
+ *             with a braking tail as the last entry, per axis, every operation rounded on its own (no fused multiply-add):
+ *               a'[K-1] = a_t = min(max(-v[K-1] / h, -alim), alim)
+ *               v'[K-1] = v[K-1] + h * a_t
+ *               p'[K-1] = (p[K-1] + h * v[K-1]) + (0.5 * h * h) * a_t
+ *             "Previous plan" is the agent's plan of step k-1, solved or held; for k = 1 the initDMPC plan (the straight-line positions,
+ *             v = a = 0).  A held plan is treated exactly as a solved one: its column goes into the next table, its first entry becomes the
+ *             state and history column k, and it counts as solved in the scene verdict, in ReachedGoal and in the mission stage rule.
+ *   over      fail and run > max_hold: the agent is not held, and the column ends the scene exactly as in dmpc_transition_mission -- the
+ *             same recorded column, K_T_used = k+1, scene_status = the OR of the raw bits (of the agents not held on that column).
+ * max_hold >= 0.  max_hold == 0: every output of the common arguments is dmpc_transition_mission's byte for byte, on failing scenes too.
+ * Outputs, each or all NULL:
+ *   hold_count   [S][N_cmd]            the columns on which the agent was held
+ *   hold_first   [S][N_cmd]            the first such column, or -1
+ *   agent_status [S][N_cmd][K_T_max]   column 0: DMPC_ST_SOLVED; column k: the solver's raw status of that step, DMPC_ST_HELD OR-ed in where
+ *                                      the agent was held; columns the scene never reached: 0
+ * scene_status[s] carries DMPC_ST_HELD in addition when any agent of the scene was held on a column < K_T_used[s], and is as in
+ * dmpc_transition_mission otherwise: DMPC_ST_SOLVED | DMPC_ST_REACHED | DMPC_ST_HELD is a transition that arrived with holds.  Whether a flown
+ * transition kept its clearance is what dmpc_postcheck* and dmpc_postcheck_clearance answer on the resident histories, unchanged.
+ * A DMPC_DEVICE_ALL context runs the call on its first GPU; there is no RCCL form.  max_hold < 0, or what dmpc_transition_mission refuses:
+ * -1 and a message that starts with the entry's name, nothing launched. */
+DMPC_API int dmpc_transition_hold(dmpc_ctx *ctx, int S, int N, int N_cmd, int Q, const double *po, const double *goals, const int32_t *deadline,
+                         const double *path, int P, int K_T_max, double error_tol, int max_hold, double *pk, double *vk, double *ak,
+                         int32_t *K_T_used, int32_t *scene_status, int32_t *stage_col, int32_t *hold_count, int32_t *hold_first,
+                         int32_t *agent_status);
 
 /* Multi-GPU: the agents of every scene sharded over the GPUs of one node, ONE PROCESS (rank) PER GPU, each with its own
  * context.  Replaces the thread clusters of DMPC::solveParallelDMPCv2 (dmpc/cpp/dmpc.cpp:1570-1686): contiguous agent ranges,

@@ -16,6 +16,7 @@ VARIANTS = dict(bound=0, bound2=1, all3=2, hard=3, ondemand=4, ellip=5, softall=
 ST_SOLVED, ST_OUTBOUND, ST_COLL, ST_INFEAS, ST_CAPACITY, ST_ITERCAP = 1, 2, 4, 8, 16, 32
 PRECISIONS = dict(f64=0, mixed=1, f32factor=2, low=3)
 ST_REACHED = 256   # scene_status of transition(): every agent reached its goal
+ST_HELD = 64       # transition(on_fail="hold") / mission(on_fail="hold"): the agent flew its previous plan on this column
 INFO_LEN = 8
 I_VIOLK, I_NROWS, I_TRIES, I_CASE, I_ITERS, I_NSLACK, I_NACTIVE, I_MAXQ = range(8)
 K_HOR = 15
@@ -38,6 +39,7 @@ ABI_SYMBOLS = [
     "dmpc_postcheck_clearance",
     "dmpc_transition_mission",
     "dmpc_postcheck_setpoints",
+    "dmpc_transition_hold",
 ]
 
 
@@ -136,6 +138,8 @@ def load():
                                            C.c_double, C.c_double, dp, ip, ip]
     # missions: a transition through a sequence of goal sets (additive, still revision 8)
     L.dmpc_transition_mission.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, ip, dp, C.c_int, C.c_int, C.c_double, dp, dp, dp, ip, ip, ip]
+    L.dmpc_transition_hold.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, ip, dp, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, dp, ip, ip, ip,
+                                       ip, ip, ip]
     # flight setpoints p, v, a at 100 Hz and the limits report (additive, still revision 8)
     L.dmpc_postcheck_setpoints.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
                                            dp, dp, dp, dp, ip, dp, ip, dp, dp, ip]
@@ -353,19 +357,45 @@ class Dmpc:
         k = min(int(nr[0]), max_rows)
         return dict(xi=xi[:k], rhs=rhs[:k], slack_coef=sc[:k], kc=kc[:k], nrows=int(nr[0]), viol_k=int(vk[0]), status=int(st[0]))
 
-    def transition(self, po, pf, K_T_max, error_tol=0.01, histories=True, path=None):
+    def _transition_hold(self, S, N, n_cmd, Q, po, goals, deadline, path, P, K_T_max, error_tol, max_hold, lead, histories):
+        """dmpc_transition_hold on prepared arrays (lead: the leading shape of the per-agent outputs); what mission() returns, and hold_count,
+        hold_first [lead], agent_status [lead, K_T_max]"""
+        nul, inul = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
+        used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+        stage_col = np.zeros((S, Q), dtype=np.int32)
+        cnt, first = np.zeros(lead, dtype=np.int32), np.zeros(lead, dtype=np.int32)
+        log = np.zeros(lead + (K_T_max,), dtype=np.int32)
+        pk = vk = ak = None
+        if histories:
+            pk, vk, ak = (np.zeros(lead + (K_T_max, 3)) for _ in range(3))
+        self._chk(self._L.dmpc_transition_hold(self._ctx, S, N, n_cmd, Q, _dp(po), _dp(goals), _ip(deadline) if deadline is not None else inul,
+                                               _dp(path) if path is not None else nul, P, int(K_T_max), float(error_tol), int(max_hold),
+                                               _dp(pk) if histories else nul, _dp(vk) if histories else nul, _dp(ak) if histories else nul,
+                                               _ip(used), _ip(sst), _ip(stage_col), _ip(cnt), _ip(first), _ip(log)))
+        return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, stage_col=stage_col, hold_count=cnt, hold_first=first, agent_status=log)
+
+    def transition(self, po, pf, K_T_max, error_tol=0.01, histories=True, path=None, on_fail="stop", max_hold=14):
         """histories=False: pk/vk/ak are not downloaded (they stay on the device for postcheck()).
+        on_fail="hold" (dmpc_transition_hold; "stop": the entries below, unchanged): an agent whose solve failed flies its previous plan, shifted
+        by one entry and with a braking tail, for up to max_hold consecutive columns while the scene goes on; the dict then also has hold_count,
+        hold_first (per agent) and agent_status (per agent and column: the raw status, ST_HELD where held), and scene_status carries ST_HELD.
         pf with FEWER agents than po (N_cmd = pf's agents < N = po's, the reference's _pf.cols() / _po.cols(); dmpc_transition_cmd): the vehicles
         behind the first N_cmd are not commanded and stay at po as static obstacles; histories, K_T_used and scene_status cover the commanded ones.
         path [S,M,P,3] (or [M,P,3]; dmpc_transition_scripted): M scripted vehicles behind the commanded agents of po / pf (same agent count in
         both), sample t of a path = the vehicle's position at history column t, held at its last sample once the path has ended."""
         po, pf = _f(po), _f(pf)
+        if on_fail not in ("stop", "hold"):
+            raise DmpcError(f"transition: on_fail is 'stop' or 'hold', not {on_fail!r}")
         if path is not None:
             if po.shape != pf.shape or po.ndim not in (2, 3) or po.shape[-1] != 3:
                 raise DmpcError(f"transition: with path, po {tuple(po.shape)} and pf {tuple(pf.shape)} must cover the same commanded agents")
             shp = po.shape[:-1]
             path, M, P = _path(path, shp, "transition")
             S, n_cmd = (1, shp[0]) if len(shp) == 1 else shp
+            if on_fail == "hold":   # (pf [S][N_cmd][3] is goals [S][1][N_cmd][3])
+                out = self._transition_hold(S, n_cmd + M, n_cmd, 1, po, pf, None, path, P, K_T_max, error_tol, max_hold, shp, histories)
+                del out["stage_col"]
+                return out
             used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
             nul = C.POINTER(C.c_double)()
             pk = vk = ak = None
@@ -376,6 +406,10 @@ class Dmpc:
                                                        _ip(used), _ip(sst)))
             return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst)
         S, N, n_cmd, shp = _n_cmd(po.shape[:-1], pf, "transition")
+        if on_fail == "hold":
+            out = self._transition_hold(S, N, n_cmd, 1, po, pf, None, None, 0, K_T_max, error_tol, max_hold, shp, histories)
+            del out["stage_col"]
+            return out
         used = np.zeros(S, dtype=np.int32)
         sst = np.zeros(S, dtype=np.int32)
         if histories:
@@ -393,13 +427,16 @@ class Dmpc:
                                                   _ip(used), _ip(sst)))
         return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst)
 
-    def mission(self, po, goals, K_T_max, error_tol=0.01, histories=True, deadline=None, path=None):
+    def mission(self, po, goals, K_T_max, error_tol=0.01, histories=True, deadline=None, path=None, on_fail="stop", max_hold=14):
         """dmpc_transition_mission: one transition through the Q goal sets goals [Q,N_cmd,3] (next to an unbatched po) or [S,Q,N_cmd,3].  A stage
         ends at the first column where its goals are reached or -- deadline [Q] / [S,Q], 0 = none, the last 0 -- its deadline has passed; the
         next step is solved with the next goal set, the last stage ends the trial.  po with MORE vehicles than the goals: static vehicles, as
         transition(); path [S,M,P,3]: scripted vehicles, po then covers the commanded agents.  Returns what transition() returns, and stage_col
-        [S,Q]: the column each stage ended on (-1: it never did)."""
+        [S,Q]: the column each stage ended on (-1: it never did).  on_fail, max_hold: as transition() (a held plan counts as a solved one in the
+        stage rule)."""
         po, goals = _f(po), _f(goals)
+        if on_fail not in ("stop", "hold"):
+            raise DmpcError(f"mission: on_fail is 'stop' or 'hold', not {on_fail!r}")
         if po.ndim not in (2, 3) or goals.ndim != po.ndim + 1 or po.shape[-1] != 3 or goals.shape[-1] != 3 or goals.shape[:-3] != po.shape[:-2]:
             raise DmpcError(f"mission: goals {tuple(goals.shape)} must be [Q,N_cmd,3] next to po [N,3], or [S,Q,N_cmd,3] next to po [S,N,3]: po is {tuple(po.shape)}")
         S = 1 if po.ndim == 2 else po.shape[0]
@@ -415,6 +452,8 @@ class Dmpc:
         nul, inul = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
         if deadline is not None:
             deadline = np.ascontiguousarray(np.broadcast_to(np.asarray(deadline, dtype=np.int32), (S, Q)))
+        if on_fail == "hold":
+            return self._transition_hold(S, N + M, n_cmd, Q, po, goals, deadline, path, P, K_T_max, error_tol, max_hold, lead, histories)
         used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
         stage_col = np.zeros((S, Q), dtype=np.int32)
         pk = vk = ak = None

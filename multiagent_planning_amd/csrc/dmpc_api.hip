@@ -158,6 +158,7 @@ struct dmpc_ctx {
     DevBuf pc_p, pc_v, pc_a, pc_M, pc_w, pc_scene, pc_agent, pc_interp;   // post-check work buffers
     DevBuf pc_static;                                                      // post-check: positions of the uncommanded vehicles + their per-scene minimum
     DevBuf path;                                                           // dmpc_transition_scripted: the scripted vehicles' paths [S][M][P][3], resident for the call
+    DevBuf hold_out, hold_state;                                           // dmpc_transition_hold: the second set of p / v / a output rows 3 x [S][N_cmd][3K]; ints: run, hold_count, hold_first [S][N_cmd] each, agent_status [S][N_cmd][K_T_max]
     DevBuf mis_goals, mis_state;                                           // dmpc_transition_mission: goal sets [S][Q][N_cmd][3]; ints: stage [S], k_start [S], stage_col [S][Q], deadline [S][Q]
     DevBuf pc_sc_path, pc_sc_y, pc_sc_M, pc_sc_w, pc_sc_pts, pc_sc_interp; // dmpc_postcheck_scripted: paths, knots, second derivatives, scratch, sample batch, p_scripted
     DevBuf pc_pts, pc_cell, pc_fill, pc_start, pc_sorted, pc_on;           // post-check, large scenes: cell grid of a batch of samples
@@ -1023,9 +1024,19 @@ struct Mission {
     const int32_t *deadline;   // [S][Q] or null
     int32_t *stage_col;        // [S][Q] or null
 };
+// hold != null (dmpc_transition_hold): an agent whose solve failed flies its previous plan, shifted, for up to max_hold consecutive columns
+// (hold_kernel, between the solve and the post step of every column).  The post step is never fused into the solve launch then: the held plan
+// has to be in place before the state advances.  The step's output rows alternate between two sets, so that the previous plan's v and a still
+// stand in the other set after the solve; the previous positions are the agent's column of the table the step read.
+struct Hold {
+    int max_hold;
+    int32_t *hold_count, *hold_first;   // [S][N_cmd] or null
+    int32_t *agent_status;              // [S][N_cmd][K_T_max] or null
+};
 static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
                           double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                          int32_t *scene_status, const double *path = nullptr, int P = 0, const Mission *mission = nullptr)
+                          int32_t *scene_status, const double *path = nullptr, int P = 0, const Mission *mission = nullptr,
+                          const Hold *hold = nullptr)
 {
     if (mission) pf = mission->goals;
     if (!ctx) { g_err = "dmpc_transition: ctx is NULL"; return -1; }
@@ -1097,6 +1108,27 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
         hipLaunchKernelGGL(mission_stage_kernel, dim3((unsigned)S), dim3(mis_threads), 0, st, N_cmd, Q, 0, (const double *)ctx->mis_goals.as<double>(),
                            (const int *)mis_dl, ctx->flags.as<int>(), ctx->scene_done.as<int>(), mis_stage, mis_k0, mis_col, ctx->pf.as<double>());
     double *cur = ctx->lT.as<double>(), *nxt = ctx->lT2.as<double>();
+    double *outs[2][3] = {{ctx->pout.as<double>(), ctx->vout.as<double>(), ctx->aout.as<double>()},
+                          {ctx->pout.as<double>(), ctx->vout.as<double>(), ctx->aout.as<double>()}};   // (hold: the second set follows)
+    int *hold_run = nullptr, *hold_cnt = nullptr, *hold_1st = nullptr, *hold_log = nullptr;
+    const unsigned hold_blocks = (unsigned)((A + 63) / 64);
+    auto launch_hold = [&](int k, int set) {   // the hold rule on column k; the step wrote outs[set], the previous plan's v, a stand in outs[set ^ 1]
+        hipLaunchKernelGGL(hold_kernel, dim3(hold_blocks), dim3(64), 0, st, (int)A, N_cmd, N, K_T_max, k, hold->max_hold, ctx->prm.h, ctx->prm.alim,
+                           (const double *)cur, nxt, (const double *)outs[set ^ 1][1], (const double *)outs[set ^ 1][2], outs[set][0], outs[set][1],
+                           outs[set][2], ctx->status.as<int>(), (const int *)ctx->scene_done.as<int>(), hold_run, hold_log, hold_cnt, hold_1st);
+    };
+    if (hold) {
+        if (A > 0x7fffffffu) FAIL(ctx, "dmpc_transition_hold: S * N_cmd overflows");
+        const size_t row_bytes = A * N3 * 8;
+        if (ctx->hold_out.ensure(3 * row_bytes) || ctx->hold_state.ensure((3 * A + A * (size_t)K_T_max) * 4)) FAIL(ctx, "device allocation failed");
+        for (int j = 0; j < 3; ++j) outs[0][j] = ctx->hold_out.as<double>() + (size_t)j * A * N3;   // (step k writes set k & 1: the first step the context's own rows)
+        hold_run = ctx->hold_state.as<int>(); hold_cnt = hold_run + A; hold_1st = hold_cnt + A; hold_log = hold_1st + A;
+        HIPCHK(ctx, hipMemsetAsync(outs[0][1], 0, 2 * row_bytes, st));   // the initDMPC plan: v = a = 0 (its positions are the first table)
+        HIPCHK(ctx, hipMemsetAsync(hold_cnt, 0, A * 4, st));
+        HIPCHK(ctx, hipMemsetAsync(hold_1st, 0xff, A * 4, st));
+        HIPCHK(ctx, hipMemsetAsync(hold_log, 0, A * (size_t)K_T_max * 4, st));
+        launch_hold(0, 1);   // column 0: every status is DMPC_ST_SOLVED -- run = 0 and the log's first column, also of a scene that is over already
+    }
     ctx->post_acc_S = 0;   // the scene accumulators of the fused post-step start from zero in every transition
     const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;   // the scan of every step reads an fp32 copy of the current table
     // The host looks at the per-step verdicts every `chunk` MPC steps -- one window BEHIND the steps it enqueues: the verdicts of window c
@@ -1146,15 +1178,17 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
                             ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>()};
         StepIO io;
         io.lT = cur; io.x_p = xp; io.x_v = xv; io.x_a = xa; io.pf = ctx->pf.as<double>();
-        io.p_out = ctx->pout.as<double>(); io.v_out = ctx->vout.as<double>(); io.a_out = ctx->aout.as<double>(); io.lT_next = nxt;
+        double **out = outs[k & 1];
+        io.p_out = out[0]; io.v_out = out[1]; io.a_out = out[2]; io.lT_next = nxt;
         io.status = ctx->status.as<int32_t>();
-        io.scene_done = ctx->scene_done.as<int>(); io.lTf = mixed ? ctx->lTf.as<float>() : nullptr; io.post = &post;
+        io.scene_done = ctx->scene_done.as<int>(); io.lTf = mixed ? ctx->lTf.as<float>() : nullptr; io.post = hold ? nullptr : &post;
         const StepShape sh{S, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ 0, /*c_count*/ N_cmd};
         if (launch_step(ctx, sh, io, st)) return -1;
+        if (hold) launch_hold(k, k & 1);
         // state advance + history column + scene verdict in one launch (unless the solve kernel did them: tiny launches)
         if (!ctx->post_fused)
         hipLaunchKernelGGL(post_step_kernel, dim3((unsigned)S), dim3(N_cmd >= 256 ? 256 : 128), 0, st, N_cmd, K_T_max, k, error_tol,
-                           (const double *)ctx->pout.as<double>(), (const double *)ctx->vout.as<double>(), (const double *)ctx->aout.as<double>(),
+                           (const double *)out[0], (const double *)out[1], (const double *)out[2],
                            (const int *)ctx->status.as<int32_t>(), xp, xv, xa, (const double *)ctx->pf.as<double>(), ctx->hist_p.as<double>(),
                            ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>(),
                            (const int *)ctx->scene_done.as<int>());
@@ -1181,7 +1215,19 @@ static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
         HIPCHK(ctx, hipMemcpyAsync(ak, ctx->hist_a.p, hist, hipMemcpyDeviceToHost, st));
     }
     if (mission && mission->stage_col) HIPCHK(ctx, hipMemcpyAsync(mission->stage_col, mis_col, (size_t)S * Q * 4, hipMemcpyDeviceToHost, st));
+    std::vector<int32_t> held(hold ? A : 0);
+    if (hold) {
+        HIPCHK(ctx, hipMemcpyAsync(held.data(), hold_cnt, A * 4, hipMemcpyDeviceToHost, st));
+        if (hold->hold_first) HIPCHK(ctx, hipMemcpyAsync(hold->hold_first, hold_1st, A * 4, hipMemcpyDeviceToHost, st));
+        if (hold->agent_status) HIPCHK(ctx, hipMemcpyAsync(hold->agent_status, hold_log, A * (size_t)K_T_max * 4, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(ctx, hipStreamSynchronize(st));
+    if (hold) {   // (every hold the device recorded stands on a column < K_T_used: the steps behind a scene's end skip it)
+        for (int s = 0; s < S; ++s)
+            for (int i = 0; i < N_cmd; ++i)
+                if (held[(size_t)s * N_cmd + i] > 0) { scene_status[s] |= DMPC_ST_HELD; break; }
+        if (hold->hold_count) std::memcpy(hold->hold_count, held.data(), A * 4);
+    }
     ctx->hist_S = S; ctx->hist_N = N_cmd; ctx->hist_KT = K_T_max;   // (the resident histories are the commanded agents')
     return 0;
 }
@@ -1200,7 +1246,8 @@ static void copy_debug_options(dmpc_ctx *dst, const dmpc_ctx *src)
 // threads): the tail of one half overlaps the bulk of the other (512 transitions of 100 agents: 103 -> 60 ms).
 static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
                           double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                          int32_t *scene_status, const double *path = nullptr, int P = 0, const Mission *mission = nullptr)
+                          int32_t *scene_status, const double *path = nullptr, int P = 0, const Mission *mission = nullptr,
+                          const Hold *hold = nullptr)
 {
     ctx->split_at.clear();
     // uncommanded vehicles on a DMPC_DEVICE_ALL context: the first GPU alone (the rule for N < 2 G below); the batch split further down applies unchanged
@@ -1248,7 +1295,7 @@ static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
     int parts = ctx->opt.split_parts > 0 ? ctx->opt.split_parts : (S >= 128 ? 4 : (S >= 32 ? 2 : 1));
     if (parts > S) parts = S;
     if (parts < 2 || ctx->opt.no_split || ctx->grp || N < 1 || N_cmd < 1 || N_cmd > N || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status)
-        return transition_one(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, P, mission);
+        return transition_one(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, P, mission, hold);
     while ((int)ctx->children.size() < parts - 1) {
         dmpc_ctx *ch = dmpc_create(&ctx->prm, ctx->device, ctx->precision);
         if (!ch) FAIL(ctx, "dmpc_transition: further context: " + g_err);
@@ -1273,9 +1320,13 @@ static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *
             part = Mission{mission->Q, mission->goals + q0 * N_cmd * 3, mission->deadline ? mission->deadline + q0 : nullptr,
                            mission->stage_col ? mission->stage_col + q0 : nullptr};
         }
+        Hold hpart{};     // hold: the part's scenes' slices of the three per-agent arrays
+        if (hold)
+            hpart = Hold{hold->max_hold, hold->hold_count ? hold->hold_count + a0 : nullptr, hold->hold_first ? hold->hold_first + a0 : nullptr,
+                         hold->agent_status ? hold->agent_status + a0 * (size_t)K_T_max : nullptr};
         rc[(size_t)i] = transition_one(c, sn, N, N_cmd, po + t0 * 3, pf + a0 * 3, K_T_max, error_tol, pk ? pk + h0 : nullptr, vk ? vk + h0 : nullptr,
                                        ak ? ak + h0 : nullptr, K_T_used + s0, scene_status + s0, path ? path + (size_t)s0 * (N - N_cmd) * P * 3 : nullptr, P,
-                                       mission ? &part : nullptr);
+                                       mission ? &part : nullptr, hold ? &hpart : nullptr);
     };
     std::vector<std::thread> th;
     for (int i = 1; i < parts; ++i) th.emplace_back(run, i);
@@ -1336,27 +1387,52 @@ extern "C" int dmpc_transition_scripted(dmpc_ctx *ctx, int S, int N_cmd, int M, 
 // Missions: a transition through a sequence of goal sets.  No reference counterpart (the reference flies one leg); the step is the
 // reference's, the stage rule the loop a caller of dmpc_step_batch[_cmd] could write on the host -- applied on the device after the verdict of
 // every column (mission_stage_kernel), so that the host keeps reading the verdicts one window behind.
+// the shared argument check of dmpc_transition_mission and dmpc_transition_hold
+static int check_mission(dmpc_ctx *ctx, const std::string &who, int S, int N, int N_cmd, int Q, const double *po, const double *goals, const int32_t *deadline,
+                         const double *path, int P, int K_T_max, const double *pk, const double *vk, const double *ak, const int32_t *K_T_used,
+                         const int32_t *scene_status)
+{
+    if (check_cmd(ctx, who.c_str(), S, N, N_cmd)) return -1;
+    if (Q < 1) FAIL(ctx, who + ": Q must be >= 1 (a mission has at least one stage)");
+    if (!goals) FAIL(ctx, who + ": goals is NULL");
+    if (path && check_scripted(ctx, who.c_str(), S, N_cmd, N - N_cmd, P)) return -1;
+    if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, who + ": pk, vk, ak must be all given or all NULL");
+    if (K_T_max < 2 || !po || !K_T_used || !scene_status) FAIL(ctx, who + ": bad arguments");
+    if ((size_t)S * (size_t)Q > 0x7fffffffu) FAIL(ctx, who + ": S * Q overflows");
+    if (deadline)
+        for (int s = 0; s < S; ++s) {
+            for (int q = 0; q < Q; ++q)
+                if (deadline[(size_t)s * Q + q] < 0) FAIL(ctx, who + ": a deadline is negative (0: none)");
+            if (deadline[(size_t)s * Q + Q - 1] != 0) FAIL(ctx, who + ": the last stage's deadline must be 0 (the last stage ends the trial when it is reached)");
+        }
+    return 0;
+}
+
 extern "C" int dmpc_transition_mission(dmpc_ctx *ctx, int S, int N, int N_cmd, int Q, const double *po, const double *goals, const int32_t *deadline,
                                        const double *path, int P, int K_T_max, double error_tol, double *pk, double *vk, double *ak,
                                        int32_t *K_T_used, int32_t *scene_status, int32_t *stage_col)
 {
     if (!ctx) { g_err = "dmpc_transition_mission: ctx is NULL"; return -1; }
-    if (check_cmd(ctx, "dmpc_transition_mission", S, N, N_cmd)) return -1;
-    if (Q < 1) FAIL(ctx, "dmpc_transition_mission: Q must be >= 1 (a mission has at least one stage)");
-    if (!goals) FAIL(ctx, "dmpc_transition_mission: goals is NULL");
-    if (path && check_scripted(ctx, "dmpc_transition_mission", S, N_cmd, N - N_cmd, P)) return -1;
-    if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, "dmpc_transition_mission: pk, vk, ak must be all given or all NULL");
-    if (K_T_max < 2 || !po || !K_T_used || !scene_status) FAIL(ctx, "dmpc_transition_mission: bad arguments");
-    if ((size_t)S * (size_t)Q > 0x7fffffffu) FAIL(ctx, "dmpc_transition_mission: S * Q overflows");
-    if (deadline)
-        for (int s = 0; s < S; ++s) {
-            for (int q = 0; q < Q; ++q)
-                if (deadline[(size_t)s * Q + q] < 0) FAIL(ctx, "dmpc_transition_mission: a deadline is negative (0: none)");
-            if (deadline[(size_t)s * Q + Q - 1] != 0) FAIL(ctx, "dmpc_transition_mission: the last stage's deadline must be 0 (the last stage ends the trial when it is reached)");
-        }
+    if (check_mission(ctx, "dmpc_transition_mission", S, N, N_cmd, Q, po, goals, deadline, path, P, K_T_max, pk, vk, ak, K_T_used, scene_status)) return -1;
     const Mission mission{Q, goals, deadline, stage_col};
     // (a DMPC_DEVICE_ALL context: its first GPU)
     return transition_any(ctx, S, N, N_cmd, po, goals, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, path ? P : 0, &mission);
+}
+
+// Hold policy: dmpc_transition_mission in which an agent whose solve failed flies its previous plan while the scene goes on.  No reference
+// counterpart (the reference's failure-rate experiment stops the trial); the rule is in include/dmpc_hip.h, the device side is hold_kernel.
+extern "C" int dmpc_transition_hold(dmpc_ctx *ctx, int S, int N, int N_cmd, int Q, const double *po, const double *goals, const int32_t *deadline,
+                                    const double *path, int P, int K_T_max, double error_tol, int max_hold, double *pk, double *vk, double *ak,
+                                    int32_t *K_T_used, int32_t *scene_status, int32_t *stage_col, int32_t *hold_count, int32_t *hold_first,
+                                    int32_t *agent_status)
+{
+    if (!ctx) { g_err = "dmpc_transition_hold: ctx is NULL"; return -1; }
+    if (check_mission(ctx, "dmpc_transition_hold", S, N, N_cmd, Q, po, goals, deadline, path, P, K_T_max, pk, vk, ak, K_T_used, scene_status)) return -1;
+    if (max_hold < 0) FAIL(ctx, "dmpc_transition_hold: max_hold must be >= 0 (0: no agent is ever held, dmpc_transition_mission)");
+    const Mission mission{Q, goals, deadline, stage_col};
+    const Hold hold{max_hold, hold_count, hold_first, agent_status};
+    // (a DMPC_DEVICE_ALL context: its first GPU)
+    return transition_any(ctx, S, N, N_cmd, po, goals, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, path ? P : 0, &mission, &hold);
 }
 
 // the fill of dmpc_transition_scripted for callers that loop over dmpc_step_device_cmd themselves

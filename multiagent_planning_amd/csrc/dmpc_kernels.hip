@@ -2302,4 +2302,69 @@ __global__ void mission_stage_kernel(int N, int Q, int k, const double *__restri
     }
 }
 
+// Hold policy (dmpc_transition_hold): between the solve of the step that produces history column k and its post step, over the S * N_cmd
+// commanded agents, one wave per 64 of them.  An agent whose status is not exactly ST_SOLVED has failed; while its run of consecutive failures
+// is <= max_hold it is HELD: its plan of this step is its previous plan shifted by one entry, with a braking tail appended
+//   a_t = clamp(-v[K-1] / h, -alim, alim),  v' = v[K-1] + h a_t,  p' = (p[K-1] + h v[K-1]) + (0.5 h h) a_t        (per axis)
+// -- every operation rounded on its own (contraction is switched off in the kernel: the rounded-multiply intrinsics are plain products that
+// the compiler would fuse), so that a host loop reproduces the bits.  The previous positions are the agent's
+// column of the table the step read (lT [S][3K][N]), the previous v / a rows stand in the OTHER set of the alternating output buffers
+// (pv, pa [S][N_cmd][3K]).  The shifted plan goes into the current output rows (the next step's "previous") and into the agent's column of
+// lT_next; the working status becomes ST_SOLVED, so that post_step_kernel and mission_stage_kernel take the held plan as a solved one.  An
+// agent past its budget keeps its raw status and ends the scene there as in dmpc_transition.
+//   run, hold_count, hold_first: [S][N_cmd]; log: [S][N_cmd][KT], column k = the raw status, ST_HELD OR-ed in where the agent was held
+// Phase 1 is per lane (one status load; an agent that did not fail stores run = 0 and its log entry); phase 2 visits the wave's held agents
+// one after the other (they are rare), lane j < 3K moving entry j of p, v and a: the 45 stores at stride N into lT_next are one store
+// instruction of 45 lanes per held agent, as the solvers' output stage writes a column.
+enum { ST_HELD = 64 /* = DMPC_ST_HELD; the internal ST_QOVER of the same value never survives a step */ };
+__global__ __launch_bounds__(64) void hold_kernel(int total, int N_cmd, int N, int KT, int k, int max_hold, double h, double alim,
+                                                  const double *__restrict__ lT, double *__restrict__ lT_next, const double *__restrict__ pv,
+                                                  const double *__restrict__ pa, double *__restrict__ p_out, double *__restrict__ v_out,
+                                                  double *__restrict__ a_out, int *status, const int *__restrict__ scene_done, int *run, int *log,
+                                                  int *hold_count, int *hold_first)
+{
+#pragma clang fp contract(off)   // the tail as the host loop computes it: no fused multiply-add
+    const int lane = (int)threadIdx.x;
+    const int first = (int)blockIdx.x * 64;
+    const int ag = first + lane;
+    bool held = false;
+    if (ag < total && (k == 0 || !scene_done[ag / N_cmd])) {   // (k = 0, behind the verdict of the initDMPC column: every status is ST_SOLVED -- run = 0 and the log's first column)
+        const int st = status[ag];
+        int r = 0, rec = st;
+        if (st != ST_SOLVED) {
+            r = run[ag] + 1;
+            held = r <= max_hold;
+            if (held) {
+                rec |= ST_HELD;
+                hold_count[ag] += 1;
+                if (hold_first[ag] < 0) hold_first[ag] = k;
+            }
+        }
+        run[ag] = r;
+        log[(size_t)ag * KT + k] = rec;
+    }
+    unsigned long long m = __ballot(held);
+    const double half_hh = (0.5 * h) * h;
+    while (m) {   // (wave-uniform)
+        const int a = first + (__ffsll((long long)m) - 1);
+        m &= m - 1;
+        const int s = a / N_cmd, i = a - s * N_cmd;
+        if (lane < N3) {
+            const size_t col = (size_t)s * N3 * N + i, row = (size_t)a * N3 + lane;
+            double pn, vn, an;
+            if (lane < N3 - 3) {
+                pn = lT[col + (size_t)(lane + 3) * N]; vn = pv[row + 3]; an = pa[row + 3];
+            } else {
+                const double pl = lT[col + (size_t)lane * N], vl = pv[row];
+                an = fmin(fmax(-vl / h, -alim), alim);
+                vn = vl + h * an;
+                pn = (pl + h * vl) + half_hh * an;
+            }
+            p_out[row] = pn; v_out[row] = vn; a_out[row] = an;
+            lT_next[col + (size_t)lane * N] = pn;
+        }
+        if (lane == 0) status[a] = ST_SOLVED;
+    }
+}
+
 }  // namespace dmpc
