@@ -187,6 +187,9 @@ struct dmpc_ctx {
     int64_t prof_n = 0;
 };
 
+// workgroups of 256 threads for n elements of a grid-stride kernel, at most cap
+static unsigned grid_1d(size_t n, size_t cap) { return (unsigned)std::min((n + 255) / 256, cap); }
+
 #define FAIL(ctx, msg)                                   \
     do {                                                 \
         std::string m_ = (msg);                          \
@@ -719,8 +722,6 @@ extern "C" int dmpc_profile_read(dmpc_ctx *ctx, double *avg_ms, int64_t *n_launc
 }
 
 static int table_f32(dmpc_ctx *ctx, const double *src, DevBuf &dst, size_t n, hipStream_t st);
-static int group_transition(dmpc_ctx *root, int S, int N, const double *po, const double *pf, int K_T_max, double error_tol, double *pk,
-                            double *vk, double *ak, int32_t *K_T_used, int32_t *scene_status);
 static int group_step_batch(dmpc_ctx *root, int S, int N, const double *l, const double *x_p, const double *x_v, const double *x_a,
                             const double *pf, double *p_out, double *v_out, double *a_out, int32_t *status, int32_t *info);
 
@@ -776,9 +777,7 @@ extern "C" int dmpc_table_from_rows_device(dmpc_ctx *ctx, int S, int G, int C, c
     if (!ctx) { g_err = "dmpc_table_from_rows_device: ctx is NULL"; return -1; }
     if (S < 1 || G < 1 || C < 1 || !rows || !lT) FAIL(ctx, "dmpc_table_from_rows_device: bad arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t total = (size_t)S * G * C * N3;
-    const unsigned blocks = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(table_from_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, G, C, rows, lT);
+    hipLaunchKernelGGL(table_from_rows_kernel, dim3(grid_1d((size_t)S * G * C * N3, 4096)), dim3(256), 0, (hipStream_t)stream, S, G, C, rows, lT);
     HIPCHK(ctx, hipGetLastError());
     return 0;
 }
@@ -821,8 +820,7 @@ static int ensure_step_scratch(dmpc_ctx *ctx, size_t agents_table, size_t agents
 static int table_f32(dmpc_ctx *ctx, const double *src, DevBuf &dst, size_t n, hipStream_t st)
 {
     if (dst.ensure(n * 4)) FAIL(ctx, "device allocation failed (fp32 table)");
-    const unsigned blocks = (unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-    hipLaunchKernelGGL(table_to_f32_kernel, dim3(blocks), dim3(256), 0, st, n, src, dst.as<float>());
+    hipLaunchKernelGGL(table_to_f32_kernel, dim3(grid_1d(n, 4096)), dim3(256), 0, st, n, src, dst.as<float>());
     return 0;
 }
 
@@ -1011,447 +1009,20 @@ extern "C" int dmpc_init_batch(dmpc_ctx *ctx, int S, int N, const double *po, co
     return 0;
 }
 
-// the whole `for k = 1:K_T` loop on the device (dmpc_soft_bound.m:115-148, failure_rate.m:99-127) for the N_cmd commanded agents of N vehicles
-// (DMPC::solveParallelDMPCv2, dmpc.cpp:1570-1730: N = _po.cols(), N_cmd = _pf.cols()).  State, goals, outputs, histories, status and the
-// scene verdict are sized and strided by N_cmd (A agents); the tables and neighbour structures by N (T columns).  N_cmd == N: dmpc_transition.
-// path != null (dmpc_transition_scripted): the N - N_cmd vehicles behind the commanded ones follow path[S][N - N_cmd][P][3]; po is then
-// [S][N_cmd][3], and one launch before every step writes their columns of the current table (scripted_cols_kernel).
-// mission != null (dmpc_transition_mission): pf is ignored, the goal sets are mission->goals [S][Q][N_cmd][3], resident for the call; stage 0's go
-// into ctx->pf, and one launch after the verdict of every column (mission_stage_kernel) applies the stage rule there.
-struct Mission {
-    int Q;
-    const double *goals;       // [S][Q][N_cmd][3]
-    const int32_t *deadline;   // [S][Q] or null
-    int32_t *stage_col;        // [S][Q] or null
-};
-// hold != null (dmpc_transition_hold): an agent whose solve failed flies its previous plan, shifted, for up to max_hold consecutive columns
-// (hold_kernel, between the solve and the post step of every column).  The post step is never fused into the solve launch then: the held plan
-// has to be in place before the state advances.  The step's output rows alternate between two sets, so that the previous plan's v and a still
-// stand in the other set after the solve; the previous positions are the agent's column of the table the step read.
-struct Hold {
-    int max_hold;
-    int32_t *hold_count, *hold_first;   // [S][N_cmd] or null
-    int32_t *agent_status;              // [S][N_cmd][K_T_max] or null
-};
-static int transition_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
-                          double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                          int32_t *scene_status, const double *path = nullptr, int P = 0, const Mission *mission = nullptr,
-                          const Hold *hold = nullptr)
+// Batched transitions are bound, MPC step by MPC step, by the slowest agent of the whole batch while most of the GPU idles.  Scenes are independent,
+// so a large batch is run in parts side by side: the tail of one part overlaps the bulk of another (512 transitions of 100 agents, two halves: 103 ->
+// 60 ms).  Launches of fewer than ~2000 agents are one-agent workgroups, which the hardware interleaves across streams freely (persistent launches
+// hold a CU's whole LDS), so many small parts overlap best.  sharded (a DMPC_DEVICE_ALL context): batches of 64 or more scenes as TWO groups -- while
+// one half's ranks exchange their predictions the other half's solve kernels keep the GPUs busy.  want: option split_parts.  Returns every part's first scene, and S.
+static std::vector<int> batch_parts(int S, int want, bool sharded)
 {
-    if (mission) pf = mission->goals;
-    if (!ctx) { g_err = "dmpc_transition: ctx is NULL"; return -1; }
-    if (S < 1 || N < 1 || N_cmd < 1 || N_cmd > N || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status || ((pk || vk || ak) && !(pk && vk && ak)))
-        FAIL(ctx, "dmpc_transition: bad arguments");
-    if (path && (P < 1 || N_cmd >= N)) FAIL(ctx, "dmpc_transition_scripted: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t A = (size_t)S * N_cmd, T = (size_t)S * N;
-    if (ensure_step_scratch(ctx, T, A)) return -1;
-    const size_t hist = A * (size_t)K_T_max * 24;
-    if (ctx->lT2.ensure(T * N3 * 8) || ctx->po.ensure(T * 24) || ctx->hist_p.ensure(hist) || ctx->hist_v.ensure(hist) ||
-        ctx->hist_a.ensure(hist) || ctx->flags.ensure((size_t)K_T_max * S * 8) || ctx->scene_done.ensure((size_t)S * 4))
-        FAIL(ctx, "device allocation failed");
-    hipStream_t st = ctx->stream;
-    double *xp = ctx->xp.as<double>(), *xv = ctx->xv.as<double>(), *xa = ctx->xa.as<double>();
-    const size_t path_bytes = path ? (T - A) * (size_t)P * 24 : 0;
-    if (path) {   // the paths go up once per call
-        if (ctx->path.ensure(path_bytes)) FAIL(ctx, "device allocation failed");
-        HIPCHK(ctx, hipMemcpyAsync(ctx->path.p, path, path_bytes, hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, po, (path ? A : T) * 24, hipMemcpyHostToDevice, st));
-    const int Q = mission ? mission->Q : 1;
-    int *mis_stage = nullptr, *mis_k0 = nullptr, *mis_col = nullptr, *mis_dl = nullptr;
-    if (mission) {   // the goal sets and the deadlines go up once per call; stage = k_start = 0, stage_col = -1
-        const size_t SQ = (size_t)S * Q;
-        if (ctx->pf.ensure(A * 24) || ctx->mis_goals.ensure(SQ * N_cmd * 24) || ctx->mis_state.ensure((2 * (size_t)S + 2 * SQ) * 4)) FAIL(ctx, "device allocation failed");
-        mis_stage = ctx->mis_state.as<int>(); mis_k0 = mis_stage + S; mis_col = mis_k0 + S; mis_dl = mission->deadline ? mis_col + SQ : nullptr;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->mis_goals.p, mission->goals, SQ * N_cmd * 24, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpy2DAsync(ctx->pf.p, (size_t)N_cmd * 24, ctx->mis_goals.p, (size_t)Q * N_cmd * 24, (size_t)N_cmd * 24, (size_t)S, hipMemcpyDeviceToDevice, st));
-        HIPCHK(ctx, hipMemsetAsync(mis_stage, 0, 2 * (size_t)S * 4, st));
-        HIPCHK(ctx, hipMemsetAsync(mis_col, 0xff, SQ * 4, st));
-        if (mis_dl) HIPCHK(ctx, hipMemcpyAsync(mis_dl, mission->deadline, SQ * 4, hipMemcpyHostToDevice, st));
-    } else
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, pf, A * 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(ctx->flags.p, 0, (size_t)K_T_max * S * 8, st));
-    HIPCHK(ctx, hipMemsetAsync(ctx->scene_done.p, 0, (size_t)S * 4, st));
-    HIPCHK(ctx, hipMemsetAsync(ctx->hist_p.p, 0, hist, st));
-    HIPCHK(ctx, hipMemsetAsync(ctx->hist_v.p, 0, hist, st));
-    HIPCHK(ctx, hipMemsetAsync(ctx->hist_a.p, 0, hist, st));
-    // k = 1: initDMPC (dmpc_soft_bound.m:117-121): state = (po, 0, 0), table = straight lines
-    if (N_cmd == N || path) HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
-    else HIPCHK(ctx, hipMemcpy2DAsync(xp, (size_t)N_cmd * 24, ctx->po.p, (size_t)N * 24, (size_t)N_cmd * 24, (size_t)S, hipMemcpyDeviceToDevice, st));   // the commanded agents' starts, packed
-    HIPCHK(ctx, hipMemsetAsync(xv, 0, A * 24, st));
-    HIPCHK(ctx, hipMemsetAsync(xa, 0, A * 24, st));
-    hipLaunchKernelGGL(init_rows_kernel, dim3((unsigned)((A * N3 + 255) / 256)), dim3(256), 0, st, (int)A, ctx->prm.h,
-                       (const double *)(N_cmd == N ? ctx->po.as<double>() : xp), ctx->pf.as<double>(), ctx->rows.as<double>());
-    if (N_cmd == N) {
-        if (dmpc_table_from_rows_device(ctx, S, 1, N, ctx->rows.as<double>(), ctx->lT.as<double>(), st)) return -1;
-    } else {
-        // the commanded columns of the first table from the initDMPC rows; the static columns -- po replicated over the horizon (dmpc.cpp:1633-1649)
-        // -- into BOTH tables of the ping-pong pair, once: the solve kernels write the columns of the agents they solved and nothing else
-        const size_t nc = A * N3, ns = (T - A) * N3;
-        hipLaunchKernelGGL(cmd_cols_from_rows_kernel, dim3((unsigned)((nc + 255) / 256 > 4096 ? 4096 : (nc + 255) / 256)), dim3(256), 0, st, S, N, N_cmd,
-                           (const double *)ctx->rows.as<double>(), ctx->lT.as<double>());
-        if (!path) {   // (scripted vehicles: their columns are written before every step, the first included -- window k = 1 of the first table)
-            hipLaunchKernelGGL(static_cols_kernel, dim3((unsigned)((ns + 255) / 256 > 4096 ? 4096 : (ns + 255) / 256)), dim3(256), 0, st, S, N, N_cmd,
-                               (const double *)ctx->po.as<double>(), ctx->lT.as<double>(), ctx->lT2.as<double>());
-        }
-    }
-    const unsigned rb = (unsigned)((A * 3 + 255) / 256);
-    hipLaunchKernelGGL(record_kernel, dim3(rb), dim3(256), 0, st, S, N_cmd, K_T_max, 0, xp, xv, xa, ctx->hist_p.as<double>(),
-                       ctx->hist_v.as<double>(), ctx->hist_a.as<double>());
-    // ReachedGoal is also evaluated on the initDMPC column (failure_rate.m:125 runs after k = 1 as well)
-    HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->status.p, DMPC_ST_SOLVED, A, st));
-    hipLaunchKernelGGL(scene_reduce_kernel, dim3((unsigned)S), dim3(256), 0, st, N_cmd, error_tol, xp, ctx->pf.as<double>(),
-                       (const int *)ctx->status.as<int32_t>(), ctx->flags.as<int>(), ctx->scene_done.as<int>());
-    const unsigned mis_threads = N_cmd * 3 >= 256 ? 256 : 64;
-    if (mission)   // a first stage that is reached on the initDMPC column ends there
-        hipLaunchKernelGGL(mission_stage_kernel, dim3((unsigned)S), dim3(mis_threads), 0, st, N_cmd, Q, 0, (const double *)ctx->mis_goals.as<double>(),
-                           (const int *)mis_dl, ctx->flags.as<int>(), ctx->scene_done.as<int>(), mis_stage, mis_k0, mis_col, ctx->pf.as<double>());
-    double *cur = ctx->lT.as<double>(), *nxt = ctx->lT2.as<double>();
-    double *outs[2][3] = {{ctx->pout.as<double>(), ctx->vout.as<double>(), ctx->aout.as<double>()},
-                          {ctx->pout.as<double>(), ctx->vout.as<double>(), ctx->aout.as<double>()}};   // (hold: the second set follows)
-    int *hold_run = nullptr, *hold_cnt = nullptr, *hold_1st = nullptr, *hold_log = nullptr;
-    const unsigned hold_blocks = (unsigned)((A + 63) / 64);
-    auto launch_hold = [&](int k, int set) {   // the hold rule on column k; the step wrote outs[set], the previous plan's v, a stand in outs[set ^ 1]
-        hipLaunchKernelGGL(hold_kernel, dim3(hold_blocks), dim3(64), 0, st, (int)A, N_cmd, N, K_T_max, k, hold->max_hold, ctx->prm.h, ctx->prm.alim,
-                           (const double *)cur, nxt, (const double *)outs[set ^ 1][1], (const double *)outs[set ^ 1][2], outs[set][0], outs[set][1],
-                           outs[set][2], ctx->status.as<int>(), (const int *)ctx->scene_done.as<int>(), hold_run, hold_log, hold_cnt, hold_1st);
-    };
-    if (hold) {
-        if (A > 0x7fffffffu) FAIL(ctx, "dmpc_transition_hold: S * N_cmd overflows");
-        const size_t row_bytes = A * N3 * 8;
-        if (ctx->hold_out.ensure(3 * row_bytes) || ctx->hold_state.ensure((3 * A + A * (size_t)K_T_max) * 4)) FAIL(ctx, "device allocation failed");
-        for (int j = 0; j < 3; ++j) outs[0][j] = ctx->hold_out.as<double>() + (size_t)j * A * N3;   // (step k writes set k & 1: the first step the context's own rows)
-        hold_run = ctx->hold_state.as<int>(); hold_cnt = hold_run + A; hold_1st = hold_cnt + A; hold_log = hold_1st + A;
-        HIPCHK(ctx, hipMemsetAsync(outs[0][1], 0, 2 * row_bytes, st));   // the initDMPC plan: v = a = 0 (its positions are the first table)
-        HIPCHK(ctx, hipMemsetAsync(hold_cnt, 0, A * 4, st));
-        HIPCHK(ctx, hipMemsetAsync(hold_1st, 0xff, A * 4, st));
-        HIPCHK(ctx, hipMemsetAsync(hold_log, 0, A * (size_t)K_T_max * 4, st));
-        launch_hold(0, 1);   // column 0: every status is DMPC_ST_SOLVED -- run = 0 and the log's first column, also of a scene that is over already
-    }
-    ctx->post_acc_S = 0;   // the scene accumulators of the fused post-step start from zero in every transition
-    const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;   // the scan of every step reads an fp32 copy of the current table
-    // The host looks at the per-step verdicts every `chunk` MPC steps -- one window BEHIND the steps it enqueues: the verdicts of window c
-    // are copied to pinned host memory behind an event, the steps of window c+1 are enqueued, and only then the host waits for the event
-    // of window c.  The device never idles while the host reads flags (a stream synchronisation per window cost 40-45 us of idle GPU per
-    // 8 steps: 8 % of a single-scene transition); the steps enqueued past the end of a trial are skipped on the device (scene_done), so
-    // what a scene records and reports does not change.
-    const size_t flag_ints = (size_t)K_T_max * S * 2;
-    if (ctx->flags_host_cap < flag_ints) {
-        if (ctx->flags_host) (void)hipHostFree(ctx->flags_host);
-        ctx->flags_host = nullptr; ctx->flags_host_cap = 0;
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->flags_host, flag_ints * 4, hipHostMallocDefault));
-        ctx->flags_host_cap = flag_ints;
-    }
-    int32_t *flags = ctx->flags_host;
-    for (int u = 0; u < 2; ++u)
-        if (!ctx->flag_ev[u]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->flag_ev[u], hipEventDisableTiming));
-    std::vector<int> done(S, 0);
-    for (int s = 0; s < S; ++s) { K_T_used[s] = K_T_max; scene_status[s] = DMPC_ST_SOLVED; }
-    int ndone = 0;
-    const int chunk = 8;
-    int pend_k0 = -1, pend_k1 = -1, pend_ev = 0, nwin = 0;   // the window whose verdicts are in flight to the host
-    auto digest = [&]() -> int {   // wait for the pending window and fold its verdicts into done / K_T_used / scene_status
-        if (pend_k0 < 0) return 0;
-        HIPCHK(ctx, hipEventSynchronize(ctx->flag_ev[pend_ev]));
-        for (int kk = pend_k0; kk <= pend_k1; ++kk)
-            for (int s = 0; s < S; ++s) {
-                if (done[s]) continue;
-                const int32_t reached = flags[((size_t)kk * S + s) * 2], stbits = flags[((size_t)kk * S + s) * 2 + 1];
-                if (stbits & ~DMPC_ST_SOLVED) {   // some agent failed: the reference aborts the trial
-                    done[s] = 1; ndone++; K_T_used[s] = kk + 1; scene_status[s] = stbits;
-                } else if (reached) {             // ReachedGoal.m (failure_rate.m:125)
-                    done[s] = 1; ndone++; K_T_used[s] = kk + 1; scene_status[s] = DMPC_ST_SOLVED | DMPC_ST_REACHED;
-                }
-            }
-        pend_k0 = -1;
-        return 0;
-    };
-    const size_t n_scr = (T - A) * N3;
-    const unsigned scr_blocks = (unsigned)((n_scr + 255) / 256 > 4096 ? 4096 : (n_scr + 255) / 256);
-    for (int k = 1; k < K_T_max && ndone < S; ++k) {
-        if (path)   // the scripted columns of the current table: window k-1 .. k+K-2 of every path (before the fp32 copy, which then covers them)
-            hipLaunchKernelGGL(scripted_cols_kernel, dim3(scr_blocks), dim3(256), 0, st, S, N, N_cmd, P, k, (const double *)ctx->path.as<double>(), cur,
-                               (float *)nullptr);
-        if (mixed && table_f32(ctx, cur, ctx->lTf, T * N3, st)) return -1;   // (all N columns, the static ones included)
-        const PostStep post{K_T_max, k, error_tol, xp, xv, xa, ctx->hist_p.as<double>(), ctx->hist_v.as<double>(), ctx->hist_a.as<double>(),
-                            ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>()};
-        StepIO io;
-        io.lT = cur; io.x_p = xp; io.x_v = xv; io.x_a = xa; io.pf = ctx->pf.as<double>();
-        double **out = outs[k & 1];
-        io.p_out = out[0]; io.v_out = out[1]; io.a_out = out[2]; io.lT_next = nxt;
-        io.status = ctx->status.as<int32_t>();
-        io.scene_done = ctx->scene_done.as<int>(); io.lTf = mixed ? ctx->lTf.as<float>() : nullptr; io.post = hold ? nullptr : &post;
-        const StepShape sh{S, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ 0, /*c_count*/ N_cmd};
-        if (launch_step(ctx, sh, io, st)) return -1;
-        if (hold) launch_hold(k, k & 1);
-        // state advance + history column + scene verdict in one launch (unless the solve kernel did them: tiny launches)
-        if (!ctx->post_fused)
-        hipLaunchKernelGGL(post_step_kernel, dim3((unsigned)S), dim3(N_cmd >= 256 ? 256 : 128), 0, st, N_cmd, K_T_max, k, error_tol,
-                           (const double *)out[0], (const double *)out[1], (const double *)out[2],
-                           (const int *)ctx->status.as<int32_t>(), xp, xv, xa, (const double *)ctx->pf.as<double>(), ctx->hist_p.as<double>(),
-                           ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>(),
-                           (const int *)ctx->scene_done.as<int>());
-        if (mission)   // the stage rule on column k, behind its verdict (post_step_kernel above, or the fused post step of the solve launch)
-            hipLaunchKernelGGL(mission_stage_kernel, dim3((unsigned)S), dim3(mis_threads), 0, st, N_cmd, Q, k, (const double *)ctx->mis_goals.as<double>(),
-                               (const int *)mis_dl, ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>(), mis_stage, mis_k0, mis_col,
-                               ctx->pf.as<double>());
-        HIPCHK(ctx, hipGetLastError());
-        std::swap(cur, nxt);   // l = new_l (dmpc_soft_bound.m:146)
-        if (k % chunk == 0 || k == K_T_max - 1) {
-            if (digest()) return -1;                                         // the window before this one (its steps ran while this one was enqueued)
-            const int k0 = k <= chunk ? 0 : ((k - 1) / chunk) * chunk + 1;   // (the first window includes the initDMPC column)
-            HIPCHK(ctx, hipMemcpyAsync(&flags[(size_t)k0 * S * 2], ctx->flags.as<int>() + (size_t)k0 * S * 2,
-                                       (size_t)(k - k0 + 1) * S * 8, hipMemcpyDeviceToHost, st));
-            pend_ev = nwin++ & 1;
-            HIPCHK(ctx, hipEventRecord(ctx->flag_ev[pend_ev], st));
-            pend_k0 = k0; pend_k1 = k;
-        }
-    }
-    if (digest()) return -1;
-    if (pk) {   // the histories stay resident for dmpc_postcheck either way; the download is optional
-        HIPCHK(ctx, hipMemcpyAsync(pk, ctx->hist_p.p, hist, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(vk, ctx->hist_v.p, hist, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(ak, ctx->hist_a.p, hist, hipMemcpyDeviceToHost, st));
-    }
-    if (mission && mission->stage_col) HIPCHK(ctx, hipMemcpyAsync(mission->stage_col, mis_col, (size_t)S * Q * 4, hipMemcpyDeviceToHost, st));
-    std::vector<int32_t> held(hold ? A : 0);
-    if (hold) {
-        HIPCHK(ctx, hipMemcpyAsync(held.data(), hold_cnt, A * 4, hipMemcpyDeviceToHost, st));
-        if (hold->hold_first) HIPCHK(ctx, hipMemcpyAsync(hold->hold_first, hold_1st, A * 4, hipMemcpyDeviceToHost, st));
-        if (hold->agent_status) HIPCHK(ctx, hipMemcpyAsync(hold->agent_status, hold_log, A * (size_t)K_T_max * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (hold) {   // (every hold the device recorded stands on a column < K_T_used: the steps behind a scene's end skip it)
-        for (int s = 0; s < S; ++s)
-            for (int i = 0; i < N_cmd; ++i)
-                if (held[(size_t)s * N_cmd + i] > 0) { scene_status[s] |= DMPC_ST_HELD; break; }
-        if (hold->hold_count) std::memcpy(hold->hold_count, held.data(), A * 4);
-    }
-    ctx->hist_S = S; ctx->hist_N = N_cmd; ctx->hist_KT = K_T_max;   // (the resident histories are the commanded agents')
-    return 0;
-}
-
-// development options of a context handed to a context it creates for itself (further parts of a split batch, the second group)
-static void copy_debug_options(dmpc_ctx *dst, const dmpc_ctx *src)
-{
-    for (const DevOptionEntry &t : dev_options)
-        if (t.inherited) dst->opt.*(t.member) = src->opt.*(t.member);   // (each member as its own value: grid_min_part too)
-    for (dmpc_ctx *pc : dst->peers) copy_debug_options(pc, src);
-    for (dmpc_ctx *ch : dst->children) copy_debug_options(ch, src);
-}
-
-// Batched transitions are bound, MPC step by MPC step, by the slowest agent of the whole batch while most of the GPU
-// idles.  Scenes are independent, so a large batch is run as two halves on two contexts (= two HIP streams, two host
-// threads): the tail of one half overlaps the bulk of the other (512 transitions of 100 agents: 103 -> 60 ms).
-static int transition_any(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
-                          double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                          int32_t *scene_status, const double *path = nullptr, int P = 0, const Mission *mission = nullptr,
-                          const Hold *hold = nullptr)
-{
-    ctx->split_at.clear();
-    // uncommanded vehicles on a DMPC_DEVICE_ALL context: the first GPU alone (the rule for N < 2 G below); the batch split further down applies unchanged
-    // (a mission too: its first GPU, whether or not every vehicle is commanded)
-    if (ctx->grp && N_cmd == N && !mission) {   // every visible GPU: the agents of each scene sharded over them (dmpc_multigpu.hip)
-        if (S < 1 || N < 1 || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status || ((pk || vk || ak) && !(pk && vk && ak))) FAIL(ctx, "dmpc_transition: bad arguments");
-        // Batches of 64 or more scenes run as TWO groups side by side (a second set of rank contexts, threads and streams on the same
-        // GPUs): scenes are independent, so while one half's ranks exchange their predictions (peer copies, barrier, events) the
-        // other half's solve kernels keep the GPUs busy -- the per-step exchange is off the critical path.
-        const int gparts = ctx->opt.no_split ? 1 : (ctx->opt.split_parts > 0 ? (ctx->opt.split_parts > 2 ? 2 : ctx->opt.split_parts) : (S >= 64 ? 2 : 1));
-        // fewer agents than twice the GPUs (the reference's small swarms on an 8-GPU node): the first GPU alone, as dmpc_step_batch does --
-        // sharding N = 4 agents over 8 GPUs is impossible and over 2-3 of them nothing but barriers and peer copies
-        if (N < 2 * ctx->grp->G) return transition_one(ctx, S, N, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
-        if (gparts < 2) return group_transition(ctx, S, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
-        if (ctx->children.empty()) {
-            const int keep = g_emulate_devices.load();
-            if (ctx->grp_emulated) g_emulate_devices.store(ctx->grp->G);
-            dmpc_ctx *other = dmpc_create(&ctx->prm, DMPC_DEVICE_ALL, ctx->precision);
-            g_emulate_devices.store(keep);
-            if (!other || !other->grp || other->grp->G != ctx->grp->G) { if (other) dmpc_destroy(other); FAIL(ctx, "dmpc_transition: second group: " + g_err); }
-            copy_debug_options(other, ctx);   // (and to its rank contexts)
-            other->opt.no_split = 1;
-            ctx->children.push_back(other);
-        }
-        dmpc_ctx *other = ctx->children[0];
-        if (std::memcmp(&other->prm, &ctx->prm, sizeof(dmpc_params)) != 0 && dmpc_set_params(other, &ctx->prm)) FAIL(ctx, "dmpc_transition: second group: " + other->err);
-        const int S0 = S / 2;
-        const size_t a0 = (size_t)S0 * N, h0 = a0 * (size_t)K_T_max * 3;
-        int rc1 = 0;
-        std::thread th([&]() {
-            rc1 = group_transition(other, S - S0, N, po + a0 * 3, pf + a0 * 3, K_T_max, error_tol, pk ? pk + h0 : nullptr, vk ? vk + h0 : nullptr,
-                                   ak ? ak + h0 : nullptr, K_T_used + S0, scene_status + S0);
-        });
-        const int rc0 = group_transition(ctx, S0, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
-        th.join();
-        (void)hipSetDevice(ctx->device);
-        if (rc1) FAIL(ctx, other->err);
-        if (rc0) return -1;
-        ctx->split_at = {0, S0, S};
-        ctx->hist_S = S;
-        return 0;
-    }
-    // parts: every part runs its own MPC loop on its own stream; launches of fewer than ~2000 agents are one-agent workgroups, which the
-    // hardware interleaves across streams freely (persistent launches hold a CU's whole LDS), so many small parts overlap best
-    int parts = ctx->opt.split_parts > 0 ? ctx->opt.split_parts : (S >= 128 ? 4 : (S >= 32 ? 2 : 1));
-    if (parts > S) parts = S;
-    if (parts < 2 || ctx->opt.no_split || ctx->grp || N < 1 || N_cmd < 1 || N_cmd > N || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status)
-        return transition_one(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, P, mission, hold);
-    while ((int)ctx->children.size() < parts - 1) {
-        dmpc_ctx *ch = dmpc_create(&ctx->prm, ctx->device, ctx->precision);
-        if (!ch) FAIL(ctx, "dmpc_transition: further context: " + g_err);
-        copy_debug_options(ch, ctx);
-        ch->opt.no_split = 1;
-        ctx->children.push_back(ch);
-    }
-    for (int i = 0; i < parts - 1; ++i)
-        if (std::memcmp(&ctx->children[(size_t)i]->prm, &ctx->prm, sizeof(dmpc_params)) != 0 && dmpc_set_params(ctx->children[(size_t)i], &ctx->prm))
-            FAIL(ctx, "dmpc_transition: further context: " + ctx->children[(size_t)i]->err);
+    const int parts = sharded ? (want > 0 ? std::min(want, 2) : (S >= 64 ? 2 : 1)) : std::min(S, want > 0 ? want : (S >= 128 ? 4 : (S >= 32 ? 2 : 1)));
     std::vector<int> at((size_t)parts + 1);
     for (int i = 0; i <= parts; ++i) at[(size_t)i] = (int)((long)S * i / parts);
-    std::vector<int> rc((size_t)parts, 0);
-    auto run = [&](int i) {
-        dmpc_ctx *c = i ? ctx->children[(size_t)i - 1] : ctx;
-        const int s0 = at[(size_t)i], sn = at[(size_t)i + 1] - s0;
-        const size_t a0 = (size_t)s0 * N_cmd, h0 = a0 * (size_t)K_T_max * 3;   // po is strided by N, everything else by N_cmd ...
-        const size_t t0 = path ? a0 : (size_t)s0 * N;                          // ... (scripted vehicles: po covers the commanded agents, and each part gets its scenes' paths)
-        Mission part{};   // a mission: the part's scenes' slices of the goal sets, the deadlines and stage_col
-        if (mission) {
-            const size_t q0 = (size_t)s0 * mission->Q;
-            part = Mission{mission->Q, mission->goals + q0 * N_cmd * 3, mission->deadline ? mission->deadline + q0 : nullptr,
-                           mission->stage_col ? mission->stage_col + q0 : nullptr};
-        }
-        Hold hpart{};     // hold: the part's scenes' slices of the three per-agent arrays
-        if (hold)
-            hpart = Hold{hold->max_hold, hold->hold_count ? hold->hold_count + a0 : nullptr, hold->hold_first ? hold->hold_first + a0 : nullptr,
-                         hold->agent_status ? hold->agent_status + a0 * (size_t)K_T_max : nullptr};
-        rc[(size_t)i] = transition_one(c, sn, N, N_cmd, po + t0 * 3, pf + a0 * 3, K_T_max, error_tol, pk ? pk + h0 : nullptr, vk ? vk + h0 : nullptr,
-                                       ak ? ak + h0 : nullptr, K_T_used + s0, scene_status + s0, path ? path + (size_t)s0 * (N - N_cmd) * P * 3 : nullptr, P,
-                                       mission ? &part : nullptr, hold ? &hpart : nullptr);
-    };
-    std::vector<std::thread> th;
-    for (int i = 1; i < parts; ++i) th.emplace_back(run, i);
-    run(0);
-    for (auto &t : th) t.join();
-    for (int i = 1; i < parts; ++i)
-        if (rc[(size_t)i]) FAIL(ctx, ctx->children[(size_t)i - 1]->err);
-    if (rc[0]) return -1;
-    ctx->split_at = at;   // the resident histories are split over the contexts (dmpc_postcheck knows)
-    ctx->hist_S = S;
-    return 0;
+    return at;
 }
 
-extern "C" int dmpc_transition(dmpc_ctx *ctx, int S, int N, const double *po, const double *pf, int K_T_max,
-                               double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                               int32_t *scene_status)
-{
-    if (!ctx) { g_err = "dmpc_transition: ctx is NULL"; return -1; }
-    return transition_any(ctx, S, N, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
-}
-
-// DMPC::solveParallelDMPCv2 (dmpc.cpp:1570-1730) with N_cmd = _pf.cols() < N = _po.cols(): the uncommanded vehicles are static columns of the table
-extern "C" int dmpc_transition_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *po, const double *pf, int K_T_max,
-                                   double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                                   int32_t *scene_status)
-{
-    if (!ctx) { g_err = "dmpc_transition_cmd: ctx is NULL"; return -1; }
-    if (check_cmd(ctx, "dmpc_transition_cmd", S, N, N_cmd)) return -1;
-    if (K_T_max < 2 || !po || !pf || !K_T_used || !scene_status || ((pk || vk || ak) && !(pk && vk && ak))) FAIL(ctx, "dmpc_transition_cmd: bad arguments");
-    return transition_any(ctx, S, N, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status);
-}
-
-// Scripted vehicles: the uncommanded vehicles of dmpc_transition_cmd MOVE along paths the caller knows.  No reference counterpart
-// (DMPC::solveParallelDMPCv2 freezes uncommanded vehicles, dmpc.cpp:1633-1649); a commanded agent sees such a column as it sees any neighbour.
-static int check_scripted(dmpc_ctx *ctx, const char *entry, int S, int N_cmd, int M, int P)
-{
-    if (S < 1) FAIL(ctx, std::string(entry) + ": S must be >= 1");
-    if (N_cmd < 1) FAIL(ctx, std::string(entry) + ": N_cmd must be >= 1 (commanded agents first, scripted vehicles behind them)");
-    if (M < 1) FAIL(ctx, std::string(entry) + ": M must be >= 1 (no scripted vehicle: use the entry without them)");
-    if (P < 1) FAIL(ctx, std::string(entry) + ": P must be >= 1 (every path has at least its start)");
-    if ((long)N_cmd + M > 0x7fffffffL) FAIL(ctx, std::string(entry) + ": N_cmd + M overflows");
-    return 0;
-}
-
-extern "C" int dmpc_transition_scripted(dmpc_ctx *ctx, int S, int N_cmd, int M, int P, const double *po, const double *pf, const double *path,
-                                        int K_T_max, double error_tol, double *pk, double *vk, double *ak, int32_t *K_T_used,
-                                        int32_t *scene_status)
-{
-    if (!ctx) { g_err = "dmpc_transition_scripted: ctx is NULL"; return -1; }
-    if (check_scripted(ctx, "dmpc_transition_scripted", S, N_cmd, M, P)) return -1;
-    if (!path) FAIL(ctx, "dmpc_transition_scripted: path is NULL");
-    if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, "dmpc_transition_scripted: pk, vk, ak must be all given or all NULL");
-    if (K_T_max < 2 || !po || !pf || !K_T_used || !scene_status) FAIL(ctx, "dmpc_transition_scripted: bad arguments");
-    // (a DMPC_DEVICE_ALL context: N_cmd < N, its first GPU)
-    return transition_any(ctx, S, N_cmd + M, N_cmd, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, P);
-}
-
-// Missions: a transition through a sequence of goal sets.  No reference counterpart (the reference flies one leg); the step is the
-// reference's, the stage rule the loop a caller of dmpc_step_batch[_cmd] could write on the host -- applied on the device after the verdict of
-// every column (mission_stage_kernel), so that the host keeps reading the verdicts one window behind.
-// the shared argument check of dmpc_transition_mission and dmpc_transition_hold
-static int check_mission(dmpc_ctx *ctx, const std::string &who, int S, int N, int N_cmd, int Q, const double *po, const double *goals, const int32_t *deadline,
-                         const double *path, int P, int K_T_max, const double *pk, const double *vk, const double *ak, const int32_t *K_T_used,
-                         const int32_t *scene_status)
-{
-    if (check_cmd(ctx, who.c_str(), S, N, N_cmd)) return -1;
-    if (Q < 1) FAIL(ctx, who + ": Q must be >= 1 (a mission has at least one stage)");
-    if (!goals) FAIL(ctx, who + ": goals is NULL");
-    if (path && check_scripted(ctx, who.c_str(), S, N_cmd, N - N_cmd, P)) return -1;
-    if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, who + ": pk, vk, ak must be all given or all NULL");
-    if (K_T_max < 2 || !po || !K_T_used || !scene_status) FAIL(ctx, who + ": bad arguments");
-    if ((size_t)S * (size_t)Q > 0x7fffffffu) FAIL(ctx, who + ": S * Q overflows");
-    if (deadline)
-        for (int s = 0; s < S; ++s) {
-            for (int q = 0; q < Q; ++q)
-                if (deadline[(size_t)s * Q + q] < 0) FAIL(ctx, who + ": a deadline is negative (0: none)");
-            if (deadline[(size_t)s * Q + Q - 1] != 0) FAIL(ctx, who + ": the last stage's deadline must be 0 (the last stage ends the trial when it is reached)");
-        }
-    return 0;
-}
-
-extern "C" int dmpc_transition_mission(dmpc_ctx *ctx, int S, int N, int N_cmd, int Q, const double *po, const double *goals, const int32_t *deadline,
-                                       const double *path, int P, int K_T_max, double error_tol, double *pk, double *vk, double *ak,
-                                       int32_t *K_T_used, int32_t *scene_status, int32_t *stage_col)
-{
-    if (!ctx) { g_err = "dmpc_transition_mission: ctx is NULL"; return -1; }
-    if (check_mission(ctx, "dmpc_transition_mission", S, N, N_cmd, Q, po, goals, deadline, path, P, K_T_max, pk, vk, ak, K_T_used, scene_status)) return -1;
-    const Mission mission{Q, goals, deadline, stage_col};
-    // (a DMPC_DEVICE_ALL context: its first GPU)
-    return transition_any(ctx, S, N, N_cmd, po, goals, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, path ? P : 0, &mission);
-}
-
-// Hold policy: dmpc_transition_mission in which an agent whose solve failed flies its previous plan while the scene goes on.  No reference
-// counterpart (the reference's failure-rate experiment stops the trial); the rule is in include/dmpc_hip.h, the device side is hold_kernel.
-extern "C" int dmpc_transition_hold(dmpc_ctx *ctx, int S, int N, int N_cmd, int Q, const double *po, const double *goals, const int32_t *deadline,
-                                    const double *path, int P, int K_T_max, double error_tol, int max_hold, double *pk, double *vk, double *ak,
-                                    int32_t *K_T_used, int32_t *scene_status, int32_t *stage_col, int32_t *hold_count, int32_t *hold_first,
-                                    int32_t *agent_status)
-{
-    if (!ctx) { g_err = "dmpc_transition_hold: ctx is NULL"; return -1; }
-    if (check_mission(ctx, "dmpc_transition_hold", S, N, N_cmd, Q, po, goals, deadline, path, P, K_T_max, pk, vk, ak, K_T_used, scene_status)) return -1;
-    if (max_hold < 0) FAIL(ctx, "dmpc_transition_hold: max_hold must be >= 0 (0: no agent is ever held, dmpc_transition_mission)");
-    const Mission mission{Q, goals, deadline, stage_col};
-    const Hold hold{max_hold, hold_count, hold_first, agent_status};
-    // (a DMPC_DEVICE_ALL context: its first GPU)
-    return transition_any(ctx, S, N, N_cmd, po, goals, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, path ? P : 0, &mission, &hold);
-}
-
-// the fill of dmpc_transition_scripted for callers that loop over dmpc_step_device_cmd themselves
-extern "C" int dmpc_scripted_cols_device(dmpc_ctx *ctx, int S, int N, int N_cmd, int P, const double *path_dev, int k, double *lT, float *lTf,
-                                         void *stream)
-{
-    if (!ctx) { g_err = "dmpc_scripted_cols_device: ctx is NULL"; return -1; }
-    if (check_cmd(ctx, "dmpc_scripted_cols_device", S, N, N_cmd)) return -1;
-    if (check_scripted(ctx, "dmpc_scripted_cols_device", S, N_cmd, N - N_cmd, P)) return -1;
-    if (k < 1) FAIL(ctx, "dmpc_scripted_cols_device: k must be >= 1 (the MPC step that produces history column k)");
-    if (!path_dev || !lT) FAIL(ctx, "dmpc_scripted_cols_device: NULL pointer");
-    if (ctx->grp) FAIL(ctx, "dmpc_scripted_cols_device: device pointers belong to ONE GPU; a DMPC_DEVICE_ALL context drives several (use the host-pointer entry points)");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)S * (N - N_cmd) * N3;
-    hipLaunchKernelGGL(scripted_cols_kernel, dim3((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, S, N,
-                       N_cmd, P, k, path_dev, lT, lTf);
-    HIPCHK(ctx, hipGetLastError());
-    return 0;
-}
+#include "dmpc_transition.hip"   // the closed loop: the record of a call, transition_one, transition_any, the five entries
 
 // What every post-check starts with (failure_rate.m:136-162): the histories on the device (uploaded, or the resident ones copied), r_factor,
 // h_scaled and the sample count of every scene, the rescaled knots and their spline.  `who`: the entry's name in the messages; pf may be NULL.

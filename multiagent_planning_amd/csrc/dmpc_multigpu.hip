@@ -291,19 +291,17 @@ static int gather_histories(dmpc_ctx *ctx, int S, int N, int KT)
     DevBuf *own[3] = {&ctx->hist_p, &ctx->hist_v, &ctx->hist_a}, *dstb[3] = {&ctx->full_p, &ctx->full_v, &ctx->full_a};
     if (ctx->grp) {
         GroupShared *sh = ctx->grp;
-        dmpc_ctx *root = nullptr;
         // rank 0 allocates, publishes; everybody writes its slab (a kernel storing through the peer mapping, or a staged copy)
         if (rank == 0) {
             for (int u = 0; u < 3; ++u) if (dstb[u]->ensure(full)) { sh->abort.store(1); FAIL(ctx, "device allocation failed (gathered histories)"); }
             sh->hist_dst[0] = ctx->full_p.as<double>(); sh->hist_dst[1] = ctx->full_v.as<double>(); sh->hist_dst[2] = ctx->full_a.as<double>();
         }
-        (void)root;
         if (!sh->wait()) FAIL(ctx, "group gather: another rank failed");
         const bool same = sh->dev[0] == ctx->device;
         int can = 1;
         if (!same && hipDeviceCanAccessPeer(&can, ctx->device, sh->dev[0]) != hipSuccess) can = 0;
         const size_t total = (size_t)S * cnt * per;
-        const unsigned blocks = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+        const unsigned blocks = grid_1d(total, 8192);
         for (int u = 0; u < 3; ++u) {
             if (same || can)
                 hipLaunchKernelGGL(mg::hist_place_kernel, dim3(blocks), dim3(256), 0, st, S, N, KT, (int)lo, (int)cnt, (int)cnt, (const double *)own[u]->p, sh->hist_dst[u]);
@@ -326,16 +324,14 @@ static int gather_histories(dmpc_ctx *ctx, int S, int N, int KT)
     if (ctx->gath.ensure((size_t)G * slab * 8) || ctx->sendbuf.ensure(slab * 8)) FAIL(ctx, "device allocation failed (gathered histories)");
     for (int u = 0; u < 3; ++u) {
         if (dstb[u]->ensure(full)) FAIL(ctx, "device allocation failed (gathered histories)");
-        const unsigned blocks = (unsigned)((slab + 255) / 256 > 8192 ? 8192 : (slab + 255) / 256);
-        hipLaunchKernelGGL(mg::hist_pad_kernel, dim3(blocks), dim3(256), 0, st, S, KT, (int)cnt, (int)cmax, (const double *)own[u]->p, ctx->sendbuf.as<double>());
+        hipLaunchKernelGGL(mg::hist_pad_kernel, dim3(grid_1d(slab, 8192)), dim3(256), 0, st, S, KT, (int)cnt, (int)cmax, (const double *)own[u]->p, ctx->sendbuf.as<double>());
         const int rc = a->AllGather(ctx->sendbuf.p, ctx->gath.p, slab, mg::kDouble, (mg::Comm)ctx->comm, st);
         if (rc) FAIL(ctx, std::string("ncclAllGather (histories): ") + a->GetErrorString(rc));
         for (int g = 0; g < G; ++g) {
             int32_t glo = 0, gcnt = 0;
             (void)dmpc_partition(N, G, g, &glo, &gcnt, nullptr);
             const size_t tot = (size_t)S * gcnt * per;
-            const unsigned bl = (unsigned)((tot + 255) / 256 > 8192 ? 8192 : (tot + 255) / 256);
-            hipLaunchKernelGGL(mg::hist_place_kernel, dim3(bl), dim3(256), 0, st, S, N, KT, (int)glo, (int)gcnt, (int)cmax,
+            hipLaunchKernelGGL(mg::hist_place_kernel, dim3(grid_1d(tot, 8192)), dim3(256), 0, st, S, N, KT, (int)glo, (int)gcnt, (int)cmax,
                                (const double *)(ctx->gath.as<double>() + (size_t)g * slab), dstb[u]->as<double>());
         }
     }
@@ -348,20 +344,15 @@ static int gather_histories(dmpc_ctx *ctx, int S, int N, int KT)
 
 // the whole transition of S scenes for THIS rank's agents (see the header); gather != 0: the scene-wide histories are assembled
 // afterwards (gather_histories: the input of dmpc_postcheck)
-static int transition_sharded_impl(dmpc_ctx *ctx, int S, int N, const double *po, const double *pf, int K_T_max, double error_tol,
-                                   double *pk, double *vk, double *ak, int32_t *K_T_used, int32_t *scene_status, int gather)
+static int transition_sharded_impl(dmpc_ctx *ctx, const TransitionCall &c, int gather)
 {
-    if (!ctx) { g_err = "dmpc_transition_sharded: ctx is NULL"; return -1; }
-    const int G = ctx->nranks, rank = ctx->rank;
+    const int S = c.S, N = c.N, K_T_max = c.K_T_max, G = ctx->nranks, rank = ctx->rank;
     int32_t lo = 0, cnt = 0, cmax = 0;
-    if (S < 1 || K_T_max < 2 || !po || !pf || !K_T_used || !scene_status || ((pk || vk || ak) && !(pk && vk && ak)) ||
-        dmpc_partition(N, G, rank, &lo, &cnt, &cmax))
-        FAIL(ctx, "dmpc_transition_sharded: bad arguments");
+    if (dmpc_partition(N, G, rank, &lo, &cnt, &cmax)) FAIL(ctx, "dmpc_transition_sharded: bad arguments");   // (more ranks than agents)
     if (G > 1 && !ctx->comm && !ctx->grp && !ctx->debug_rank) FAIL(ctx, "dmpc_transition_sharded: no communicator");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;
-    const size_t A = (size_t)S * N, Aown = (size_t)S * cnt, tab = (size_t)G * S * N3 * cmax, chunk = (size_t)S * N3 * cmax;
-    const size_t hist = Aown * (size_t)K_T_max * 24;
+    const size_t A = (size_t)S * N, Aown = (size_t)S * cnt, tab = (size_t)G * S * N3 * cmax, chunk = (size_t)S * N3 * cmax, hist = Aown * (size_t)K_T_max * 24;
     if (ensure_step_scratch(ctx, A, Aown)) return -1;
     if (ctx->lT.ensure(tab * 8) || ctx->lT2.ensure(tab * 8) || ctx->po.ensure(A * 24) || ctx->mg_pf.ensure(A * 24) || ctx->sendbuf.ensure(chunk * 8) ||
         ctx->hist_p.ensure(hist) || ctx->hist_v.ensure(hist) || ctx->hist_a.ensure(hist) || ctx->flags.ensure((size_t)K_T_max * S * 8) ||
@@ -370,13 +361,9 @@ static int transition_sharded_impl(dmpc_ctx *ctx, int S, int N, const double *po
         FAIL(ctx, "device allocation failed");
     hipStream_t st = ctx->stream;
     double *xp = ctx->xp.as<double>(), *xv = ctx->xv.as<double>(), *xa = ctx->xa.as<double>(), *own_pf = ctx->pf.as<double>();
-    HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, po, A * 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->mg_pf.p, pf, A * 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(ctx->flags.p, 0, (size_t)K_T_max * S * 8, st));
-    HIPCHK(ctx, hipMemsetAsync(ctx->scene_done.p, 0, (size_t)S * 4, st));
-    HIPCHK(ctx, hipMemsetAsync(ctx->hist_p.p, 0, hist, st));
-    HIPCHK(ctx, hipMemsetAsync(ctx->hist_v.p, 0, hist, st));
-    HIPCHK(ctx, hipMemsetAsync(ctx->hist_a.p, 0, hist, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, c.po, A * 24, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->mg_pf.p, c.pf, A * 24, hipMemcpyHostToDevice, st));
+    if (reset_run_buffers(ctx, S, K_T_max, hist, st)) return -1;
     HIPCHK(ctx, hipMemsetAsync(ctx->sendbuf.p, 0, chunk * 8, st));
     HIPCHK(ctx, hipMemsetAsync(ctx->mg_fall.p, 0, (size_t)G * S * 16, st));
     // group transport: the peers PUSH their verdict flags into this rank's mg_fall right after the first barrier, on their own streams --
@@ -386,24 +373,18 @@ static int transition_sharded_impl(dmpc_ctx *ctx, int S, int N, const double *po
     hipLaunchKernelGGL(init_rows_kernel, dim3((unsigned)((A * N3 + 255) / 256)), dim3(256), 0, st, (int)A, ctx->prm.h, ctx->po.as<double>(),
                        ctx->mg_pf.as<double>(), ctx->rows.as<double>());
     const int rem = N % G;
-    {
-        const unsigned blocks = (unsigned)((tab + 255) / 256 > 4096 ? 4096 : (tab + 255) / 256);
-        hipLaunchKernelGGL(mg::table_from_rows_padded_kernel, dim3(blocks), dim3(256), 0, st, S, N, G, (int)cmax, rem, (const double *)ctx->rows.as<double>(),
-                           ctx->lT.as<double>());
-    }
+    hipLaunchKernelGGL(mg::table_from_rows_padded_kernel, dim3(grid_1d(tab, 4096)), dim3(256), 0, st, S, N, G, (int)cmax, rem,
+                       (const double *)ctx->rows.as<double>(), ctx->lT.as<double>());
     const unsigned sb = (unsigned)((Aown * 3 + 255) / 256);
     hipLaunchKernelGGL(mg::slice_agents_kernel, dim3(sb), dim3(256), 0, st, S, N, (int)lo, (int)cnt, (const double *)ctx->po.as<double>(), xp);
     hipLaunchKernelGGL(mg::slice_agents_kernel, dim3(sb), dim3(256), 0, st, S, N, (int)lo, (int)cnt, (const double *)ctx->mg_pf.as<double>(), own_pf);
-    HIPCHK(ctx, hipMemsetAsync(xv, 0, Aown * 24, st));
-    HIPCHK(ctx, hipMemsetAsync(xa, 0, Aown * 24, st));
-    hipLaunchKernelGGL(record_kernel, dim3(sb), dim3(256), 0, st, S, (int)cnt, K_T_max, 0, xp, xv, xa, ctx->hist_p.as<double>(),
-                       ctx->hist_v.as<double>(), ctx->hist_a.as<double>());
+    for (double *x : {xv, xa}) HIPCHK(ctx, hipMemsetAsync(x, 0, Aown * 24, st));
+    hipLaunchKernelGGL(record_kernel, dim3(sb), dim3(256), 0, st, S, (int)cnt, K_T_max, 0, xp, xv, xa, ctx->hist_p.as<double>(), ctx->hist_v.as<double>(), ctx->hist_a.as<double>());
     // Mixed precision: the TABLE of the transition is fp32 -- the scan reads it, and what the ranks exchange per step is the fp32
     // chunk (half the payload); each rank keeps the fp64 predictions of its OWN chunk beside it (the solve's fallback for agents
     // that were not solved).  fp64: the table is the fp64 one and so is the payload.
-    double *cur = ctx->lT.as<double>(), *nxt = ctx->lT2.as<double>();
+    double *cur = ctx->lT.as<double>(), *nxt = ctx->lT2.as<double>(), *own_cur = ctx->own64.as<double>();
     float *curf = ctx->lTf.as<float>(), *nxtf = ctx->lTf2.as<float>();
-    double *own_cur = ctx->own64.as<double>();
     if (mixed) {
         if (table_f32(ctx, cur, ctx->lTf, tab, st)) return -1;
         curf = ctx->lTf.as<float>();
@@ -416,28 +397,22 @@ static int transition_sharded_impl(dmpc_ctx *ctx, int S, int N, const double *po
     auto publish = [&](const int *floc) -> int {   // this step's predictions (ctx->sendbuf, fp64) into everybody's next table
         fall = ctx->mg_fall.as<int>() + (ctx->grp ? (size_t)(ctx->grp_steps & 1) * G * S * 2 : 0);
         if (!mixed) return exchange(ctx, ctx->sendbuf.p, nxt, chunk, 8, floc, fall, S * 2, st);
-        const unsigned bl = (unsigned)((chunk + 255) / 256 > 4096 ? 4096 : (chunk + 255) / 256);
-        hipLaunchKernelGGL(mg::chunk_to_f32_kernel, dim3(bl), dim3(256), 0, st, chunk, (const double *)ctx->sendbuf.as<double>(), ctx->sendbuf32.as<float>());
+        hipLaunchKernelGGL(mg::chunk_to_f32_kernel, dim3(grid_1d(chunk, 4096)), dim3(256), 0, st, chunk, (const double *)ctx->sendbuf.as<double>(), ctx->sendbuf32.as<float>());
         return exchange(ctx, ctx->sendbuf32.p, nxtf, chunk, 4, floc, fall, S * 2, st);
     };
     // ReachedGoal on the initDMPC column (as dmpc_transition): own verdicts, exchanged with a throw-away table exchange
     HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->status.p, DMPC_ST_SOLVED, Aown, st));
-    hipLaunchKernelGGL(scene_reduce_kernel, dim3((unsigned)S), dim3(256), 0, st, (int)cnt, error_tol, xp, own_pf, (const int *)ctx->status.as<int32_t>(),
+    hipLaunchKernelGGL(scene_reduce_kernel, dim3((unsigned)S), dim3(256), 0, st, (int)cnt, c.error_tol, xp, own_pf, (const int *)ctx->status.as<int32_t>(),
                        ctx->mg_floc.as<int>(), (int *)nullptr);
     if (publish(ctx->mg_floc.as<int>())) return -1;
-    hipLaunchKernelGGL(mg::combine_flags_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, G, S, (const int *)fall,
-                       ctx->flags.as<int>(), ctx->scene_done.as<int>());
+    hipLaunchKernelGGL(mg::combine_flags_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, G, S, (const int *)fall, ctx->flags.as<int>(), ctx->scene_done.as<int>());
     std::vector<int32_t> flags((size_t)K_T_max * S * 2, 0);
-    std::vector<int> done(S, 0);
-    for (int s = 0; s < S; ++s) { K_T_used[s] = K_T_max; scene_status[s] = DMPC_ST_SOLVED; }
-    int ndone = 0;
-    const int chunk_steps = 8;   // the host looks at the per-step verdicts every 8 MPC steps
-    for (int k = 1; k < K_T_max && ndone < S; ++k) {
+    VerdictFold verdict; verdict.init(c);
+    for (int k = 1; k < K_T_max && verdict.ndone < S; ++k) {
         StepIO io;
         io.lT = cur; io.x_p = xp; io.x_v = xv; io.x_a = xa; io.pf = own_pf;
         io.p_out = ctx->pout.as<double>(); io.v_out = ctx->vout.as<double>(); io.a_out = ctx->aout.as<double>(); io.lT_next = ctx->sendbuf.as<double>();
-        io.status = ctx->status.as<int32_t>();
-        io.scene_done = ctx->scene_done.as<int>(); io.short_from = rem; io.lTf = mixed ? curf : nullptr; io.own_prev = mixed ? own_cur : nullptr;
+        io.status = ctx->status.as<int32_t>(); io.scene_done = ctx->scene_done.as<int>(); io.short_from = rem; io.lTf = mixed ? curf : nullptr; io.own_prev = mixed ? own_cur : nullptr;
         const StepShape sh{S, G, /*C*/ cmax, /*g_local*/ rank, /*c_first*/ 0, /*c_count*/ cnt};
         if (launch_step(ctx, sh, io, st)) {
             // a rank that cannot take its step must not leave the others waiting in the exchange: the group's barriers are released by
@@ -448,7 +423,7 @@ static int transition_sharded_impl(dmpc_ctx *ctx, int S, int N, const double *po
         }
         // state advance + history column + this rank's verdict per scene (all own agents at their goals / OR of their status
         // bits) in one launch, then the exchange: predictions into the next table, verdicts of all ranks next to them
-        hipLaunchKernelGGL(post_step_kernel, dim3((unsigned)S), dim3(cnt >= 256 ? 256 : 128), 0, st, (int)cnt, K_T_max, k, error_tol,
+        hipLaunchKernelGGL(post_step_kernel, dim3((unsigned)S), dim3(cnt >= 256 ? 256 : 128), 0, st, (int)cnt, K_T_max, k, c.error_tol,
                            (const double *)ctx->pout.as<double>(), (const double *)ctx->vout.as<double>(), (const double *)ctx->aout.as<double>(),
                            (const int *)ctx->status.as<int32_t>(), xp, xv, xa, (const double *)own_pf, ctx->hist_p.as<double>(), ctx->hist_v.as<double>(),
                            ctx->hist_a.as<double>(), ctx->mg_floc.as<int>(), (int *)nullptr, (const int *)ctx->scene_done.as<int>());
@@ -459,36 +434,32 @@ static int transition_sharded_impl(dmpc_ctx *ctx, int S, int N, const double *po
                            ctx->flags.as<int>() + (size_t)k * S * 2, ctx->scene_done.as<int>());
         std::swap(cur, nxt);   // l = new_l (dmpc_soft_bound.m:146)
         std::swap(curf, nxtf);
-        if (k % chunk_steps == 0 || k == K_T_max - 1) {
-            const int k0 = k <= chunk_steps ? 0 : ((k - 1) / chunk_steps) * chunk_steps + 1;
-            HIPCHK(ctx, hipMemcpyAsync(&flags[(size_t)k0 * S * 2], ctx->flags.as<int>() + (size_t)k0 * S * 2, (size_t)(k - k0 + 1) * S * 8,
-                                       hipMemcpyDeviceToHost, st));
+        if (VerdictFold::window_ends(k, K_T_max)) {   // the host looks at the verdicts of a window once its steps have run
+            const int k0 = VerdictFold::window_start(k);
+            HIPCHK(ctx, hipMemcpyAsync(&flags[(size_t)k0 * S * 2], ctx->flags.as<int>() + (size_t)k0 * S * 2, (size_t)(k - k0 + 1) * S * 8, hipMemcpyDeviceToHost, st));
             HIPCHK(ctx, hipStreamSynchronize(st));
-            for (int kk = k0; kk <= k; ++kk)
-                for (int s = 0; s < S; ++s) {
-                    if (done[s]) continue;
-                    const int32_t reached = flags[((size_t)kk * S + s) * 2], stbits = flags[((size_t)kk * S + s) * 2 + 1];
-                    if (stbits & ~DMPC_ST_SOLVED) { done[s] = 1; ndone++; K_T_used[s] = kk + 1; scene_status[s] = stbits; }   // the same rule as dmpc_transition
-                    else if (reached) { done[s] = 1; ndone++; K_T_used[s] = kk + 1; scene_status[s] = DMPC_ST_SOLVED | DMPC_ST_REACHED; }
-                }
+            verdict.fold(flags.data(), k0, k);
         }
     }
-    if (pk) {
-        HIPCHK(ctx, hipMemcpyAsync(pk, ctx->hist_p.p, hist, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(vk, ctx->hist_v.p, hist, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(ak, ctx->hist_a.p, hist, hipMemcpyDeviceToHost, st));
-    }
+    if (download_histories(ctx, c, hist, st)) return -1;
     HIPCHK(ctx, hipStreamSynchronize(st));
     ctx->hist_S = 0;   // the resident histories hold only this rank's agents: not a dmpc_postcheck input ...
     if (gather) return gather_histories(ctx, S, N, K_T_max);   // ... unless they are assembled
     return 0;
 }
 
+// the two entries: `who` is refused on a DMPC_DEVICE_ALL context, the common check speaks as dmpc_transition_sharded for both
+static int transition_sharded_entry(dmpc_ctx *ctx, const char *who, const TransitionCall &c, int gather)
+{
+    if (ctx && ctx->grp) FAIL(ctx, std::string(who) + ": a DMPC_DEVICE_ALL context shards by itself (call dmpc_transition)");
+    if (!ctx) { g_err = "dmpc_transition_sharded: ctx is NULL"; return -1; }
+    return check_call(ctx, "dmpc_transition_sharded", c) ? -1 : transition_sharded_impl(ctx, c, gather);
+}
+
 extern "C" int dmpc_transition_sharded(dmpc_ctx *ctx, int S, int N, const double *po, const double *pf, int K_T_max, double error_tol,
                                        double *pk, double *vk, double *ak, int32_t *K_T_used, int32_t *scene_status)
 {
-    if (ctx && ctx->grp) FAIL(ctx, "dmpc_transition_sharded: a DMPC_DEVICE_ALL context shards by itself (call dmpc_transition)");
-    return transition_sharded_impl(ctx, S, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, 0);
+    return transition_sharded_entry(ctx, "dmpc_transition_sharded", {S, N, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status}, 0);
 }
 
 // same, and afterwards every rank assembles the scene-wide histories on its device (one all-gather per array): dmpc_postcheck with
@@ -496,8 +467,7 @@ extern "C" int dmpc_transition_sharded(dmpc_ctx *ctx, int S, int N, const double
 extern "C" int dmpc_transition_sharded_gather(dmpc_ctx *ctx, int S, int N, const double *po, const double *pf, int K_T_max, double error_tol,
                                               double *pk, double *vk, double *ak, int32_t *K_T_used, int32_t *scene_status)
 {
-    if (ctx && ctx->grp) FAIL(ctx, "dmpc_transition_sharded_gather: a DMPC_DEVICE_ALL context shards by itself (call dmpc_transition)");
-    return transition_sharded_impl(ctx, S, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, 1);
+    return transition_sharded_entry(ctx, "dmpc_transition_sharded_gather", {S, N, N, po, pf, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status}, 1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -528,23 +498,21 @@ static int group_run(dmpc_ctx *root, F &&body)
     return rc[0] ? -1 : 0;
 }
 
-static int group_transition(dmpc_ctx *root, int S, int N, const double *po, const double *pf, int K_T_max, double error_tol, double *pk,
-                            double *vk, double *ak, int32_t *K_T_used, int32_t *scene_status)
+static int group_transition(dmpc_ctx *root, const TransitionCall &c)
 {
     const int G = root->grp->G;
-    if (G > N) FAIL(root, "dmpc_transition: more GPUs than agents");
-    std::vector<std::vector<int32_t>> used((size_t)G, std::vector<int32_t>((size_t)S)), sst((size_t)G, std::vector<int32_t>((size_t)S));
-    const int rc = group_run(root, [&](dmpc_ctx *c, int r) -> int {
-        return transition_sharded_impl(c, S, N, po, pf, K_T_max, error_tol, nullptr, nullptr, nullptr, r ? used[(size_t)r].data() : K_T_used,
-                                       r ? sst[(size_t)r].data() : scene_status, 1);
+    if (G > c.N) FAIL(root, "dmpc_transition: more GPUs than agents");
+    if (c.S < 1) FAIL(root, "dmpc_transition_sharded: bad arguments");   // (the empty half of one scene split in two: split_parts = 2)
+    std::vector<std::vector<int32_t>> used((size_t)G, std::vector<int32_t>((size_t)c.S)), sst((size_t)G, std::vector<int32_t>((size_t)c.S));
+    const int rc = group_run(root, [&](dmpc_ctx *rank_ctx, int r) -> int {   // rank 0 reports the verdicts; the histories come from its gathered ones
+        TransitionCall own = c; own.pk = own.vk = own.ak = nullptr;
+        if (r) { own.K_T_used = used[(size_t)r].data(); own.scene_status = sst[(size_t)r].data(); }
+        return transition_sharded_impl(rank_ctx, own, 1);
     });
     if (rc) return -1;
-    if (pk) {   // rank 0 holds the scene-wide histories now
-        const size_t hist = (size_t)S * N * (size_t)K_T_max * 24;
+    if (c.pk) {   // rank 0 holds the scene-wide histories now
         HIPCHK(root, hipSetDevice(root->device));
-        HIPCHK(root, hipMemcpyAsync(pk, root->hist_p.p, hist, hipMemcpyDeviceToHost, root->stream));
-        HIPCHK(root, hipMemcpyAsync(vk, root->hist_v.p, hist, hipMemcpyDeviceToHost, root->stream));
-        HIPCHK(root, hipMemcpyAsync(ak, root->hist_a.p, hist, hipMemcpyDeviceToHost, root->stream));
+        if (download_histories(root, c, (size_t)c.S * c.N * (size_t)c.K_T_max * 24, root->stream)) return -1;
         HIPCHK(root, hipStreamSynchronize(root->stream));
     }
     return 0;
@@ -565,8 +533,7 @@ static int group_step_batch(dmpc_ctx *root, int S, int N, const double *l, const
         hipStream_t st = c->stream;
         HIPCHK(c, hipMemcpyAsync(c->rows.p, l, A * N3 * 8, hipMemcpyHostToDevice, st));
         const int rem = N % G;
-        const unsigned blocks = (unsigned)((tab + 255) / 256 > 4096 ? 4096 : (tab + 255) / 256);
-        hipLaunchKernelGGL(mg::table_from_rows_padded_kernel, dim3(blocks), dim3(256), 0, st, S, N, G, (int)cmax, rem, (const double *)c->rows.as<double>(),
+        hipLaunchKernelGGL(mg::table_from_rows_padded_kernel, dim3(grid_1d(tab, 4096)), dim3(256), 0, st, S, N, G, (int)cmax, rem, (const double *)c->rows.as<double>(),
                            c->lT.as<double>());
         // own agents' states: rows [lo, lo + cnt) of every scene (strided host arrays)
         const double *src[4] = {x_p, x_v, x_a, pf};

@@ -298,3 +298,35 @@ def test_refusals_name_the_entry_and_leave_the_context_usable():
     rc, again = ho.raw_hold(d, po, g, None, path, outputs=(0, 0, 0))                  # (and every new output may be NULL)
     assert rc == 0, _err(d)
     _same(again, ok, COMMON, "after the refusals")
+
+
+# ---- 10. a batch in parts --------------------------------------------------------------------------------------------------------------------------
+def _in_parts_and_whole(b):
+    """bound, max_hold = 2, deadlines and all nine outputs, on a context that runs the batch in three parts and on one that never splits"""
+    out = []
+    for option in ("split_parts", 3), ("no_split", 1):
+        d = mp.Dmpc("bound", **ms.KW).debug_option(*option)
+        rc, r = ho.raw_hold(d, b["po"], b["goals"], b["deadline"], b["path"], K_T_max=ms.KT, error_tol=ms.ERROR_TOL, max_hold=2)
+        assert rc == 0, _err(d)
+        out.append((d, r))
+    return out
+
+
+def test_a_batch_in_three_parts_equals_the_whole_batch():
+    """every per-scene array of a call reaches the part that runs its scenes: Q = 3 with deadlines, stage_col and the three hold outputs.  (a) the five
+    four-agent scenes of test_gpu_mission.py::test_scenes_of_a_batch_switch_on_their_own in parts of 1, 2, 2; (b) the three wall crossings with their
+    paths in parts of 1, 1, 1, the one that is held (seed 0) last; then dmpc_postcheck on the histories the parts left resident"""
+    a = ms.batch(["reached", "deadline", "column0", "coincident", "reached"], [0, 0, 0, 0, 3])
+    (_, parts), (_, whole) = _in_parts_and_whole(a)
+    print("(a) stage_col", whole["stage_col"].tolist(), "K_T_used", whole["K_T_used"], "status", whole["scene_status"])
+    assert len({tuple(c) for c in whole["stage_col"]}) >= 3
+    _same(parts, whole, ho.OUTPUTS, "(a) five scenes in parts of 1, 2, 2")
+    b = ms.batch(["failure"] * 3, [1, 5, 0])
+    (dp, parts), (dw, whole) = _in_parts_and_whole(b)
+    print("(b) holds per scene", whole["hold_count"].sum(axis=1), "K_T_used", whole["K_T_used"], "status", whole["scene_status"], "stage_col", whole["stage_col"].tolist())
+    assert whole["hold_count"][2].sum() > 0
+    _same(parts, whole, ho.OUTPUTS, "(b) three wall crossings in parts of 1, 1, 1")
+    pf = b["goals"][:, -1]
+    pc = [d.postcheck(whole["K_T_used"], pf, KT_alloc=ms.KT, path=b["path"]) for d in (dp, dw)]
+    assert set(pc[0]) == set(pc[1]) and np.isfinite(pc[1]["min_dist"]).all()
+    _same(pc[0], pc[1], sorted(pc[0]), "postcheck on the resident histories of the parts")

@@ -5,7 +5,9 @@
   python tools/gpu_launch_trace.py --compare DIR_A DIR_B
 
 The comparison is of the ordered lists of (kernel name, grid size, workgroup size, LDS bytes) per dispatch; it prints the first difference or
-"identical" and exits 0 / 1.  Every case is a host-pointer step of one context (dmpc_step_batch): no child context, no second group."""
+"identical" and exits 0 / 1.  Every case is a host-pointer step of one context (dmpc_step_batch): no child context, no second group.
+--closed-loop (in place of the step cases): one small call of every closed-loop entry -- dmpc_transition, _cmd, _scripted, _mission, _hold, and
+dmpc_transition / _mission in mixed precision -- each on one context and one stream (tools/gpu_transition_probe.py: single_context)."""
 import csv
 import glob
 import os
@@ -44,6 +46,12 @@ def compare(dir_a, dir_b):
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "--compare":
         sys.exit(compare(sys.argv[2], sys.argv[3]))
+    if sys.argv[1:] == ["--closed-loop"]:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import gpu_transition_probe as probe
+        for name, r in probe.single_context(probe.scenes()):
+            print(f"{name}: K_T_used {r['K_T_used'].tolist()} status {r['scene_status'].tolist()}", flush=True)
+        sys.exit(0)
     import test_gpu_launch_plan as plan
     c = plan.ncu()
     for cid, variant, precision, shape, opts, _ in plan.CASES:
