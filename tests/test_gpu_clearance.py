@@ -11,6 +11,7 @@ import pytest
 import multiagent_planning_amd as mp
 from multiagent_planning_amd import workload as wl
 import clearance as cl
+import mission as ms
 import scripted as sc
 
 pytestmark = pytest.mark.gpu
@@ -215,6 +216,43 @@ def test_bad_arguments_are_refused_by_name_and_launch_nothing():
     lone = d.clearance([5], pk[:1, -1], pk[:1], vk[:1], ak[:1])
     assert np.isposinf(lone["dist"]).all() and (lone["partner"] == -1).all()
     assert np.isnan(d.clearance([5], pk[:1, -1], pk[:1], vk[:1], ak[:1], mask=[0])["dist"]).all()
+
+
+# ---- 8: the resident histories of a split batch -----------------------------------------------------------------------------------------------
+SPLIT_USED = np.array([12, 7, 9, 12, 5], dtype=np.int32)
+SPLIT_MASK = np.array([1, 1, 0, 1, 1], dtype=np.int32)
+SPLIT_SEEDS = [0, 1, 2, 3, 5]           # (scene("path", 4) stops on column 2 with a failed agent)
+
+
+@pytest.mark.parametrize("kind", ["static", "scripted"])
+def test_resident_histories_of_a_split_batch(kind):
+    """S = 5 scenes of tests/mission.py -- four commanded agents, two static / two scripted vehicles -- through a transition with
+    split_parts = 3: parts of 1, 2 and 2 scenes (cut at 1 and 3), whose histories stay on three contexts.  The clearance arrays of the resident
+    call (each part searched where it lives, every array offset per part) == those of the same call on host histories on a context that
+    never splits, byte for byte; so are the post-check's outputs, with po_static (dmpc_postcheck_cmd) and, scripted, with the path."""
+    b = ms.batch(["static" if kind == "static" else "path"] * 5, SPLIT_SEEDS)
+    pf = b["goals"][:, 0]
+    d = mp.Dmpc("bound", **ms.KW).debug_option("split_parts", 3)
+    tr = d.transition(b["po"], pf, KT_SMALL, ms.ERROR_TOL, path=b["path"])
+    assert (tr["K_T_used"] == KT_SMALL).all() and tr["pk"].shape == (5, 4, KT_SMALL, 3)
+    hist = (tr["pk"], tr["vk"], tr["ak"])
+    e = mp.Dmpc("bound", **ms.KW).debug_option("no_split", 1)
+    pos = b["po"][:, 4:] if kind == "static" else np.repeat(ms.STATIC[None], 5, axis=0)
+    extra = dict(po_static=pos) if kind == "static" else dict(path=b["path"])
+    res = d.clearance(SPLIT_USED, pf, KT_alloc=KT_SMALL, mask=SPLIT_MASK, **extra)
+    host = e.clearance(SPLIT_USED, pf, *hist, mask=SPLIT_MASK, **extra)
+    _same(res, host, f"{kind}: split resident / host histories")
+    assert np.isnan(host["dist"][2]).all() and (host["partner"][2] == -1).all()
+    on = SPLIT_MASK == 1
+    assert np.isfinite(host["dist"][on]).all() and (host["partner"][on][..., 1] >= 4).all() and len(set(host["dist"][on, 0, 1])) == 4
+    print(f"{kind}: nearest vehicle per scene {host['dist'][:, :, 1].min(axis=1)}")
+    for ex in (dict(po_static=pos), extra)[:1 if kind == "static" else 2]:
+        a = d.postcheck(SPLIT_USED, pf, KT_alloc=KT_SMALL, mask=SPLIT_MASK, interp=True, **ex)
+        h = e.postcheck(SPLIT_USED, pf, *hist, mask=SPLIT_MASK, interp=True, **ex)
+        assert set(a) == set(h) and ("min_dist_static" in h or "p_scripted" in h)
+        for k in h:
+            assert a[k].dtype == h[k].dtype and a[k].shape == h[k].shape and a[k].tobytes() == h[k].tobytes(), (kind, sorted(ex), k)
+        assert (h["n_samples"][on] > 0).all() and h["n_samples"][2] == 0 and len(set(h["n_samples"][on])) > 1
 
 
 # ---- the MEX gateway ---------------------------------------------------------------------------------------------------------------------------

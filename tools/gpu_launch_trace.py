@@ -7,7 +7,9 @@
 The comparison is of the ordered lists of (kernel name, grid size, workgroup size, LDS bytes) per dispatch; it prints the first difference or
 "identical" and exits 0 / 1.  Every case is a host-pointer step of one context (dmpc_step_batch): no child context, no second group.
 --closed-loop (in place of the step cases): one small call of every closed-loop entry -- dmpc_transition, _cmd, _scripted, _mission, _hold, and
-dmpc_transition / _mission in mixed precision -- each on one context and one stream (tools/gpu_transition_probe.py: single_context)."""
+dmpc_transition / _mission in mixed precision -- each on one context and one stream (tools/gpu_transition_probe.py: single_context).
+--postcheck (likewise): the calls of tools/gpu_postcheck_probe.py that enqueue on one stream -- every post-check entry on host and on resident
+histories, the scenes of 300 agents on the cell grid with their brute-force pass (single_context there)."""
 import csv
 import glob
 import os
@@ -51,6 +53,12 @@ if __name__ == "__main__":
         import gpu_transition_probe as probe
         for name, r in probe.single_context(probe.scenes()):
             print(f"{name}: K_T_used {r['K_T_used'].tolist()} status {r['scene_status'].tolist()}", flush=True)
+        sys.exit(0)
+    if sys.argv[1:] == ["--postcheck"]:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import gpu_postcheck_probe as probe
+        for name, r in probe.single_context():
+            print(f"{name}: {sum(v is not None for v in r.values())} arrays", flush=True)
         sys.exit(0)
     import test_gpu_launch_plan as plan
     c = plan.ncu()

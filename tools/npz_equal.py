@@ -8,8 +8,8 @@ for k in a.files:
     if any(s in k for s in skip): continue
     x, y = a[k], b[k]
     if k.startswith("info"): x, y = x[..., :4], y[..., :4]   # (branch record; iteration statistics may differ between builds)
-    if not np.array_equal(x, y):
+    if x.dtype != y.dtype or x.shape != y.shape or np.ascontiguousarray(x).tobytes() != np.ascontiguousarray(y).tobytes():   # (bytes: NaN equals NaN)
         bad += 1
-        d = np.abs(x.astype(float) - y.astype(float)).max()
+        d = np.nanmax(np.abs(x.astype(float) - y.astype(float))) if x.shape == y.shape and x.size else np.nan
         print(f"{k}: differs (max abs {d:.3e})")
 print("identical" if not bad else f"{bad} arrays differ", f"({len(a.files)} arrays)")
