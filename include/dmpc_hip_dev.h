@@ -20,6 +20,15 @@ DMPC_API int dmpc_debug_set_rank(dmpc_ctx *ctx, int nranks, int rank);
 DMPC_API int dmpc_debug_trace(dmpc_ctx *ctx, int agent, int cap, double *host_out);
 /* the scan's hand-off headers of the last step (8 ints per agent) */
 DMPC_API int dmpc_debug_read_hdr(dmpc_ctx *ctx, int *host_out, int n_agents);
+/* the neighbour-list build of the last step that built lists.  shape[12] = S, G, C, cells along x, y, z, ncell, build (0: all-pairs box test,
+ * no cell grid; 1: the five kernels; 2: the two launches of one scene), list capacity, close capacity, agents of the launch (S * c_count),
+ * pieces per list count.  out = NULL: the shape alone.  Otherwise these arrays as 4-byte words, one behind the other (the cell grid's are
+ * empty with build = 0, the close pairs' with a close capacity of 0): bbox [G][S][18][C], largest half extents [S][3][3] (as the build left them if
+ * this entry had been called on the context before the step -- a refused call will do: such a context keeps a copy, one device-to-device copy per
+ * build; otherwise zeros after build 2, whose counters the step's scan kernel sets back for the next step), start
+ * [S][3][ncell + 1], entry records [2][S][3][G C][4] (the two 16-byte halves), nbr_cnt [agents][pieces], nbr_list [agents][capacity],
+ * close_cnt [agents], close_list [agents][close capacity][2].  Refused before any list build and when out_bytes is too small. */
+DMPC_API int dmpc_debug_read_grid(dmpc_ctx *ctx, int *shape, void *out, size_t out_bytes);
 /* force the solve launch order of the next launches (n = 0: the built-in policy) */
 DMPC_API int dmpc_debug_set_order(dmpc_ctx *ctx, const int *host_order, int n);
 /* a coalesced streaming read of `bytes` bytes at 8 or 16 bytes per lane, `reps` launches: the known byte count rocprofv3's FETCH_SIZE is

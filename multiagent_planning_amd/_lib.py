@@ -154,6 +154,8 @@ def load():
     L.dmpc_group_size.argtypes = [vp]
     L.dmpc_debug_emulate_devices.argtypes = [C.c_int]
     L.dmpc_debug_option.argtypes = [vp, C.c_char_p, C.c_int]
+    if hasattr(L, "dmpc_debug_read_grid"):   # (absent from the older builds tools/with_lib.py may load)
+        L.dmpc_debug_read_grid.argtypes = [vp, ip, vp, C.c_size_t]
     L.dmpc_solve_count.restype = C.c_int64
     L.dmpc_solve_count.argtypes = [vp]
     L.dmpc_profile.argtypes = [vp, C.c_int]
@@ -287,6 +289,35 @@ class Dmpc:
         crash_min, no_fast_exit, iter_cap, split_parts ...); never arithmetic"""
         self._chk(self._L.dmpc_debug_option(self._ctx, name.encode(), int(value)))
         return self
+
+    def debug_watch_grid(self):
+        """development / tests: list builds of this context keep a copy of their largest half extents from now on (the two-launch build's are set
+        back to zero by the step's own scan kernel); any call of dmpc_debug_read_grid arms this, here one made before a build"""
+        self._L.dmpc_debug_read_grid(self._ctx, _ip(np.zeros(12, dtype=np.int32)), None, 0)
+        return self
+
+    def debug_read_grid(self):
+        """development / tests: what the last list build of a step left on the device (dmpc_debug_read_grid): the shape -- S, G, C, n (cells
+        per axis), ncell, build (0: all-pairs box test, 1: five kernels, 2: two launches), cap, close_cap, agents, parts -- and bbox [G,S,18,C]
+        fp32, maxhalf [S,3,3] fp32, start [S,3,ncell+1], ent [2,S,3,G*C,4] fp32 (word 0 of the first half: the code's bits), nbr_cnt
+        [agents,parts], nbr_list [agents,cap], close_cnt [agents], close_list [agents,close_cap,2]; the grid's arrays are empty with build = 0;
+        maxhalf after the two-launch build needs debug_watch_grid before the step (zeros otherwise)"""
+        sh = np.zeros(12, dtype=np.int32)
+        self._chk(self._L.dmpc_debug_read_grid(self._ctx, _ip(sh), None, 0))
+        S, G, Cc, nx, ny, nz, ncell, build, cap, ccap, agents, parts = (int(x) for x in sh)
+        g = 1 if build else 0
+        shapes = dict(bbox=(G, S, 18, Cc), maxhalf=(g * S, 3, 3), start=(g * S, 3, ncell + 1), ent=(2, g * S, 3, G * Cc, 4), nbr_cnt=(agents, parts),
+                      nbr_list=(agents, cap), close_cnt=(agents if ccap else 0,), close_list=(agents, ccap, 2))
+        words = np.zeros(sum(int(np.prod(v)) for v in shapes.values()), dtype=np.int32)
+        self._chk(self._L.dmpc_debug_read_grid(self._ctx, _ip(sh), words.ctypes.data_as(C.c_void_p), words.nbytes))
+        out = dict(S=S, G=G, C=Cc, n=(nx, ny, nz), ncell=ncell, build=build, cap=cap, close_cap=ccap, agents=agents, parts=parts)
+        at = 0
+        for k, shp in shapes.items():
+            n = int(np.prod(shp))
+            a = words[at:at + n].reshape(shp)
+            out[k] = a.view(np.float32) if k in ("bbox", "maxhalf", "ent") else a
+            at += n
+        return out
 
     def close(self):
         if getattr(self, "_ctx", None):

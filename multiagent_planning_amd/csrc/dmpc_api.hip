@@ -155,6 +155,13 @@ struct dmpc_ctx {
     bool grid_clean = false; // the cell grid's counters were left zero by the last scan launch (grid_clean_key: for which buffer / size)
     unsigned long long grid_clean_key = 0;
     DevBuf grid;             // cell grid of the neighbour lists (counts, starts, entries)
+    struct ListsBuilt {      // the last list build, for dmpc_debug_read_grid (S = 0: none yet)
+        int S = 0, G = 0, C = 0, n[3] = {0, 0, 0}, ncell = 0, build = 0, cap = 0, close_cap = 0, agents = 0, parts = 0;
+        const int *maxhalf = nullptr, *start = nullptr; const void *ent = nullptr;   // inside `grid`
+        bool armed = false;      // dmpc_debug_read_grid was called on this context: builds from now on keep a copy of their half extents
+        bool kept = false;       // ... and the last one did (the two-launch build's are set back to zero by the step's scan kernel)
+    } lists_built;
+    DevBuf maxhalf_kept;     // [S][3][3], filled right after grid_prep_kernel / grid_bin_kernel on an armed context
     DevBuf pc_p, pc_v, pc_a, pc_M, pc_w, pc_scene, pc_agent, pc_interp;   // post-check work buffers
     DevBuf pc_static;                                                      // post-check: positions of the uncommanded vehicles + their per-scene minimum
     DevBuf path;                                                           // dmpc_transition_scripted: the scripted vehicles' paths [S][M][P][3], resident for the call
@@ -671,6 +678,34 @@ extern "C" int dmpc_debug_read_hdr(dmpc_ctx *ctx, int *host_out, int n_agents)
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if ((size_t)n_agents * 32 > ctx->hdr.cap) { ctx->err = "dmpc_debug_read_hdr: more agents than the last step had"; return -1; }
     HIPCHK(ctx, hipMemcpy(host_out, ctx->hdr.p, (size_t)n_agents * 32, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// development aid (not part of the public header): what the last list build of a step left on the device (include/dmpc_hip_dev.h has the layout)
+extern "C" int dmpc_debug_read_grid(dmpc_ctx *ctx, int *shape, void *out, size_t out_bytes)
+{
+    if (!ctx || !shape) return -1;
+    dmpc_ctx::ListsBuilt &b = ctx->lists_built;
+    b.armed = true;
+    if (b.S == 0) { ctx->err = "dmpc_debug_read_grid: no step of this context has built neighbour lists"; return -1; }
+    const int sh[12] = {b.S, b.G, b.C, b.n[0], b.n[1], b.n[2], b.ncell, b.build, b.cap, b.close_cap, b.agents, b.parts};
+    memcpy(shape, sh, sizeof(sh));
+    if (!out) return 0;
+    const size_t nag = (size_t)b.G * b.C, grid = b.build ? 1 : 0, agents = (size_t)b.agents;
+    const struct { const void *src; size_t words; } part[] = {
+        {ctx->bbox.p, nag * b.S * 6 * NSEG}, {b.kept ? ctx->maxhalf_kept.p : b.maxhalf, grid * b.S * NSEG * 3}, {b.start, grid * b.S * NSEG * ((size_t)b.ncell + 1)},
+        {b.ent, grid * 2 * b.S * NSEG * nag * 4}, {ctx->nbr_cnt.p, agents * b.parts}, {ctx->nbr_list.p, agents * b.cap},
+        {ctx->close_cnt.p, b.close_cap ? agents : 0}, {ctx->close_list.p, agents * b.close_cap * 2}};
+    size_t words = 0;
+    for (const auto &q : part) words += q.words;
+    if (out_bytes < words * 4) { ctx->err = "dmpc_debug_read_grid: the buffer is too small (" + std::to_string(words * 4) + " bytes)"; return -1; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    char *dst = (char *)out;
+    for (const auto &q : part) {
+        if (q.words) HIPCHK(ctx, hipMemcpy(dst, q.src, q.words * 4, hipMemcpyDeviceToHost));
+        dst += q.words * 4;
+    }
     return 0;
 }
 

@@ -107,27 +107,49 @@ static const SolveKernel solve_kernels_plain[] = {   // one agent per workgroup
     {false, 48, 48, false, (const void *)dmpc_solve_kernel<false, 48>},
     {true, 64, 64, true, (const void *)dmpc_solve_kernel<true, 64, float>}, {false, 48, 48, true, (const void *)dmpc_solve_kernel<false, 48, float>}};
 
-// The list builders' kernels that read the prediction table: its fp64 original, or the fp32 copy of mixed precision.
-static void launch_list_inputs(dmpc_ctx *ctx, int total, int C, int short_from, bool fused, bool nbr_major, const GridGeom &gg, size_t n_zero, const double *lT, const float *lTf,
-                               int *g_cnt, int *g_mh, int *g_cell, int *g_pos, hipStream_t st)
+// the neighbour lists of large scenes
+constexpr int GRID_CELLS_DEFAULT = 2;                 // row of plan_lists' cell geometries taken when option grid_cells names none
+constexpr size_t GRID_FILL2_LDS_MAX = 128 * 1024;     // dynamic LDS of a grid_fill2_kernel block up to which one scene's grid is built in two launches
+struct ListPlan {
+    bool build = false;      // lists at all
+    bool use_grid = false;   // from the cell grid + distance filter (grid_query_kernel); else the all-pairs box test (nbr_kernel)
+    bool fused = false;      // ONE scene: the grid in two launches (grid_prep_kernel, grid_fill2_kernel) instead of five
+    bool nbr_major = false;  // the neighbour-major fp32 copy of the table is made
+    long cap = 0;            // entries per agent
+    double R = 0, Rsel = 0;  // radius of the boxes' test / of the scan's selection
+    size_t gq_lds = 0;
+    bool close = false;      // the query also leaves the (neighbour, step) pairs inside rmin: the scan tests those instead of walking its list
+    int close_cap = 0;       // records per agent
+    GridGeom gg{};
+    int ncell = 1;
+};
+// the cell grid's buffer (carve_grid)
+struct GridBuffers {
+    int *cnt = nullptr, *maxhalf = nullptr, *start = nullptr, *cell = nullptr, *pos = nullptr;
+    f4_t *ent = nullptr;
+    size_t n_zero = 0;   // ints zeroed together at the buffer's front: counts and largest half extents
+};
+
+// The list builders' kernels that read the prediction table, by the table's type: its fp64 original, or the fp32 copy of mixed precision.
+template <typename TT>
+static void launch_list_inputs(dmpc_ctx *ctx, const StepShape &sh, const ListPlan &L, const GridBuffers &g, const TT *lT, int short_from, hipStream_t st)
 {
+    const int total = sh.G * sh.S * sh.C, C = sh.C;
     const size_t tot = (size_t)total * 64;
     const dim3 gA((unsigned)((total + 255) / 256)), gC((unsigned)((tot + 255) / 256)), b(256);
     float *bbox = ctx->bbox.as<float>(), *bbox_nm = ctx->bbox_nm.as<float>(), *lrow = ctx->lrow.as<float>();
-    if (!fused) {
-        if (lTf) hipLaunchKernelGGL(bbox_kernel<float>, gA, b, 0, st, total, C, lTf, bbox, bbox_nm);
-        else hipLaunchKernelGGL(bbox_kernel<double>, gA, b, 0, st, total, C, lT, bbox, bbox_nm);
+    if (L.fused) {   // (grid_prep_kernel makes the boxes and the copy)
+        hipLaunchKernelGGL(grid_prep_kernel<TT>, dim3(gA.x + gC.x), b, 0, st, total, C, short_from, L.gg, (int)gA.x, lT, bbox, bbox_nm, lrow, g.cell, g.pos, g.cnt, g.maxhalf);
+        return;
     }
-    if (nbr_major && !fused) {   // (fused: grid_prep_kernel makes the copy)
-        if (lTf) hipLaunchKernelGGL(table_nbrmajor_kernel<float>, gC, b, 0, st, tot, C, lTf, lrow, g_cnt, n_zero);
-        else hipLaunchKernelGGL(table_nbrmajor_kernel<double>, gC, b, 0, st, tot, C, lT, lrow, g_cnt, n_zero);
-    }
-    if (fused) {
-        const int nbA = (int)gA.x;
-        if (lTf) hipLaunchKernelGGL(grid_prep_kernel<float>, dim3(gA.x + gC.x), b, 0, st, total, C, short_from, gg, nbA, lTf, bbox, bbox_nm, lrow, g_cell, g_pos, g_cnt, g_mh);
-        else hipLaunchKernelGGL(grid_prep_kernel<double>, dim3(gA.x + gC.x), b, 0, st, total, C, short_from, gg, nbA, lT, bbox, bbox_nm, lrow, g_cell, g_pos, g_cnt, g_mh);
-    }
+    hipLaunchKernelGGL(bbox_kernel<TT>, gA, b, 0, st, total, C, lT, bbox, bbox_nm);
+    if (L.nbr_major) hipLaunchKernelGGL(table_nbrmajor_kernel<TT>, gC, b, 0, st, tot, C, lT, lrow, g.cnt, g.n_zero);
 }
+// Instantiated explicitly, and HERE: the compiler emits the device code of bbox_kernel, table_nbrmajor_kernel and grid_prep_kernel where the host first
+// names an instantiation, and the code object keeps its order -- one-agent solve kernels, list builders, scan kernels, persistent solve kernels (see
+// solve_kernels_plain) -- only while these two lines stand between the two solve tables.  (That is also why ListPlan stands up here and not with the plan.)
+template void launch_list_inputs<float>(dmpc_ctx *, const StepShape &, const ListPlan &, const GridBuffers &, const float *, int, hipStream_t);
+template void launch_list_inputs<double>(dmpc_ctx *, const StepShape &, const ListPlan &, const GridBuffers &, const double *, int, hipStream_t);
 
 // The scan kernel by row type, table type and exit: the super-ellipsoid of order 4 (all-neighbour variants) has its own scan kernels,
 // without the unconstrained exit.
@@ -188,25 +210,6 @@ struct TierPlan {
     bool persistent = false;
     int wgs = 0;               // persistent form: workgroups
     int queue_chunk = 0;       // persistent form: positions per ticket of the queue's light bulk
-};
-
-// the neighbour lists of large scenes
-constexpr int GRID_CELLS_DEFAULT = 2;                 // row of plan_lists' cell geometries taken when option grid_cells names none
-constexpr size_t GRID_FILL2_LDS_MAX = 128 * 1024;     // dynamic LDS of a grid_fill2_kernel block up to which one scene's grid is built in two launches
-struct ListPlan {
-    bool build = false;      // lists at all
-    bool use_grid = false;   // from the cell grid + distance filter (grid_query_kernel); else the all-pairs box test (nbr_kernel)
-    bool fused = false;      // ONE scene: the grid in two launches (grid_prep_kernel, grid_fill2_kernel) instead of five
-    bool nbr_major = false;  // the neighbour-major fp32 copy of the table is made
-    long cap = 0;            // entries per agent
-    double R = 0, Rsel = 0;  // radius of the boxes' test / of the scan's selection
-    size_t gq_lds = 0;
-    bool close = false;      // the query also leaves the (neighbour, step) pairs inside rmin: the scan tests those instead of walking its list
-    int close_cap = 0;       // records per agent
-    GridGeom gg{};
-    int ncell = 1;
-    size_t n_cnt = 0, n_mh = 0, n_st = 0, n_hd = 0;   // the grid buffer's partition (ints): counts, largest half extents, starts, header in all
-    size_t n_zero = 0;                                // ints zeroed together at the buffer's front
 };
 
 struct StepPlan {
@@ -281,7 +284,6 @@ static ListPlan plan_lists(const dmpc_ctx *ctx, const StepPlan &pl)
     // near-neighbour selections); solveEllipDMPC / solveSoftDMPC / solveSoftDMPCrepair take every neighbour
     L.build = sh.G * sh.C >= o.cull_min && !o.no_cull && pl.finite_radius;
     if (!L.build) return L;
-    const int total = sh.G * sh.S * sh.C;
     // neighbour lists from the boxes (nbr_kernel): up to 4096 entries per agent, within 1 GB of scratch
     const size_t agents = (size_t)pl.total;
     L.cap = ((long)sh.G * sh.C + 63) & ~63L;
@@ -336,11 +338,6 @@ static ListPlan plan_lists(const dmpc_ctx *ctx, const StepPlan &pl)
     };
     cells((o.grid_cells >= 0 && o.grid_cells < n_geoms) ? o.grid_cells : GRID_CELLS_DEFAULT);
     if (L.ncell > 32 * 32 * 32) cells(0);
-    // one grid per third of the horizon (keyed by the centre of that segment's box: a third of the extent of the whole horizon's).  One
-    // buffer: [S][3][ncell] counts, [S][3][3] largest half extents (zeroed together), [S][3][ncell + 1] starts, [3][G S C] cells, [S][3][G C] entries
-    L.n_cnt = (size_t)sh.S * NSEG * L.ncell; L.n_mh = (size_t)sh.S * NSEG * 3; L.n_st = (size_t)sh.S * NSEG * (L.ncell + 1);
-    L.n_hd = (L.n_cnt + L.n_mh + L.n_st + 2 * (size_t)NSEG * total + 7) & ~(size_t)7;   // (the entry records behind it are 32-byte aligned)
-    L.n_zero = L.n_cnt + L.n_mh;
     // (every block of grid_fill2_kernel keeps the prefix of all NSEG x (ncell + 1) counts in its LDS: up to GRID_FILL2_LDS_MAX = 128 KB of a
     // CU's 160 -- 10 921 cells; the 8 200 of geometry 2 at N = 10^4 take 96 KB, one block per CU, 40 blocks -- above it the five kernels)
     L.fused = sh.S == 1 && o.prep_fuse && (size_t)NSEG * (L.ncell + 1) * 4 <= GRID_FILL2_LDS_MAX;
@@ -500,12 +497,29 @@ static int fill_params(dmpc_ctx *ctx, const StepPlan &pl, const StepIO &io, Step
     return 0;
 }
 
+// ctx->grid carved for a plan's cell grid; true: the allocation failed.  One grid per third of the horizon (keyed by the centre of that segment's box:
+// a third of the extent of the whole horizon's).  Ints, in this order: [S][3][ncell] counts, [S][3][3] largest half extents (zeroed together),
+// [S][3][ncell + 1] starts, [3][G S C] cells, [3][G S C] positions within the cell (the two-launch build); behind them, 32-byte aligned, the entry
+// records: two arrays [S][3][G C] of 16-byte halves.
+static bool carve_grid(dmpc_ctx *ctx, const StepShape &sh, const ListPlan &L, GridBuffers &g)
+{
+    const size_t total = (size_t)sh.G * sh.S * sh.C, grids = (size_t)sh.S * NSEG;
+    const size_t n_cnt = grids * L.ncell, n_mh = grids * 3, n_st = grids * ((size_t)L.ncell + 1);
+    const size_t n_hd = (n_cnt + n_mh + n_st + 2 * NSEG * total + 7) & ~(size_t)7;
+    if (ctx->grid.ensure((n_hd + 8 * NSEG * total) * 4)) return true;
+    g.cnt = ctx->grid.as<int>(); g.maxhalf = g.cnt + n_cnt; g.start = g.maxhalf + n_mh; g.cell = g.start + n_st; g.pos = g.cell + NSEG * total;
+    g.ent = (f4_t *)(g.cnt + n_hd);
+    g.n_zero = n_cnt + n_mh;
+    return false;
+}
+
 // neighbour lists of large scenes: segment boxes, the neighbour-major copy of the table, the cell grid (five kernels, or two for one
 // scene), and the lists themselves from the grid query or the all-pairs box test
 static int build_neighbour_lists(dmpc_ctx *ctx, const StepPlan &pl, const StepIO &io, StepParams &P, hipStream_t st)
 {
     const ListPlan &L = pl.lists;
     if (!L.build) return 0;
+    ctx->lists_built.S = 0; ctx->lists_built.kept = false;   // (nothing to read until this build is through)
     const dmpc_params &p = ctx->prm;
     const int S = pl.sh.S, G = pl.sh.G, C = pl.sh.C, g_local = pl.sh.g_local, c_first = pl.sh.c_first, c_count = pl.sh.c_count;
     const int total = G * S * C, short_from = io.short_from;
@@ -516,13 +530,8 @@ static int build_neighbour_lists(dmpc_ctx *ctx, const StepPlan &pl, const StepIO
     if (ctx->nbr_list.ensure(agents * (size_t)L.cap * 4) || ctx->nbr_cnt.ensure(agents * 4 * NBR_PARTS)) FAIL(ctx, "device allocation failed (neighbour lists)");
     // (grid geometry and buffer first: the counters are zeroed by the neighbour-major copy kernel, which runs anyway -- a memset of an odd
     // size is two fill launches, 9 us)
-    int *g_cnt = nullptr, *g_mh = nullptr, *g_st = nullptr, *g_cell = nullptr, *g_pos = nullptr;
-    f4_t *g_ent = nullptr;
-    if (L.use_grid) {
-        if (ctx->grid.ensure((L.n_hd + 8 * (size_t)NSEG * total) * 4)) FAIL(ctx, "device allocation failed (neighbour grid)");
-        g_cnt = ctx->grid.as<int>(); g_mh = g_cnt + L.n_cnt; g_st = g_mh + L.n_mh; g_cell = g_st + L.n_st; g_pos = g_cell + (size_t)NSEG * total;
-        g_ent = (f4_t *)(g_cnt + L.n_hd);
-    }
+    GridBuffers g;
+    if (L.use_grid && carve_grid(ctx, pl.sh, L, g)) FAIL(ctx, "device allocation failed (neighbour grid)");
     if (L.nbr_major) {   // neighbour-major fp32 copy of the table: the list walk of the per-step distance scan, the distance test of the grid query
         if (ctx->lrow.ensure((size_t)total * 64 * 4)) FAIL(ctx, "device allocation failed (neighbour-major table)");
         if (p.variant != DMPC_VAR_HARD) P.lrow = ctx->lrow.p;
@@ -530,30 +539,36 @@ static int build_neighbour_lists(dmpc_ctx *ctx, const StepPlan &pl, const StepIO
     if (L.fused) {
         // the counters are zero when the last scan launch left them so (for this buffer and size); a memset otherwise (first step, another batch shape in between)
         // (n_zero follows the cell count: up to 3 x 32^3 + 9, seventeen bits -- multiplied through the word, not shifted out of it)
-        const unsigned long long key = (unsigned long long)(size_t)g_cnt ^ ((unsigned long long)L.n_zero * 0x9E3779B97F4A7C15ull) ^ ((unsigned long long)total << 20);
-        if (!ctx->grid_clean || ctx->grid_clean_key != key) HIPCHK(ctx, hipMemsetAsync(g_cnt, 0, L.n_zero * 4, st));
+        const unsigned long long key = (unsigned long long)(size_t)g.cnt ^ ((unsigned long long)g.n_zero * 0x9E3779B97F4A7C15ull) ^ ((unsigned long long)total << 20);
+        if (!ctx->grid_clean || ctx->grid_clean_key != key) HIPCHK(ctx, hipMemsetAsync(g.cnt, 0, g.n_zero * 4, st));
         ctx->grid_clean = false; ctx->grid_clean_key = key;
-        P.gzero = g_cnt; P.gzero_n = (int)L.n_zero;
+        P.gzero = g.cnt; P.gzero_n = (int)g.n_zero;
     } else if (L.use_grid)
         ctx->grid_clean = false;
-    launch_list_inputs(ctx, total, C, short_from, L.fused, L.nbr_major, L.gg, L.n_zero, io.lT, io.lTf, g_cnt, g_mh, g_cell, g_pos, st);
+    if (io.lTf) launch_list_inputs(ctx, pl.sh, L, g, io.lTf, short_from, st);
+    else launch_list_inputs(ctx, pl.sh, L, g, io.lT, short_from, st);
     if (L.fused) {
         const size_t lds_fill = (size_t)NSEG * (L.ncell + 1) * 4;
         if ((int)lds_fill > ctx->max_lds_fill2) {   // (the limit of a kernel's dynamic LDS is 64 KB until it is raised)
             HIPCHK(ctx, hipFuncSetAttribute((const void *)grid_fill2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fill));
             ctx->max_lds_fill2 = (int)lds_fill;
         }
-        hipLaunchKernelGGL(grid_fill2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), lds_fill, st, total, C, L.ncell, (float)(1.0 / p.c), (const int *)g_cell, (const int *)g_pos, (const int *)g_cnt, g_st, (const float *)ctx->lrow.as<float>(), g_ent);
+        hipLaunchKernelGGL(grid_fill2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), lds_fill, st, total, C, L.ncell, (float)(1.0 / p.c), (const int *)g.cell, (const int *)g.pos, (const int *)g.cnt, g.start, (const float *)ctx->lrow.as<float>(), g.ent);
     } else if (L.use_grid) {
-        hipLaunchKernelGGL(grid_bin_kernel, dim3((unsigned)((total + 255) / 256), NSEG), dim3(256), 0, st, total, S, C, short_from, L.gg, (const float *)ctx->bbox_nm.as<float>(), g_cell, g_cnt, g_mh);
-        hipLaunchKernelGGL(grid_scan_kernel, dim3((unsigned)(S * NSEG)), dim3(L.ncell > 512 ? 1024 : 256), 0, st, L.ncell, g_cnt, g_st);
-        hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, S, C, L.ncell, (float)(1.0 / p.c), (const int *)g_cell, g_cnt, (const int *)g_st, (const float *)ctx->lrow.as<float>(), g_ent);
+        hipLaunchKernelGGL(grid_bin_kernel, dim3((unsigned)((total + 255) / 256), NSEG), dim3(256), 0, st, total, S, C, short_from, L.gg, (const float *)ctx->bbox_nm.as<float>(), g.cell, g.cnt, g.maxhalf);
+        hipLaunchKernelGGL(grid_scan_kernel, dim3((unsigned)(S * NSEG)), dim3(1024), 0, st, L.ncell, g.cnt, g.start);
+        hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, S, C, L.ncell, (float)(1.0 / p.c), (const int *)g.cell, g.cnt, (const int *)g.start, (const float *)ctx->lrow.as<float>(), g.ent);
+    }
+    if (L.use_grid && ctx->lists_built.armed) {   // (dmpc_debug_read_grid: the half extents as the build left them)
+        if (ctx->maxhalf_kept.ensure((size_t)S * NSEG * 3 * 4)) FAIL(ctx, "device allocation failed (neighbour grid)");
+        HIPCHK(ctx, hipMemcpyAsync(ctx->maxhalf_kept.p, g.maxhalf, (size_t)S * NSEG * 3 * 4, hipMemcpyDeviceToDevice, st));
+        ctx->lists_built.kept = true;
     }
     if (L.close && (ctx->close_list.ensure(agents * (size_t)L.close_cap * 8) || ctx->close_cnt.ensure(agents * 4))) FAIL(ctx, "device allocation failed (close pairs)");
     if (L.use_grid) {
         hipLaunchKernelGGL(grid_query_kernel, dim3((unsigned)pl.total), dim3(64 * GQ_WAVES), L.gq_lds, st, S, G, C, g_local, c_first, c_count, L.gg,
                            (float)L.R, (float)(L.R * p.c), (float)(1.0 / p.c), (float)(L.Rsel * L.Rsel * 1.002), (const float *)ctx->bbox_nm.as<float>(), (const float *)ctx->lrow.as<float>(),
-                           (const int *)g_st, (const f4_t *)g_ent, (const int *)g_mh, (int)L.cap, (G == 1 && c_first == 0 && c_count == C && !short_from) ? 1 : 0,
+                           (const int *)g.start, (const f4_t *)g.ent, (const int *)g.maxhalf, (int)L.cap, (G == 1 && c_first == 0 && c_count == C && !short_from) ? 1 : 0,
                            ctx->nbr_list.as<int>(), ctx->nbr_cnt.as<int>(),
                            L.close ? (float)(p.rmin * p.rmin) * 1.001f : -1.f, L.close_cap, L.close ? ctx->close_list.as<int>() : nullptr, L.close ? ctx->close_cnt.as<int>() : nullptr);
         if (L.close) { P.close_list = ctx->close_list.as<int>(); P.close_cnt = ctx->close_cnt.as<int>(); P.close_cap = L.close_cap; }
@@ -564,6 +579,11 @@ static int build_neighbour_lists(dmpc_ctx *ctx, const StepPlan &pl, const StepIO
     }
     P.nbr_cap = (int)L.cap; P.nbr_list = ctx->nbr_list.as<int>(); P.nbr_cnt = ctx->nbr_cnt.as<int>();
     P.nbr_parts = L.use_grid ? 1 : NBR_PARTS;   // (the query writes a list as one run; nbr_cnt keeps NBR_PARTS slots per agent either way)
+    dmpc_ctx::ListsBuilt &b = ctx->lists_built;   // (dmpc_debug_read_grid)
+    b.S = S; b.G = G; b.C = C; b.ncell = L.use_grid ? L.ncell : 0; b.build = L.fused ? 2 : (L.use_grid ? 1 : 0);
+    for (int a = 0; a < 3; ++a) b.n[a] = L.use_grid ? L.gg.n[a] : 0;
+    b.cap = (int)L.cap; b.close_cap = L.close_cap; b.agents = pl.total; b.parts = NBR_PARTS;
+    b.maxhalf = g.maxhalf; b.start = g.start; b.ent = g.ent;
     return 0;
 }
 

@@ -252,26 +252,7 @@ __global__ void sample_table_kernel(int S, int N, int Nc, int KTa, const int *__
     cell_of[t] = c;
     atomicAdd(&fill[((size_t)s * SB + b) * ((size_t)g.nx * g.ny * g.nz) + c], 1);
 }
-// block per (scene, sample): start[c] = number of agents in cells < c (ncell + 1 entries); the counts go back to zero
-__global__ void grid_scan_kernel(int ncell, int *__restrict__ fill, int *__restrict__ start)
-{
-    __shared__ int part[1024];
-    int *f = fill + (size_t)blockIdx.x * ncell, *st = start + (size_t)blockIdx.x * (ncell + 1);
-    const int per = (ncell + 1023) / 1024, lo = threadIdx.x * per, hi = lo + per < ncell ? lo + per : ncell;
-    int a = 0;
-    for (int c = lo; c < hi; ++c) a += f[c];
-    part[threadIdx.x] = a;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {   // inclusive scan of the partial sums
-        const int v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - a;
-    for (int c = lo; c < hi; ++c) { st[c] = run; run += f[c]; f[c] = 0; }
-    if (threadIdx.x == 1023) st[ncell] = part[1023];
-}
+// (the exclusive prefix of the counts, block per (scene, sample): dmpc::grid_scan_kernel, dmpc_lists.hip)
 // thread per (scene, sample, agent): slot of the agent in its cell (the order inside a cell is arbitrary: only a minimum is taken)
 __global__ void grid_scatter_kernel(size_t total, int N, int ncell, const int *__restrict__ cell_of, const int *__restrict__ start,
                                     int *__restrict__ fill, int *__restrict__ sorted)

@@ -184,7 +184,7 @@ static bool pc_grid_ensure(dmpc_ctx *ctx, size_t sbn, size_t tot, int ncell)
 static int pc_grid_build(dmpc_ctx *ctx, size_t sbn, size_t tot, int N, int ncell)
 {
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(pc::grid_scan_kernel, dim3((unsigned)sbn), dim3(1024), 0, st, ncell, ctx->pc_fill.as<int>(), ctx->pc_start.as<int>());
+    hipLaunchKernelGGL(grid_scan_kernel, dim3((unsigned)sbn), dim3(1024), 0, st, ncell, ctx->pc_fill.as<int>(), ctx->pc_start.as<int>());
     hipLaunchKernelGGL(pc::grid_scatter_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, tot, N, ncell,
                        (const int *)ctx->pc_cell.as<int>(), (const int *)ctx->pc_start.as<int>(), ctx->pc_fill.as<int>(), ctx->pc_sorted.as<int>());
     HIPCHK(ctx, hipMemsetAsync(ctx->pc_fill.p, 0, sbn * ncell * 4, st));

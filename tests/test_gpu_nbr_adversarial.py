@@ -2,7 +2,8 @@
 CPU in tests/test_nbrcases_cpu.py).
 
 Whether a collision row is built at all is decided by filters that run before the scan: the segment-box test (nbr_kernel), the cell grid
-with its chord pre-test (grid_prep / grid_bin / grid_fill* / grid_query_kernel) and the close pairs the query hands to the scan.  Each must
+with its chord pre-test (csrc/dmpc_lists.hip: grid_prep / grid_bin / grid_fill* / grid_query_kernel and the device functions both builds share --
+box_cell, chord_record, nbrmajor_word; the grid itself is checked in tests/test_gpu_grid_build.py) and the close pairs the query hands to the scan.  Each must
 return a superset of what the whole-table walk selects, so every output word of every leg must equal the walk's (option no_cull).  The fp64
 walk itself is tied to the CPU oracle -- an independent fp64 statement of the selection: identical branch records, trajectories to 1e-9 --
 because equality with the walk alone cannot see a mistake the walk shares.

@@ -15,9 +15,12 @@ from multiagent_planning_amd import workload as wl
 pytestmark = pytest.mark.gpu
 
 
-def _steps(variant, kw, po, pf, nsteps, precision="f64", table=None, **opts):
-    """closed-loop steps from rest at po; table: the first step's prediction table instead of initDMPC's straight lines"""
+def _steps(variant, kw, po, pf, nsteps, precision="f64", table=None, keep=None, **opts):
+    """closed-loop steps from rest at po; table: the first step's prediction table instead of initDMPC's straight lines; keep: a list the
+    context is appended to, armed to keep its grid's half extents (tests/test_gpu_grid_build.py reads its grid afterwards)"""
     d = mp.Dmpc(variant, precision=precision, **kw)
+    if keep is not None:
+        keep.append(d.debug_watch_grid())
     for k_, v_ in opts.items():
         d.debug_option(k_, v_)
     l = d.init_batch(po, pf)[0] if table is None else table
