@@ -621,6 +621,32 @@ DMPC_API int dmpc_random_exchange(dmpc_ctx *ctx, int S, int N, const double *pmi
 DMPC_API int dmpc_random_sets_device(dmpc_ctx *ctx, int S, int N, const double *pmin, const double *pmax, double rmin, double c,
                             uint64_t seed, int exchange, double *d_po_pf, void *stream);
 
+/* Goal assignment ahead of a transition: S scenes of N agents at po and N goals, both [S][N][3]; which agent takes which goal is the
+ * library's choice: the permutation that minimises sum_i c(i, perm[i]), c(i,j) = |E1 (po_i - g_j)|^2 with E1 = diag(1,1,1/c) of the context's
+ * parameters -- the metric of the collision ellipsoid.  For that labelling (po_i - po_j)' E1^2 (g_i - g_j) >= 0 for every pair, so two agents
+ * on initDMPC's straight lines never come closer than min(|po_i - po_j|, |g_i - g_j|) / sqrt(2) in that metric.  No reference counterpart.
+ * The rule is pinned so that the result depends on nothing but the inputs (tests/assign.py restates it; the device equals it bit for bit):
+ *   cost      cinv = 1.0 / c; dx, dy = po_i - g_j; dz = (po_i - g_j)_z * cinv; c(i,j) = (dx*dx + dy*dy) + dz*dz, each operation rounded on its own
+ *   solver    forward auction with eps-scaling in synchronous (Jacobi) rounds: cmax = max c(i,j); price = 0;
+ *             e = cmax / 4; while (e > eps) { phase(e); e = e / 4; } phase(eps).  A phase unassigns every agent, keeps the prices, and runs
+ *             rounds until no agent is unassigned.
+ *   round     every agent i unassigned at its start takes m_j = c(i,j) + price[j] over all goals; j1 = the smallest m_j (ties: the smallest j),
+ *             m2 = the smallest over j != j1; it bids (price[j1] + (m2 - m_j1)) + e for j1 (N == 1: price[0] + e).  After all bids every goal that
+ *             received one goes to the highest bidder (ties: the smallest i), its price becomes that bid, its previous owner is unassigned.
+ *   cap       rounds counts the rounds of all phases; a scene that would need more than max_rounds (<= 0: 1 << 20) stops and reports
+ *             rounds = -1, perm = -1 everywhere, cost = NaN and pf_assigned zero (price: as the rounds left it); the other scenes are unaffected.
+ * On return m_perm[i] - min_j m_j <= eps for every agent up to rounding, hence a total within N eps of the optimum.
+ * perm [S][N] (the goal of agent i), pf_assigned [S][N][3] = goals[perm[i]], price [S][N] (per goal), cost [S] = sum of c(i, perm[i]) in
+ * increasing i, rounds [S]; any output may be NULL.  fp64 whatever the context's precision; a DMPC_DEVICE_ALL context runs the call on its
+ * first GPU; a fleet with uncommanded vehicles passes its commanded agents only.  Refused (-1, nothing launched): S < 1, N < 1, po or goals
+ * NULL, eps not a finite positive number.
+ * The _device form takes device pointers and enqueues on the caller's stream; scenes of more than 1024 agents take round launches, whose
+ * done flags the host reads window by window, so for them the call returns only once every scene has finished. */
+DMPC_API int dmpc_assign_goals(dmpc_ctx *ctx, int S, int N, const double *po, const double *goals, double eps, int max_rounds,
+                      int32_t *perm, double *pf_assigned, double *price, double *cost, int32_t *rounds);
+DMPC_API int dmpc_assign_goals_device(dmpc_ctx *ctx, int S, int N, const double *po, const double *goals, double eps, int max_rounds,
+                             int32_t *perm, double *pf_assigned, double *price, double *cost, int32_t *rounds, void *stream);
+
 /* Standalone forms of the path's small helpers (fused into the step kernels inside the solvers), for callers that
  * invoke them on their own as the reference's scripts do.  Host pointers, synchronous.
  *   dmpc_prop_state   propStatedmpc.m:1-8 (A_initp given): p = A_p a + A_initp [po;vo], v = A_v a + 1 (x) vo  -> pass

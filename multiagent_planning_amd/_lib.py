@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "dmpc_transition_mission",
     "dmpc_postcheck_setpoints",
     "dmpc_transition_hold",
+    "dmpc_assign_goals", "dmpc_assign_goals_device",
 ]
 
 
@@ -143,6 +144,9 @@ def load():
     # flight setpoints p, v, a at 100 Hz and the limits report (additive, still revision 8)
     L.dmpc_postcheck_setpoints.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
                                            dp, dp, dp, dp, ip, dp, ip, dp, dp, ip]
+    # goal assignment ahead of a transition (additive, still revision 8)
+    L.dmpc_assign_goals.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int, ip, dp, dp, dp, ip]
+    L.dmpc_assign_goals_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -405,8 +409,35 @@ class Dmpc:
                                                _ip(used), _ip(sst), _ip(stage_col), _ip(cnt), _ip(first), _ip(log)))
         return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, stage_col=stage_col, hold_count=cnt, hold_first=first, agent_status=log)
 
-    def transition(self, po, pf, K_T_max, error_tol=0.01, histories=True, path=None, on_fail="stop", max_hold=14):
+    def assign(self, po, goals, eps=None, max_rounds=0):
+        """dmpc_assign_goals: which agent takes which goal.  po, goals [S,N,3] (or [N,3]); the permutation that minimises the sum of
+        |E1 (po_i - goals_perm[i])|^2, E1 = diag(1,1,1/c) of the context's parameters, by the forward auction include/dmpc_hip.h pins, to within
+        N eps of the optimum.  eps=None means 1e-4 / N, so that the total is within 1e-4 m^2 of optimal: an interface choice, not a measurement.
+        max_rounds <= 0: 1 << 20.  Returns dict(perm [S,N] int32 (the goal of agent i), pf [S,N,3] = goals[perm], price [S,N] (per goal),
+        cost [S], rounds [S]); a scene that met the round cap has rounds = -1, perm = -1, cost = NaN and pf zero."""
+        po, goals = _f(po), _f(goals)
+        if po.ndim not in (2, 3) or po.shape != goals.shape or po.shape[-1] != 3:
+            raise DmpcError(f"assign: po {tuple(po.shape)} and goals {tuple(goals.shape)} must both be [S,N,3] (or [N,3])")
+        lead = po.shape[:-1]
+        S, N = (1, lead[0]) if len(lead) == 1 else lead
+        eps = 1e-4 / max(N, 1) if eps is None else float(eps)
+        perm, pf, price = np.zeros(lead, dtype=np.int32), np.zeros(lead + (3,)), np.zeros(lead)
+        cost, rounds = np.zeros(lead[:-1]), np.zeros(lead[:-1], dtype=np.int32)
+        self._chk(self._L.dmpc_assign_goals(self._ctx, int(S), int(N), _dp(po), _dp(goals), eps, int(max_rounds), _ip(perm), _dp(pf), _dp(price),
+                                            _dp(cost), _ip(rounds)))
+        return dict(perm=perm, pf=pf, price=price, cost=cost, rounds=rounds)
+
+    def _assigned(self, what, start, goals):
+        """assign() for transition() / mission(): a scene that met the round cap has no labelling to fly"""
+        a = self.assign(start, goals)
+        if (np.asarray(a["rounds"]) < 0).any():
+            raise DmpcError(f"{what}: the goal assignment met its round cap")
+        return a
+
+    def transition(self, po, pf, K_T_max, error_tol=0.01, histories=True, path=None, on_fail="stop", max_hold=14, assign=False):
         """histories=False: pk/vk/ak are not downloaded (they stay on the device for postcheck()).
+        assign=True: the goals are a formation, not a labelling: the commanded agents are assigned to them first (assign(), default eps), agent i
+        flies to pf[perm[i]], and the dict also has perm.
         on_fail="hold" (dmpc_transition_hold; "stop": the entries below, unchanged): an agent whose solve failed flies its previous plan, shifted
         by one entry and with a braking tail, for up to max_hold consecutive columns while the scene goes on; the dict then also has hold_count,
         hold_first (per agent) and agent_status (per agent and column: the raw status, ST_HELD where held), and scene_status carries ST_HELD.
@@ -415,6 +446,15 @@ class Dmpc:
         path [S,M,P,3] (or [M,P,3]; dmpc_transition_scripted): M scripted vehicles behind the commanded agents of po / pf (same agent count in
         both), sample t of a path = the vehicle's position at history column t, held at its last sample once the path has ended."""
         po, pf = _f(po), _f(pf)
+        if assign:
+            if pf.size == po.size:
+                pf = pf.reshape(po.shape)
+            if pf.ndim != po.ndim or pf.ndim not in (2, 3) or pf.shape[-1] != 3 or pf.shape[-2] > po.shape[-2]:
+                raise DmpcError(f"transition: with assign, pf {tuple(pf.shape)} must cover the first agents of po {tuple(po.shape)}")
+            a = self._assigned("transition", po[..., :pf.shape[-2], :], pf)
+            out = self.transition(po, a["pf"], K_T_max, error_tol, histories, path, on_fail, max_hold)
+            out["perm"] = a["perm"]
+            return out
         if on_fail not in ("stop", "hold"):
             raise DmpcError(f"transition: on_fail is 'stop' or 'hold', not {on_fail!r}")
         if path is not None:
@@ -458,18 +498,30 @@ class Dmpc:
                                                   _ip(used), _ip(sst)))
         return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst)
 
-    def mission(self, po, goals, K_T_max, error_tol=0.01, histories=True, deadline=None, path=None, on_fail="stop", max_hold=14):
+    def mission(self, po, goals, K_T_max, error_tol=0.01, histories=True, deadline=None, path=None, on_fail="stop", max_hold=14, assign=False):
         """dmpc_transition_mission: one transition through the Q goal sets goals [Q,N_cmd,3] (next to an unbatched po) or [S,Q,N_cmd,3].  A stage
         ends at the first column where its goals are reached or -- deadline [Q] / [S,Q], 0 = none, the last 0 -- its deadline has passed; the
         next step is solved with the next goal set, the last stage ends the trial.  po with MORE vehicles than the goals: static vehicles, as
         transition(); path [S,M,P,3]: scripted vehicles, po then covers the commanded agents.  Returns what transition() returns, and stage_col
         [S,Q]: the column each stage ended on (-1: it never did).  on_fail, max_hold: as transition() (a held plan counts as a solved one in the
-        stage rule)."""
+        stage rule).  assign=True: every goal set is a formation: the commanded agents are assigned to goals[0] from po, then stage by stage -- the
+        assigned goals of stage q are the starts of stage q+1 -- and the dict also has perm [S,Q,N_cmd]."""
         po, goals = _f(po), _f(goals)
         if on_fail not in ("stop", "hold"):
             raise DmpcError(f"mission: on_fail is 'stop' or 'hold', not {on_fail!r}")
         if po.ndim not in (2, 3) or goals.ndim != po.ndim + 1 or po.shape[-1] != 3 or goals.shape[-1] != 3 or goals.shape[:-3] != po.shape[:-2]:
             raise DmpcError(f"mission: goals {tuple(goals.shape)} must be [Q,N_cmd,3] next to po [N,3], or [S,Q,N_cmd,3] next to po [S,N,3]: po is {tuple(po.shape)}")
+        if assign:
+            if not 1 <= goals.shape[-2] <= po.shape[-2]:
+                raise DmpcError(f"mission: goals have {goals.shape[-2]} agents, po {po.shape[-2]}: the commanded agents are the FIRST N_cmd <= N vehicles")
+            start, flown, perms = po[..., :goals.shape[-2], :], np.empty_like(goals), []
+            for q in range(goals.shape[-3]):
+                a = self._assigned("mission", start, goals[..., q, :, :])
+                start = flown[..., q, :, :] = a["pf"]
+                perms.append(a["perm"])
+            out = self.mission(po, flown, K_T_max, error_tol, histories, deadline, path, on_fail, max_hold)
+            out["perm"] = np.stack(perms, axis=-2)
+            return out
         S = 1 if po.ndim == 2 else po.shape[0]
         Q, n_cmd, N = goals.shape[-3], goals.shape[-2], po.shape[-2]
         lead = po.shape[:-2] + (n_cmd,)
@@ -781,6 +833,11 @@ class Dmpc:
 
     def advance_device(self, count, p_out, v_out, a_out, status, x_p, x_v, x_a, stream=0):
         self._chk(self._L.dmpc_advance_device(self._ctx, count, p_out, v_out, a_out, status, x_p, x_v, x_a, stream or None))
+
+    def assign_goals_device(self, S, N, po, goals, eps, max_rounds=0, perm=0, pf=0, price=0, cost=0, rounds=0, stream=0):
+        """dmpc_assign_goals_device: po, goals [S,N,3] fp64 and the outputs (0: not wanted; perm, rounds int32) on the device"""
+        self._chk(self._L.dmpc_assign_goals_device(self._ctx, S, N, po, goals, float(eps), int(max_rounds), perm or None, pf or None, price or None,
+                                                   cost or None, rounds or None, stream or None))
 
     def profile(self, enable=True):
         self._chk(self._L.dmpc_profile(self._ctx, 1 if enable else 0))

@@ -147,6 +147,10 @@ struct dmpc_ctx {
     int hist_S = 0, hist_N = 0, hist_KT = 0;   // shape of the histories left resident by the last dmpc_transition
     int32_t *flags_host = nullptr; size_t flags_host_cap = 0;   // pinned: per-step verdicts of dmpc_transition
     hipEvent_t flag_ev[2] = {nullptr, nullptr};
+    DevBuf asg_io, asg_work;                                               // dmpc_assign_goals: staged inputs / outputs of the host form; scratch of the round launches
+    int32_t *asg_host = nullptr; size_t asg_host_cap = 0;                  // pinned: the scenes' done flags of two windows of rounds
+    hipEvent_t asg_ev[2] = {nullptr, nullptr};
+    int max_lds_assign = 0;  // dynamic-LDS limit assign_one_kernel was last raised to
     int pc_fallback_scenes = 0;   // last dmpc_postcheck: scenes of a cell-grid search that were searched again by brute force
     std::vector<dmpc_ctx *> children;   // further contexts (own stream and buffers) for the other parts of a split batch of transitions
     std::vector<int> split_at;          // non-empty: the last dmpc_transition left scenes [split_at[i], split_at[i+1]) in part i (0: here, i > 0: children[i-1])
@@ -582,6 +586,8 @@ extern "C" void dmpc_destroy(dmpc_ctx *ctx)
     for (auto &ev : ctx->ev_pool) { (void)hipEventDestroy(ev.t0); (void)hipEventDestroy(ev.t1); (void)hipEventDestroy(ev.t2); }
     for (int u = 0; u < 2; ++u) if (ctx->flag_ev[u]) (void)hipEventDestroy(ctx->flag_ev[u]);
     if (ctx->flags_host) (void)hipHostFree(ctx->flags_host);
+    for (int u = 0; u < 2; ++u) if (ctx->asg_ev[u]) (void)hipEventDestroy(ctx->asg_ev[u]);
+    if (ctx->asg_host) (void)hipHostFree(ctx->asg_host);
     if (ctx->dbg) (void)hipFree(ctx->dbg);
     if (ctx->d_tables) (void)hipFree(ctx->d_tables);
     hipStream_t st = ctx->stream;
@@ -1263,6 +1269,8 @@ extern "C" int dmpc_random_sets_device(dmpc_ctx *ctx, int S, int N, const double
     return random_sets(ctx, "dmpc_random_sets_device", S, N, pmin, pmax, rmin, exchange ? 1.0 : c, seed, exchange ? 1 : 0, d_po_pf,
                        (hipStream_t)stream);
 }
+
+#include "dmpc_assign.hip"   // goal assignment: the auction's kernels and the two entries
 
 
 // ---------------------------------------------------------------------------------------------

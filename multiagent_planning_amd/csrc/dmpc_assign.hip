@@ -1,0 +1,490 @@
+// dmpc_assign.hip -- goal assignment ahead of a transition: which agent takes which point of the next formation (dmpc_assign_goals).
+//
+// There is no reference counterpart (randomTest.m / randomExchange.m hand out labelled goals).  The rule is pinned in include/dmpc_hip.h and
+// restated in numpy by tests/assign.py, which the device must equal bit for bit: the forward auction with eps-scaling in synchronous
+// (Jacobi) rounds over the cost c(i,j) = |E1 (po_i - g_j)|^2, E1 = diag(1,1,1/c).  Nothing in the result depends on launch geometry, batch
+// size or the order the device visits anything in:
+//   bidding     one wave per unassigned agent (a compacted list), lanes stride over the goals (SoA in LDS: coordinates + price, 32 B per
+//               goal), per-lane top-2 of m = c + price, then a wave butterfly that merges by the total order (m ascending, j ascending)
+//   resolution  bids are positive doubles, their bit patterns order as unsigned integers: atomicMax per goal finds the winning bid,
+//               atomicMin over the bidders that made it finds the smallest agent
+//   no dense cost matrix: costs are recomputed from the 3 + 1 doubles per goal
+// Scenes of up to DMPC_ASSIGN_ONE_LAUNCH_MAX agents run in ONE launch (assign_one_kernel: one workgroup per scene, everything in LDS,
+// workgroup barriers between the stages of a round).  Larger scenes take two launches per round (assign_bid_kernel streams the goals through
+// LDS tile by tile, 16 bidders share a tile; assign_settle_kernel, one workgroup per scene, resolves, applies and keeps the phase state) and
+// the host reads the scenes' done flags one window of rounds behind, as dmpc_transition reads its verdicts.
+//
+// Included into dmpc_api.hip (single translation unit).  Every kernel rounds each operation on its own (fp contraction off).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace asg {
+
+constexpr int ONE_MAX = DMPC_ASSIGN_ONE_LAUNCH_MAX;
+constexpr int TILE = 2048;          // goals per LDS tile of assign_bid_kernel (64 KB)
+constexpr int BID_WAVES = 16;       // bidders that share a tile
+constexpr int WINDOW = 64;          // rounds the host launches between two looks at the done flags
+constexpr int NONE = 0x7fffffff;
+constexpr int DEFAULT_ROUNDS = 1 << 20;
+constexpr size_t ONE_LDS_PER_AGENT = 9 * 8 + 6 * 4;   // assign_one_kernel: 9 doubles and 6 ints per agent
+
+struct Best { double m1, m2; int j1; };   // smallest m, smallest m over j != j1, the goal of m1
+
+struct State {                      // of one scene, between the round launches
+    unsigned long long cmax_bits;
+    double e;
+    int cnt, cur, rounds, last;     // bidders of the next round, which half of `list` holds them, rounds so far, this phase runs at eps
+};
+
+struct Work {                       // scratch of the round launches, [S][N] each ([S][2][N]: list)
+    double *price, *bidv;
+    unsigned long long *bidval;
+    int *owner, *assigned, *bidwin, *bidj, *list;
+    State *state;
+    int *done;                      // [S] 0: running, 1: finished, -1: stopped at the round cap
+};
+
+__device__ inline double pair_cost(double px, double py, double pz, double gx, double gy, double gz, double cinv)
+{
+#pragma clang fp contract(off)
+    const double dx = px - gx, dy = py - gy, dz = (pz - gz) * cinv;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// lanes stride over goals jbase .. jbase + n - 1 (ascending per lane: a strict < keeps the smallest j of equal values)
+__device__ inline void scan_goals(Best &b, int lane, int n, int jbase, const double *gx, const double *gy, const double *gz, const double *pr,
+                                  double px, double py, double pz, double cinv)
+{
+#pragma clang fp contract(off)
+    for (int j = lane; j < n; j += 64) {
+        const double m = pair_cost(px, py, pz, gx[j], gy[j], gz[j], cinv) + pr[j];
+        if (m < b.m1) { b.m2 = b.m1; b.m1 = m; b.j1 = jbase + j; }
+        else if (m < b.m2) b.m2 = m;
+    }
+}
+
+// the merge is defined by the order (m ascending, j ascending), so every lane ends with the same bits whatever the tree
+__device__ inline Best wave_best(Best b)
+{
+    for (int off = 1; off < 64; off <<= 1) {
+        const double o1 = __shfl_xor(b.m1, off), o2 = __shfl_xor(b.m2, off);
+        const int oj = __shfl_xor(b.j1, off);
+        if (o1 < b.m1 || (o1 == b.m1 && oj < b.j1)) {
+            b.m2 = o2 < b.m1 ? o2 : b.m1;
+            b.m1 = o1; b.j1 = oj;
+        } else {
+            b.m2 = b.m2 < o1 ? b.m2 : o1;
+        }
+    }
+    return b;
+}
+
+__device__ inline double make_bid(const Best &b, double price_j1, double e, int N)
+{
+#pragma clang fp contract(off)
+    return N == 1 ? price_j1 + e : (price_j1 + (b.m2 - b.m1)) + e;
+}
+
+__device__ inline double wave_max(double v)
+{
+    for (int off = 1; off < 64; off <<= 1) { const double o = __shfl_xor(v, off); v = o > v ? o : v; }
+    return v;
+}
+
+// e of the first phase / of the phase after one at e: (e, last)
+__device__ inline void next_e(double cand, double eps, double &e, int &last)
+{
+    if (cand > eps) { e = cand; last = 0; } else { e = eps; last = 1; }
+}
+
+// The resolution of one round by ONE workgroup, on LDS or global arrays alike: lc[0 .. cnt) bid (bidj, bidv; bidval holds every goal's highest
+// bid); the next round's bidders -- losers and displaced owners -- are appended to ln, counted in *n_next (zero on entry).  Leaves bidval / bidwin
+// as it found them (0 / NONE).  A previous owner did not bid and a winner owned nothing, so no two threads write one agent's `assigned`.
+__device__ inline void resolve_round(int cnt, const int *lc, int *ln, int *n_next, int *bidj, const double *bidv, unsigned long long *bidval,
+                                     int *bidwin, int *owner, int *assigned, double *price)
+{
+    const int tid = threadIdx.x, nt = blockDim.x;
+    for (int t = tid; t < cnt; t += nt) {             // the smallest agent among a goal's highest bidders
+        const int i = lc[t], j = bidj[i];
+        if ((unsigned long long)__double_as_longlong(bidv[i]) == bidval[j]) atomicMin(&bidwin[j], i);
+    }
+    __syncthreads();
+    for (int t = tid; t < cnt; t += nt) {             // losers bid again next round
+        const int i = lc[t];
+        if (__hip_atomic_load(&bidwin[bidj[i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != i) { bidj[i] = -1; ln[atomicAdd(n_next, 1)] = i; }
+    }
+    __syncthreads();
+    for (int t = tid; t < cnt; t += nt) {             // winners take their goals
+        const int i = lc[t], j = bidj[i];
+        if (j >= 0) {
+            const int prev = owner[j];
+            if (prev >= 0) { assigned[prev] = -1; ln[atomicAdd(n_next, 1)] = prev; }
+            owner[j] = i; assigned[i] = j; price[j] = bidv[i];
+            bidval[j] = 0ull; bidwin[j] = NONE;
+        }
+    }
+    __syncthreads();
+}
+
+// what a scene stopped at the round cap reports (one workgroup; price: as the rounds left it)
+__device__ inline void write_capped(int N, size_t s, const double *price, int32_t *perm, double *pf, double *price_out, double *cost,
+                                    int32_t *rounds_out)
+{
+    for (int i = threadIdx.x; i < N; i += blockDim.x) {
+        if (perm) perm[s * N + i] = -1;
+        if (pf) { pf[(s * N + i) * 3] = 0.0; pf[(s * N + i) * 3 + 1] = 0.0; pf[(s * N + i) * 3 + 2] = 0.0; }
+        if (price_out) price_out[s * N + i] = price[i];
+    }
+    if (threadIdx.x == 0) { if (cost) cost[s] = __builtin_nan(""); if (rounds_out) rounds_out[s] = -1; }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// N <= ONE_MAX: the whole auction of a scene in one workgroup
+// ---------------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void assign_one_kernel(int N, const double *__restrict__ po, const double *__restrict__ goals, double cinv,
+                                                          double eps, int max_rounds, int32_t *__restrict__ perm, double *__restrict__ pf,
+                                                          double *__restrict__ price_out, double *__restrict__ cost, int32_t *__restrict__ rounds_out)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double sh[];
+    double *gx = sh, *gy = gx + N, *gz = gy + N, *pr = gz + N, *px = pr + N, *py = px + N, *pz = py + N, *bidv = pz + N;
+    unsigned long long *bidval = (unsigned long long *)(bidv + N);
+    int *owner = (int *)(bidval + N), *assigned = owner + N, *bidwin = assigned + N, *bidj = bidwin + N;
+    int *list[2] = {bidj + N, bidj + 2 * (size_t)N};
+    __shared__ unsigned long long s_cmax;
+    __shared__ int s_cnt[2];
+    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
+    const size_t s = blockIdx.x;
+    po += s * N * 3; goals += s * N * 3;
+
+    for (int i = tid; i < N; i += nt) {
+        px[i] = po[3 * i]; py[i] = po[3 * i + 1]; pz[i] = po[3 * i + 2];
+        gx[i] = goals[3 * i]; gy[i] = goals[3 * i + 1]; gz[i] = goals[3 * i + 2];
+        pr[i] = 0.0; bidval[i] = 0ull; bidwin[i] = NONE;
+    }
+    if (tid == 0) { s_cmax = 0ull; s_cnt[0] = s_cnt[1] = 0; }
+    __syncthreads();
+    double mx = 0.0;
+    for (int i = wave; i < N; i += nw)
+        for (int j = lane; j < N; j += 64) {
+            const double c = pair_cost(px[i], py[i], pz[i], gx[j], gy[j], gz[j], cinv);
+            mx = c > mx ? c : mx;
+        }
+    mx = wave_max(mx);
+    if (lane == 0) atomicMax(&s_cmax, (unsigned long long)__double_as_longlong(mx));   // non-negative doubles order like their bit patterns
+    __syncthreads();
+    const double cmax = __longlong_as_double((long long)s_cmax);
+
+    double e; int last;
+    next_e(cmax / 4.0, eps, e, last);
+    int rounds = 0, cur = 0;
+    bool capped = false;
+    for (;;) {                                        // phases
+        for (int i = tid; i < N; i += nt) { assigned[i] = -1; owner[i] = -1; list[cur][i] = i; }
+        int cnt = N;
+        __syncthreads();
+        while (cnt > 0) {                             // rounds
+            if (rounds == max_rounds) { capped = true; break; }
+            ++rounds;
+            const int *lc = list[cur];
+            int *ln = list[cur ^ 1];
+            if (tid == 0) s_cnt[cur ^ 1] = 0;
+            for (int t = wave; t < cnt; t += nw) {    // bids
+                const int i = lc[t];
+                Best b = {__builtin_inf(), __builtin_inf(), NONE};
+                scan_goals(b, lane, N, 0, gx, gy, gz, pr, px[i], py[i], pz[i], cinv);
+                b = wave_best(b);
+                if (lane == 0) {
+                    const int j1 = b.j1 < N ? b.j1 : 0;   // (no finite value anywhere: a scene of NaNs ends at the round cap, inside the arrays)
+                    const double bid = make_bid(b, pr[j1], e, N);
+                    bidj[i] = j1; bidv[i] = bid;
+                    atomicMax(&bidval[j1], (unsigned long long)__double_as_longlong(bid));
+                }
+            }
+            __syncthreads();
+            resolve_round(cnt, lc, ln, &s_cnt[cur ^ 1], bidj, bidv, bidval, bidwin, owner, assigned, pr);
+            cur ^= 1;
+            cnt = s_cnt[cur];
+        }
+        if (capped || last) break;
+        next_e(e / 4.0, eps, e, last);
+    }
+
+    if (capped) { write_capped(N, s, pr, perm, pf, price_out, cost, rounds_out); return; }
+    for (int i = tid; i < N; i += nt) {
+        const int j = assigned[i];
+        if (perm) perm[s * N + i] = j;
+        if (price_out) price_out[s * N + i] = pr[i];
+        if (pf) { pf[(s * N + i) * 3] = gx[j]; pf[(s * N + i) * 3 + 1] = gy[j]; pf[(s * N + i) * 3 + 2] = gz[j]; }
+        bidv[i] = pair_cost(px[i], py[i], pz[i], gx[j], gy[j], gz[j], cinv);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double sum = 0.0;
+        for (int i = 0; i < N; ++i) sum = sum + bidv[i];   // in increasing i, one addition at a time
+        if (cost) cost[s] = sum;
+        if (rounds_out) rounds_out[s] = rounds;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// N > ONE_MAX: round launches
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// grid (G, S), 256 threads: the largest cost of a scene (a maximum: whatever the order)
+__global__ __launch_bounds__(256) void assign_cmax_kernel(int N, const double *__restrict__ po, const double *__restrict__ goals, double cinv, Work w)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t s = blockIdx.y;
+    po += s * N * 3; goals += s * N * 3;
+    double mx = 0.0;
+    for (int i = blockIdx.x * 4 + wave; i < N; i += gridDim.x * 4) {
+        const double x = po[3 * i], y = po[3 * i + 1], z = po[3 * i + 2];
+        for (int j = lane; j < N; j += 64) {
+            const double c = pair_cost(x, y, z, goals[3 * j], goals[3 * j + 1], goals[3 * j + 2], cinv);
+            mx = c > mx ? c : mx;
+        }
+    }
+    mx = wave_max(mx);
+    if (lane == 0) atomicMax(&w.state[s].cmax_bits, (unsigned long long)__double_as_longlong(mx));
+}
+
+// every agent unassigned, every goal free, the bidders' list = everybody (one workgroup of a scene; the caller synchronises)
+__device__ inline void phase_reset(int N, size_t s, const Work &w, int cur)
+{
+    for (int i = threadIdx.x; i < N; i += blockDim.x) {
+        w.assigned[s * N + i] = -1; w.owner[s * N + i] = -1; w.list[(s * 2 + cur) * N + i] = i;
+    }
+}
+
+// grid S, 1024 threads: prices zero, the first phase
+__global__ __launch_bounds__(1024) void assign_begin_kernel(int N, double eps, Work w)
+{
+    const size_t s = blockIdx.x;
+    for (int i = threadIdx.x; i < N; i += blockDim.x) { w.price[s * N + i] = 0.0; w.bidval[s * N + i] = 0ull; w.bidwin[s * N + i] = NONE; }
+    phase_reset(N, s, w, 0);
+    if (threadIdx.x == 0) {
+        State &st = w.state[s];
+        next_e(__longlong_as_double((long long)st.cmax_bits) / 4.0, eps, st.e, st.last);
+        st.cnt = N; st.cur = 0; st.rounds = 0;
+        w.done[s] = 0;
+    }
+}
+
+// grid (G, S), BID_WAVES waves: one wave per bidder of the scene's list, the goals streamed through LDS in tiles the workgroup's bidders share
+__global__ __launch_bounds__(BID_WAVES * 64) void assign_bid_kernel(int N, const double *__restrict__ po, const double *__restrict__ goals,
+                                                                    double cinv, Work w)
+{
+#pragma clang fp contract(off)
+    __shared__ double gx[TILE], gy[TILE], gz[TILE], pr[TILE];
+    const size_t s = blockIdx.y;
+    if (w.done[s]) return;
+    const State st = w.state[s];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int *lc = w.list + (s * 2 + st.cur) * N;
+    const double *price = w.price + s * N;
+    po += s * N * 3; goals += s * N * 3;
+    for (int chunk = blockIdx.x; chunk * BID_WAVES < st.cnt; chunk += gridDim.x) {
+        const int t = chunk * BID_WAVES + wave;
+        const bool active = t < st.cnt;
+        const int i = active ? lc[t] : 0;
+        const double x = po[3 * i], y = po[3 * i + 1], z = po[3 * i + 2];
+        Best b = {__builtin_inf(), __builtin_inf(), NONE};
+        for (int base = 0; base < N; base += TILE) {
+            const int n = N - base < TILE ? N - base : TILE;
+            __syncthreads();
+            for (int j = tid; j < n; j += BID_WAVES * 64) {
+                gx[j] = goals[3 * (size_t)(base + j)]; gy[j] = goals[3 * (size_t)(base + j) + 1]; gz[j] = goals[3 * (size_t)(base + j) + 2];
+                pr[j] = price[base + j];
+            }
+            __syncthreads();
+            if (active) scan_goals(b, lane, n, base, gx, gy, gz, pr, x, y, z, cinv);
+        }
+        if (active) {
+            b = wave_best(b);
+            if (lane == 0) {
+                const int j1 = b.j1 < N ? b.j1 : 0;
+                const double bid = make_bid(b, price[j1], st.e, N);
+                w.bidj[s * N + i] = j1; w.bidv[s * N + i] = bid;
+                atomicMax(&w.bidval[s * N + j1], (unsigned long long)__double_as_longlong(bid));
+            }
+        }
+    }
+}
+
+// grid S, 1024 threads: the round's resolution, the next round's bidders, the phase schedule, the round cap and -- once -- the outputs
+__global__ __launch_bounds__(1024) void assign_settle_kernel(int N, const double *__restrict__ po, const double *__restrict__ goals, double cinv,
+                                                             double eps, int max_rounds, Work w, int32_t *__restrict__ perm,
+                                                             double *__restrict__ pf, double *__restrict__ price_out, double *__restrict__ cost,
+                                                             int32_t *__restrict__ rounds_out)
+{
+#pragma clang fp contract(off)
+    __shared__ int s_cnt;
+    __shared__ double s_part[1024];
+    const size_t s = blockIdx.x;
+    if (w.done[s]) return;
+    const State st = w.state[s];
+    const int tid = threadIdx.x;
+    const int *lc = w.list + (s * 2 + st.cur) * N;
+    int *ln = w.list + (s * 2 + (st.cur ^ 1)) * N;
+    double *price = w.price + s * N, *bidv = w.bidv + s * N;
+    unsigned long long *bidval = w.bidval + s * N;
+    int *owner = w.owner + s * N, *assigned = w.assigned + s * N, *bidwin = w.bidwin + s * N, *bidj = w.bidj + s * N;
+    po += s * N * 3; goals += s * N * 3;
+    if (tid == 0) s_cnt = 0;                          // (first added to behind resolve_round's first barrier)
+    resolve_round(st.cnt, lc, ln, &s_cnt, bidj, bidv, bidval, bidwin, owner, assigned, price);
+    const int cnt = s_cnt, rounds = st.rounds + 1;
+    if (cnt > 0 || !st.last) {                        // another round
+        const bool capped = rounds == max_rounds;
+        double e = st.e; int last = st.last, cur = st.cur ^ 1, next_cnt = cnt;
+        if (cnt == 0 && !capped) {                    // ... of the next phase
+            next_e(st.e / 4.0, eps, e, last);
+            phase_reset(N, s, w, cur);
+            next_cnt = N;
+        }
+        if (capped) write_capped(N, s, price, perm, pf, price_out, cost, rounds_out);
+        if (tid == 0) {
+            State &o = w.state[s];
+            o.e = e; o.last = last; o.cur = cur; o.cnt = next_cnt; o.rounds = rounds;
+            if (capped) w.done[s] = -1;
+        }
+        return;
+    }
+    // finished: the outputs; the cost in increasing i, one addition at a time (thread 0, the terms staged 1024 at a time)
+    double sum = 0.0;
+    for (int base = 0; base < N; base += 1024) {
+        const int i = base + tid;
+        if (i < N) {
+            const int j = assigned[i];
+            if (perm) perm[s * N + i] = j;
+            if (pf) { pf[(s * N + i) * 3] = goals[3 * j]; pf[(s * N + i) * 3 + 1] = goals[3 * j + 1]; pf[(s * N + i) * 3 + 2] = goals[3 * j + 2]; }
+            if (price_out) price_out[s * N + i] = price[i];
+            s_part[tid] = pair_cost(po[3 * i], po[3 * i + 1], po[3 * i + 2], goals[3 * j], goals[3 * j + 1], goals[3 * j + 2], cinv);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const int n = N - base < 1024 ? N - base : 1024;
+            for (int k = 0; k < n; ++k) sum = sum + s_part[k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        w.state[s].rounds = rounds;
+        w.done[s] = 1;
+        if (cost) cost[s] = sum;
+        if (rounds_out) rounds_out[s] = rounds;
+    }
+}
+
+}   // namespace asg
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------------------------------------------------------------------
+static int assign_check(dmpc_ctx *ctx, const char *who, int S, int N, const void *po, const void *goals, double eps)
+{
+    if (!ctx) { g_err = std::string(who) + ": ctx is NULL"; return -1; }
+    if (S < 1 || N < 1) FAIL(ctx, std::string(who) + ": S and N must be at least 1");
+    if (!po || !goals) FAIL(ctx, std::string(who) + ": po and goals must be given");
+    if (!(eps > 0) || !std::isfinite(eps)) FAIL(ctx, std::string(who) + ": eps must be a finite positive number");
+    return 0;
+}
+
+// the auction on device arrays, enqueued on st.  Scenes above the one-launch boundary: the host waits for the done flags of each window of
+// rounds while the next window is already enqueued, so the call returns with at most the last window's (idle) launches still in flight.
+static int assign_run(dmpc_ctx *ctx, int S, int N, const double *po, const double *goals, double eps, int max_rounds, int32_t *perm, double *pf,
+                      double *price, double *cost, int32_t *rounds, hipStream_t st)
+{
+    const double cinv = 1.0 / ctx->prm.c;
+    const int cap = max_rounds <= 0 ? asg::DEFAULT_ROUNDS : max_rounds;
+    if (N <= asg::ONE_MAX) {
+        const int lds = (int)(asg::ONE_LDS_PER_AGENT * (size_t)N);
+        if (lds > ctx->max_lds_assign) {
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)asg::assign_one_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            ctx->max_lds_assign = lds;
+        }
+        hipLaunchKernelGGL(asg::assign_one_kernel, dim3((unsigned)S), dim3(N <= 256 ? 256 : 1024), (size_t)lds, st, N, po, goals, cinv, eps, cap,
+                           perm, pf, price, cost, rounds);
+        HIPCHK(ctx, hipGetLastError());
+        return 0;
+    }
+    const size_t SN = (size_t)S * N;
+    // price, bidv, bidval [SN] x 8 | owner, assigned, bidwin, bidj [SN] x 4, list [2 SN] x 4 | state [S] | done [S]
+    const size_t bytes = SN * 48 + (size_t)S * sizeof(asg::State) + (size_t)S * 4;
+    if (ctx->asg_work.ensure(bytes)) FAIL(ctx, "device allocation failed");
+    asg::Work w;
+    w.price = ctx->asg_work.as<double>(); w.bidv = w.price + SN; w.bidval = (unsigned long long *)(w.bidv + SN);
+    w.owner = (int *)(w.bidval + SN); w.assigned = w.owner + SN; w.bidwin = w.assigned + SN; w.bidj = w.bidwin + SN; w.list = w.bidj + SN;
+    w.state = (asg::State *)(w.list + 2 * SN); w.done = (int *)(w.state + S);
+    if (ctx->asg_host_cap < (size_t)2 * S) {
+        if (ctx->asg_host) (void)hipHostFree(ctx->asg_host);
+        ctx->asg_host = nullptr; ctx->asg_host_cap = 0;
+        HIPCHK(ctx, hipHostMalloc((void **)&ctx->asg_host, (size_t)2 * S * 4, hipHostMallocDefault));
+        ctx->asg_host_cap = (size_t)2 * S;
+    }
+    for (int u = 0; u < 2; ++u)
+        if (!ctx->asg_ev[u]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->asg_ev[u], hipEventDisableTiming));
+    HIPCHK(ctx, hipMemsetAsync(w.state, 0, (size_t)S * sizeof(asg::State), st));
+    const unsigned g_rows = (unsigned)std::min((N + 3) / 4, 1024), g_bid = (unsigned)std::min((N + asg::BID_WAVES - 1) / asg::BID_WAVES, 512);
+    hipLaunchKernelGGL(asg::assign_cmax_kernel, dim3(g_rows, (unsigned)S), dim3(256), 0, st, N, po, goals, cinv, w);
+    hipLaunchKernelGGL(asg::assign_begin_kernel, dim3((unsigned)S), dim3(1024), 0, st, N, eps, w);
+    HIPCHK(ctx, hipGetLastError());
+    long launched = 0;
+    for (int k = 0;; ++k) {
+        for (int r = 0; r < asg::WINDOW; ++r) {
+            hipLaunchKernelGGL(asg::assign_bid_kernel, dim3(g_bid, (unsigned)S), dim3(asg::BID_WAVES * 64), 0, st, N, po, goals, cinv, w);
+            hipLaunchKernelGGL(asg::assign_settle_kernel, dim3((unsigned)S), dim3(1024), 0, st, N, po, goals, cinv, eps, cap, w, perm, pf, price,
+                               cost, rounds);
+        }
+        HIPCHK(ctx, hipGetLastError());
+        launched += asg::WINDOW;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->asg_host + (size_t)(k & 1) * S, w.done, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipEventRecord(ctx->asg_ev[k & 1], st));
+        bool over = launched >= (long)cap;            // every scene has finished or met the cap by now
+        if (!over && k >= 1) {                        // the window before this one
+            HIPCHK(ctx, hipEventSynchronize(ctx->asg_ev[(k - 1) & 1]));
+            const int32_t *d = ctx->asg_host + (size_t)((k - 1) & 1) * S;
+            over = true;
+            for (int s = 0; s < S; ++s) over = over && d[s] != 0;
+        }
+        if (over) {
+            HIPCHK(ctx, hipEventSynchronize(ctx->asg_ev[k & 1]));   // the pinned flags are at rest when the call returns
+            if (k >= 1) HIPCHK(ctx, hipEventSynchronize(ctx->asg_ev[(k - 1) & 1]));
+            break;
+        }
+    }
+    return 0;
+}
+
+extern "C" int dmpc_assign_goals_device(dmpc_ctx *ctx, int S, int N, const double *po, const double *goals, double eps, int max_rounds,
+                                        int32_t *perm, double *pf_assigned, double *price, double *cost, int32_t *rounds, void *stream)
+{
+    if (assign_check(ctx, "dmpc_assign_goals_device", S, N, po, goals, eps)) return -1;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return assign_run(ctx, S, N, po, goals, eps, max_rounds, perm, pf_assigned, price, cost, rounds, (hipStream_t)stream);
+}
+
+extern "C" int dmpc_assign_goals(dmpc_ctx *ctx, int S, int N, const double *po, const double *goals, double eps, int max_rounds, int32_t *perm,
+                                 double *pf_assigned, double *price, double *cost, int32_t *rounds)
+{
+    if (assign_check(ctx, "dmpc_assign_goals", S, N, po, goals, eps)) return -1;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t SN = (size_t)S * N;
+    // po, goals, pf [SN][3] | price [SN] | cost [S] | perm [SN] | rounds [S]
+    if (ctx->asg_io.ensure(SN * 84 + (size_t)S * 12)) FAIL(ctx, "device allocation failed");
+    double *d_po = ctx->asg_io.as<double>(), *d_g = d_po + 3 * SN, *d_pf = d_g + 3 * SN, *d_price = d_pf + 3 * SN, *d_cost = d_price + SN;
+    int32_t *d_perm = (int32_t *)(d_cost + S), *d_rounds = d_perm + SN;
+    HIPCHK(ctx, hipMemcpyAsync(d_po, po, SN * 24, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(d_g, goals, SN * 24, hipMemcpyHostToDevice, st));
+    if (assign_run(ctx, S, N, d_po, d_g, eps, max_rounds, perm ? d_perm : nullptr, pf_assigned ? d_pf : nullptr, price ? d_price : nullptr,
+                   cost ? d_cost : nullptr, rounds ? d_rounds : nullptr, st))
+        return -1;
+    if (perm) HIPCHK(ctx, hipMemcpyAsync(perm, d_perm, SN * 4, hipMemcpyDeviceToHost, st));
+    if (pf_assigned) HIPCHK(ctx, hipMemcpyAsync(pf_assigned, d_pf, SN * 24, hipMemcpyDeviceToHost, st));
+    if (price) HIPCHK(ctx, hipMemcpyAsync(price, d_price, SN * 8, hipMemcpyDeviceToHost, st));
+    if (cost) HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+    if (rounds) HIPCHK(ctx, hipMemcpyAsync(rounds, d_rounds, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}

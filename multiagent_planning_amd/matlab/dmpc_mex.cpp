@@ -22,6 +22,8 @@
 //   Ain            = dmpc_mex('rows_dense', params, xi, kc, A)                          -diff_mat*A of structured rows
 //   [pk,vk,ak,K_T_used,scene_status] = dmpc_mex('transition', params, po, pf, K_T_max, error_tol)   the whole k-loop on the GPU
 //   [pk,vk,ak,K_T_used,scene_status,stage_col] = dmpc_mex('mission', params, po, goals, K_T_max, error_tol[, deadline])   goals 3 x N_cmd x Q: see below
+//   [perm,pf,cost,rounds] = dmpc_mex('assign', params, po, goals[, eps[, max_rounds]])  goal assignment (dmpc_assign_goals): po, goals 3 x N; perm 1 x N, 1-based:
+//                                                                                    agent i takes goals(:,perm(i)) = pf(:,i); eps default 1e-4 / N
 //   inbounds       = dmpc_mex('is_inbounds', params, p, pmin, pmax)                    is_inbounds.m
 //   pass           = dmpc_mex('reached_goal', params, p, pf, error_tol)                ReachedGoal.m
 //   tol            = dmpc_mex('max_deviation', params, p, prev_p)                      maxDeviation.m (p, prev_p: 3 x K)
@@ -455,6 +457,26 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
             plhs[5] = mxCreateDoubleMatrix(1, (mwSize)Q, mxREAL);
             for (int q = 0; q < Q; ++q) mxGetPr(plhs[5])[q] = (double)col[(size_t)q];
         }
+        return;
+    }
+    if (!std::strcmp(cmd, "assign")) {   // which agent takes which goal (dmpc_assign_goals); a scene that met the round cap: perm 0, cost NaN, rounds -1
+        need(nrhs >= 4 && nrhs <= 6, "assign: (cmd, params, po, goals[, eps[, max_rounds]])");
+        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3);
+        need(N >= 1 && mxGetM(prhs[2]) == 3 && mxGetM(prhs[3]) == 3 && mxGetNumberOfElements(prhs[2]) == (size_t)3 * N &&
+             mxGetNumberOfElements(prhs[3]) == (size_t)3 * N, "po and goals must both be 3 x N");
+        const double eps = nrhs > 4 && mxGetNumberOfElements(prhs[4]) > 0 ? mxGetScalar(prhs[4]) : 1e-4 / N;
+        const int max_rounds = nrhs > 5 ? (int)mxGetScalar(prhs[5]) : 0;
+        std::vector<int32_t> perm((size_t)N, 0);
+        mxArray *pf = mxCreateDoubleMatrix(3, (mwSize)N, mxREAL);
+        double cost = 0.0;
+        int32_t rounds = 0;
+        if (dmpc_assign_goals(ctx, 1, N, mxGetPr(prhs[2]), mxGetPr(prhs[3]), eps, max_rounds, perm.data(), mxGetPr(pf), nullptr, &cost, &rounds))
+            mexErrMsgIdAndTxt("dmpc:assign", "%s", dmpc_last_error(ctx));
+        plhs[0] = mxCreateDoubleMatrix(1, (mwSize)N, mxREAL);
+        for (int i = 0; i < N; ++i) mxGetPr(plhs[0])[i] = (double)(perm[(size_t)i] + 1);
+        if (nlhs > 1) plhs[1] = pf;
+        if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(cost);
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)rounds);
         return;
     }
     if (!std::strcmp(cmd, "random_test") || !std::strcmp(cmd, "random_exchange")) {   // randomTest.m / randomExchange.m
