@@ -148,6 +148,8 @@ __global__ __launch_bounds__(64) void nbr_kernel(int S, int G, int C, int g_loca
 //     2 046 records per agent = 655 MB per step out of the L2s, at ~80 instructions per round of 64: without any survivor the kernel took
 //     90 of 106 us, without the stream 18 (both compiled out); its loads were NOT in flight during the previous round's test until the
 //     instruction stream was read (see the loop), and putting them in flight changed nothing -- throughput, not latency.
+//     After round 6: 96 -> 86 us with finer cells (810 - 2 074 candidates per agent); 86 -> 74 us with a lane's run taken from a bit count
+//     instead of a binary search over the runs' prefix sums (58 -> 13 instructions per round for the fetch, see the loop).
 // --------------------------------------------------------------------------------------------
 struct GridGeom {
     float org[3], inv[3];   // cell index along axis a = clamp(floor((x - org[a]) * inv[a]), 0, n[a] - 1)
@@ -399,11 +401,29 @@ constexpr int GQ_STAGE = 128;      // staging list of box-test survivors per wav
 // AGAIN and forming the same distances -- are appended to a per-agent list behind a counter in LDS (the three waves share it) and written out
 // coalesced: close_list[agent][close_cap] records {code, step}, close_cnt[agent] (-1: more than close_cap, the scan walks the list as before).
 // A neighbour is an entry of ONE cell per segment and a step belongs to one segment: no pair is recorded twice.
+// Lane -> run of the fetch: per wave the entry bases of a batch's non-empty runs by ordinal (GQ_RUNS ints) and a bit window over
+// GQ_WIN positions of the batch's concatenation (one 32-bit word per lane).  Fixed sizes: nothing here grows with the agent count.
+constexpr int GQ_RUNS = 64;
+constexpr int GQ_WIN = 2048;
+constexpr int GQ_WAVE_INTS = GQ_STAGE + GQ_RUNS + GQ_WIN / 32;   // stage, run bases, window
+static_assert(GQ_WIN / 32 == 64, "the window is one word per lane");
 inline size_t grid_query_lds(int nagents, int close_cap = 0)
 {
-    return (((size_t)((nagents + 31) / 32) * 4 + GQ_WAVES * GQ_STAGE * 4 + 15) & ~(size_t)15) + 16 * 16 + (close_cap > 0 ? 16 + (size_t)close_cap * 8 : 0);
+    return (((size_t)((nagents + 31) / 32) * 4 + GQ_WAVES * GQ_WAVE_INTS * 4 + 15) & ~(size_t)15) + 16 * 16 + (close_cap > 0 ? 16 + (size_t)close_cap * 8 : 0);
 }
 typedef float f2_t __attribute__((ext_vector_type(2)));
+// inclusive prefix sum of an int over the lanes (the gfx9 DPP scan of wave_scan_sum: row_shr 1/2/4/8, the two row broadcasts; a lane
+// without a source adds 0).  A wave collective: never inside a lane-dependent branch.
+__device__ __forceinline__ int wave_scan_add(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
+    return v;
+}
 __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G, int C, int g_local, int c_first, int c_count, GridGeom gg, float R, float Rz, float e1z, float thr2,
                                                                    const float *__restrict__ bbox_nm, const float *__restrict__ lrow, const int *__restrict__ start,
                                                                    const f4_t *__restrict__ ent, const int *__restrict__ maxhalf, int cap, int cell_order,
@@ -422,8 +442,10 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
     const int cl = c_first + ci;
     const int oid = scene * c_count + ci;   // where this agent's list goes
     unsigned *bits = (unsigned *)dmpc_smem;
-    int *stage = (int *)(dmpc_smem + (size_t)nwords * 4) + wave * GQ_STAGE;
-    f4_t *ownrow = (f4_t *)(dmpc_smem + (((size_t)nwords * 4 + GQ_WAVES * GQ_STAGE * 4 + 15) & ~(size_t)15));
+    int *stage = (int *)(dmpc_smem + (size_t)nwords * 4) + wave * GQ_WAVE_INTS;
+    int *runbase = stage + GQ_STAGE;                       // entry base of the batch's non-empty run of ordinal o
+    unsigned *win = (unsigned *)(runbase + GQ_RUNS);       // the bit window, as it is built (the rounds read it from a register)
+    f4_t *ownrow = (f4_t *)(dmpc_smem + (((size_t)nwords * 4 + GQ_WAVES * GQ_WAVE_INTS * 4 + 15) & ~(size_t)15));
     int *ccnt = (int *)(ownrow + 16), *crec = ccnt + 4;   // close pairs: counter (16 bytes), close_cap records of two ints (only there when close_cap > 0)
     for (int i = (int)threadIdx.x; i < nwords; i += 64 * GQ_WAVES) bits[i] = 0u;
     if (close_cap > 0 && threadIdx.x == 0) *ccnt = 0;
@@ -516,28 +538,23 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
                 rb = st[row0 + c_lo[0]]; re = st[row0 + c_hi[0] + 1];
             }
             // The runs of this batch as ONE sequence of entries (a run holds ~50 entries at N = 10^4: a round of 64 lanes per run left a third of
-            // the lanes idle and, worse, made every run a memory round trip of its own): lanes = the next 64 entries of the concatenation, each
-            // lane finds its run in the prefix sums of the run lengths (six shuffles) -- half the rounds.
+            // the lanes idle and, worse, made every run a memory round trip of its own): lanes = the next 64 entries of the concatenation.
+            // Lane -> run without a search (it was a binary search over the prefix sums, six dependent ds_bpermute round trips per round and
+            // 60 % of a round's instructions): the NON-EMPTY runs are numbered in order (an empty run holds no position; the search passed
+            // over it because its prefix equals its predecessor's), run o leaves its entry base in runbase[o] and -- all but the last one --
+            // a bit at its LAST position in a window over the positions.  The run of position v is then the number of bits below v: the
+            // bits of the rounds before (a prefix of the words' popcounts, once per window) + v_mbcnt over the round's own 64 bits.  The
+            // window is 64 words, a word per lane, and stays in a register: a round reads its two words and the prefix with v_readlane.
+            // Without the last run's bit the lanes past tot, which take position tot - 1, count the last run as well.
             const int len = re - rb;
-            int pre = len;   // inclusive prefix of the run lengths
-            for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(pre, off); if (lane >= off) pre += o; }
+            const int pre = wave_scan_add(len);   // inclusive prefix of the run lengths
             const int tot = __builtin_amdgcn_readlane(pre, 63);
-            const int basev = rb - (pre - len);   // entry index of sequence position v in run j: basev_j + v
-            const int nround = (tot + 63) >> 6;
+            const unsigned long long ne = __ballot(len > 0);
+            LSYNC();
+            if (len > 0) runbase[lanes_below(ne, lane)] = rb - (pre - len);   // entry index of sequence position v in run o: runbase[o] + v
+            const int endpos = (len > 0 && pre < tot) ? pre - 1 : -1;
+            int ord0 = 0;   // ordinal of the run at the window's first position
             struct Rec { f4_t a, b; bool hv; };
-            // (the loads of a round are issued UNCONDITIONALLY, into registers of their own -- two record sets, the loop unrolled by two: a
-            // fetch behind a branch, or a copy of the loaded registers at the loop's end, makes the compiler wait for the loads it has just
-            // issued (s_waitcnt vmcnt(0)) and the prefetch is gone: that was the state of this loop until the instruction stream was read)
-            auto fetch = [&](int k, Rec &rc) {
-                const int vi = 64 * k + lane;
-                rc.hv = vi < tot;
-                const int vq = rc.hv ? vi : tot - 1;
-                int j = 0;   // the first run whose inclusive prefix exceeds vq
-#pragma unroll
-                for (int step = 32; step > 0; step >>= 1) { const int pm = __shfl(pre, j + step - 1); if (pm <= vq) j += step; }
-                const size_t ei = (size_t)(__shfl(basev, j) + vq);
-                rc.a = en[ei]; rc.b = en2[ei];
-            };
             auto test = [&](const Rec &rc) {
                 // closest approach of the two chords at equal time: r(t) = q + t e on [0, 1], against radius + both deviations.  (Any t gives
                 // an upper bound of the minimum; the rounded t* is off by parts in 10^6 and |r(t)|^2 is flat there to second order.)
@@ -565,15 +582,38 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
                     }
                 }
             };
-            if (nround > 0) {
-                Rec ra, rb2;
-                fetch(0, ra);
-                for (int k = 0; k < nround; k += 2) {
-                    fetch(k + 1 < nround ? k + 1 : nround - 1, rb2);   // (past the end: the last round once more, never tested)
-                    test(ra);
-                    if (k + 1 >= nround) break;
-                    fetch(k + 2 < nround ? k + 2 : nround - 1, ra);
-                    test(rb2);
+            for (int w0 = 0; w0 < tot; w0 += GQ_WIN) {   // (one window unless a batch holds more than GQ_WIN candidates)
+                win[lane] = 0u;
+                LSYNC();
+                if ((unsigned)(endpos - w0) < (unsigned)GQ_WIN) atomicOr(win + ((endpos - w0) >> 5), 1u << ((endpos - w0) & 31));   // (per lane, no collective)
+                LSYNC();
+                const unsigned myw = win[lane];
+                const int cumi = wave_scan_add(__popc(myw));
+                const int cumw = ord0 + cumi - __popc(myw);   // runs that end before this lane's word
+                ord0 += __builtin_amdgcn_readlane(cumi, 63);
+                const int nround = ((tot - w0 < GQ_WIN ? tot - w0 : GQ_WIN) + 63) >> 6;
+                // (the loads of a round are issued UNCONDITIONALLY, into registers of their own -- two record sets, the loop unrolled by two: a
+                // fetch behind a branch, or a copy of the loaded registers at the loop's end, makes the compiler wait for the loads it has just
+                // issued (s_waitcnt vmcnt(0)) and the prefetch is gone: that was the state of this loop until the instruction stream was read)
+                auto fetch = [&](int k, Rec &rc) {
+                    const int vi = w0 + 64 * k + lane;
+                    rc.hv = vi < tot;
+                    const int vq = rc.hv ? vi : tot - 1;
+                    const unsigned mlo = (unsigned)__builtin_amdgcn_readlane((int)myw, 2 * k), mhi = (unsigned)__builtin_amdgcn_readlane((int)myw, 2 * k + 1);
+                    const int o = (int)__builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, (unsigned)__builtin_amdgcn_readlane(cumw, 2 * k)));
+                    const unsigned eb = (unsigned)(runbase[o] + vq) << 4;   // (a byte offset of 32 bits from a uniform base: no 64-bit address arithmetic per lane; a scene's entries are below 2^28)
+                    rc.a = *(const f4_t *)((const char *)en + eb); rc.b = *(const f4_t *)((const char *)en2 + eb);
+                };
+                if (nround > 0) {
+                    Rec ra, rb2;
+                    fetch(0, ra);
+                    for (int k = 0; k < nround; k += 2) {
+                        fetch(k + 1 < nround ? k + 1 : nround - 1, rb2);   // (past the end: the last round once more, never tested)
+                        test(ra);
+                        if (k + 1 >= nround) break;
+                        fetch(k + 2 < nround ? k + 2 : nround - 1, ra);
+                        test(rb2);
+                    }
                 }
             }
         }
@@ -593,9 +633,9 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
     const UDiv div_c((unsigned)C);
     for (int w0 = 0; w0 < nwords; w0 += 64) {
         unsigned word = w0 + lane < nwords ? bits[w0 + lane] : 0u;
+        if (__ballot(word != 0u) == 0ull) continue;   // (most chunks of a large scene: the neighbours are a hundred of 10^4)
         const int mycnt = __popc(word);
-        int pre = mycnt;   // inclusive prefix of the lanes' counts
-        for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(pre, off); if (lane >= off) pre += o; }
+        const int pre = wave_scan_add(mycnt);   // inclusive prefix of the lanes' counts
         const int wave_total = __builtin_amdgcn_readlane(pre, 63);
         int pos = total + pre - mycnt;
         while (word) {
