@@ -399,6 +399,47 @@ DMPC_API int dmpc_transition_hold(dmpc_ctx *ctx, int S, int N, int N_cmd, int Q,
                          int32_t *K_T_used, int32_t *scene_status, int32_t *stage_col, int32_t *hold_count, int32_t *hold_first,
                          int32_t *agent_status);
 
+/* Routes: EVERY COMMANDED AGENT THROUGH WAYPOINTS OF ITS OWN, switched per agent on the device.  NO REFERENCE COUNTERPART: DMPC has no global
+ * planner -- an agent whose straight line is blocked by a wall of uncommanded vehicles parks in front of it -- and a mission switches a whole
+ * scene at once, every agent braking at every intermediate formation.  The step is the reference's; this entry is that step in the loop a caller
+ * of dmpc_step_batch[_cmd] could write on the host, with the rule below applied between two steps, on the device.  Additive: the ABI revision stays 8.
+ *   waypoints [S][N_cmd][W][3], W >= 1; n_wp [S][N_cmd] (int32, each 1 .. W) or NULL = every agent has W.  An agent's last waypoint,
+ *             waypoints[s][i][n_wp-1], is its goal; entries behind it are never read.
+ *   capture   > 0, metres; timeout >= 0, columns, 0 = none.
+ *   state     per commanded agent: cur[i], the index of its current waypoint, and since[i], the column on which that waypoint became current; both
+ *             start at 0.  The goal the QP of agent i sees is waypoints[s][i][cur[i]].  Column 0 is the initDMPC column: its straight lines run
+ *             from po to every agent's waypoint 0.
+ *   the rule  after the post step of history column k (column 0 included), with bits = the OR of the status words and the states as that column
+ *             recorded them, in this order:
+ *             1. bits & ~DMPC_ST_SOLVED: the scene stops exactly as in dmpc_transition; no waypoint switches on that column.
+ *             2. all_last = every agent has cur[i] == n_wp[i]-1, evaluated BEFORE any switch of this column.  all_last and ReachedGoal on
+ *                column k (the post step's verdict: max_i |p_i - goal_i| < error_tol): the trial ends, DMPC_ST_SOLVED | DMPC_ST_REACHED,
+ *                K_T_used = k+1.  While all_last is false a column never reports DMPC_ST_REACHED and never ends the trial, also when every agent
+ *                happens to be within error_tol of its current waypoint.
+ *             3. otherwise every agent with cur[i] < n_wp[i]-1 switches when (a) d2 < capture * capture, d2 = (dx*dx + dy*dy) + dz*dz,
+ *                d = p_i(k) - waypoints[s][i][cur[i]], in fp64 with every operation rounded on its own (no fused multiply-add), or
+ *                (b) timeout > 0 and k - since[i] >= timeout.  On a switch wp_col[s][i][cur[i]] = k, cur[i] += 1, since[i] = k, and the step that
+ *                produces column k+1 is the first one solved with the new waypoint.
+ *             AT MOST ONE WAYPOINT PER AGENT AND COLUMN: the next waypoint is first examined on column k+1, also when it is met already.
+ *             THE TABLE IS NOT REWRITTEN: for that one step the neighbours see the plan made for the old waypoint, as a host loop's would.
+ *             The rule reads the fp64 states in every precision mode.
+ *   failure   max_hold >= 0, the policy of dmpc_transition_hold: 0 stops the scene at the first failed agent; a held plan counts as a solved one
+ *             in the rule above.  hold_count, hold_first, agent_status and DMPC_ST_HELD are dmpc_transition_hold's.
+ * po, path, P, pk / vk / ak (resident afterwards; dmpc_postcheck* and dmpc_postcheck_clearance take pf = the last waypoints), K_T_used and
+ * scene_status are dmpc_transition_hold's: static vehicles with N_cmd < N and no path, scripted ones with a path.  Outputs, each or both NULL:
+ *   wp_col    [S][N_cmd][W]   the column on which the agent left waypoint w; -1 where it never did, for its last waypoint and for w >= n_wp
+ *   wp_index  [S][N_cmd]      cur[i] when the scene ended
+ * W == 1 with timeout == 0: every common output is dmpc_transition_hold's with Q == 1 byte for byte (max_hold == 0: dmpc_transition / _cmd /
+ * _scripted).  Every n_wp == W, a capture too small to fire and timeout == T: dmpc_transition_mission on goals[q][i] = waypoints[i][q] with
+ * deadline = [T, .., T, 0] byte for byte, wherever no intermediate stage is reached before its deadline.  Batch split as dmpc_transition (each
+ * part gets its scenes' waypoints, n_wp and outputs); a DMPC_DEVICE_ALL context runs the call on its first GPU; there is no RCCL form.
+ * W < 1, a NULL waypoints, an n_wp entry outside 1 .. W, a capture that is not > 0 (NaN included), timeout < 0, max_hold < 0, or what
+ * dmpc_transition_hold refuses of the common arguments: -1 and a message that starts with the entry's name, nothing launched. */
+DMPC_API int dmpc_transition_route(dmpc_ctx *ctx, int S, int N, int N_cmd, int W, const double *po, const double *waypoints, const int32_t *n_wp,
+                          double capture, int timeout, const double *path, int P, int K_T_max, double error_tol, int max_hold, double *pk,
+                          double *vk, double *ak, int32_t *K_T_used, int32_t *scene_status, int32_t *wp_col, int32_t *wp_index,
+                          int32_t *hold_count, int32_t *hold_first, int32_t *agent_status);
+
 /* Multi-GPU: the agents of every scene sharded over the GPUs of one node, ONE PROCESS (rank) PER GPU, each with its own
  * context.  Replaces the thread clusters of DMPC::solveParallelDMPCv2 (dmpc/cpp/dmpc.cpp:1570-1686): contiguous agent ranges,
  * N/G each, the first N mod G one more (:1600-1625; dmpc_partition), every cluster reading the previous predictions of all

@@ -16,7 +16,7 @@ VARIANTS = dict(bound=0, bound2=1, all3=2, hard=3, ondemand=4, ellip=5, softall=
 ST_SOLVED, ST_OUTBOUND, ST_COLL, ST_INFEAS, ST_CAPACITY, ST_ITERCAP = 1, 2, 4, 8, 16, 32
 PRECISIONS = dict(f64=0, mixed=1, f32factor=2, low=3)
 ST_REACHED = 256   # scene_status of transition(): every agent reached its goal
-ST_HELD = 64       # transition(on_fail="hold") / mission(on_fail="hold"): the agent flew its previous plan on this column
+ST_HELD = 64       # transition(on_fail="hold") / mission(on_fail="hold") / route(on_fail="hold"): the agent flew its previous plan on this column
 INFO_LEN = 8
 I_VIOLK, I_NROWS, I_TRIES, I_CASE, I_ITERS, I_NSLACK, I_NACTIVE, I_MAXQ = range(8)
 K_HOR = 15
@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "dmpc_postcheck_setpoints",
     "dmpc_transition_hold",
     "dmpc_assign_goals", "dmpc_assign_goals_device",
+    "dmpc_transition_route",
 ]
 
 
@@ -147,6 +148,9 @@ def load():
     # goal assignment ahead of a transition (additive, still revision 8)
     L.dmpc_assign_goals.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int, ip, dp, dp, dp, ip]
     L.dmpc_assign_goals_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp]
+    # routes: every agent through waypoints of its own (additive, still revision 8)
+    L.dmpc_transition_route.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, ip, C.c_double, C.c_int, dp, C.c_int, C.c_int, C.c_double, C.c_int,
+                                        dp, dp, dp, ip, ip, ip, ip, ip, ip, ip]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -547,6 +551,58 @@ class Dmpc:
                                                   _dp(pk) if histories else nul, _dp(vk) if histories else nul, _dp(ak) if histories else nul,
                                                   _ip(used), _ip(sst), _ip(stage_col)))
         return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, stage_col=stage_col)
+
+    def route(self, po, waypoints, K_T_max, capture, n_wp=None, timeout=0, error_tol=0.01, histories=True, path=None, on_fail="stop", max_hold=14):
+        """dmpc_transition_route: one transition in which every commanded agent flies through waypoints of its own, waypoints [N_cmd,W,3] (next
+        to an unbatched po) or [S,N_cmd,W,3]; n_wp [N_cmd] / [S,N_cmd] (1 .. W; None: every agent has W) counts an agent's waypoints, the last
+        of them is its goal.  An agent leaves a waypoint that is not its last at the first column where it is closer to it than capture (metres)
+        or -- timeout > 0, in columns -- has flown towards it for timeout columns; the next step is solved with its next waypoint.  The trial ends
+        when every agent is on its last waypoint and they are all reached.  po with MORE vehicles than the waypoints: static vehicles, as
+        transition(); path [S,M,P,3]: scripted vehicles, po then covers the commanded agents.  Returns what transition() returns, and wp_col
+        [S,N_cmd,W]: the column on which the agent left each waypoint (-1: it never did), wp_index [S,N_cmd]: the waypoint it was flying to when
+        the scene ended.  on_fail, max_hold: as transition() (a held plan counts as a solved one in the waypoint rule)."""
+        po, waypoints = _f(po), _f(waypoints)
+        if on_fail not in ("stop", "hold"):
+            raise DmpcError(f"route: on_fail is 'stop' or 'hold', not {on_fail!r}")
+        if (po.ndim not in (2, 3) or waypoints.ndim != po.ndim + 1 or po.shape[-1] != 3 or waypoints.shape[-1] != 3 or waypoints.shape[:-3] != po.shape[:-2]
+                or waypoints.shape[-2] < 1):
+            raise DmpcError(f"route: waypoints {tuple(waypoints.shape)} must be [N_cmd,W,3] next to po [N,3], or [S,N_cmd,W,3] next to po [S,N,3]: po is {tuple(po.shape)}")
+        S = 1 if po.ndim == 2 else po.shape[0]
+        n_cmd, W, N = waypoints.shape[-3], waypoints.shape[-2], po.shape[-2]
+        lead = po.shape[:-2] + (n_cmd,)
+        M = P = 0
+        if path is not None:
+            if N != n_cmd:
+                raise DmpcError(f"route: with path, po {tuple(po.shape)} and waypoints {tuple(waypoints.shape)} must cover the same commanded agents")
+            path, M, P = _path(path, lead, "route")
+        elif n_cmd < 1 or n_cmd > N:
+            raise DmpcError(f"route: waypoints have {n_cmd} agents, po {N}: the commanded agents are the FIRST N_cmd <= N vehicles")
+        if n_wp is not None:
+            n_wp = np.asarray(n_wp)
+            if n_wp.shape != lead or not np.issubdtype(n_wp.dtype, np.integer) or n_wp.min() < 1 or n_wp.max() > W:
+                raise DmpcError(f"route: n_wp must be integers in 1 .. W = {W} of shape {lead}")
+            n_wp = np.ascontiguousarray(n_wp, dtype=np.int32)
+        if not float(capture) > 0.0:
+            raise DmpcError(f"route: capture must be > 0 (metres), not {capture!r}")
+        if int(timeout) < 0:
+            raise DmpcError(f"route: timeout must be >= 0 (columns; 0: none), not {timeout!r}")
+        hold = on_fail == "hold"
+        nul, inul = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
+        used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+        wp_col, wp_index = np.zeros(lead + (W,), dtype=np.int32), np.zeros(lead, dtype=np.int32)
+        cnt, first, log = np.zeros(lead, dtype=np.int32), np.zeros(lead, dtype=np.int32), np.zeros(lead + (K_T_max,), dtype=np.int32)
+        pk = vk = ak = None
+        if histories:
+            pk, vk, ak = (np.zeros(lead + (K_T_max, 3)) for _ in range(3))
+        self._chk(self._L.dmpc_transition_route(self._ctx, S, N + M, n_cmd, W, _dp(po), _dp(waypoints), _ip(n_wp) if n_wp is not None else inul,
+                                                float(capture), int(timeout), _dp(path) if path is not None else nul, P, int(K_T_max), float(error_tol),
+                                                int(max_hold) if hold else 0, _dp(pk) if histories else nul, _dp(vk) if histories else nul,
+                                                _dp(ak) if histories else nul, _ip(used), _ip(sst), _ip(wp_col), _ip(wp_index),
+                                                _ip(cnt) if hold else inul, _ip(first) if hold else inul, _ip(log) if hold else inul))
+        out = dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, wp_col=wp_col, wp_index=wp_index)
+        if hold:
+            out.update(hold_count=cnt, hold_first=first, agent_status=log)
+        return out
 
     # ---- multi-GPU (one process per GPU): dmpc_multigpu.hip ----
     @staticmethod

@@ -171,6 +171,7 @@ struct dmpc_ctx {
     DevBuf path;                                                           // dmpc_transition_scripted: the scripted vehicles' paths [S][M][P][3], resident for the call
     DevBuf hold_out, hold_state;                                           // dmpc_transition_hold: the second set of p / v / a output rows 3 x [S][N_cmd][3K]; ints: run, hold_count, hold_first [S][N_cmd] each, agent_status [S][N_cmd][K_T_max]
     DevBuf mis_goals, mis_state;                                           // dmpc_transition_mission: goal sets [S][Q][N_cmd][3]; ints: stage [S], k_start [S], stage_col [S][Q], deadline [S][Q]
+    DevBuf route_wp, route_state;                                          // dmpc_transition_route: waypoints [S][N_cmd][W][3]; ints: n_wp, cur, since [S][N_cmd] each, wp_col [S][N_cmd][W]
     DevBuf pc_sc_path, pc_sc_y, pc_sc_M, pc_sc_w, pc_sc_pts, pc_sc_interp; // dmpc_postcheck_scripted: paths, knots, second derivatives, scratch, sample batch, p_scripted
     DevBuf pc_pts, pc_cell, pc_fill, pc_start, pc_sorted, pc_on;           // post-check, large scenes: cell grid of a batch of samples
     DevBuf pc_cl_part, pc_cl_run, pc_cl_out;                               // dmpc_postcheck_clearance: partials of a sample batch, running best, report
@@ -1063,7 +1064,7 @@ static std::vector<int> batch_parts(int S, int want, bool sharded)
     return at;
 }
 
-#include "dmpc_transition.hip"   // the closed loop: the record of a call, transition_one, transition_any, the five entries
+#include "dmpc_transition.hip"   // the closed loop: the record of a call, transition_one, transition_any, the six entries
 
 #include "dmpc_postcheck_host.hip"   // the post-checks on the host: the record of a call, PcPrep, the three checks, pc_run, the five entries
 

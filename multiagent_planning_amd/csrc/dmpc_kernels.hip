@@ -1694,6 +1694,48 @@ __global__ void mission_stage_kernel(int N, int Q, int k, const double *__restri
     }
 }
 
+// Routes (dmpc_transition_route): the waypoint rule of one scene after the post step of history column k, one block per scene, a stride loop over
+// its N commanded agents.  Launched where mission_stage_kernel is, in stream order behind whatever wrote flags[s] and scene_done[s] for column k;
+// what the comment there says of the fused post step's accumulators holds here as well.
+//   wp [S][N][W][3], n_wp [S][N] (1 .. W), x_p [S][N][3]: the states column k recorded, flags: column k's [S][2], cur / since [S][N], wp_col [S][N][W]
+// An agent belongs to one thread (i = threadIdx.x + j blockDim.x) in both loops, so its cur / since / wp_col need no barrier of their own; the
+// scene's two flag words are read by every thread in front of the barrier and rewritten by thread 0 behind it.  Every value the branches test
+// is the same for all threads of a block.  A scene that failed or arrived keeps scene_done set, so none of its later columns is written
+// (bits == 0) and its waypoints stay as they were.
+__global__ void route_kernel(int N, int W, int k, double cap2, int timeout, const double *__restrict__ wp, const int *__restrict__ n_wp,
+                             const double *__restrict__ x_p, int *flags, int *scene_done, int *cur, int *since, int *wp_col, double *pf)
+{
+#pragma clang fp contract(off)   // the capture test as the host loop computes it: no fused multiply-add
+    const int s = blockIdx.x;
+    const int bits = flags[(size_t)s * 2 + 1];
+    const size_t a0 = (size_t)s * N;
+    int last = 1;   // all_last over this thread's agents, BEFORE any switch of this column
+    for (int i = threadIdx.x; i < N; i += blockDim.x) last &= cur[a0 + i] == n_wp[a0 + i] - 1;
+    __syncthreads();   // every thread has read the scene's words before thread 0 rewrites them
+    const int all_last = __syncthreads_and(last);
+    if (bits == 0) return;             // column k was never written (the scene had stopped before)
+    if (bits & ~ST_SOLVED) return;     // a failed agent stops the scene as in dmpc_transition: scene_done stays set, no waypoint switches
+    if (all_last) return;              // every agent flies to its goal: the verdict stands as the post step wrote it (reached ends the trial)
+    for (int i = threadIdx.x; i < N; i += blockDim.x) {
+        const size_t ag = a0 + i;
+        const int c = cur[ag];
+        if (c >= n_wp[ag] - 1) continue;
+        const double *w = wp + (ag * W + c) * 3;
+        const double dx = x_p[ag * 3] - w[0], dy = x_p[ag * 3 + 1] - w[1], dz = x_p[ag * 3 + 2] - w[2];
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        if (!(d2 < cap2 || (timeout > 0 && k - since[ag] >= timeout))) continue;
+        // the agent leaves waypoint c on column k: the step that produces column k + 1 is solved with the next one; the table is left as it is
+        wp_col[ag * W + c] = k;
+        cur[ag] = c + 1;
+        since[ag] = k;
+        for (int d = 0; d < 3; ++d) pf[ag * 3 + d] = w[3 + d];
+    }
+    if (threadIdx.x == 0) {
+        flags[(size_t)s * 2] = 0;      // the host must not read "reached" while some agent is not on its last waypoint
+        scene_done[s] = 0;             // (the status word is clean here: a failed scene returned above and stays done)
+    }
+}
+
 // Hold policy (dmpc_transition_hold): between the solve of the step that produces history column k and its post step, over the S * N_cmd
 // commanded agents, one wave per 64 of them.  An agent whose status is not exactly ST_SOLVED has failed; while its run of consecutive failures
 // is <= max_hold it is HELD: its plan of this step is its previous plan shifted by one entry, with a braking tail appended

@@ -27,26 +27,40 @@ struct Hold {
     explicit operator bool() const { return max_hold >= 0; }
 };
 
+// A route (dmpc_transition_route; W = 0: none): pf is ignored, every commanded agent has waypoints of its own, resident for the call; waypoint 0 of
+// every agent goes into ctx->pf, and one launch after the verdict of every column (route_kernel) applies the waypoint rule there, per agent.
+// Route and mission are never both set.
+struct Route {
+    int W = 0;
+    const double *waypoints = nullptr;   // [S][N_cmd][W][3]
+    const int32_t *n_wp = nullptr;       // [S][N_cmd] or null: every agent has W
+    double capture = 0.0; int timeout = 0;
+    int32_t *wp_col = nullptr;           // [S][N_cmd][W] or null
+    int32_t *wp_index = nullptr;         // [S][N_cmd] or null
+    explicit operator bool() const { return W > 0; }
+};
+
 // one call of a transition entry, as the entry filled it
 struct TransitionCall {
     int S, N, N_cmd;
-    const double *po, *pf;   // (a mission: pf is its goals)
+    const double *po, *pf;   // (a mission: pf is its goals; a route: its waypoints)
     int K_T_max; double error_tol;
     double *pk, *vk, *ak;    // all three or none
     int32_t *K_T_used, *scene_status;
     const double *path = nullptr; int P = 0;
-    Mission mission; Hold hold;
+    Mission mission; Hold hold; Route route;
     // the same call for scenes [s0, s0 + sn): the one place that knows each array's stride per scene
     TransitionCall scenes(int s0, int sn) const {
         auto at = [](auto *p, size_t off) { return p ? p + off : nullptr; };
-        const size_t a0 = (size_t)s0 * N_cmd, q0 = (size_t)s0 * mission.Q, h0 = a0 * (size_t)K_T_max;
+        const size_t a0 = (size_t)s0 * N_cmd, q0 = (size_t)s0 * mission.Q, h0 = a0 * (size_t)K_T_max, w0 = a0 * (size_t)route.W;
         TransitionCall c = *this; c.S = sn;
         c.po = at(po, (path ? a0 : (size_t)s0 * N) * 3);   // (scripted vehicles: po covers the commanded agents)
         c.path = at(path, (size_t)s0 * (N - N_cmd) * P * 3);
         c.pk = at(pk, h0 * 3); c.vk = at(vk, h0 * 3); c.ak = at(ak, h0 * 3);
         c.K_T_used = at(K_T_used, s0); c.scene_status = at(scene_status, s0);
         c.mission.goals = at(mission.goals, q0 * N_cmd * 3); c.mission.deadline = at(mission.deadline, q0); c.mission.stage_col = at(mission.stage_col, q0);
-        c.pf = mission ? c.mission.goals : at(pf, a0 * 3);
+        c.route.waypoints = at(route.waypoints, w0 * 3); c.route.n_wp = at(route.n_wp, a0); c.route.wp_col = at(route.wp_col, w0); c.route.wp_index = at(route.wp_index, a0);
+        c.pf = mission ? c.mission.goals : route ? c.route.waypoints : at(pf, a0 * 3);
         c.hold.hold_count = at(hold.hold_count, a0); c.hold.hold_first = at(hold.hold_first, a0); c.hold.agent_status = at(hold.agent_status, h0);
         return c;
     }
@@ -103,11 +117,12 @@ static int download_histories(dmpc_ctx *ctx, const TransitionCall &c, size_t his
     return 0;
 }
 
-// the device side of the goals: one leg's pf, or a mission's goal sets and, in ctx->mis_state, every scene's stage, its first column, stage_col, deadlines
+// the device side of the goals: one leg's pf (a route's waypoints: RouteDev), or a mission's goal sets and, in ctx->mis_state, every scene's stage, its first column, stage_col, deadlines
 struct MissionDev {
     dmpc_ctx *ctx; const TransitionCall &c; hipStream_t st;
     int *stage_of = nullptr, *k_start = nullptr, *col = nullptr, *dl = nullptr;   // [S], [S], [S][Q], [S][Q] (null: no deadlines)
     int begin() {   // the goal sets and the deadlines go up once per call; stage 0's goals into ctx->pf; stage = k_start = 0, stage_col = -1
+        if (c.route) return 0;   // (RouteDev::begin fills ctx->pf)
         const Mission &m = c.mission;
         const size_t S = (size_t)c.S, SQ = S * m.Q, set = (size_t)c.N_cmd * 24;
         if (!m) { HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, c.pf, S * set, hipMemcpyHostToDevice, st)); return 0; }
@@ -128,6 +143,43 @@ struct MissionDev {
     }
     int finish() {
         if (c.mission.stage_col) HIPCHK(ctx, hipMemcpyAsync(c.mission.stage_col, col, (size_t)c.S * c.mission.Q * 4, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+};
+
+// the device side of a route: the waypoints in ctx->route_wp and, in ctx->route_state, n_wp, every agent's current waypoint, the column it became
+// current on, and wp_col
+struct RouteDev {
+    dmpc_ctx *ctx; const TransitionCall &c; hipStream_t st;
+    int *n_wp = nullptr, *cur = nullptr, *since = nullptr, *col = nullptr;   // [S][N_cmd] each, [S][N_cmd][W]
+    std::vector<double> first; std::vector<int32_t> count;                    // waypoint 0 of every agent; n_wp where the caller passed none (alive until the call's last synchronisation)
+    int begin() {   // the waypoints and n_wp go up once per call; waypoint 0 of every agent into ctx->pf; cur = since = 0, wp_col = -1
+        const Route &r = c.route;
+        if (!r) return 0;
+        const size_t A = (size_t)c.S * c.N_cmd, AW = A * r.W;
+        if (ctx->pf.ensure(A * 24) || ctx->route_wp.ensure(AW * 24) || ctx->route_state.ensure((3 * A + AW) * 4)) FAIL(ctx, "device allocation failed");
+        n_wp = ctx->route_state.as<int>(); cur = n_wp + A; since = cur + A; col = since + A;
+        first.resize(A * 3);
+        for (size_t a = 0; a < A; ++a) std::memcpy(&first[a * 3], r.waypoints + a * r.W * 3, 24);
+        if (!r.n_wp) count.assign(A, r.W);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->route_wp.p, r.waypoints, AW * 24, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, first.data(), A * 24, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(n_wp, r.n_wp ? r.n_wp : count.data(), A * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemsetAsync(cur, 0, 2 * A * 4, st));
+        HIPCHK(ctx, hipMemsetAsync(col, 0xff, AW * 4, st));
+        return 0;
+    }
+    void rule(int k) {   // the waypoint rule on column k, behind its verdict
+        if (!c.route) return;
+        hipLaunchKernelGGL(route_kernel, dim3((unsigned)c.S), dim3(c.N_cmd * 3 >= 256 ? 256u : 64u), 0, st, c.N_cmd, c.route.W, k,
+                           c.route.capture * c.route.capture, c.route.timeout, (const double *)ctx->route_wp.as<double>(), (const int *)n_wp,
+                           (const double *)ctx->xp.as<double>(), ctx->flags.as<int>() + (size_t)k * c.S * 2, ctx->scene_done.as<int>(), cur, since, col,
+                           ctx->pf.as<double>());
+    }
+    int finish() {
+        const size_t A = (size_t)c.S * c.N_cmd;
+        if (c.route.wp_col) HIPCHK(ctx, hipMemcpyAsync(c.route.wp_col, col, A * c.route.W * 4, hipMemcpyDeviceToHost, st));
+        if (c.route.wp_index) HIPCHK(ctx, hipMemcpyAsync(c.route.wp_index, cur, A * 4, hipMemcpyDeviceToHost, st));
         return 0;
     }
 };
@@ -199,8 +251,8 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
         HIPCHK(ctx, hipMemcpyAsync(ctx->path.p, c.path, path_bytes, hipMemcpyHostToDevice, st));
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, c.po, (scripted ? A : T) * 24, hipMemcpyHostToDevice, st));
-    MissionDev mission{ctx, c, st}; HoldDev hold{ctx, c, st};
-    if (mission.begin()) return -1;
+    MissionDev mission{ctx, c, st}; HoldDev hold{ctx, c, st}; RouteDev route{ctx, c, st};
+    if (mission.begin() || route.begin()) return -1;
     if (reset_run_buffers(ctx, S, K_T_max, hist, st)) return -1;
     // ---- column 0: initDMPC (dmpc_soft_bound.m:117-121): state = (po, 0, 0), table = straight lines
     if (N_cmd == N || scripted) HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
@@ -224,7 +276,7 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
     HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->status.p, DMPC_ST_SOLVED, A, st));
     hipLaunchKernelGGL(scene_reduce_kernel, dim3((unsigned)S), dim3(256), 0, st, N_cmd, c.error_tol, xp, ctx->pf.as<double>(),
                        (const int *)ctx->status.as<int32_t>(), ctx->flags.as<int>(), ctx->scene_done.as<int>());
-    mission.stage(0);
+    mission.stage(0); route.rule(0);
     double *cur = ctx->lT.as<double>(), *nxt = ctx->lT2.as<double>();
     if (hold.begin()) return -1;
     hold.apply(0, cur, nxt);
@@ -272,7 +324,7 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
                                (const double *)out[0], (const double *)out[1], (const double *)out[2],
                                (const int *)ctx->status.as<int32_t>(), xp, xv, xa, (const double *)ctx->pf.as<double>(), ctx->hist_p.as<double>(),
                                ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), verdict_k, ctx->scene_done.as<int>(), (const int *)ctx->scene_done.as<int>());
-        mission.stage(k);
+        mission.stage(k); route.rule(k);
         HIPCHK(ctx, hipGetLastError());
         std::swap(cur, nxt);   // l = new_l (dmpc_soft_bound.m:146)
         if (VerdictFold::window_ends(k, K_T_max)) {
@@ -286,7 +338,7 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
     }
     // ---- end: the last window, the downloads
     if (digest()) return -1;
-    if (download_histories(ctx, c, hist, st) || mission.finish() || hold.finish()) return -1;
+    if (download_histories(ctx, c, hist, st) || mission.finish() || route.finish() || hold.finish()) return -1;
     HIPCHK(ctx, hipStreamSynchronize(st));
     hold.report();
     ctx->hist_S = S; ctx->hist_N = N_cmd; ctx->hist_KT = K_T_max;   // (the resident histories are the commanded agents')
@@ -342,13 +394,13 @@ static int run_parts(dmpc_ctx *ctx, const TransitionCall &c, const std::vector<i
 }
 
 // A batch in parts (batch_parts), each on a context, HIP stream and host thread of its own.  A DMPC_DEVICE_ALL context shards the agents of each scene
-// over every visible GPU (dmpc_multigpu.hip) -- unless there are uncommanded vehicles or a mission, or fewer agents than twice the GPUs (the
+// over every visible GPU (dmpc_multigpu.hip) -- unless there are uncommanded vehicles, a mission or a route, or fewer agents than twice the GPUs (the
 // reference's small swarms on an 8-GPU node: sharding N = 4 agents over 8 GPUs is impossible and over 2-3 of them nothing but barriers and peer
 // copies): the first GPU alone then, unsplit, as dmpc_step_batch does.
 static int transition_any(dmpc_ctx *ctx, const TransitionCall &c)
 {
     ctx->split_at.clear();
-    const bool sharded = ctx->grp && c.N_cmd == c.N && !c.mission;
+    const bool sharded = ctx->grp && c.N_cmd == c.N && !c.mission && !c.route;
     if (sharded && c.N < 2 * ctx->grp->G) return transition_one(ctx, c);
     int (*const body)(dmpc_ctx *, const TransitionCall &) = sharded ? group_transition : transition_one;
     const std::vector<int> at = batch_parts(c.S, ctx->opt.split_parts, sharded);
@@ -442,6 +494,35 @@ extern "C" int dmpc_transition_hold(dmpc_ctx *ctx, int S, int N, int N_cmd, int 
                            Mission{Q, goals, deadline, stage_col}, Hold{max_hold, hold_count, hold_first, agent_status}};
     if (check_mission(ctx, "dmpc_transition_hold", c)) return -1;
     if (max_hold < 0) FAIL(ctx, "dmpc_transition_hold: max_hold must be >= 0 (0: no agent is ever held, dmpc_transition_mission)");
+    return transition_any(ctx, c);   // (a DMPC_DEVICE_ALL context: its first GPU)
+}
+
+// Routes: every commanded agent through waypoints of its own, switched per agent on the device.  No reference counterpart (DMPC has no global
+// planner: an agent whose straight line is blocked by uncommanded vehicles parks in front of them); the step is the reference's, the rule -- pinned
+// in include/dmpc_hip.h -- the loop a caller of dmpc_step_batch[_cmd] could write on the host, applied after the verdict of every column (route_kernel).
+extern "C" int dmpc_transition_route(dmpc_ctx *ctx, int S, int N, int N_cmd, int W, const double *po, const double *waypoints, const int32_t *n_wp,
+                                     double capture, int timeout, const double *path, int P, int K_T_max, double error_tol, int max_hold, double *pk,
+                                     double *vk, double *ak, int32_t *K_T_used, int32_t *scene_status, int32_t *wp_col, int32_t *wp_index,
+                                     int32_t *hold_count, int32_t *hold_first, int32_t *agent_status)
+{
+    const std::string who = "dmpc_transition_route";
+    if (!ctx) { g_err = who + ": ctx is NULL"; return -1; }
+    TransitionCall c{S, N, N_cmd, po, waypoints, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, path ? P : 0, Mission{},
+                     Hold{max_hold, hold_count, hold_first, agent_status}};
+    c.route = Route{W, waypoints, n_wp, capture, timeout, wp_col, wp_index};
+    if (check_cmd(ctx, who.c_str(), S, N, N_cmd)) return -1;
+    if (W < 1) FAIL(ctx, who + ": W must be >= 1 (every agent has at least its goal)");
+    if (!waypoints) FAIL(ctx, who + ": waypoints is NULL");
+    if (path && check_scripted(ctx, who.c_str(), S, N_cmd, N - N_cmd, P)) return -1;
+    if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, who + ": pk, vk, ak must be all given or all NULL");
+    if (check_call(ctx, who, c)) return -1;
+    if ((size_t)S * (size_t)N_cmd * (size_t)W > 0x7fffffffu) FAIL(ctx, who + ": S * N_cmd * W overflows");
+    if (!(capture > 0.0)) FAIL(ctx, who + ": capture must be > 0 (metres)");
+    if (timeout < 0) FAIL(ctx, who + ": timeout is negative (0: none)");
+    if (max_hold < 0) FAIL(ctx, who + ": max_hold must be >= 0 (0: no agent is ever held)");
+    if (n_wp)
+        for (size_t a = 0; a < (size_t)S * N_cmd; ++a)
+            if (n_wp[a] < 1 || n_wp[a] > W) FAIL(ctx, who + ": an n_wp entry is outside 1 .. W");
     return transition_any(ctx, c);   // (a DMPC_DEVICE_ALL context: its first GPU)
 }
 

@@ -22,6 +22,7 @@
 //   Ain            = dmpc_mex('rows_dense', params, xi, kc, A)                          -diff_mat*A of structured rows
 //   [pk,vk,ak,K_T_used,scene_status] = dmpc_mex('transition', params, po, pf, K_T_max, error_tol)   the whole k-loop on the GPU
 //   [pk,vk,ak,K_T_used,scene_status,stage_col] = dmpc_mex('mission', params, po, goals, K_T_max, error_tol[, deadline])   goals 3 x N_cmd x Q: see below
+//   [pk,vk,ak,K_T_used,scene_status,wp_col] = dmpc_mex('route', params, po, waypoints, K_T_max, error_tol, capture[, n_wp[, timeout]])   waypoints 3 x W x N_cmd: see below
 //   [perm,pf,cost,rounds] = dmpc_mex('assign', params, po, goals[, eps[, max_rounds]])  goal assignment (dmpc_assign_goals): po, goals 3 x N; perm 1 x N, 1-based:
 //                                                                                    agent i takes goals(:,perm(i)) = pf(:,i); eps default 1e-4 / N
 //   inbounds       = dmpc_mex('is_inbounds', params, p, pmin, pmax)                    is_inbounds.m
@@ -35,6 +36,10 @@
 // Missions (dmpc_transition_mission, no reference counterpart): 'mission' is 'transition' through the Q goal sets goals(:,:,q) one after the
 // other -- a stage ends at the first column where its goals are reached or its deadline (1 x Q, 0 = none, the last 0) has passed; stage_col
 // (1 x Q) holds the 0-based history column each stage ended on, -1 for a stage that never did.  N_cmd < N: static vehicles, as 'transition'.
+// Routes (dmpc_transition_route, no reference counterpart): 'route' is 'transition' with waypoints of its own for every commanded agent,
+// waypoints(:,w,i) -- agent i leaves a waypoint that is not its last when it is closer to it than capture (metres) or has flown towards it for
+// timeout columns (0 = none); n_wp (1 x N_cmd, default W each) counts an agent's waypoints, the last of them is its goal; wp_col (W x N_cmd) holds
+// the 0-based history column on which the agent left each waypoint, -1 where it never did.  A failed agent stops the scene (max_hold = 0).
 // `params` is a struct with the fields of dmpc_params (variant as the DMPC_VAR_* integer).
 // The signature-preserving wrappers (solveSoftDMPCbound.m, ...) in this directory call 'solve_one'
 // and convert status bits into the reference's [] + flag conventions.
@@ -456,6 +461,36 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 5) {
             plhs[5] = mxCreateDoubleMatrix(1, (mwSize)Q, mxREAL);
             for (int q = 0; q < Q; ++q) mxGetPr(plhs[5])[q] = (double)col[(size_t)q];
+        }
+        return;
+    }
+    if (!std::strcmp(cmd, "route")) {   // one trial with waypoints of its own for every commanded agent (dmpc_transition_route)
+        need(nrhs >= 7 && nrhs <= 9, "route: (cmd, params, po, waypoints, K_T_max, error_tol, capture[, n_wp[, timeout]])");
+        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3), KT = (int)mxGetScalar(prhs[4]);
+        const mwSize *wd = mxGetDimensions(prhs[3]);
+        const int W = mxGetNumberOfDimensions(prhs[3]) >= 2 ? (int)wd[1] : 0;
+        const int Nc = W >= 1 ? (int)(mxGetNumberOfElements(prhs[3]) / ((size_t)3 * W)) : 0;
+        need(N >= 1 && W >= 1 && Nc >= 1 && Nc <= N && wd[0] == 3 && mxGetNumberOfElements(prhs[3]) == (size_t)3 * W * Nc && KT >= 2,
+             "po must be 3 x N, waypoints 3 x W x N_cmd (N_cmd <= N, W >= 1), K_T_max >= 2");
+        const bool with_n = nrhs >= 8 && mxGetNumberOfElements(prhs[7]) > 0;
+        need(!with_n || mxGetNumberOfElements(prhs[7]) == (size_t)Nc, "n_wp must have N_cmd elements (or be empty)");
+        std::vector<int32_t> n_wp((size_t)Nc, W), col((size_t)Nc * W, -1);
+        for (int i = 0; with_n && i < Nc; ++i) n_wp[(size_t)i] = (int32_t)mxGetPr(prhs[7])[i];
+        const int timeout = nrhs >= 9 ? (int)mxGetScalar(prhs[8]) : 0;
+        const mwSize d3[3] = {3, (mwSize)KT, (mwSize)Nc};
+        plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        mxArray *v = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), *a = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        int32_t used = 0, sst = 0;
+        if (dmpc_transition_route(ctx, 1, N, Nc, W, mxGetPr(prhs[2]), mxGetPr(prhs[3]), with_n ? n_wp.data() : nullptr, mxGetScalar(prhs[6]), timeout,
+                                  nullptr, 0, KT, mxGetScalar(prhs[5]), 0, mxGetPr(plhs[0]), mxGetPr(v), mxGetPr(a), &used, &sst, col.data(), nullptr,
+                                  nullptr, nullptr, nullptr))
+            mexErrMsgIdAndTxt("dmpc:route", "%s", dmpc_last_error(ctx));
+        if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);
+        if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
+        if (nlhs > 5) {
+            plhs[5] = mxCreateDoubleMatrix((mwSize)W, (mwSize)Nc, mxREAL);
+            for (size_t j = 0; j < col.size(); ++j) mxGetPr(plhs[5])[j] = (double)col[j];
         }
         return;
     }
