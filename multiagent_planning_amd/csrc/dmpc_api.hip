@@ -637,6 +637,11 @@ extern "C" int dmpc_profile(dmpc_ctx *ctx, int enable)
 // ---------------------------------------------------------------------------------------------
 
 #include "dmpc_launch.hip"   // plan_step, the five stages, launch_step
+#include "dmpc_step.hip"     // the single step: scratch, StepIO and mixed-precision helpers, the record of a host-pointer call, the step entries
+
+// ---------------------------------------------------------------------------------------------
+// development aids, the profile's readers
+// ---------------------------------------------------------------------------------------------
 
 // development aid (not part of the public header): trace the active-set iterations of one agent
 extern "C" int dmpc_debug_trace(dmpc_ctx *ctx, int agent, int cap, double *host_out)
@@ -761,294 +766,6 @@ extern "C" int dmpc_profile_read(dmpc_ctx *ctx, double *avg_ms, int64_t *n_launc
     const int rc = dmpc_profile_read2(ctx, &a, &b, n_launches);
     if (avg_ms) *avg_ms = a + b;
     return rc;
-}
-
-static int table_f32(dmpc_ctx *ctx, const double *src, DevBuf &dst, size_t n, hipStream_t st);
-static int group_step_batch(dmpc_ctx *root, int S, int N, const double *l, const double *x_p, const double *x_v, const double *x_a,
-                            const double *pf, double *p_out, double *v_out, double *a_out, int32_t *status, int32_t *info);
-
-extern "C" int dmpc_step_device(dmpc_ctx *ctx, int S, int G, int C, int g_local, const double *lT, const double *x_p,
-                                const double *x_v, const double *x_a, const double *pf, double *p_out, double *v_out,
-                                double *a_out, double *lT_next, int32_t *status, int32_t *info, void *stream)
-{
-    if (!ctx) { g_err = "dmpc_step_device: ctx is NULL"; return -1; }
-    if (S < 1 || G < 1 || C < 1 || g_local < 0 || g_local >= G) FAIL(ctx, "dmpc_step_device: bad S/G/C/g_local");
-    if (!lT || !x_p || !x_v || !x_a || !pf || !p_out || !v_out || !a_out || !status) FAIL(ctx, "dmpc_step_device: NULL pointer");
-    if (ctx->grp) FAIL(ctx, "dmpc_step_device: device pointers belong to ONE GPU; a DMPC_DEVICE_ALL context drives several (use the host-pointer entry points)");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // mixed precision: the caller's table stays fp64; the scan reads an fp32 copy made here (half the bytes of the O(N) part)
-    const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;
-    if (mixed && table_f32(ctx, lT, ctx->lTf, (size_t)G * S * N3 * C, (hipStream_t)stream)) return -1;
-    StepIO io;
-    io.lT = lT; io.x_p = x_p; io.x_v = x_v; io.x_a = x_a; io.pf = pf;
-    io.p_out = p_out; io.v_out = v_out; io.a_out = a_out; io.lT_next = lT_next; io.status = status; io.info = info;
-    io.lTf = mixed ? ctx->lTf.as<float>() : nullptr;
-    const StepShape sh{S, G, C, g_local, /*c_first*/ 0, /*c_count*/ C};
-    return launch_step(ctx, sh, io, (hipStream_t)stream);
-}
-
-// uncommanded vehicles: 1 <= N_cmd <= N (the shared argument check of the *_cmd entries)
-static int check_cmd(dmpc_ctx *ctx, const char *entry, int S, int N, int N_cmd)
-{
-    if (S < 1 || N < 1) FAIL(ctx, std::string(entry) + ": S and N must be >= 1");
-    if (N_cmd < 1 || N_cmd > N) FAIL(ctx, std::string(entry) + ": N_cmd must be in 1 .. N (commanded agents first, uncommanded vehicles behind them)");
-    return 0;
-}
-
-extern "C" int dmpc_step_device_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *lT, const double *x_p, const double *x_v,
-                                    const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out, double *lT_next,
-                                    int32_t *status, int32_t *info, void *stream)
-{
-    if (!ctx) { g_err = "dmpc_step_device_cmd: ctx is NULL"; return -1; }
-    if (check_cmd(ctx, "dmpc_step_device_cmd", S, N, N_cmd)) return -1;
-    if (!lT || !x_p || !x_v || !x_a || !pf || !p_out || !v_out || !a_out || !status) FAIL(ctx, "dmpc_step_device_cmd: NULL pointer");
-    if (ctx->grp) FAIL(ctx, "dmpc_step_device_cmd: device pointers belong to ONE GPU; a DMPC_DEVICE_ALL context drives several (use the host-pointer entry points)");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;   // (the fp32 copy covers all N columns, the static ones included)
-    if (mixed && table_f32(ctx, lT, ctx->lTf, (size_t)S * N3 * N, (hipStream_t)stream)) return -1;
-    StepIO io;
-    io.lT = lT; io.x_p = x_p; io.x_v = x_v; io.x_a = x_a; io.pf = pf;
-    io.p_out = p_out; io.v_out = v_out; io.a_out = a_out; io.lT_next = lT_next; io.status = status; io.info = info;
-    io.lTf = mixed ? ctx->lTf.as<float>() : nullptr;
-    const StepShape sh{S, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ 0, /*c_count*/ N_cmd};
-    return launch_step(ctx, sh, io, (hipStream_t)stream);
-}
-
-extern "C" int dmpc_table_from_rows_device(dmpc_ctx *ctx, int S, int G, int C, const double *rows, double *lT, void *stream)
-{
-    if (!ctx) { g_err = "dmpc_table_from_rows_device: ctx is NULL"; return -1; }
-    if (S < 1 || G < 1 || C < 1 || !rows || !lT) FAIL(ctx, "dmpc_table_from_rows_device: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(table_from_rows_kernel, dim3(grid_1d((size_t)S * G * C * N3, 4096)), dim3(256), 0, (hipStream_t)stream, S, G, C, rows, lT);
-    HIPCHK(ctx, hipGetLastError());
-    return 0;
-}
-
-extern "C" int dmpc_advance_device(dmpc_ctx *ctx, int count, const double *p_out, const double *v_out, const double *a_out,
-                                   const int32_t *status, double *x_p, double *x_v, double *x_a, void *stream)
-{
-    if (!ctx) { g_err = "dmpc_advance_device: ctx is NULL"; return -1; }
-    if (count < 1 || !p_out || !v_out || !a_out || !status || !x_p || !x_v || !x_a) FAIL(ctx, "dmpc_advance_device: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(advance_kernel, dim3((unsigned)((count * 3 + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, count, p_out, v_out, a_out, (const int *)status, x_p, x_v, x_a);
-    HIPCHK(ctx, hipGetLastError());
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// host-pointer entry points
-// ---------------------------------------------------------------------------------------------
-
-static int ensure_step_scratch(dmpc_ctx *ctx, size_t agents_table, size_t agents_solved)
-{
-    int rc = 0;
-    rc |= ctx->rows.ensure(agents_table * N3 * 8);
-    rc |= ctx->lT.ensure(agents_table * N3 * 8);
-    rc |= ctx->xp.ensure(agents_solved * 24);
-    rc |= ctx->xv.ensure(agents_solved * 24);
-    rc |= ctx->xa.ensure(agents_solved * 24);
-    rc |= ctx->pf.ensure(agents_solved * 24);
-    rc |= ctx->pout.ensure(agents_solved * N3 * 8);
-    rc |= ctx->vout.ensure(agents_solved * N3 * 8);
-    rc |= ctx->aout.ensure(agents_solved * N3 * 8);
-    rc |= ctx->status.ensure(agents_solved * 4);
-    rc |= ctx->info.ensure(agents_solved * 32);
-    if (rc) FAIL(ctx, "device allocation failed");
-    return 0;
-}
-
-// mixed precision: fp32 copy of a table (n doubles) for the scan
-static int table_f32(dmpc_ctx *ctx, const double *src, DevBuf &dst, size_t n, hipStream_t st)
-{
-    if (dst.ensure(n * 4)) FAIL(ctx, "device allocation failed (fp32 table)");
-    hipLaunchKernelGGL(table_to_f32_kernel, dim3(grid_1d(n, 4096)), dim3(256), 0, st, n, src, dst.as<float>());
-    return 0;
-}
-
-// one MPC step of the first N_cmd agents of every scene against a table of N rows, on this context's device (N_cmd == N: dmpc_step_batch)
-static int step_batch_one(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *l, const double *x_p, const double *x_v,
-                          const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out,
-                          int32_t *status, int32_t *info)
-{
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t T = (size_t)S * N, A = (size_t)S * N_cmd;   // table rows, agents solved
-    if (ensure_step_scratch(ctx, T, A)) return -1;
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rows.p, l, T * N3 * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->xp.p, x_p, A * 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->xv.p, x_v, A * 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->xa.p, x_a, A * 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, pf, A * 24, hipMemcpyHostToDevice, st));
-    if (dmpc_table_from_rows_device(ctx, S, 1, N, ctx->rows.as<double>(), ctx->lT.as<double>(), st)) return -1;
-    const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;
-    if (mixed && table_f32(ctx, ctx->lT.as<double>(), ctx->lTf, T * N3, st)) return -1;
-    StepIO io;
-    io.lT = ctx->lT.as<double>(); io.x_p = ctx->xp.as<double>(); io.x_v = ctx->xv.as<double>(); io.x_a = ctx->xa.as<double>(); io.pf = ctx->pf.as<double>();
-    io.p_out = ctx->pout.as<double>(); io.v_out = ctx->vout.as<double>(); io.a_out = ctx->aout.as<double>();
-    io.status = ctx->status.as<int32_t>(); io.info = ctx->info.as<int32_t>();
-    io.lTf = mixed ? ctx->lTf.as<float>() : nullptr;
-    const StepShape sh{S, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ 0, /*c_count*/ N_cmd};
-    if (launch_step(ctx, sh, io, st)) return -1;
-    HIPCHK(ctx, hipMemcpyAsync(p_out, ctx->pout.p, A * N3 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(v_out, ctx->vout.p, A * N3 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(a_out, ctx->aout.p, A * N3 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(status, ctx->status.p, A * 4, hipMemcpyDeviceToHost, st));
-    if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->info.p, A * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return 0;
-}
-
-extern "C" int dmpc_step_batch(dmpc_ctx *ctx, int S, int N, const double *l, const double *x_p, const double *x_v,
-                               const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out,
-                               int32_t *status, int32_t *info)
-{
-    if (!ctx) { g_err = "dmpc_step_batch: ctx is NULL"; return -1; }
-    if (S < 1 || N < 1) FAIL(ctx, "dmpc_step_batch: S and N must be >= 1");
-    if (!l || !x_p || !x_v || !x_a || !pf || !p_out || !v_out || !a_out || !status) FAIL(ctx, "dmpc_step_batch: NULL pointer");
-    if (ctx->grp && N >= ctx->grp->G) return group_step_batch(ctx, S, N, l, x_p, x_v, x_a, pf, p_out, v_out, a_out, status, info);
-    return step_batch_one(ctx, S, N, N, l, x_p, x_v, x_a, pf, p_out, v_out, a_out, status, info);
-}
-
-// DMPC::solveParallelDMPCv2's cluster_solvev2 (dmpc.cpp:1792-1841) for the N_cmd = _pf.cols() commanded vehicles of N = _po.cols() (:1572-1573)
-extern "C" int dmpc_step_batch_cmd(dmpc_ctx *ctx, int S, int N, int N_cmd, const double *l, const double *x_p, const double *x_v,
-                                   const double *x_a, const double *pf, double *p_out, double *v_out, double *a_out,
-                                   int32_t *status, int32_t *info)
-{
-    if (!ctx) { g_err = "dmpc_step_batch_cmd: ctx is NULL"; return -1; }
-    if (check_cmd(ctx, "dmpc_step_batch_cmd", S, N, N_cmd)) return -1;
-    if (!l || !x_p || !x_v || !x_a || !pf || !p_out || !v_out || !a_out || !status) FAIL(ctx, "dmpc_step_batch_cmd: NULL pointer");
-    if (N_cmd == N) return dmpc_step_batch(ctx, S, N, l, x_p, x_v, x_a, pf, p_out, v_out, a_out, status, info);
-    return step_batch_one(ctx, S, N, N_cmd, l, x_p, x_v, x_a, pf, p_out, v_out, a_out, status, info);   // (a DMPC_DEVICE_ALL context: its first GPU)
-}
-
-extern "C" int dmpc_solve_one(dmpc_ctx *ctx, int N, int n, const double *l, const double *po, const double *vo,
-                              const double *ao, const double *pf, double *p, double *v, double *a, int32_t *status,
-                              int32_t *info)
-{
-    if (!ctx) { g_err = "dmpc_solve_one: ctx is NULL"; return -1; }
-    if (N < 1 || n < 0 || n >= N) FAIL(ctx, "dmpc_solve_one: agent index out of range");
-    if (!l || !po || !vo || !ao || !pf || !p || !v || !a || !status) FAIL(ctx, "dmpc_solve_one: NULL pointer");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ensure_step_scratch(ctx, (size_t)N, 1)) return -1;
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rows.p, l, (size_t)N * N3 * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->xp.p, po, 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->xv.p, vo, 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->xa.p, ao, 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, pf, 24, hipMemcpyHostToDevice, st));
-    if (dmpc_table_from_rows_device(ctx, 1, 1, N, ctx->rows.as<double>(), ctx->lT.as<double>(), st)) return -1;
-    const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;
-    if (mixed && table_f32(ctx, ctx->lT.as<double>(), ctx->lTf, (size_t)N * N3, st)) return -1;
-    StepIO io;
-    io.lT = ctx->lT.as<double>(); io.x_p = ctx->xp.as<double>(); io.x_v = ctx->xv.as<double>(); io.x_a = ctx->xa.as<double>(); io.pf = ctx->pf.as<double>();
-    io.p_out = ctx->pout.as<double>(); io.v_out = ctx->vout.as<double>(); io.a_out = ctx->aout.as<double>();
-    io.status = ctx->status.as<int32_t>(); io.info = ctx->info.as<int32_t>();
-    io.lTf = mixed ? ctx->lTf.as<float>() : nullptr;
-    const StepShape sh{/*S*/ 1, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ n, /*c_count*/ 1};
-    if (launch_step(ctx, sh, io, st)) return -1;
-    HIPCHK(ctx, hipMemcpyAsync(p, ctx->pout.p, N3 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(v, ctx->vout.p, N3 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(a, ctx->aout.p, N3 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(status, ctx->status.p, 4, hipMemcpyDeviceToHost, st));
-    if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->info.p, 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return 0;
-}
-
-// a5/a6 standalone: scan + collision rows of ONE agent in the reference's row order
-// (CheckCollSoftDMPC.m + CollConstrSoftDMPC.m and variants), without pruning.  Host pointers.
-extern "C" int dmpc_rows_one(dmpc_ctx *ctx, int N, int n, const double *l, const double *po, const double *vo,
-                             int max_rows, double *xi, double *rhs, double *slack_coef, int32_t *kc, int32_t *nrows,
-                             int32_t *viol_k, int32_t *status)
-{
-    if (!ctx) { g_err = "dmpc_rows_one: ctx is NULL"; return -1; }
-    if (N < 1 || n < 0 || n >= N || max_rows < 0) FAIL(ctx, "dmpc_rows_one: bad arguments");
-    if (!l || !po || !vo || !nrows || !viol_k || !status) FAIL(ctx, "dmpc_rows_one: NULL pointer");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ensure_step_scratch(ctx, (size_t)N, 1)) return -1;
-    hipStream_t st = ctx->stream;
-    const dmpc_params &p = ctx->prm;
-    const bool soft = variant_soft(p.variant);
-    double zero3[3] = {0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rows.p, l, (size_t)N * N3 * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->xp.p, po, 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->xv.p, vo, 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->xa.p, zero3, 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, zero3, 24, hipMemcpyHostToDevice, st));
-    if (dmpc_table_from_rows_device(ctx, 1, 1, N, ctx->rows.as<double>(), ctx->lT.as<double>(), st)) return -1;
-    StepParams P;
-    memset(&P, 0, sizeof(P));
-    P.variant = p.variant; P.S = 1; P.G = 1; P.C = N; P.g_local = 0; P.c_first = n; P.c_count = 1;
-    const long want = (p.variant == DMPC_VAR_HARD ? (long)K : (p.variant == DMPC_VAR_ALL3 ? 3L : 1L)) * (N > 1 ? N - 1 : 1);
-    P.nrmax = (int)((want + 1) & ~1L);   // the exact worst case: nothing is pruned or truncated here
-    P.ell_order = p.order;
-    P.h = p.h; P.rmin = p.rmin; P.e1z = 1.0 / p.c; P.e2z = p.order == 4 ? 1.0 / (p.c * p.c * p.c * p.c) : 1.0 / (p.c * p.c);   // E1 = E^-1, E2 = E^-order
-    if (p.variant == DMPC_VAR_SCP) { P.e1z = 1.0; P.e2z = 1.0; }   // solveDMPC: plain Euclidean norm (CheckCollDMPC.m:6, CollConstrDMPC.m:12-13)
-    P.alim = p.alim; P.Q1 = p.Q1; P.S1 = p.S1; P.term = p.term;
-    for (int d = 0; d < 3; ++d) { P.pmin[d] = p.pmin[d]; P.pmax[d] = p.pmax[d]; }
-    P.tables = ctx->d_tables; P.lT = ctx->lT.as<double>();
-    for (int i = 0; i < 3; ++i) P.hsum[i] = ctx->hsum[i];
-    P.x_p = ctx->xp.as<double>(); P.x_v = ctx->xv.as<double>(); P.x_a = ctx->xa.as<double>(); P.pf = ctx->pf.as<double>();
-    P.status = ctx->status.as<int32_t>(); P.no_prune = 1; P.qcap = QMAX; P.qover_bit = ST_CAPACITY;
-    const size_t per = (size_t)P.nrmax * (soft ? 7 : 4);
-    if (ctx->rowbuf.ensure(per * 8) || ctx->rowkc.ensure((size_t)P.nrmax * 4) || ctx->hdr.ensure(32)) FAIL(ctx, "device allocation failed");
-    P.rowbuf = ctx->rowbuf.as<double>(); P.rowkc = ctx->rowkc.as<int>(); P.hdr = ctx->hdr.as<int>();
-    P.lds_per_wave = (int)scan_lds_bytes();
-    // (order 4 -- the all-neighbour variants only, check_params -- has its own scan kernels: dist = |E1 d|_4, xi = E2 d.^3, prev_dist = dist^3)
-    if (p.order == 4) {
-        if (soft) hipLaunchKernelGGL((dmpc_scan_kernel<true, double, false, true>), dim3(1), dim3(64), scan_lds_bytes(), st, P);
-        else hipLaunchKernelGGL((dmpc_scan_kernel<false, double, false, true>), dim3(1), dim3(64), scan_lds_bytes(), st, P);
-    } else if (soft) hipLaunchKernelGGL((dmpc_scan_kernel<true, double, false>), dim3(1), dim3(64), scan_lds_bytes(), st, P);
-    else hipLaunchKernelGGL((dmpc_scan_kernel<false, double, false>), dim3(1), dim3(64), scan_lds_bytes(), st, P);
-    HIPCHK(ctx, hipGetLastError());
-    int hdr[8];
-    HIPCHK(ctx, hipMemcpyAsync(hdr, ctx->hdr.p, 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    const int nr = hdr[0];
-    *nrows = hdr[1]; *viol_k = hdr[2]; *status = hdr[3] & (DMPC_ST_COLL | DMPC_ST_CAPACITY);
-    const int cnt = nr < max_rows ? nr : max_rows;
-    if (cnt > 0 && xi && rhs && kc) {
-        std::vector<double> buf(per);
-        std::vector<int> kbuf(P.nrmax);
-        HIPCHK(ctx, hipMemcpy(buf.data(), ctx->rowbuf.p, per * 8, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(kbuf.data(), ctx->rowkc.p, (size_t)P.nrmax * 4, hipMemcpyDeviceToHost));
-        // reference order: horizon step major, neighbour index minor (the hard variant's rows are emitted
-        // neighbour-chunk major on the device): stable sort by constrained step
-        std::vector<int> idx(nr);
-        for (int i = 0; i < nr; ++i) idx[i] = i;
-        if (p.variant == DMPC_VAR_HARD || p.variant == DMPC_VAR_ALL3)
-            std::stable_sort(idx.begin(), idx.end(), [&](int a_, int b_) { return kbuf[a_] < kbuf[b_]; });
-        for (int i = 0; i < cnt; ++i) {
-            const int j = idx[i];
-            xi[3 * i] = buf[3 * j]; xi[3 * i + 1] = buf[3 * j + 1]; xi[3 * i + 2] = buf[3 * j + 2];
-            rhs[i] = buf[(size_t)3 * P.nrmax + j];
-            if (slack_coef) slack_coef[i] = soft ? buf[(size_t)4 * P.nrmax + j] : 0.0;
-            kc[i] = kbuf[j] + 1;   // 1-based like the reference's k_ctr
-        }
-    }
-    return 0;
-}
-
-extern "C" int dmpc_init_batch(dmpc_ctx *ctx, int S, int N, const double *po, const double *pf, double *l_out,
-                               double *v_out, double *a_out)
-{
-    if (!ctx) { g_err = "dmpc_init_batch: ctx is NULL"; return -1; }
-    if (S < 1 || N < 1 || !po || !pf || !l_out) FAIL(ctx, "dmpc_init_batch: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t A = (size_t)S * N;
-    if (ctx->po.ensure(A * 24) || ctx->pf.ensure(A * 24) || ctx->rows.ensure(A * N3 * 8)) FAIL(ctx, "device allocation failed");
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, po, A * 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->pf.p, pf, A * 24, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(init_rows_kernel, dim3((unsigned)((A * N3 + 255) / 256)), dim3(256), 0, st, (int)A, ctx->prm.h,
-                       ctx->po.as<double>(), ctx->pf.as<double>(), ctx->rows.as<double>());
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(l_out, ctx->rows.p, A * N3 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (v_out) memset(v_out, 0, A * N3 * 8);   // initDMPC.m:11-12: v = a = zeros(3,k_hor)
-    if (a_out) memset(a_out, 0, A * N3 * 8);
-    return 0;
 }
 
 // Batched transitions are bound, MPC step by MPC step, by the slowest agent of the whole batch while most of the GPU idles.  Scenes are independent,

@@ -424,27 +424,36 @@ static StepPlan plan_step(const dmpc_ctx *ctx, const StepShape &sh)
 // the stages
 // ---------------------------------------------------------------------------------------------
 
-// the constant part of the parameter block, the row scratch, and a closed loop's post step when the launch fuses it
-static int fill_params(dmpc_ctx *ctx, const StepPlan &pl, const StepIO &io, StepParams &P, hipStream_t st)
+// the parameter block zeroed, and the part of it that a context's parameters, tables and hsum decide alone (every launch of the scan family starts
+// from it: a step's, and dmpc_rows_one's single wave)
+static void fill_constants(const dmpc_ctx *ctx, StepParams &P)
 {
     const dmpc_params &p = ctx->prm;
-    const DevOptions &o = ctx->opt;
-    const StepShape &sh = pl.sh;
     memset(&P, 0, sizeof(P));
-    P.variant = p.variant; P.S = sh.S; P.G = sh.G; P.C = sh.C; P.g_local = sh.g_local;
-    P.c_first = sh.c_first; P.c_count = sh.c_count;
-    P.nrmax = pl.nrmax;
-    if (p.variant == DMPC_VAR_HARD && (sh.G > 256 || sh.C >= (1 << 20)))   // packing of the scan's candidate list
-        FAIL(ctx, "solveHardDMPC scan: at most 256 chunks of fewer than 2^20 agents");
+    P.variant = p.variant;
     P.max_tries = p.max_tries;
     P.ell_order = p.order;
     P.h = p.h; P.rmin = p.rmin; P.e1z = 1.0 / p.c; P.e2z = p.order == 4 ? 1.0 / (p.c * p.c * p.c * p.c) : 1.0 / (p.c * p.c);   // E1 = E^-1, E2 = E^-order
-    if (pl.scp) { P.e1z = 1.0; P.e2z = 1.0; }   // solveDMPC: plain Euclidean norm (CheckCollDMPC.m:6, CollConstrDMPC.m:12-13)
+    if (p.variant == DMPC_VAR_SCP) { P.e1z = 1.0; P.e2z = 1.0; }   // solveDMPC: plain Euclidean norm (CheckCollDMPC.m:6, CollConstrDMPC.m:12-13)
     P.alim = p.alim; P.Q1 = p.Q1; P.S1 = p.S1; P.term = p.term;
     P.Qfar = p.Qfar > 0 ? p.Qfar : 1000.0; P.Qnear = p.Qnear > 0 ? p.Qnear : 10000.0; P.Sfree = p.Sfree > 0 ? p.Sfree : 10.0;
     for (int d = 0; d < 3; ++d) { P.pmin[d] = p.pmin[d]; P.pmax[d] = p.pmax[d]; }
     P.tables = ctx->d_tables;
     for (int i = 0; i < 3; ++i) P.hsum[i] = ctx->hsum[i];
+    P.scp_tol = p.tol;
+}
+
+// the parameter block of a step: the constant part, the launch's shape and arrays, the row scratch, and a closed loop's post step when the launch fuses it
+static int fill_params(dmpc_ctx *ctx, const StepPlan &pl, const StepIO &io, StepParams &P, hipStream_t st)
+{
+    const DevOptions &o = ctx->opt;
+    const StepShape &sh = pl.sh;
+    fill_constants(ctx, P);
+    P.S = sh.S; P.G = sh.G; P.C = sh.C; P.g_local = sh.g_local;
+    P.c_first = sh.c_first; P.c_count = sh.c_count;
+    P.nrmax = pl.nrmax;
+    if (ctx->prm.variant == DMPC_VAR_HARD && (sh.G > 256 || sh.C >= (1 << 20)))   // packing of the scan's candidate list
+        FAIL(ctx, "solveHardDMPC scan: at most 256 chunks of fewer than 2^20 agents");
     // mixed precision: the scan reads the fp32 copy lTf of the table; lT (fp64, chunk g_local) is the solve's fallback
     P.lT = io.lTf ? (const double *)io.lTf : io.lT;
     P.own_prev = io.lTf ? (io.own_prev ? io.own_prev : io.lT + (size_t)sh.g_local * sh.S * N3 * sh.C) : nullptr;
@@ -461,7 +470,6 @@ static int fill_params(dmpc_ctx *ctx, const StepPlan &pl, const StepIO &io, Step
     P.dbg = ctx->dbg; P.dbg_agent = ctx->dbg_agent; P.dbg_cap = ctx->dbg_cap;
     P.iter_cap = o.iter_cap;
     P.rsolve_cap = o.rsolve_cap;
-    P.scp_tol = p.tol;
     P.dep_tol_f32 = std::pow(10.0, -(double)o.f32_dep_exp);
     P.no_level_check = o.no_level_check;
     P.no_level_skip = o.no_level_skip;

@@ -263,14 +263,10 @@ extern "C" int dmpc_step_sharded_device(dmpc_ctx *ctx, int S, int N, const doubl
     hipStream_t st = (hipStream_t)stream;
     const size_t chunk = (size_t)S * N3 * cmax;
     if (ctx->sendbuf.ensure(chunk * 8)) FAIL(ctx, "device allocation failed (exchange buffer)");
-    const int rem = N % G;
     // mixed precision: the caller's tables are fp64 (and so is the payload of this entry point); the scan reads an fp32 copy
-    const bool mixed = (ctx->precision & DMPC_PREC_MIXED) != 0;
-    if (mixed && table_f32(ctx, lT, ctx->lTf, (size_t)G * chunk, st)) return -1;
-    StepIO io;
-    io.lT = lT; io.x_p = x_p; io.x_v = x_v; io.x_a = x_a; io.pf = pf;
-    io.p_out = p_out; io.v_out = v_out; io.a_out = a_out; io.lT_next = ctx->sendbuf.as<double>(); io.status = status; io.info = info;
-    io.short_from = rem; io.lTf = mixed ? ctx->lTf.as<float>() : nullptr;
+    StepIO io = caller_io(lT, x_p, x_v, x_a, pf, p_out, v_out, a_out, /*lT_next*/ ctx->sendbuf.as<double>(), status, info);
+    io.short_from = N % G;
+    if (mixed_table(ctx, io, (size_t)G * chunk, st)) return -1;
     const StepShape sh{S, G, /*C*/ cmax, /*g_local*/ rank, /*c_first*/ 0, /*c_count*/ cnt};
     if (launch_step(ctx, sh, io, st)) return -1;
     return exchange(ctx, ctx->sendbuf.p, lT_next, chunk, 8, nullptr, nullptr, 0, st);
@@ -409,10 +405,9 @@ static int transition_sharded_impl(dmpc_ctx *ctx, const TransitionCall &c, int g
     std::vector<int32_t> flags((size_t)K_T_max * S * 2, 0);
     VerdictFold verdict; verdict.init(c);
     for (int k = 1; k < K_T_max && verdict.ndone < S; ++k) {
-        StepIO io;
-        io.lT = cur; io.x_p = xp; io.x_v = xv; io.x_a = xa; io.pf = own_pf;
-        io.p_out = ctx->pout.as<double>(); io.v_out = ctx->vout.as<double>(); io.a_out = ctx->aout.as<double>(); io.lT_next = ctx->sendbuf.as<double>();
-        io.status = ctx->status.as<int32_t>(); io.scene_done = ctx->scene_done.as<int>(); io.short_from = rem; io.lTf = mixed ? curf : nullptr; io.own_prev = mixed ? own_cur : nullptr;
+        StepIO io = scratch_io(ctx);   // (xp, xv, xa, own_pf and the output rows are the scratch's; a closed loop takes no info)
+        io.lT = cur; io.lT_next = ctx->sendbuf.as<double>(); io.info = nullptr;
+        io.scene_done = ctx->scene_done.as<int>(); io.short_from = rem; io.lTf = mixed ? curf : nullptr; io.own_prev = mixed ? own_cur : nullptr;
         const StepShape sh{S, G, /*C*/ cmax, /*g_local*/ rank, /*c_first*/ 0, /*c_count*/ cnt};
         if (launch_step(ctx, sh, io, st)) {
             // a rank that cannot take its step must not leave the others waiting in the exchange: the group's barriers are released by
@@ -518,44 +513,29 @@ static int group_transition(dmpc_ctx *root, const TransitionCall &c)
     return 0;
 }
 
-// dmpc_step_batch on a group: every rank uploads the scene tables, solves its cluster, and writes its agents' rows of the outputs
-static int group_step_batch(dmpc_ctx *root, int S, int N, const double *l, const double *x_p, const double *x_v, const double *x_a,
-                            const double *pf, double *p_out, double *v_out, double *a_out, int32_t *status, int32_t *info)
+// dmpc_step_batch on a group: every rank uploads the scene tables, solves its cluster, and writes its agents' rows of the outputs (its slice of
+// the call: the states up and the outputs down are strided copies, a row per scene)
+static int group_step_batch(dmpc_ctx *root, const StepCall &c)
 {
     const int G = root->grp->G;
-    if (G > N) FAIL(root, "dmpc_step_batch: more GPUs than agents");
-    return group_run(root, [&](dmpc_ctx *c, int r) -> int {
+    if (G > c.N) FAIL(root, "dmpc_step_batch: more GPUs than agents");
+    return group_run(root, [&](dmpc_ctx *rank_ctx, int r) -> int {
         int32_t lo = 0, cnt = 0, cmax = 0;
-        if (dmpc_partition(N, G, r, &lo, &cnt, &cmax)) return -1;
-        HIPCHK(c, hipSetDevice(c->device));
-        const size_t A = (size_t)S * N, Aown = (size_t)S * cnt, tab = (size_t)G * S * N3 * cmax;
-        if (ensure_step_scratch(c, A, Aown) || c->lT.ensure(tab * 8) || c->po.ensure(A * 24)) FAIL(c, "device allocation failed");
-        hipStream_t st = c->stream;
-        HIPCHK(c, hipMemcpyAsync(c->rows.p, l, A * N3 * 8, hipMemcpyHostToDevice, st));
-        const int rem = N % G;
-        hipLaunchKernelGGL(mg::table_from_rows_padded_kernel, dim3(grid_1d(tab, 4096)), dim3(256), 0, st, S, N, G, (int)cmax, rem, (const double *)c->rows.as<double>(),
-                           c->lT.as<double>());
-        // own agents' states: rows [lo, lo + cnt) of every scene (strided host arrays)
-        const double *src[4] = {x_p, x_v, x_a, pf};
-        double *dst[4] = {c->xp.as<double>(), c->xv.as<double>(), c->xa.as<double>(), c->pf.as<double>()};
-        for (int u = 0; u < 4; ++u)
-            HIPCHK(c, hipMemcpy2DAsync(dst[u], (size_t)cnt * 24, src[u] + (size_t)lo * 3, (size_t)N * 24, (size_t)cnt * 24, (size_t)S, hipMemcpyHostToDevice, st));
-        const bool mixed = (c->precision & DMPC_PREC_MIXED) != 0;
-        if (mixed && table_f32(c, c->lT.as<double>(), c->lTf, tab, st)) return -1;
-        StepIO io;
-        io.lT = c->lT.as<double>(); io.x_p = dst[0]; io.x_v = dst[1]; io.x_a = dst[2]; io.pf = dst[3];
-        io.p_out = c->pout.as<double>(); io.v_out = c->vout.as<double>(); io.a_out = c->aout.as<double>();
-        io.status = c->status.as<int32_t>(); io.info = c->info.as<int32_t>();
-        io.short_from = rem; io.lTf = mixed ? c->lTf.as<float>() : nullptr;
-        const StepShape sh{S, G, /*C*/ cmax, /*g_local*/ r, /*c_first*/ 0, /*c_count*/ cnt};
-        if (launch_step(c, sh, io, st)) return -1;
-        double *out[3] = {p_out, v_out, a_out};
-        const double *dev[3] = {c->pout.as<double>(), c->vout.as<double>(), c->aout.as<double>()};
-        for (int u = 0; u < 3; ++u)
-            HIPCHK(c, hipMemcpy2DAsync(out[u] + (size_t)lo * N3, (size_t)N * N3 * 8, dev[u], (size_t)cnt * N3 * 8, (size_t)cnt * N3 * 8, (size_t)S, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpy2DAsync(status + lo, (size_t)N * 4, c->status.p, (size_t)cnt * 4, (size_t)cnt * 4, (size_t)S, hipMemcpyDeviceToHost, st));
-        if (info) HIPCHK(c, hipMemcpy2DAsync(info + (size_t)lo * 8, (size_t)N * 32, c->info.p, (size_t)cnt * 32, (size_t)cnt * 32, (size_t)S, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        return 0;
+        if (dmpc_partition(c.N, G, r, &lo, &cnt, &cmax)) return -1;
+        HIPCHK(rank_ctx, hipSetDevice(rank_ctx->device));
+        const StepCall own = c.agents(lo, cnt);
+        hipStream_t st = rank_ctx->stream;
+        // stage: as one GPU does, but the table is the rank-major one [G][S][3K][cmax] with its padding, built in front of the states' copies
+        const size_t T = (size_t)c.S * c.N, tab = (size_t)G * c.S * N3 * cmax;
+        if (ensure_step_scratch(rank_ctx, T, (size_t)c.S * cnt) || rank_ctx->lT.ensure(tab * 8) || rank_ctx->po.ensure(T * 24)) FAIL(rank_ctx, "device allocation failed");
+        HIPCHK(rank_ctx, hipMemcpyAsync(rank_ctx->rows.p, c.l, T * N3 * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(mg::table_from_rows_padded_kernel, dim3(grid_1d(tab, 4096)), dim3(256), 0, st, c.S, c.N, G, (int)cmax, c.N % G,
+                           (const double *)rank_ctx->rows.as<double>(), rank_ctx->lT.as<double>());
+        if (upload_states(rank_ctx, own, st)) return -1;
+        StepIO io = scratch_io(rank_ctx);
+        if (mixed_table(rank_ctx, io, tab, st)) return -1;
+        io.short_from = c.N % G;
+        if (launch_step(rank_ctx, {c.S, G, /*C*/ cmax, /*g_local*/ r, /*c_first*/ 0, /*c_count*/ cnt}, io, st)) return -1;
+        return fetch_step(rank_ctx, own, st);
     });
 }

@@ -311,9 +311,9 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
         int *const verdict_k = ctx->flags.as<int>() + (size_t)k * S * 2;
         const PostStep post{K_T_max, k, c.error_tol, xp, xv, xa, ctx->hist_p.as<double>(), ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), verdict_k, ctx->scene_done.as<int>()};
         double **out = hold.outs[k & 1];
-        StepIO io;
-        io.lT = cur; io.x_p = xp; io.x_v = xv; io.x_a = xa; io.pf = ctx->pf.as<double>();
-        io.p_out = out[0]; io.v_out = out[1]; io.a_out = out[2]; io.lT_next = nxt; io.status = ctx->status.as<int32_t>();
+        StepIO io = scratch_io(ctx);   // (xp, xv, xa, the goals and the status are the scratch's; a closed loop takes no info)
+        io.lT = cur; io.lT_next = nxt; io.info = nullptr;
+        io.p_out = out[0]; io.v_out = out[1]; io.a_out = out[2];
         io.scene_done = ctx->scene_done.as<int>(); io.lTf = mixed ? ctx->lTf.as<float>() : nullptr; io.post = c.hold ? nullptr : &post;
         const StepShape sh{S, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ 0, /*c_count*/ N_cmd};
         if (launch_step(ctx, sh, io, st)) return -1;

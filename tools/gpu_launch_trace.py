@@ -9,7 +9,9 @@ The comparison is of the ordered lists of (kernel name, grid size, workgroup siz
 --closed-loop (in place of the step cases): one small call of every closed-loop entry -- dmpc_transition, _cmd, _scripted, _mission, _hold, and
 dmpc_transition / _mission in mixed precision -- each on one context and one stream (tools/gpu_transition_probe.py: single_context).
 --postcheck (likewise): the calls of tools/gpu_postcheck_probe.py that enqueue on one stream -- every post-check entry on host and on resident
-histories, the scenes of 300 agents on the cell grid with their brute-force pass (single_context there)."""
+histories, the scenes of 300 agents on the cell grid with their brute-force pass (single_context there).
+--step-entries (likewise): one small call of every single-step entry on one context each -- dmpc_init_batch, dmpc_step_batch, _cmd, dmpc_solve_one,
+dmpc_step_device, _cmd in fp64 and mixed precision, dmpc_rows_one per variant (tools/gpu_step_probe.py: single_context)."""
 import csv
 import glob
 import os
@@ -57,6 +59,12 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["--postcheck"]:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import gpu_postcheck_probe as probe
+        for name, r in probe.single_context():
+            print(f"{name}: {sum(v is not None for v in r.values())} arrays", flush=True)
+        sys.exit(0)
+    if sys.argv[1:] == ["--step-entries"]:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import gpu_step_probe as probe
         for name, r in probe.single_context():
             print(f"{name}: {sum(v is not None for v in r.values())} arrays", flush=True)
         sys.exit(0)
