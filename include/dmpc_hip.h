@@ -688,6 +688,41 @@ DMPC_API int dmpc_assign_goals(dmpc_ctx *ctx, int S, int N, const double *po, co
 DMPC_API int dmpc_assign_goals_device(dmpc_ctx *ctx, int S, int N, const double *po, const double *goals, double eps, int max_rounds,
                              int32_t *perm, double *pf_assigned, double *price, double *cost, int32_t *rounds, void *stream);
 
+/* Route planning ahead of a transition (additive, the ABI revision stays 8): which way round the static vehicles every commanded agent goes.
+ * DMPC has no global planner -- an agent whose straight line is blocked by a wall of uncommanded vehicles parks in front of it -- and
+ * dmpc_transition_route flies waypoints somebody has to supply; this entry supplies them.  No reference counterpart.
+ * S scenes; po_cmd and goals [S][N_cmd][3]: the commanded agents' starts and goals; obst [S][M][3], M >= 0 (NULL allowed when M == 0): the
+ * vehicles to go round (the rows of po behind the commanded ones; a caller may add a snapshot of scripted vehicles).  Commanded agents do not
+ * block each other: keeping them apart is DMPC's job.  rmin, c, pmin and pmax are the context's.
+ * The rule is pinned so that the result depends on nothing but the inputs (tests/plan.py restates it; the device equals it bit for bit).  Every
+ * fp64 operation is rounded on its own, no fused multiply-add; everything after the blocked predicate is integer arithmetic:
+ *   grid      n_a = max(1, (int)ceil((pmax_a - pmin_a) / cell)) cells per axis; the cell of a point is clamp((int)floor((p_a - pmin_a) / cell),
+ *             0, n_a - 1) -- points outside the box are clamped --, its centre pmin_a + (i_a + 0.5) * cell.  n_x n_y n_z <= DMPC_PLAN_MAX_CELLS.
+ *   blocked   a cell is blocked if for some obstacle m (dx*dx + dy*dy) + dz*dz < R*R with dx, dy = centre - obst_m, dz = (centre - obst_m)_z * cinv,
+ *             cinv = 1.0 / c, R = rmin + margin.  For agent i with start cell s_i (of po_cmd) and goal cell g_i:
+ *             free_i(q) = !blocked(q) || q == s_i || q == g_i.
+ *   field     D(g_i) = 0; level L+1 is every unlabelled cell with free_i that has a 6-neighbour at level L; the sweep stops once s_i is labelled
+ *             or a level adds nothing.  s_i unlabelled: DMPC_PLAN_UNREACHABLE, n_wp = 1, every slot the goal, hops = -1.  Else hops = D(s_i).
+ *   descent   the path c_0 = s_i .. c_H = g_i: from c_t the first neighbour in the order -x, +x, -y, +y, -z, +z with D = D(c_t) - 1.
+ *   clear     clear(a, b) with L = max_axis |b - a|: for j = 0 .. 2L the cell q_axis = (2L a_axis + j (b_axis - a_axis) + L) / (2L) (integer
+ *             division) must be free_i.
+ *   pruning   anchor t0 = 0; until t0 == H: t1 = the largest t > t0 that is t0 + 1 or has clear(c_t0, c_t); emit t1; t0 = t1.  A waypoint is
+ *             the centre of c_t, except that an emitted t == H is the goal itself, bit for bit.  H == 0: n_wp = 1.  More than W emissions: the
+ *             first W - 1 are kept, the goal takes slot W - 1, DMPC_PLAN_TRUNCATED.  Slots from n_wp on hold the goal.
+ * waypoints [S][N_cmd][W][3], n_wp, plan_status, hops [S][N_cmd] int32; any output may be NULL.  waypoints and n_wp are laid out as
+ * dmpc_transition_route takes them.  fp64 whatever the context's precision; a DMPC_DEVICE_ALL context runs the call on its first GPU; there
+ * is no RCCL form.  Refused (-1, nothing launched, a message that starts with the entry's name): S < 1, N_cmd < 1, M < 0, W < 1; po_cmd or goals
+ * NULL, obst NULL with M > 0; cell or margin not finite, cell <= 0, margin < 0; more than DMPC_PLAN_MAX_CELLS cells (the message has the count).
+ * The _device form takes device pointers and enqueues on the caller's stream. */
+#define DMPC_PLAN_MAX_CELLS 32768
+#define DMPC_PLAN_OK 0
+#define DMPC_PLAN_TRUNCATED 1
+#define DMPC_PLAN_UNREACHABLE 2
+DMPC_API int dmpc_plan_routes(dmpc_ctx *ctx, int S, int N_cmd, int M, int W, const double *po_cmd, const double *goals, const double *obst,
+                     double cell, double margin, double *waypoints, int32_t *n_wp, int32_t *plan_status, int32_t *hops);
+DMPC_API int dmpc_plan_routes_device(dmpc_ctx *ctx, int S, int N_cmd, int M, int W, const double *po_cmd, const double *goals, const double *obst,
+                            double cell, double margin, double *waypoints, int32_t *n_wp, int32_t *plan_status, int32_t *hops, void *stream);
+
 /* Standalone forms of the path's small helpers (fused into the step kernels inside the solvers), for callers that
  * invoke them on their own as the reference's scripts do.  Host pointers, synchronous.
  *   dmpc_prop_state   propStatedmpc.m:1-8 (A_initp given): p = A_p a + A_initp [po;vo], v = A_v a + 1 (x) vo  -> pass

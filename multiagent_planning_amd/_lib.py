@@ -16,6 +16,7 @@ VARIANTS = dict(bound=0, bound2=1, all3=2, hard=3, ondemand=4, ellip=5, softall=
 ST_SOLVED, ST_OUTBOUND, ST_COLL, ST_INFEAS, ST_CAPACITY, ST_ITERCAP = 1, 2, 4, 8, 16, 32
 PRECISIONS = dict(f64=0, mixed=1, f32factor=2, low=3)
 ST_REACHED = 256   # scene_status of transition(): every agent reached its goal
+PLAN_OK, PLAN_TRUNCATED, PLAN_UNREACHABLE = 0, 1, 2   # plan_status of plan()
 ST_HELD = 64       # transition(on_fail="hold") / mission(on_fail="hold") / route(on_fail="hold"): the agent flew its previous plan on this column
 INFO_LEN = 8
 I_VIOLK, I_NROWS, I_TRIES, I_CASE, I_ITERS, I_NSLACK, I_NACTIVE, I_MAXQ = range(8)
@@ -42,6 +43,7 @@ ABI_SYMBOLS = [
     "dmpc_transition_hold",
     "dmpc_assign_goals", "dmpc_assign_goals_device",
     "dmpc_transition_route",
+    "dmpc_plan_routes", "dmpc_plan_routes_device",
 ]
 
 
@@ -151,6 +153,9 @@ def load():
     # routes: every agent through waypoints of its own (additive, still revision 8)
     L.dmpc_transition_route.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, ip, C.c_double, C.c_int, dp, C.c_int, C.c_int, C.c_double, C.c_int,
                                         dp, dp, dp, ip, ip, ip, ip, ip, ip, ip]
+    # route planning round static vehicles, ahead of route() (additive, still revision 8)
+    L.dmpc_plan_routes.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, dp, C.c_double, C.c_double, dp, ip, ip, ip]
+    L.dmpc_plan_routes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -604,6 +609,36 @@ class Dmpc:
             out.update(hold_count=cnt, hold_first=first, agent_status=log)
         return out
 
+    def plan(self, po, goals, cell, margin=0.0, W=4, obstacles=None):
+        """dmpc_plan_routes: which way round the static vehicles every commanded agent goes.  goals [S,N_cmd,3] (or [N_cmd,3]); po [S,N,3] with
+        N >= N_cmd rows as in transition(): the rows behind the goals are the obstacles; obstacles [S,M,3] (or [M,3]): further obstacle points
+        (a snapshot of scripted vehicles, say), behind po's.  A wavefront over a grid of `cell` metres on the context's workspace, a cell blocked
+        when its centre is within rmin + margin of an obstacle in the collision metric, the cell path pruned by line of sight to at most W
+        waypoints -- the rule include/dmpc_hip.h pins.  Returns dict(waypoints [S,N_cmd,W,3], n_wp [S,N_cmd], plan_status [S,N_cmd] (PLAN_OK,
+        PLAN_TRUNCATED: more corners than W, the goal took the last slot, PLAN_UNREACHABLE: no way, the goal alone), hops [S,N_cmd] (cells of
+        the path, -1: no way)); waypoints and n_wp go into route() as they are."""
+        po, goals = _f(po), _f(goals)
+        if (po.ndim not in (2, 3) or goals.ndim != po.ndim or po.shape[-1] != 3 or goals.shape[-1] != 3 or goals.shape[:-2] != po.shape[:-2]
+                or not 1 <= goals.shape[-2] <= po.shape[-2]):
+            raise DmpcError(f"plan: goals {tuple(goals.shape)} must be [S,N_cmd,3] next to po [S,N,3] (or [N_cmd,3] next to [N,3]) with N_cmd <= N: po is {tuple(po.shape)}")
+        n_cmd = goals.shape[-2]
+        lead = goals.shape[:-1]
+        S = 1 if po.ndim == 2 else po.shape[0]
+        obst = po[..., n_cmd:, :]
+        if obstacles is not None:
+            obstacles = _f(obstacles)
+            if obstacles.ndim != po.ndim or obstacles.shape[-1] != 3 or obstacles.shape[:-2] != po.shape[:-2]:
+                raise DmpcError(f"plan: obstacles {tuple(obstacles.shape)} must be [S,M,3] next to po [S,N,3] (or [M,3] next to [N,3])")
+            obst = np.concatenate([obst, obstacles], axis=-2)
+        obst = _f(obst)
+        M, W = obst.shape[-2], int(W)
+        wp = np.zeros(lead + (max(W, 1), 3))
+        n_wp, st, hops = (np.zeros(lead, dtype=np.int32) for _ in range(3))
+        self._chk(self._L.dmpc_plan_routes(self._ctx, int(S), int(n_cmd), int(M), W, _dp(np.ascontiguousarray(po[..., :n_cmd, :])), _dp(goals),
+                                           _dp(obst) if M else C.POINTER(C.c_double)(), float(cell), float(margin), _dp(wp), _ip(n_wp), _ip(st),
+                                           _ip(hops)))
+        return dict(waypoints=wp, n_wp=n_wp, plan_status=st, hops=hops)
+
     # ---- multi-GPU (one process per GPU): dmpc_multigpu.hip ----
     @staticmethod
     def comm_unique_id():
@@ -894,6 +929,11 @@ class Dmpc:
         """dmpc_assign_goals_device: po, goals [S,N,3] fp64 and the outputs (0: not wanted; perm, rounds int32) on the device"""
         self._chk(self._L.dmpc_assign_goals_device(self._ctx, S, N, po, goals, float(eps), int(max_rounds), perm or None, pf or None, price or None,
                                                    cost or None, rounds or None, stream or None))
+
+    def plan_routes_device(self, S, n_cmd, M, W, po_cmd, goals, obst, cell, margin, waypoints=0, n_wp=0, plan_status=0, hops=0, stream=0):
+        """dmpc_plan_routes_device: po_cmd, goals [S,n_cmd,3], obst [S,M,3] fp64 and the outputs (0: not wanted; all but waypoints int32) on the device"""
+        self._chk(self._L.dmpc_plan_routes_device(self._ctx, S, n_cmd, M, W, po_cmd, goals, obst or None, float(cell), float(margin), waypoints or None,
+                                                  n_wp or None, plan_status or None, hops or None, stream or None))
 
     def profile(self, enable=True):
         self._chk(self._L.dmpc_profile(self._ctx, 1 if enable else 0))

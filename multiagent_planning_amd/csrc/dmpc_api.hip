@@ -151,6 +151,8 @@ struct dmpc_ctx {
     int32_t *asg_host = nullptr; size_t asg_host_cap = 0;                  // pinned: the scenes' done flags of two windows of rounds
     hipEvent_t asg_ev[2] = {nullptr, nullptr};
     int max_lds_assign = 0;  // dynamic-LDS limit assign_one_kernel was last raised to
+    DevBuf plan_io, plan_mask;                                             // dmpc_plan_routes: staged inputs / outputs of the host form; the scenes' blocked bitmasks
+    int max_lds_plan = 0;    // dynamic-LDS limit plan_route_kernel was last raised to
     int pc_fallback_scenes = 0;   // last dmpc_postcheck: scenes of a cell-grid search that were searched again by brute force
     std::vector<dmpc_ctx *> children;   // further contexts (own stream and buffers) for the other parts of a split batch of transitions
     std::vector<int> split_at;          // non-empty: the last dmpc_transition left scenes [split_at[i], split_at[i+1]) in part i (0: here, i > 0: children[i-1])
@@ -989,6 +991,7 @@ extern "C" int dmpc_random_sets_device(dmpc_ctx *ctx, int S, int N, const double
 }
 
 #include "dmpc_assign.hip"   // goal assignment: the auction's kernels and the two entries
+#include "dmpc_plan.hip"     // route planning round static vehicles: the wavefront planner's kernels and the two entries
 
 
 // ---------------------------------------------------------------------------------------------

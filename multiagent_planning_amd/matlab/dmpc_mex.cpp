@@ -25,6 +25,7 @@
 //   [pk,vk,ak,K_T_used,scene_status,wp_col] = dmpc_mex('route', params, po, waypoints, K_T_max, error_tol, capture[, n_wp[, timeout]])   waypoints 3 x W x N_cmd: see below
 //   [perm,pf,cost,rounds] = dmpc_mex('assign', params, po, goals[, eps[, max_rounds]])  goal assignment (dmpc_assign_goals): po, goals 3 x N; perm 1 x N, 1-based:
 //                                                                                    agent i takes goals(:,perm(i)) = pf(:,i); eps default 1e-4 / N
+//   [waypoints,n_wp,plan_status,hops] = dmpc_mex('plan', params, po, goals, cell[, margin[, W[, obstacles]]])   route planning (dmpc_plan_routes): see below
 //   inbounds       = dmpc_mex('is_inbounds', params, p, pmin, pmax)                    is_inbounds.m
 //   pass           = dmpc_mex('reached_goal', params, p, pf, error_tol)                ReachedGoal.m
 //   tol            = dmpc_mex('max_deviation', params, p, prev_p)                      maxDeviation.m (p, prev_p: 3 x K)
@@ -40,6 +41,11 @@
 // waypoints(:,w,i) -- agent i leaves a waypoint that is not its last when it is closer to it than capture (metres) or has flown towards it for
 // timeout columns (0 = none); n_wp (1 x N_cmd, default W each) counts an agent's waypoints, the last of them is its goal; wp_col (W x N_cmd) holds
 // the 0-based history column on which the agent left each waypoint, -1 where it never did.  A failed agent stops the scene (max_hold = 0).
+// Route planning (dmpc_plan_routes, no reference counterpart): 'plan' finds the waypoints 'route' flies -- po 3 x N, goals 3 x N_cmd, N_cmd <= N: the
+// vehicles behind the commanded ones are the obstacles to go round, obstacles (3 x M) adds further points; cell (metres) is the planning grid's,
+// margin (default 0) widens rmin, W (default 4) is the number of waypoint slots.  waypoints 3 x W x N_cmd and n_wp 1 x N_cmd go into 'route' as they
+// are; plan_status 1 x N_cmd: 0 ok, 1 truncated (more corners than W: the goal took the last slot), 2 no way (the goal alone); hops 1 x N_cmd: cells
+// of the path, -1 for no way.
 // `params` is a struct with the fields of dmpc_params (variant as the DMPC_VAR_* integer).
 // The signature-preserving wrappers (solveSoftDMPCbound.m, ...) in this directory call 'solve_one'
 // and convert status bits into the reference's [] + flag conventions.
@@ -512,6 +518,32 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 1) plhs[1] = pf;
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(cost);
         if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)rounds);
+        return;
+    }
+    if (!std::strcmp(cmd, "plan")) {   // which way round the static vehicles (dmpc_plan_routes): the waypoints 'route' takes
+        need(nrhs >= 5 && nrhs <= 8, "plan: (cmd, params, po, goals, cell[, margin[, W[, obstacles]]])");
+        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3), Nc = (int)(mxGetNumberOfElements(prhs[3]) / 3);
+        need(N >= 1 && Nc >= 1 && Nc <= N && mxGetM(prhs[2]) == 3 && mxGetM(prhs[3]) == 3 && mxGetNumberOfElements(prhs[2]) == (size_t)3 * N &&
+             mxGetNumberOfElements(prhs[3]) == (size_t)3 * Nc, "po must be 3 x N, goals 3 x N_cmd (N_cmd <= N)");
+        const double margin = nrhs > 5 && mxGetNumberOfElements(prhs[5]) > 0 ? mxGetScalar(prhs[5]) : 0.0;
+        const int W = nrhs > 6 && mxGetNumberOfElements(prhs[6]) > 0 ? (int)mxGetScalar(prhs[6]) : 4;
+        const int Mx = nrhs > 7 ? (int)(mxGetNumberOfElements(prhs[7]) / 3) : 0;
+        need(Mx == 0 || (mxGetM(prhs[7]) == 3 && mxGetNumberOfElements(prhs[7]) == (size_t)3 * Mx), "obstacles must be 3 x M");
+        need(W >= 1, "W must be at least 1");
+        const int M = N - Nc + Mx;
+        std::vector<double> obst(mxGetPr(prhs[2]) + (size_t)3 * Nc, mxGetPr(prhs[2]) + (size_t)3 * N);
+        if (Mx) obst.insert(obst.end(), mxGetPr(prhs[7]), mxGetPr(prhs[7]) + (size_t)3 * Mx);
+        std::vector<int32_t> n_wp((size_t)Nc, 0), st((size_t)Nc, 0), hops((size_t)Nc, 0);
+        const mwSize d3[3] = {3, (mwSize)W, (mwSize)Nc};
+        plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        if (dmpc_plan_routes(ctx, 1, Nc, M, W, mxGetPr(prhs[2]), mxGetPr(prhs[3]), M ? obst.data() : nullptr, mxGetScalar(prhs[4]), margin,
+                             mxGetPr(plhs[0]), n_wp.data(), st.data(), hops.data()))
+            mexErrMsgIdAndTxt("dmpc:plan", "%s", dmpc_last_error(ctx));
+        const std::vector<int32_t> *outs[3] = {&n_wp, &st, &hops};
+        for (int o = 0; o < 3 && nlhs > o + 1; ++o) {
+            plhs[o + 1] = mxCreateDoubleMatrix(1, (mwSize)Nc, mxREAL);
+            for (int i = 0; i < Nc; ++i) mxGetPr(plhs[o + 1])[i] = (double)(*outs[o])[(size_t)i];
+        }
         return;
     }
     if (!std::strcmp(cmd, "random_test") || !std::strcmp(cmd, "random_exchange")) {   // randomTest.m / randomExchange.m
