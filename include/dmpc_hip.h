@@ -723,6 +723,49 @@ DMPC_API int dmpc_plan_routes(dmpc_ctx *ctx, int S, int N_cmd, int M, int W, con
 DMPC_API int dmpc_plan_routes_device(dmpc_ctx *ctx, int S, int N_cmd, int M, int W, const double *po_cmd, const double *goals, const double *obst,
                             double cell, double margin, double *waypoints, int32_t *n_wp, int32_t *plan_status, int32_t *hops, void *stream);
 
+/* Re-planned routes (additive, the ABI revision stays 8): dmpc_plan_routes before column 0, dmpc_transition_route from there, and DURING THE FLIGHT
+ * the route of every agent whose remaining legs are no longer clear is planned again, on the device, between two steps.  dmpc_plan_routes plans
+ * once against points that do not move; with scripted vehicles that is a guess, and dmpc_transition_route flies the guess to the end.  No reference
+ * counterpart.  po, path, P, K_T_max, error_tol, max_hold, capture, timeout, pk / vk / ak, K_T_used, scene_status, wp_col, wp_index and the hold
+ * outputs are dmpc_transition_route's; W, cell and margin dmpc_plan_routes'; goals [S][N_cmd][3]; every >= 0 columns (0: never re-planned);
+ * ahead >= 0 columns.  tests/replan.py restates the rule; the device equals it bit for bit:
+ *   obst(k)   the obstacle set on column k.  With a path: the points sample(j, k + a), a = 0 .. ahead, of every scripted vehicle j -- M (ahead + 1)
+ *             points, sample(j, t) = path[s][j][min(t, P - 1)].  Without one: po[s][N_cmd ..], the same on every column.
+ *   blocked(k) dmpc_plan_routes' blocked predicate over obst(k), on the same grid.
+ *   column 0  waypoints, n_wp, plan_status = dmpc_plan_routes(po_cmd, goals, obst(0)); cur = since = 0; the flight is dmpc_transition_route's.
+ *   checked   after the route rule of column k, the waypoint switches of that column included, when every > 0, 0 < k < K_T_max - 1,
+ *             k % every == 0 and the scene is still running behind that rule (it has neither failed nor reached).
+ *   legs      of agent i: between the cells of x_p_i(k) (the fp64 state in every precision mode), wp[i][cur], .., wp[i][n_wp - 1].  A leg a -> b
+ *             is clear when clear(a, b) of the plan rule holds on blocked(k) with free_i = !blocked(k) or the agent's current cell or its goal's
+ *             cell; a leg with a == b when that one cell is free_i.
+ *   re-plan   some leg not clear: the agent's row of waypoints, n_wp and plan_status become the plan rule's output for start x_p_i(k), goal_i and
+ *             blocked(k) (DMPC_PLAN_UNREACHABLE: the goal alone, as it is); cur = 0, since = k, the next step is solved with the new waypoint 0,
+ *             which is first examined on column k + 1; the agent's wp_col row goes back to -1; replan_count[i] += 1, replan_col[i] = k.
+ *             The table is not rewritten.  A held agent counts as solved, as in the route rule.
+ * All floating point ends with the cell of a point and the blocked predicate, so nothing depends on launch geometry, the batch split or the order
+ * in which the device visits agents.  Outputs, each may be NULL: waypoints_out [S][N_cmd][W][3], n_wp_out, plan_status [S][N_cmd]: the plan in
+ * force when the scene ended (wp_col and wp_index refer to it); replan_count [S][N_cmd]; replan_col [S][N_cmd]: the last re-plan's column, -1 if
+ * the agent never was re-planned.  every == 0: every common output is dmpc_plan_routes on obst(0) followed by dmpc_transition_route, byte for
+ * byte.  Commanded agents do not block each other; a re-plan sees `ahead` columns and no further; there is no hysteresis beyond `every`.
+ * Batch split as dmpc_transition_route; a DMPC_DEVICE_ALL context runs the call on its first GPU; there is no RCCL form.  Refused (-1, nothing
+ * launched, a message that starts with the entry's name): what dmpc_plan_routes and dmpc_transition_route refuse of the common arguments,
+ * every < 0, ahead < 0, a NULL goals.
+ * dmpc_replan_routes_device is ONE re-plan step (check, then plan the flagged agents) on device arrays, enqueued on the caller's stream, for
+ * callers that loop over dmpc_step_device_cmd themselves: x_p, goals [S][N_cmd][3]; obst [S][M][3] = obst(k), gathered by the caller; waypoints
+ * [S][N_cmd][W][3], n_wp, cur [S][N_cmd] are read and, for a re-planned agent, rewritten; since, wp_col [S][N_cmd][W], pf [S][N_cmd][3] (the goal the
+ * next step takes), plan_status, replan_count, replan_col may be NULL; scene_done [S] or NULL: scenes with a non-zero word are skipped.  k is
+ * the column written into since and replan_col.  M == 0: nothing is blocked, nothing is launched.  It refuses what dmpc_plan_routes_device
+ * refuses, a NULL waypoints, n_wp or cur, k < 0 and a DMPC_DEVICE_ALL context. */
+DMPC_API int dmpc_transition_replan(dmpc_ctx *ctx, int S, int N, int N_cmd, int W, const double *po, const double *goals, double cell, double margin,
+                           int every, int ahead, double capture, int timeout, const double *path, int P, int K_T_max, double error_tol,
+                           int max_hold, double *pk, double *vk, double *ak, int32_t *K_T_used, int32_t *scene_status, double *waypoints_out,
+                           int32_t *n_wp_out, int32_t *plan_status, int32_t *wp_col, int32_t *wp_index, int32_t *replan_count,
+                           int32_t *replan_col, int32_t *hold_count, int32_t *hold_first, int32_t *agent_status);
+DMPC_API int dmpc_replan_routes_device(dmpc_ctx *ctx, int S, int N_cmd, int M, int W, const double *x_p, const double *goals, const double *obst,
+                              double cell, double margin, int k, double *waypoints, int32_t *n_wp, int32_t *cur, int32_t *since,
+                              int32_t *wp_col, double *pf, int32_t *plan_status, int32_t *replan_count, int32_t *replan_col,
+                              const int32_t *scene_done, void *stream);
+
 /* Standalone forms of the path's small helpers (fused into the step kernels inside the solvers), for callers that
  * invoke them on their own as the reference's scripts do.  Host pointers, synchronous.
  *   dmpc_prop_state   propStatedmpc.m:1-8 (A_initp given): p = A_p a + A_initp [po;vo], v = A_v a + 1 (x) vo  -> pass

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "dmpc_assign_goals", "dmpc_assign_goals_device",
     "dmpc_transition_route",
     "dmpc_plan_routes", "dmpc_plan_routes_device",
+    "dmpc_transition_replan", "dmpc_replan_routes_device",
 ]
 
 
@@ -156,6 +157,11 @@ def load():
     # route planning round static vehicles, ahead of route() (additive, still revision 8)
     L.dmpc_plan_routes.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, dp, C.c_double, C.c_double, dp, ip, ip, ip]
     L.dmpc_plan_routes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp]
+    # re-planned routes: plan_routes, transition_route and re-plans during the flight (additive, still revision 8)
+    L.dmpc_transition_replan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, dp,
+                                         C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, dp, ip, ip, dp, ip, ip, ip, ip, ip, ip, ip, ip, ip]
+    L.dmpc_replan_routes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp,
+                                            vp, vp, vp, vp, vp]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -639,6 +645,56 @@ class Dmpc:
                                            _ip(hops)))
         return dict(waypoints=wp, n_wp=n_wp, plan_status=st, hops=hops)
 
+    def replan(self, po, goals, K_T_max, cell, capture, margin=0.0, W=4, every=5, ahead=0, timeout=0, error_tol=0.01, histories=True, path=None,
+               on_fail="stop", max_hold=14):
+        """dmpc_transition_replan: plan() before column 0, route() from there, and every `every` columns (0: never) the agents whose remaining
+        legs are no longer clear are planned again on the device, from where they are, round the vehicles where they are on that column and on
+        the `ahead` columns behind it.  goals [N_cmd,3] next to an unbatched po, or [S,N_cmd,3]; po with MORE vehicles than goals: static
+        vehicles; path [S,M,P,3]: scripted ones, po then covers the commanded agents.  cell, margin, W: plan()'s; capture, timeout, on_fail,
+        max_hold: route()'s.  Returns what route() returns, and waypoints [S,N_cmd,W,3], n_wp, plan_status [S,N_cmd]: the plan in force when the
+        scene ended (wp_col and wp_index refer to it), replan_count [S,N_cmd], replan_col [S,N_cmd]: the last re-plan's column (-1: none)."""
+        po, goals = _f(po), _f(goals)
+        if on_fail not in ("stop", "hold"):
+            raise DmpcError(f"replan: on_fail is 'stop' or 'hold', not {on_fail!r}")
+        if (po.ndim not in (2, 3) or goals.ndim != po.ndim or po.shape[-1] != 3 or goals.shape[-1] != 3 or goals.shape[:-2] != po.shape[:-2]
+                or goals.shape[-2] < 1):
+            raise DmpcError(f"replan: goals {tuple(goals.shape)} must be [N_cmd,3] next to po [N,3], or [S,N_cmd,3] next to po [S,N,3]: po is {tuple(po.shape)}")
+        S = 1 if po.ndim == 2 else po.shape[0]
+        n_cmd, N, W = goals.shape[-2], po.shape[-2], int(W)
+        lead = goals.shape[:-1]
+        M = P = 0
+        if path is not None:
+            if N != n_cmd:
+                raise DmpcError(f"replan: with path, po {tuple(po.shape)} and goals {tuple(goals.shape)} must cover the same commanded agents")
+            path, M, P = _path(path, lead, "replan")
+        elif n_cmd > N:
+            raise DmpcError(f"replan: goals have {n_cmd} agents, po {N}: the commanded agents are the FIRST N_cmd <= N vehicles")
+        if W < 1:
+            raise DmpcError(f"replan: W must be >= 1, not {W!r}")
+        if not float(capture) > 0.0:
+            raise DmpcError(f"replan: capture must be > 0 (metres), not {capture!r}")
+        if int(timeout) < 0 or int(every) < 0 or int(ahead) < 0:
+            raise DmpcError(f"replan: timeout, every and ahead must be >= 0 (columns), not {timeout!r}, {every!r}, {ahead!r}")
+        hold = on_fail == "hold"
+        nul, inul = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
+        used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+        wp, wp_col = np.zeros(lead + (W, 3)), np.zeros(lead + (W,), dtype=np.int32)
+        n_wp, pst, wp_index, rcnt, rcol = (np.zeros(lead, dtype=np.int32) for _ in range(5))
+        cnt, first, log = np.zeros(lead, dtype=np.int32), np.zeros(lead, dtype=np.int32), np.zeros(lead + (K_T_max,), dtype=np.int32)
+        pk = vk = ak = None
+        if histories:
+            pk, vk, ak = (np.zeros(lead + (K_T_max, 3)) for _ in range(3))
+        self._chk(self._L.dmpc_transition_replan(self._ctx, S, N + M, n_cmd, W, _dp(po), _dp(goals), float(cell), float(margin), int(every), int(ahead),
+                                                 float(capture), int(timeout), _dp(path) if path is not None else nul, P, int(K_T_max), float(error_tol),
+                                                 int(max_hold) if hold else 0, _dp(pk) if histories else nul, _dp(vk) if histories else nul,
+                                                 _dp(ak) if histories else nul, _ip(used), _ip(sst), _dp(wp), _ip(n_wp), _ip(pst), _ip(wp_col), _ip(wp_index),
+                                                 _ip(rcnt), _ip(rcol), _ip(cnt) if hold else inul, _ip(first) if hold else inul, _ip(log) if hold else inul))
+        out = dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, wp_col=wp_col, wp_index=wp_index, waypoints=wp, n_wp=n_wp, plan_status=pst,
+                   replan_count=rcnt, replan_col=rcol)
+        if hold:
+            out.update(hold_count=cnt, hold_first=first, agent_status=log)
+        return out
+
     # ---- multi-GPU (one process per GPU): dmpc_multigpu.hip ----
     @staticmethod
     def comm_unique_id():
@@ -934,6 +990,15 @@ class Dmpc:
         """dmpc_plan_routes_device: po_cmd, goals [S,n_cmd,3], obst [S,M,3] fp64 and the outputs (0: not wanted; all but waypoints int32) on the device"""
         self._chk(self._L.dmpc_plan_routes_device(self._ctx, S, n_cmd, M, W, po_cmd, goals, obst or None, float(cell), float(margin), waypoints or None,
                                                   n_wp or None, plan_status or None, hops or None, stream or None))
+
+    def replan_routes_device(self, S, n_cmd, M, W, x_p, goals, obst, cell, margin, k, waypoints, n_wp, cur, since=0, wp_col=0, pf=0, plan_status=0,
+                             replan_count=0, replan_col=0, scene_done=0, stream=0):
+        """dmpc_replan_routes_device: one re-plan step on column k.  x_p, goals [S,n_cmd,3], obst [S,M,3] fp64; waypoints [S,n_cmd,W,3] fp64, n_wp,
+        cur [S,n_cmd] int32 are read and, for the agents with a leg that is not clear, rewritten; the others (0: not wanted) int32 but pf
+        [S,n_cmd,3] fp64; scene_done [S] int32: scenes to skip.  All on the device."""
+        self._chk(self._L.dmpc_replan_routes_device(self._ctx, S, n_cmd, M, W, x_p, goals, obst or None, float(cell), float(margin), int(k), waypoints, n_wp,
+                                                    cur, since or None, wp_col or None, pf or None, plan_status or None, replan_count or None,
+                                                    replan_col or None, scene_done or None, stream or None))
 
     def profile(self, enable=True):
         self._chk(self._L.dmpc_profile(self._ctx, 1 if enable else 0))

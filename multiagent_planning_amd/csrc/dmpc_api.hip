@@ -153,6 +153,8 @@ struct dmpc_ctx {
     int max_lds_assign = 0;  // dynamic-LDS limit assign_one_kernel was last raised to
     DevBuf plan_io, plan_mask;                                             // dmpc_plan_routes: staged inputs / outputs of the host form; the scenes' blocked bitmasks
     int max_lds_plan = 0;    // dynamic-LDS limit plan_route_kernel was last raised to
+    DevBuf replan_work, replan_obst, replan_goals;                         // re-planning: blocked bitmasks | flagged list | count; the obstacle points of a column; dmpc_transition_replan's goals
+    int max_lds_replan = 0;  // dynamic-LDS limit replan_route_kernel was last raised to
     int pc_fallback_scenes = 0;   // last dmpc_postcheck: scenes of a cell-grid search that were searched again by brute force
     std::vector<dmpc_ctx *> children;   // further contexts (own stream and buffers) for the other parts of a split batch of transitions
     std::vector<int> split_at;          // non-empty: the last dmpc_transition left scenes [split_at[i], split_at[i+1]) in part i (0: here, i > 0: children[i-1])
@@ -783,7 +785,8 @@ static std::vector<int> batch_parts(int S, int want, bool sharded)
     return at;
 }
 
-#include "dmpc_transition.hip"   // the closed loop: the record of a call, transition_one, transition_any, the six entries
+#include "dmpc_plan.hip"     // route planning round static vehicles, before and during a flight: the wavefront planner's kernels, the three entries
+#include "dmpc_transition.hip"   // the closed loop: the record of a call, transition_one, transition_any, the seven entries
 
 #include "dmpc_postcheck_host.hip"   // the post-checks on the host: the record of a call, PcPrep, the three checks, pc_run, the five entries
 
@@ -991,7 +994,6 @@ extern "C" int dmpc_random_sets_device(dmpc_ctx *ctx, int S, int N, const double
 }
 
 #include "dmpc_assign.hip"   // goal assignment: the auction's kernels and the two entries
-#include "dmpc_plan.hip"     // route planning round static vehicles: the wavefront planner's kernels and the two entries
 
 
 // ---------------------------------------------------------------------------------------------

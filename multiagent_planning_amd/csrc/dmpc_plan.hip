@@ -10,6 +10,14 @@
 //   plan_route_kernel   one workgroup per (scene, agent): the distance field as uint16 per cell in LDS (blocked cells are a sentinel in the same
 //                       array), level-synchronous pull sweeps, the descent by one thread into a uint16 path in LDS, the pruning with a lane per
 //                       candidate.  Every loop is bounded by a count known on entry: levels <= cells, descent <= hops, emissions <= min(hops, W).
+// Re-planning during a flight (dmpc_transition_replan, dmpc_replan_routes_device; the rule is pinned in include/dmpc_hip.h, tests/replan.py
+// restates it) adds three kernels, integer arithmetic behind the same cell of a point and the same blocked predicate:
+//   replan_obst_kernel   the obstacle points of column k -- the scripted vehicles' samples k .. k + ahead, or the static vehicles -- gathered from
+//                        the resident paths into the point buffer plan_block_kernel reads
+//   replan_check_kernel  a lane per (scene, agent): the remaining legs walked on the scene's bitmask in global memory; an agent with a leg that is
+//                        not clear is appended to a compacted list (a vector atomicAdd on a device-side count; the list's order is free)
+//   replan_route_kernel  plan_route_kernel's body with the agent taken from that list (a workgroup whose index is not below the count returns at
+//                        once: the host never reads the count) and an output stage that also restarts the agent's route state
 //
 // Included into dmpc_api.hip (single translation unit).
 #include <hip/hip_runtime.h>
@@ -77,17 +85,30 @@ __device__ inline bool los_clear(const unsigned short *field, int ax, int ay, in
     return true;
 }
 
-// grid S * N_cmd, 256 or 1024 threads, 4 * ncells bytes of dynamic LDS (field, path: uint16 [ncells] each)
-__global__ __launch_bounds__(1024) void plan_route_kernel(Grid g, int W, int N_cmd, const double *__restrict__ po, const double *__restrict__ goals,
-                                                          const unsigned long long *__restrict__ mask, int words, double *__restrict__ wp,
-                                                          int32_t *__restrict__ n_wp, int32_t *__restrict__ plan_status, int32_t *__restrict__ hops)
+// The route state a re-plan restarts (replan_route_kernel).  list / count: the agents replan_check_kernel flagged; list null: every agent, the plan
+// before column 0 (replan_count = 0, replan_col = -1).  Everything but cur may be null.
+struct Replan {
+    const int32_t *list = nullptr, *count = nullptr;
+    int k = 0;                                         // the column of the re-plan
+    int32_t *cur = nullptr, *since = nullptr;          // [S][N_cmd]
+    int32_t *wp_col = nullptr;                         // [S][N_cmd][W]
+    double *pf = nullptr;                              // [S][N_cmd][3]: the goal the next step is solved with
+    int32_t *replan_count = nullptr, *replan_col = nullptr;
+};
+
+// one workgroup per (scene, agent) -- RP: per entry of the list --, 256 or 1024 threads, 4 * ncells bytes of dynamic LDS (field, path: uint16 [ncells] each)
+template <bool RP>
+__device__ __forceinline__ void plan_route_body(const Grid &g, int W, int N_cmd, const double *__restrict__ po, const double *__restrict__ goals,
+                                                const unsigned long long *__restrict__ mask, int words, double *__restrict__ wp,
+                                                int32_t *__restrict__ n_wp, int32_t *__restrict__ plan_status, int32_t *__restrict__ hops, const Replan &rp)
 {
     extern __shared__ unsigned short plan_sh[];
     __shared__ int s_flag[3], s_best;
+    if (RP && rp.list && (int)blockIdx.x >= *rp.count) return;   // (the same for every thread of the workgroup, in front of every barrier)
     const int ncells = g.ncells, nx = g.n[0], ny = g.n[1], nz = g.n[2], nxy = nx * ny;
     unsigned short *field = plan_sh, *path = plan_sh + ncells;
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
-    const size_t a = blockIdx.x, s = a / (size_t)N_cmd;
+    const size_t a = RP && rp.list ? (size_t)rp.list[blockIdx.x] : (size_t)blockIdx.x, s = a / (size_t)N_cmd;
     const double gl[3] = {goals[3 * a], goals[3 * a + 1], goals[3 * a + 2]};
     int sc[3], gc[3];
     for (int k = 0; k < 3; ++k) {
@@ -211,6 +232,103 @@ __global__ __launch_bounds__(1024) void plan_route_kernel(Grid g, int W, int N_c
         if (plan_status) plan_status[a] = !reachable ? DMPC_PLAN_UNREACHABLE : (truncated ? DMPC_PLAN_TRUNCATED : DMPC_PLAN_OK);
         if (hops) hops[a] = reachable ? H : -1;
     }
+    if (RP) {
+        // the route starts again: slot 0 -- thread 0 wrote it in every case above -- is the goal of the next step, no waypoint has been left
+        if (tid == 0) {
+            rp.cur[a] = 0;
+            if (rp.since) rp.since[a] = rp.k;
+            if (rp.pf) { rp.pf[3 * a] = out[0]; rp.pf[3 * a + 1] = out[1]; rp.pf[3 * a + 2] = out[2]; }
+            if (rp.replan_count) rp.replan_count[a] = rp.list ? rp.replan_count[a] + 1 : 0;
+            if (rp.replan_col) rp.replan_col[a] = rp.list ? rp.k : -1;
+        }
+        if (rp.wp_col)
+            for (int k = tid; k < W; k += nt) rp.wp_col[a * (size_t)W + k] = -1;
+    }
+}
+
+// grid S * N_cmd
+__global__ __launch_bounds__(1024) void plan_route_kernel(Grid g, int W, int N_cmd, const double *__restrict__ po, const double *__restrict__ goals,
+                                                          const unsigned long long *__restrict__ mask, int words, double *__restrict__ wp,
+                                                          int32_t *__restrict__ n_wp, int32_t *__restrict__ plan_status, int32_t *__restrict__ hops)
+{
+    plan_route_body<false>(g, W, N_cmd, po, goals, mask, words, wp, n_wp, plan_status, hops, Replan{});
+}
+
+// grid S * N_cmd as well (the list has at most that many entries); po: the agents' current states x_p; wp is never null
+__global__ __launch_bounds__(1024) void replan_route_kernel(Grid g, int W, int N_cmd, const double *__restrict__ x_p, const double *__restrict__ goals,
+                                                            const unsigned long long *__restrict__ mask, int words, double *__restrict__ wp,
+                                                            int32_t *__restrict__ n_wp, int32_t *__restrict__ plan_status, Replan rp)
+{
+    plan_route_body<true>(g, W, N_cmd, x_p, goals, mask, words, wp, n_wp, plan_status, nullptr, rp);
+}
+
+// obst [S][A1][M][3], A1 = ahead + 1: with a path [S][M][P][3] the samples min(k + a, P - 1), a = 0 .. ahead, of every vehicle; without one the
+// static vehicles po[s][N_cmd + m] of po [S][N][3] (A1 = 1)
+__global__ __launch_bounds__(256) void replan_obst_kernel(int S, int M, int P, int k, int A1, const double *__restrict__ path, const double *__restrict__ po,
+                                                          int N, int N_cmd, double *__restrict__ obst)
+{
+    const size_t total = (size_t)S * A1 * M * 3;
+    for (size_t t = blockIdx.x * (size_t)256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const int d = (int)(t % 3);
+        const size_t u = t / 3, m = u % (size_t)M, v = u / (size_t)M, a = v % (size_t)A1, s = v / (size_t)A1;
+        if (path) {
+            const long col = (long)k + (long)a;
+            const size_t smp = (size_t)(col < (long)P - 1 ? col : (long)P - 1);
+            obst[t] = path[((s * M + m) * (size_t)P + smp) * 3 + d];
+        } else
+            obst[t] = po[(s * (size_t)N + N_cmd + m) * 3 + d];
+    }
+}
+
+// los_clear on a scene's bitmask, with free_i: the cells f0 and f1 are free whatever the mask says.  A leg inside one cell (L = 0) tests that cell.
+__device__ inline bool los_clear_mask(const unsigned long long *__restrict__ mask, int f0, int f1, int ax, int ay, int az, int bx, int by, int bz,
+                                      int nx, int nxy)
+{
+    const int dx = bx - ax, dy = by - ay, dz = bz - az;
+    const int mx = dx < 0 ? -dx : dx, my = dy < 0 ? -dy : dy, mz = dz < 0 ? -dz : dz;
+    const int L = mx > my ? (mx > mz ? mx : mz) : (my > mz ? my : mz), L2 = 2 * L;
+    int qx = ax, qy = ay, qz = az, rx = L, ry = L, rz = L;
+    for (int j = 0; j <= L2; ++j) {
+        const int q = qx + qy * nx + qz * nxy;
+        if (q != f0 && q != f1 && ((mask[q >> 6] >> (q & 63)) & 1ull)) return false;
+        if (j == L2) break;                            // (the last cell is b: no step behind it)
+        rx += dx; if (rx >= L2) { rx -= L2; ++qx; } else if (rx < 0) { rx += L2; --qx; }
+        ry += dy; if (ry >= L2) { ry -= L2; ++qy; } else if (ry < 0) { ry += L2; --qy; }
+        rz += dz; if (rz >= L2) { rz -= L2; ++qz; } else if (rz < 0) { rz += L2; --qz; }
+    }
+    return true;
+}
+
+// grid ceil(S * N_cmd / 256), 256 threads, a lane per agent: the legs cell(x_p) -> cell(wp[cur]) -> .. -> cell(wp[n_wp - 1]) on the scene's mask;
+// the first leg that is not clear appends the agent to list[atomicAdd(count, 1)].  scene_done (or null): scenes that are over are skipped.
+// count is zero on entry.  At most W legs of 2 L + 1 <= 2 max_a n_a - 1 cells each: bounded by counts known on entry.
+__global__ __launch_bounds__(256) void replan_check_kernel(Grid g, int W, int N_cmd, int total, const double *__restrict__ x_p, const double *__restrict__ goals,
+                                                           const double *__restrict__ wp, const int32_t *__restrict__ n_wp, const int32_t *__restrict__ cur,
+                                                           const unsigned long long *__restrict__ mask, int words, const int32_t *__restrict__ scene_done,
+                                                           int32_t *__restrict__ list, int32_t *count)
+{
+    const int ag = blockIdx.x * 256 + threadIdx.x;
+    if (ag >= total) return;
+    const size_t a = (size_t)ag, s = a / (size_t)N_cmd;
+    if (scene_done && scene_done[s]) return;
+    const int nx = g.n[0], nxy = g.n[0] * g.n[1];
+    int pc[3], gc[3];
+    for (int k = 0; k < 3; ++k) {
+        pc[k] = cell_axis(x_p[3 * a + k], g.pmin[k], g.cell, g.n[k]);
+        gc[k] = cell_axis(goals[3 * a + k], g.pmin[k], g.cell, g.n[k]);
+    }
+    const int f0 = pc[0] + pc[1] * nx + pc[2] * nxy, f1 = gc[0] + gc[1] * nx + gc[2] * nxy;
+    const int n = n_wp[a] < W ? n_wp[a] : W, c0 = cur[a] > 0 ? cur[a] : 0;
+    const unsigned long long *m = mask + s * (size_t)words;
+    bool ok = true;
+    for (int w = c0; w < n && ok; ++w) {
+        const double *p = wp + (a * (size_t)W + w) * 3;
+        int b[3];
+        for (int k = 0; k < 3; ++k) b[k] = cell_axis(p[k], g.pmin[k], g.cell, g.n[k]);
+        ok = los_clear_mask(m, f0, f1, pc[0], pc[1], pc[2], b[0], b[1], b[2], nx, nxy);
+        pc[0] = b[0]; pc[1] = b[1]; pc[2] = b[2];
+    }
+    if (!ok) list[atomicAdd(count, 1)] = ag;
 }
 
 }   // namespace pln
@@ -269,6 +387,81 @@ static int plan_run(dmpc_ctx *ctx, const pln::Grid &g, int S, int N_cmd, int M, 
                        W, N_cmd, po, goals, mask, words, wp, n_wp, plan_status, hops);
     HIPCHK(ctx, hipGetLastError());
     return 0;
+}
+
+// ---- re-planning: one step on device arrays (dmpc_replan_routes_device; dmpc_transition_replan's RouteDev drives the same functions) ----
+// everything a re-plan step reads and writes, on the device
+struct ReplanArgs {
+    pln::Grid g;
+    int S = 0, N_cmd = 0, W = 0, M = 0;                // M: obstacle points per scene
+    double margin = 0.0;
+    const double *x_p = nullptr, *goals = nullptr, *obst = nullptr;   // [S][N_cmd][3] twice, [S][M][3]
+    double *wp = nullptr;                              // [S][N_cmd][W][3]
+    int32_t *n_wp = nullptr, *plan_status = nullptr;
+    const int32_t *scene_done = nullptr;               // [S] or null
+    pln::Replan rp;                                    // (list and count are set by replan_prepare)
+};
+
+// the scratch of a re-plan step in ctx->replan_work -- mask [S][words] | list [S * N_cmd] | count -- and the LDS limit of replan_route_kernel, once
+static int replan_prepare(dmpc_ctx *ctx, ReplanArgs &r)
+{
+    const size_t A = (size_t)r.S * r.N_cmd, words = (size_t)(r.g.ncells + 63) / 64;
+    if (ctx->replan_work.ensure((size_t)r.S * words * 8 + (A + 1) * 4)) FAIL(ctx, "device allocation failed");
+    int32_t *list = (int32_t *)(ctx->replan_work.as<unsigned long long>() + (size_t)r.S * words);
+    r.rp.list = list; r.rp.count = list + A;
+    const int lds = 4 * r.g.ncells;
+    if (lds > ctx->max_lds_replan) {
+        HIPCHK(ctx, hipFuncSetAttribute((const void *)pln::replan_route_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        ctx->max_lds_replan = lds;
+    }
+    return 0;
+}
+// the blocked bitmask of every scene from r.obst
+static void replan_mask(dmpc_ctx *ctx, const ReplanArgs &r, hipStream_t st)
+{
+    const double R = ctx->prm.rmin + r.margin;
+    hipLaunchKernelGGL(pln::plan_block_kernel, dim3((unsigned)((r.g.ncells + 255) / 256), (unsigned)r.S), dim3(256), 0, st, r.g, r.M, r.obst,
+                       1.0 / ctx->prm.c, R * R, ctx->replan_work.as<unsigned long long>(), (r.g.ncells + 63) / 64);
+}
+// the planner for every agent (flagged false: the plan before column 0) or for the agents the check flags on column k, on the current mask
+static int replan_launch(dmpc_ctx *ctx, const ReplanArgs &r, bool flagged, int k, hipStream_t st)
+{
+    const int words = (r.g.ncells + 63) / 64, total = r.S * r.N_cmd;
+    const unsigned long long *mask = r.M > 0 ? ctx->replan_work.as<unsigned long long>() : nullptr;
+    pln::Replan rp = r.rp;
+    rp.k = k;
+    if (flagged) {
+        HIPCHK(ctx, hipMemsetAsync((void *)rp.count, 0, 4, st));
+        hipLaunchKernelGGL(pln::replan_check_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, r.g, r.W, r.N_cmd, total, r.x_p, r.goals,
+                           (const double *)r.wp, (const int32_t *)r.n_wp, (const int32_t *)rp.cur, mask, words, r.scene_done, (int32_t *)rp.list, (int32_t *)rp.count);
+    } else
+        rp.list = rp.count = nullptr;
+    hipLaunchKernelGGL(pln::replan_route_kernel, dim3((unsigned)total), dim3(r.g.ncells <= pln::SMALL_GRID ? 256 : 1024), (size_t)(4 * r.g.ncells), st, r.g,
+                       r.W, r.N_cmd, r.x_p, r.goals, mask, words, r.wp, r.n_wp, r.plan_status, rp);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+extern "C" int dmpc_replan_routes_device(dmpc_ctx *ctx, int S, int N_cmd, int M, int W, const double *x_p, const double *goals, const double *obst,
+                                         double cell, double margin, int k, double *waypoints, int32_t *n_wp, int32_t *cur, int32_t *since,
+                                         int32_t *wp_col, double *pf, int32_t *plan_status, int32_t *replan_count, int32_t *replan_col,
+                                         const int32_t *scene_done, void *stream)
+{
+    const char *who = "dmpc_replan_routes_device";
+    ReplanArgs r;
+    if (plan_check(ctx, who, S, N_cmd, M, W, x_p, goals, obst, cell, margin, r.g)) return -1;
+    if (!waypoints || !n_wp || !cur) FAIL(ctx, std::string(who) + ": waypoints, n_wp and cur must be given");
+    if (k < 0) FAIL(ctx, std::string(who) + ": k must not be negative");
+    if ((size_t)S * (size_t)N_cmd * (size_t)W > (size_t)0x7fffffff) FAIL(ctx, std::string(who) + ": S * N_cmd * W overflows");
+    if (ctx->grp) FAIL(ctx, std::string(who) + ": device pointers belong to ONE GPU; a DMPC_DEVICE_ALL context drives several (use the host-pointer entry points)");
+    if (M == 0) return 0;   // nothing is blocked: every leg is clear
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    r.S = S; r.N_cmd = N_cmd; r.W = W; r.M = M; r.margin = margin;
+    r.x_p = x_p; r.goals = goals; r.obst = obst; r.wp = waypoints; r.n_wp = n_wp; r.plan_status = plan_status; r.scene_done = scene_done;
+    r.rp.cur = cur; r.rp.since = since; r.rp.wp_col = wp_col; r.rp.pf = pf; r.rp.replan_count = replan_count; r.rp.replan_col = replan_col;
+    if (replan_prepare(ctx, r)) return -1;
+    replan_mask(ctx, r, (hipStream_t)stream);
+    return replan_launch(ctx, r, true, k, (hipStream_t)stream);
 }
 
 extern "C" int dmpc_plan_routes_device(dmpc_ctx *ctx, int S, int N_cmd, int M, int W, const double *po_cmd, const double *goals, const double *obst,

@@ -30,6 +30,8 @@ struct Hold {
 // A route (dmpc_transition_route; W = 0: none): pf is ignored, every commanded agent has waypoints of its own, resident for the call; waypoint 0 of
 // every agent goes into ctx->pf, and one launch after the verdict of every column (route_kernel) applies the waypoint rule there, per agent.
 // Route and mission are never both set.
+// A re-planned route (dmpc_transition_replan; goals != null): no waypoints are passed; they are planned on the device before column 0 (dmpc_plan.hip)
+// and, every `every` columns, planned again for the agents whose remaining legs are no longer clear, behind the waypoint rule of that column.
 struct Route {
     int W = 0;
     const double *waypoints = nullptr;   // [S][N_cmd][W][3]
@@ -37,6 +39,10 @@ struct Route {
     double capture = 0.0; int timeout = 0;
     int32_t *wp_col = nullptr;           // [S][N_cmd][W] or null
     int32_t *wp_index = nullptr;         // [S][N_cmd] or null
+    const double *goals = nullptr;       // [S][N_cmd][3]: a re-planned route
+    pln::Grid grid{}; double margin = 0.0; int every = 0, ahead = 0;   // (the grid of `cell` metres, as the entry's check made it)
+    double *waypoints_out = nullptr;     // [S][N_cmd][W][3] or null: the plan in force when the scene ended
+    int32_t *n_wp_out = nullptr, *plan_status = nullptr, *replan_count = nullptr, *replan_col = nullptr;   // [S][N_cmd] or null
     explicit operator bool() const { return W > 0; }
 };
 
@@ -60,7 +66,9 @@ struct TransitionCall {
         c.K_T_used = at(K_T_used, s0); c.scene_status = at(scene_status, s0);
         c.mission.goals = at(mission.goals, q0 * N_cmd * 3); c.mission.deadline = at(mission.deadline, q0); c.mission.stage_col = at(mission.stage_col, q0);
         c.route.waypoints = at(route.waypoints, w0 * 3); c.route.n_wp = at(route.n_wp, a0); c.route.wp_col = at(route.wp_col, w0); c.route.wp_index = at(route.wp_index, a0);
-        c.pf = mission ? c.mission.goals : route ? c.route.waypoints : at(pf, a0 * 3);
+        c.route.goals = at(route.goals, a0 * 3); c.route.waypoints_out = at(route.waypoints_out, w0 * 3); c.route.n_wp_out = at(route.n_wp_out, a0);
+        c.route.plan_status = at(route.plan_status, a0); c.route.replan_count = at(route.replan_count, a0); c.route.replan_col = at(route.replan_col, a0);
+        c.pf = mission ? c.mission.goals : route ? (route.goals ? c.route.goals : c.route.waypoints) : at(pf, a0 * 3);
         c.hold.hold_count = at(hold.hold_count, a0); c.hold.hold_first = at(hold.hold_first, a0); c.hold.agent_status = at(hold.agent_status, h0);
         return c;
     }
@@ -153,9 +161,41 @@ struct RouteDev {
     dmpc_ctx *ctx; const TransitionCall &c; hipStream_t st;
     int *n_wp = nullptr, *cur = nullptr, *since = nullptr, *col = nullptr;   // [S][N_cmd] each, [S][N_cmd][W]
     std::vector<double> first; std::vector<int32_t> count;                    // waypoint 0 of every agent; n_wp where the caller passed none (alive until the call's last synchronisation)
+    ReplanArgs rp;                                                            // a re-planned route: what its launches take (plan_status, replan_count, replan_col [S][N_cmd] behind wp_col)
+    int obst_cols = 0;                                                        // ... and the columns of every path its obstacle set holds (0: static vehicles)
+    void gather_obst(int k) {   // obst(k) of the rule into ctx->replan_obst
+        const int M = c.N - c.N_cmd, A1 = obst_cols ? obst_cols : 1;
+        hipLaunchKernelGGL(pln::replan_obst_kernel, dim3(grid_1d((size_t)c.S * A1 * M * 3, 4096)), dim3(256), 0, st, c.S, M, c.P, k, A1,
+                           (const double *)(obst_cols ? ctx->path.as<double>() : nullptr), (const double *)ctx->po.as<double>(), c.N, c.N_cmd, ctx->replan_obst.as<double>());
+    }
+    // a re-planned route: the goals go up once per call; the plan before column 0 -- from the commanded agents' starts, packed in ctx->xp as
+    // column 0 has them, round obst(0) -- writes the waypoints, n_wp, cur = since = 0, wp_col = -1 and waypoint 0 of every agent into ctx->pf
+    int begin_replan() {
+        const Route &r = c.route;
+        const size_t A = (size_t)c.S * c.N_cmd, AW = A * r.W;
+        const int M = c.N - c.N_cmd;
+        obst_cols = c.path ? r.ahead + 1 : 0;
+        const size_t pts = (size_t)M * (obst_cols ? obst_cols : 1);
+        if (ctx->pf.ensure(A * 24) || ctx->route_wp.ensure(AW * 24) || ctx->route_state.ensure((6 * A + AW) * 4) || ctx->replan_goals.ensure(A * 24) ||
+            ctx->replan_obst.ensure((size_t)c.S * pts * 24))
+            FAIL(ctx, "device allocation failed");
+        n_wp = ctx->route_state.as<int>(); cur = n_wp + A; since = cur + A; col = since + A;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->replan_goals.p, r.goals, A * 24, hipMemcpyHostToDevice, st));
+        double *xp = ctx->xp.as<double>();
+        if (c.N_cmd == c.N || c.path) HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
+        else HIPCHK(ctx, hipMemcpy2DAsync(xp, (size_t)c.N_cmd * 24, ctx->po.p, (size_t)c.N * 24, (size_t)c.N_cmd * 24, (size_t)c.S, hipMemcpyDeviceToDevice, st));
+        rp.g = r.grid; rp.S = c.S; rp.N_cmd = c.N_cmd; rp.W = r.W; rp.M = (int)pts; rp.margin = r.margin;
+        rp.x_p = xp; rp.goals = ctx->replan_goals.as<double>(); rp.obst = ctx->replan_obst.as<double>(); rp.wp = ctx->route_wp.as<double>();
+        rp.n_wp = n_wp; rp.plan_status = col + AW; rp.scene_done = ctx->scene_done.as<int>();
+        rp.rp.cur = cur; rp.rp.since = since; rp.rp.wp_col = col; rp.rp.pf = ctx->pf.as<double>(); rp.rp.replan_count = col + AW + A; rp.rp.replan_col = col + AW + 2 * A;
+        if (replan_prepare(ctx, rp)) return -1;
+        if (pts) { gather_obst(0); replan_mask(ctx, rp, st); }   // (static vehicles: the mask of the whole call)
+        return replan_launch(ctx, rp, false, 0, st);
+    }
     int begin() {   // the waypoints and n_wp go up once per call; waypoint 0 of every agent into ctx->pf; cur = since = 0, wp_col = -1
         const Route &r = c.route;
         if (!r) return 0;
+        if (r.goals) return begin_replan();
         const size_t A = (size_t)c.S * c.N_cmd, AW = A * r.W;
         if (ctx->pf.ensure(A * 24) || ctx->route_wp.ensure(AW * 24) || ctx->route_state.ensure((3 * A + AW) * 4)) FAIL(ctx, "device allocation failed");
         n_wp = ctx->route_state.as<int>(); cur = n_wp + A; since = cur + A; col = since + A;
@@ -169,15 +209,27 @@ struct RouteDev {
         HIPCHK(ctx, hipMemsetAsync(col, 0xff, AW * 4, st));
         return 0;
     }
-    void rule(int k) {   // the waypoint rule on column k, behind its verdict
-        if (!c.route) return;
+    int rule(int k) {   // the waypoint rule on column k, behind its verdict
+        if (!c.route) return 0;
         hipLaunchKernelGGL(route_kernel, dim3((unsigned)c.S), dim3(c.N_cmd * 3 >= 256 ? 256u : 64u), 0, st, c.N_cmd, c.route.W, k,
                            c.route.capture * c.route.capture, c.route.timeout, (const double *)ctx->route_wp.as<double>(), (const int *)n_wp,
                            (const double *)ctx->xp.as<double>(), ctx->flags.as<int>() + (size_t)k * c.S * 2, ctx->scene_done.as<int>(), cur, since, col,
                            ctx->pf.as<double>());
+        const Route &r = c.route;
+        if (!r.goals || r.every < 1 || k < 1 || k >= c.K_T_max - 1 || k % r.every || !rp.M) return 0;
+        // a re-plan column: the agents of running scenes whose remaining legs are not clear on blocked(k) are planned again from where they are
+        if (obst_cols) { gather_obst(k); replan_mask(ctx, rp, st); }
+        return replan_launch(ctx, rp, true, k, st);
     }
     int finish() {
         const size_t A = (size_t)c.S * c.N_cmd;
+        if (const Route &r = c.route; r.goals) {
+            if (r.waypoints_out) HIPCHK(ctx, hipMemcpyAsync(r.waypoints_out, rp.wp, A * r.W * 24, hipMemcpyDeviceToHost, st));
+            if (r.n_wp_out) HIPCHK(ctx, hipMemcpyAsync(r.n_wp_out, n_wp, A * 4, hipMemcpyDeviceToHost, st));
+            if (r.plan_status) HIPCHK(ctx, hipMemcpyAsync(r.plan_status, rp.plan_status, A * 4, hipMemcpyDeviceToHost, st));
+            if (r.replan_count) HIPCHK(ctx, hipMemcpyAsync(r.replan_count, rp.rp.replan_count, A * 4, hipMemcpyDeviceToHost, st));
+            if (r.replan_col) HIPCHK(ctx, hipMemcpyAsync(r.replan_col, rp.rp.replan_col, A * 4, hipMemcpyDeviceToHost, st));
+        }
         if (c.route.wp_col) HIPCHK(ctx, hipMemcpyAsync(c.route.wp_col, col, A * c.route.W * 4, hipMemcpyDeviceToHost, st));
         if (c.route.wp_index) HIPCHK(ctx, hipMemcpyAsync(c.route.wp_index, cur, A * 4, hipMemcpyDeviceToHost, st));
         return 0;
@@ -276,7 +328,8 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
     HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->status.p, DMPC_ST_SOLVED, A, st));
     hipLaunchKernelGGL(scene_reduce_kernel, dim3((unsigned)S), dim3(256), 0, st, N_cmd, c.error_tol, xp, ctx->pf.as<double>(),
                        (const int *)ctx->status.as<int32_t>(), ctx->flags.as<int>(), ctx->scene_done.as<int>());
-    mission.stage(0); route.rule(0);
+    mission.stage(0);
+    if (route.rule(0)) return -1;
     double *cur = ctx->lT.as<double>(), *nxt = ctx->lT2.as<double>();
     if (hold.begin()) return -1;
     hold.apply(0, cur, nxt);
@@ -324,7 +377,8 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
                                (const double *)out[0], (const double *)out[1], (const double *)out[2],
                                (const int *)ctx->status.as<int32_t>(), xp, xv, xa, (const double *)ctx->pf.as<double>(), ctx->hist_p.as<double>(),
                                ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), verdict_k, ctx->scene_done.as<int>(), (const int *)ctx->scene_done.as<int>());
-        mission.stage(k); route.rule(k);
+        mission.stage(k);
+        if (route.rule(k)) return -1;
         HIPCHK(ctx, hipGetLastError());
         std::swap(cur, nxt);   // l = new_l (dmpc_soft_bound.m:146)
         if (VerdictFold::window_ends(k, K_T_max)) {
@@ -523,6 +577,38 @@ extern "C" int dmpc_transition_route(dmpc_ctx *ctx, int S, int N, int N_cmd, int
     if (n_wp)
         for (size_t a = 0; a < (size_t)S * N_cmd; ++a)
             if (n_wp[a] < 1 || n_wp[a] > W) FAIL(ctx, who + ": an n_wp entry is outside 1 .. W");
+    return transition_any(ctx, c);   // (a DMPC_DEVICE_ALL context: its first GPU)
+}
+
+// Re-planned routes: dmpc_plan_routes before column 0, dmpc_transition_route from there, and every `every` columns the agents whose remaining legs are
+// no longer clear planned again on the device, from where they are, round the vehicles where they are (the rule is pinned in include/dmpc_hip.h;
+// the kernels are dmpc_plan.hip's).  No reference counterpart.
+extern "C" int dmpc_transition_replan(dmpc_ctx *ctx, int S, int N, int N_cmd, int W, const double *po, const double *goals, double cell, double margin,
+                                      int every, int ahead, double capture, int timeout, const double *path, int P, int K_T_max, double error_tol,
+                                      int max_hold, double *pk, double *vk, double *ak, int32_t *K_T_used, int32_t *scene_status, double *waypoints_out,
+                                      int32_t *n_wp_out, int32_t *plan_status, int32_t *wp_col, int32_t *wp_index, int32_t *replan_count,
+                                      int32_t *replan_col, int32_t *hold_count, int32_t *hold_first, int32_t *agent_status)
+{
+    const std::string who = "dmpc_transition_replan";
+    if (!ctx) { g_err = who + ": ctx is NULL"; return -1; }
+    TransitionCall c{S, N, N_cmd, po, goals, K_T_max, error_tol, pk, vk, ak, K_T_used, scene_status, path, path ? P : 0, Mission{},
+                     Hold{max_hold, hold_count, hold_first, agent_status}};
+    c.route = Route{W, nullptr, nullptr, capture, timeout, wp_col, wp_index, goals, pln::Grid{}, margin, every, ahead, waypoints_out, n_wp_out, plan_status,
+                    replan_count, replan_col};
+    if (check_cmd(ctx, who.c_str(), S, N, N_cmd)) return -1;
+    if (W < 1) FAIL(ctx, who + ": W must be >= 1 (every agent has at least its goal)");
+    if (!goals) FAIL(ctx, who + ": goals is NULL");
+    if (path && check_scripted(ctx, who.c_str(), S, N_cmd, N - N_cmd, P)) return -1;
+    if ((pk || vk || ak) && !(pk && vk && ak)) FAIL(ctx, who + ": pk, vk, ak must be all given or all NULL");
+    if (check_call(ctx, who, c)) return -1;
+    if ((size_t)S * (size_t)N_cmd * (size_t)W > 0x7fffffffu) FAIL(ctx, who + ": S * N_cmd * W overflows");
+    if (!(capture > 0.0)) FAIL(ctx, who + ": capture must be > 0 (metres)");
+    if (timeout < 0) FAIL(ctx, who + ": timeout is negative (0: none)");
+    if (max_hold < 0) FAIL(ctx, who + ": max_hold must be >= 0 (0: no agent is ever held)");
+    if (every < 0) FAIL(ctx, who + ": every is negative (0: the plan of column 0 is flown to the end)");
+    if (ahead < 0) FAIL(ctx, who + ": ahead is negative (0: the vehicles where they are on the column)");
+    if ((double)(N - N_cmd) * ((double)ahead + 1.0) * (double)S > (double)0x7fffffff / 3) FAIL(ctx, who + ": S * (N - N_cmd) * (ahead + 1) overflows");
+    if (plan_check(ctx, who.c_str(), S, N_cmd, 0, W, po, goals, nullptr, cell, margin, c.route.grid)) return -1;
     return transition_any(ctx, c);   // (a DMPC_DEVICE_ALL context: its first GPU)
 }
 

@@ -26,6 +26,8 @@
 //   [perm,pf,cost,rounds] = dmpc_mex('assign', params, po, goals[, eps[, max_rounds]])  goal assignment (dmpc_assign_goals): po, goals 3 x N; perm 1 x N, 1-based:
 //                                                                                    agent i takes goals(:,perm(i)) = pf(:,i); eps default 1e-4 / N
 //   [waypoints,n_wp,plan_status,hops] = dmpc_mex('plan', params, po, goals, cell[, margin[, W[, obstacles]]])   route planning (dmpc_plan_routes): see below
+//   [pk,vk,ak,K_T_used,scene_status,waypoints,n_wp,replan_count,replan_col,wp_col,plan_status] = dmpc_mex('replan', params, po, goals, K_T_max, error_tol, cell,
+//                    capture[, margin[, W[, every[, ahead[, path[, timeout]]]]]])        re-planned routes (dmpc_transition_replan): see below
 //   inbounds       = dmpc_mex('is_inbounds', params, p, pmin, pmax)                    is_inbounds.m
 //   pass           = dmpc_mex('reached_goal', params, p, pf, error_tol)                ReachedGoal.m
 //   tol            = dmpc_mex('max_deviation', params, p, prev_p)                      maxDeviation.m (p, prev_p: 3 x K)
@@ -46,6 +48,11 @@
 // margin (default 0) widens rmin, W (default 4) is the number of waypoint slots.  waypoints 3 x W x N_cmd and n_wp 1 x N_cmd go into 'route' as they
 // are; plan_status 1 x N_cmd: 0 ok, 1 truncated (more corners than W: the goal took the last slot), 2 no way (the goal alone); hops 1 x N_cmd: cells
 // of the path, -1 for no way.
+// Re-planned routes (dmpc_transition_replan, no reference counterpart): 'replan' is 'plan' before column 0, 'route' from there, and every `every`
+// columns (default 5, 0 = never) the agents whose remaining legs are no longer clear are planned again on the device, round the vehicles where they
+// are on that column and on the `ahead` (default 0) columns behind it.  path (3 x P x M, optional): scripted vehicles, po is then 3 x N_cmd; without
+// it the vehicles of po behind the goals are static obstacles.  waypoints, n_wp, plan_status: the plan in force at the end; replan_count, replan_col
+// (1 x N_cmd): re-plans per agent and the 0-based column of the last one, -1 for none; wp_col refers to the last plan.
 // `params` is a struct with the fields of dmpc_params (variant as the DMPC_VAR_* integer).
 // The signature-preserving wrappers (solveSoftDMPCbound.m, ...) in this directory call 'solve_one'
 // and convert status bits into the reference's [] + flag conventions.
@@ -543,6 +550,53 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         for (int o = 0; o < 3 && nlhs > o + 1; ++o) {
             plhs[o + 1] = mxCreateDoubleMatrix(1, (mwSize)Nc, mxREAL);
             for (int i = 0; i < Nc; ++i) mxGetPr(plhs[o + 1])[i] = (double)(*outs[o])[(size_t)i];
+        }
+        return;
+    }
+    if (!std::strcmp(cmd, "replan")) {   // plan, route and re-plans during the flight (dmpc_transition_replan)
+        need(nrhs >= 8 && nrhs <= 14, "replan: (cmd, params, po, goals, K_T_max, error_tol, cell, capture[, margin[, W[, every[, ahead[, path[, timeout]]]]]])");
+        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3), Nc = (int)(mxGetNumberOfElements(prhs[3]) / 3), KT = (int)mxGetScalar(prhs[4]);
+        need(N >= 1 && Nc >= 1 && Nc <= N && mxGetM(prhs[2]) == 3 && mxGetM(prhs[3]) == 3 && mxGetNumberOfElements(prhs[2]) == (size_t)3 * N &&
+             mxGetNumberOfElements(prhs[3]) == (size_t)3 * Nc && KT >= 2, "po must be 3 x N, goals 3 x N_cmd (N_cmd <= N), K_T_max >= 2");
+        auto opt = [&](int i, double dflt) { return nrhs > i && mxGetNumberOfElements(prhs[i]) > 0 ? mxGetScalar(prhs[i]) : dflt; };
+        const double margin = opt(8, 0.0);
+        const int W = (int)opt(9, 4.0), every = (int)opt(10, 5.0), ahead = (int)opt(11, 0.0), timeout = (int)opt(13, 0.0);
+        need(W >= 1, "W must be at least 1");
+        const bool scripted = nrhs > 12 && mxGetNumberOfElements(prhs[12]) > 0;
+        int M = 0, P = 0;
+        if (scripted) {
+            const mwSize *pd = mxGetDimensions(prhs[12]);
+            P = mxGetNumberOfDimensions(prhs[12]) >= 2 ? (int)pd[1] : 0;
+            M = P >= 1 ? (int)(mxGetNumberOfElements(prhs[12]) / ((size_t)3 * P)) : 0;
+            need(pd[0] == 3 && P >= 1 && M >= 1 && mxGetNumberOfElements(prhs[12]) == (size_t)3 * P * M && N == Nc,
+                 "path must be 3 x P x M, and po then covers the commanded agents (3 x N_cmd)");
+        }
+        const mwSize d3[3] = {3, (mwSize)KT, (mwSize)Nc}, w3[3] = {3, (mwSize)W, (mwSize)Nc};
+        plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        mxArray *v = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), *a = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        mxArray *wp = mxCreateNumericArray(3, w3, mxDOUBLE_CLASS, mxREAL);
+        std::vector<int32_t> n_wp((size_t)Nc, 0), st((size_t)Nc, 0), cnt((size_t)Nc, 0), rcol((size_t)Nc, -1), col((size_t)Nc * W, -1);
+        int32_t used = 0, sst = 0;
+        if (dmpc_transition_replan(ctx, 1, N + M, Nc, W, mxGetPr(prhs[2]), mxGetPr(prhs[3]), mxGetScalar(prhs[6]), margin, every, ahead, mxGetScalar(prhs[7]),
+                                   timeout, scripted ? mxGetPr(prhs[12]) : nullptr, P, KT, mxGetScalar(prhs[5]), 0, mxGetPr(plhs[0]), mxGetPr(v), mxGetPr(a),
+                                   &used, &sst, mxGetPr(wp), n_wp.data(), st.data(), col.data(), nullptr, cnt.data(), rcol.data(), nullptr, nullptr, nullptr))
+            mexErrMsgIdAndTxt("dmpc:replan", "%s", dmpc_last_error(ctx));
+        if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);
+        if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
+        if (nlhs > 5) plhs[5] = wp;
+        const std::vector<int32_t> *rows[3] = {&n_wp, &cnt, &rcol};
+        for (int o = 0; o < 3 && nlhs > o + 6; ++o) {
+            plhs[o + 6] = mxCreateDoubleMatrix(1, (mwSize)Nc, mxREAL);
+            for (int i = 0; i < Nc; ++i) mxGetPr(plhs[o + 6])[i] = (double)(*rows[o])[(size_t)i];
+        }
+        if (nlhs > 9) {
+            plhs[9] = mxCreateDoubleMatrix((mwSize)W, (mwSize)Nc, mxREAL);
+            for (size_t j = 0; j < col.size(); ++j) mxGetPr(plhs[9])[j] = (double)col[j];
+        }
+        if (nlhs > 10) {
+            plhs[10] = mxCreateDoubleMatrix(1, (mwSize)Nc, mxREAL);
+            for (int i = 0; i < Nc; ++i) mxGetPr(plhs[10])[i] = (double)st[(size_t)i];
         }
         return;
     }
