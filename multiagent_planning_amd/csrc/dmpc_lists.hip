@@ -474,6 +474,25 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
             const float reach = infl + __int_as_float(maxhalf[((size_t)scene * NSEG + sg) * 3 + a]);   // a neighbour's centre is at most its half extent from its box
             c_lo[a] = grid_coord(gg, a, lo - reach); c_hi[a] = grid_coord(gg, a, hi + reach);
         }
+        // The candidates: per (y, z) cell row in reach one RUN of entries (the cells of a run along x are contiguous), ~50 entries each at
+        // N = 10^4; the bounds of up to 64 runs are fetched at once (lanes = runs).  The first batch's bounds are requested HERE, as soon as the
+        // cell range exists: the own chord's deviation below needs LDS alone and runs under the trip instead of in front of it.
+        const size_t ss = (size_t)scene * NSEG + sg;
+        const int *st = start + ss * (ncell + 1);
+        const int ny = c_hi[1] - c_lo[1] + 1, nruns_all = ny * (c_hi[2] - c_lo[2] + 1);
+        const UDiv div_ny((unsigned)ny);
+        auto run_bounds = [&](int run0, int &rb, int &re) {
+            const int nruns = nruns_all - run0 < 64 ? nruns_all - run0 : 64;
+            rb = 0; re = 0;
+            if (lane < nruns) {
+                int qz, qy;
+                div_ny.divmod((unsigned)(run0 + lane), qz, qy);
+                const int row0 = ((c_lo[2] + qz) * gg.n[1] + c_lo[1] + qy) * gg.n[0];
+                rb = st[row0 + c_lo[0]]; re = st[row0 + c_hi[0] + 1];
+            }
+        };
+        int rb_first, re_first;
+        run_bounds(0, rb_first, re_first);
         // the own chord of this segment (z in the metric's scale) and the steps' largest distance from it, as grid_fill computes them
         f4_t oa0 = ownrow[SEG_STEPS * sg], oa1 = ownrow[SEG_STEPS * sg + SEG_STEPS - 1];
         oa0.z *= e1z; oa1.z *= e1z;
@@ -487,8 +506,6 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
             odev2 = fmaxf(odev2, dx * dx + dy * dy + dz * dz);
         }
         const float lim0 = sqrtf(thr2) + sqrtf(odev2) * 1.0001f + 2e-4f;   // selection radius + own deviation (+ slack for the fp32 arithmetic of the test)
-        const size_t ss = (size_t)scene * NSEG + sg;
-        const int *st = start + ss * (ncell + 1);
         const f4_t *en = ent + ss * nag, *en2 = ent + (size_t)S * NSEG * nag + ss * nag;
         int nst = 0;
         // the distance test over this segment's horizon steps on a full wave (or the rest) of staged survivors
@@ -499,17 +516,31 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
             const f4_t *row = (const f4_t *)lrow + ((size_t)(r * S + scene) * C + jc) * 16 + SEG_STEPS * sg;
             bool pass = false;
             int cmask = 0;   // steps of the segment closer than thr_close (close pairs; thr_close < thr2: a subset of the passes; never with close_cap = 0, thr_close < 0)
-            // (one step at a time, not unrolled: with one test per step the compiler made this a chain of early exits, a row quarter loaded per
-            // step, 56 registers; a second test per step on the unrolled form keeps all five quarters in registers -- 85, five waves per SIMD
-            // instead of eight.  This form is the same chain of five loads at 60 registers.)
-#pragma unroll 1
-            for (int u = 0; u < SEG_STEPS; ++u) {
-                const f4_t o = ownrow[SEG_STEPS * sg + u], w = row[u];
+            // (A loop that is NOT unrolled: with one test per step the compiler made the unrolled form a chain of early exits, a row quarter loaded
+            // per step, 56 registers; a second test per step on the unrolled form keeps all five quarters in registers -- 85, five waves per SIMD
+            // instead of eight; unrolled with three-component loads 80, and 78 with the loads held two ahead by scheduling barriers.  One step
+            // per pass of the loop was a chain of five round trips at 60 registers.  This form takes two steps per pass from two register sets
+            // of three floats in turn -- the next step's load goes out before the current step is waited for (s_waitcnt vmcnt(1)), and a set is
+            // loaded again where it was last used: no copy at the loop's end.  Three trips' worth instead of five, 61 registers, eight waves.
+            // Same loads, same comparisons in the same order over u.)
+            typedef float f3_t __attribute__((ext_vector_type(3)));
+            auto step = [&](int u, const f3_t w) {
+                const f4_t o = ownrow[SEG_STEPS * sg + u];
                 const float dx = o.x - w.x, dy = o.y - w.y, dz = (o.z - w.z) * e1z;
                 const float d2 = dx * dx + dy * dy + dz * dz;
                 pass = pass || (d2 < thr2);
                 cmask |= (d2 < thr_close) ? (1 << u) : 0;
+            };
+            static_assert(SEG_STEPS % 2 == 1, "two steps per pass of the loop, the last one behind it");
+            f3_t wa = *(const f3_t *)(row + 0);
+#pragma unroll 1
+            for (int u = 0; u < SEG_STEPS - 1; u += 2) {
+                const f3_t wb = *(const f3_t *)(row + u + 1);
+                step(u, wa);
+                wa = *(const f3_t *)(row + u + 2);
+                step(u + 1, wb);
             }
+            step(SEG_STEPS - 1, wa);
             if (have && pass) {
                 const int idx = r * C + jc;
                 atomicOr(bits + (idx >> 5), 1u << (idx & 31));
@@ -524,19 +555,10 @@ __global__ __launch_bounds__(64 * GQ_WAVES) void grid_query_kernel(int S, int G,
                 }
             }
         };
-        // The candidates: per (y, z) cell row one RUN of entries (the cells of a run along x are contiguous), ~50 entries each at N = 10^4.
-        // The bounds of up to 64 runs are fetched at once (lanes = runs); the records of the next round are in flight during a round's test.
-        const int ny = c_hi[1] - c_lo[1] + 1, nruns_all = ny * (c_hi[2] - c_lo[2] + 1);
-        const UDiv div_ny((unsigned)ny);
+        // (the runs' bounds: above; the records of the next round are in flight during a round's test)
         for (int run0 = 0; run0 < nruns_all; run0 += 64) {
-            const int nruns = nruns_all - run0 < 64 ? nruns_all - run0 : 64;
-            int rb = 0, re = 0;
-            if (lane < nruns) {
-                int qz, qy;
-                div_ny.divmod((unsigned)(run0 + lane), qz, qy);
-                const int row0 = ((c_lo[2] + qz) * gg.n[1] + c_lo[1] + qy) * gg.n[0];
-                rb = st[row0 + c_lo[0]]; re = st[row0 + c_hi[0] + 1];
-            }
+            int rb = rb_first, re = re_first;
+            if (run0 > 0) run_bounds(run0, rb, re);
             // The runs of this batch as ONE sequence of entries (a run holds ~50 entries at N = 10^4: a round of 64 lanes per run left a third of
             // the lanes idle and, worse, made every run a memory round trip of its own): lanes = the next 64 entries of the concatenation.
             // Lane -> run without a search (it was a binary search over the prefix sums, six dependent ds_bpermute round trips per round and
