@@ -688,6 +688,48 @@ DMPC_API int dmpc_assign_goals(dmpc_ctx *ctx, int S, int N, const double *po, co
 DMPC_API int dmpc_assign_goals_device(dmpc_ctx *ctx, int S, int N, const double *po, const double *goals, double eps, int max_rounds,
                              int32_t *perm, double *pf_assigned, double *price, double *cost, int32_t *rounds, void *stream);
 
+/* Rectangular goal assignment (additive, the ABI revision stays 8): S scenes of N agents at po [S][N][3] and M goals [S][M][3], N, M >= 1.
+ * More goals than agents (a formation with spare slots, a field of landing pads): the library chooses the cheapest N of the M points and says
+ * which stay empty.  Fewer goals than agents (the next figure needs 80 of the 100 drones): it chooses which M fly; the others are sent nowhere
+ * (pf_assigned = po) and stay commanded agents, so they still dodge.  The total sum of c(i, perm[i]) over the n = min(N, M) matched pairs
+ * is minimised over all ways to match n pairs; c as dmpc_assign_goals.  No reference counterpart.  dmpc_assign_goals itself is unchanged.
+ * The rule -- a forward/reverse auction with eps-scaling in synchronous (Jacobi) rounds -- is pinned so that the result depends on nothing but
+ * the inputs (tests/assign_rect.py restates it; the device equals it bit for bit).  m = max(N, M).
+ *   persons   the smaller side are the persons, the larger side the objects: agents are persons when N <= M, goals are persons when N > M;
+ *             p and o are agent or goal indices.
+ *   cost      c(p,o) is always computed from the agent-goal pair: cinv = 1.0 / c; dx, dy = po_i - g_j; dz = (po_i - g_j)_z * cinv;
+ *             (dx*dx + dy*dy) + dz*dz, each operation rounded on its own; no fused multiply-add anywhere in the rule.
+ *   schedule  cmax = max c over all N M pairs; price[o] = 0 for every object;
+ *             e = cmax / 4; while (e > eps) { forward(e); reverse(e); e = e / 4; } forward(eps); reverse(eps).
+ *   forward   dmpc_assign_goals' phase with objects in the place of goals: every person unassigned and every object unowned, prices kept; rounds
+ *             until no person is unassigned.  In a round every person p unassigned at its start takes v_o = c(p,o) + price[o] over all objects;
+ *             o1 = the smallest v (ties: the smallest o), v2 = the smallest over o != o1; it bids (price[o1] + (v2 - v1)) + e (m == 1:
+ *             price[0] + e).  Every object with bids goes to its highest bidder (ties: the smallest p), its price becomes that bid, its previous
+ *             owner is unassigned.
+ *   reverse   nothing when n == m.  Setup: u[p] = c(p, o_p) + price[o_p] for every person and its object o_p; lambda = the smallest price over
+ *             the owned objects, fixed for this call.  Rounds until no object is unowned with price > lambda.  In a round every such object o,
+ *             from the state at the round's start, takes g_p = u[p] - c(p,o) over all persons; p1 = the largest g (ties: the smallest p),
+ *             beta = g_p1, omega = the largest over p != p1 (n == 1: -inf).  lambda >= beta - e: price[o] = lambda and the object is done.
+ *             Otherwise it offers delta = min(beta - lambda, (beta - omega) + e) > 0 to p1.  Then every person with offers takes the largest
+ *             delta (ties: the smallest o): price[o] = beta_o - delta, u[p] = u[p] - delta, the person's previous object becomes unowned with
+ *             its price as it is, the person owns o.  An object whose offer was not taken changes nothing and offers again next round.
+ *   cap       rounds counts forward and reverse rounds alike; a scene that would need more than max_rounds (<= 0: 1 << 20) reports
+ *             rounds = -1, perm = -1, owner = -1, cost = NaN, pf_assigned zero and price as the rounds left it; the other scenes are unaffected.
+ * On return every person's object is within eps of its best in c + price, up to rounding, and no unowned object is priced above an owned one,
+ * up to rounding: hence a total within n eps of the optimum over all ways to match n pairs.  With N == M every output equals dmpc_assign_goals'
+ * on the same inputs bit for bit (no reverse round runs) and owner is the inverse of perm.
+ * perm [S][N] (the goal of agent i, or -1), owner [S][M] (the agent of goal j, or -1), pf_assigned [S][N][3] = goals[perm[i]], or po_i bit for
+ * bit where perm[i] = -1, price [S][max(N, M)] per object (per goal when N <= M, per agent otherwise), cost [S] = the sum of c(i, perm[i])
+ * over the assigned agents in increasing i, rounds [S]; any output may be NULL.  fp64 whatever the context's precision; a DMPC_DEVICE_ALL
+ * context runs the call on its first GPU.  Refused (-1, nothing launched, a message that starts with the entry's name): S, N or M < 1; po or
+ * goals NULL; eps not a finite positive number; max(N, M) > DMPC_ASSIGN_ONE_LAUNCH_MAX (1024; the message has both counts).  The whole auction
+ * of a scene runs in one workgroup's LDS; a round-launch path for larger rectangular scenes does not exist (larger SQUARE scenes go through
+ * dmpc_assign_goals).  The _device form takes device pointers and enqueues one launch on the caller's stream. */
+DMPC_API int dmpc_assign_rect(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int max_rounds,
+                     int32_t *perm, int32_t *owner, double *pf_assigned, double *price, double *cost, int32_t *rounds);
+DMPC_API int dmpc_assign_rect_device(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int max_rounds,
+                            int32_t *perm, int32_t *owner, double *pf_assigned, double *price, double *cost, int32_t *rounds, void *stream);
+
 /* Route planning ahead of a transition (additive, the ABI revision stays 8): which way round the static vehicles every commanded agent goes.
  * DMPC has no global planner -- an agent whose straight line is blocked by a wall of uncommanded vehicles parks in front of it -- and
  * dmpc_transition_route flies waypoints somebody has to supply; this entry supplies them.  No reference counterpart.

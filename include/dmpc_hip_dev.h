@@ -6,7 +6,8 @@
 #define DMPC_HIP_DEV_H
 #include "dmpc_hip.h"
 /* dmpc_assign_goals: scenes of up to this many agents run their whole auction in one launch, one workgroup per scene with prices and
- * ownership in LDS; larger scenes take two launches per round.  The result is the same bits on either side (tests/test_gpu_assign.py runs both). */
+ * ownership in LDS; larger scenes take two launches per round.  The result is the same bits on either side (tests/test_gpu_assign.py runs both).
+ * dmpc_assign_rect: the largest max(N, M) it accepts (it has the one-launch path only). */
 #define DMPC_ASSIGN_ONE_LAUNCH_MAX 1024
 #ifdef __cplusplus
 extern "C" {

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "dmpc_postcheck_setpoints",
     "dmpc_transition_hold",
     "dmpc_assign_goals", "dmpc_assign_goals_device",
+    "dmpc_assign_rect", "dmpc_assign_rect_device",
     "dmpc_transition_route",
     "dmpc_plan_routes", "dmpc_plan_routes_device",
     "dmpc_transition_replan", "dmpc_replan_routes_device",
@@ -151,6 +152,9 @@ def load():
     # goal assignment ahead of a transition (additive, still revision 8)
     L.dmpc_assign_goals.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int, ip, dp, dp, dp, ip]
     L.dmpc_assign_goals_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp]
+    # rectangular goal assignment: N agents, M goals (additive, still revision 8)
+    L.dmpc_assign_rect.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_int, ip, ip, dp, dp, dp, ip]
+    L.dmpc_assign_rect_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     # routes: every agent through waypoints of its own (additive, still revision 8)
     L.dmpc_transition_route.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, ip, C.c_double, C.c_int, dp, C.c_int, C.c_int, C.c_double, C.c_int,
                                         dp, dp, dp, ip, ip, ip, ip, ip, ip, ip]
@@ -442,9 +446,29 @@ class Dmpc:
                                             _dp(cost), _ip(rounds)))
         return dict(perm=perm, pf=pf, price=price, cost=cost, rounds=rounds)
 
-    def _assigned(self, what, start, goals):
-        """assign() for transition() / mission(): a scene that met the round cap has no labelling to fly"""
-        a = self.assign(start, goals)
+    def assign_rect(self, po, goals, eps=None, max_rounds=0):
+        """dmpc_assign_rect: which agent takes which goal when the counts differ.  po [S,N,3] (or [N,3]), goals [S,M,3] (or [M,3]); of all ways
+        to match min(N, M) agent-goal pairs the one that minimises the sum of |E1 (po_i - goals_perm[i])|^2 over the pairs, by the forward/reverse
+        auction include/dmpc_hip.h pins, to within min(N, M) eps of the optimum.  eps=None means 1e-4 / max(N, M): an interface choice, as
+        assign()'s.  max_rounds <= 0: 1 << 20.  max(N, M) <= 1024.  Returns dict(perm [S,N] int32 (the goal of agent i or -1), owner [S,M] int32
+        (the agent of goal j or -1), pf [S,N,3] = goals[perm], or po where perm = -1, price [S,max(N,M)] (per goal when N <= M, per agent
+        otherwise), cost [S], rounds [S]); a scene that met the round cap has rounds = -1, perm = -1, owner = -1, cost = NaN and pf zero."""
+        po, goals = _f(po), _f(goals)
+        if po.ndim not in (2, 3) or goals.ndim != po.ndim or po.shape[-1] != 3 or goals.shape[-1] != 3 or po.shape[:-2] != goals.shape[:-2]:
+            raise DmpcError(f"assign_rect: po {tuple(po.shape)} must be [S,N,3] and goals {tuple(goals.shape)} [S,M,3] (or [N,3] and [M,3])")
+        lead = po.shape[:-2]
+        S, N, M = (lead[0] if lead else 1), po.shape[-2], goals.shape[-2]
+        eps = 1e-4 / max(N, M, 1) if eps is None else float(eps)
+        perm, owner = np.zeros(lead + (N,), dtype=np.int32), np.zeros(lead + (M,), dtype=np.int32)
+        pf, price = np.zeros(lead + (N, 3)), np.zeros(lead + (max(N, M),))
+        cost, rounds = np.zeros(lead), np.zeros(lead, dtype=np.int32)
+        self._chk(self._L.dmpc_assign_rect(self._ctx, int(S), int(N), int(M), _dp(po), _dp(goals), eps, int(max_rounds), _ip(perm), _ip(owner),
+                                           _dp(pf), _dp(price), _dp(cost), _ip(rounds)))
+        return dict(perm=perm, owner=owner, pf=pf, price=price, cost=cost, rounds=rounds)
+
+    def _assigned(self, what, start, goals, rect=False):
+        """assign() -- rect: assign_rect() -- for transition() / mission(): a scene that met the round cap has no labelling to fly"""
+        a = self.assign_rect(start, goals) if rect else self.assign(start, goals)
         if (np.asarray(a["rounds"]) < 0).any():
             raise DmpcError(f"{what}: the goal assignment met its round cap")
         return a
@@ -453,6 +477,8 @@ class Dmpc:
         """histories=False: pk/vk/ak are not downloaded (they stay on the device for postcheck()).
         assign=True: the goals are a formation, not a labelling: the commanded agents are assigned to them first (assign(), default eps), agent i
         flies to pf[perm[i]], and the dict also has perm.
+        assign="rect": ALL N agents of po are commanded and pf holds any M >= 1 points [S,M,3]: assign_rect() (default eps) chooses who flies
+        where, an agent without a goal gets pf = po (it stays, and still dodges); the result is transition(po, pf_assigned, ...) plus perm and owner.
         on_fail="hold" (dmpc_transition_hold; "stop": the entries below, unchanged): an agent whose solve failed flies its previous plan, shifted
         by one entry and with a braking tail, for up to max_hold consecutive columns while the scene goes on; the dict then also has hold_count,
         hold_first (per agent) and agent_status (per agent and column: the raw status, ST_HELD where held), and scene_status carries ST_HELD.
@@ -461,6 +487,15 @@ class Dmpc:
         path [S,M,P,3] (or [M,P,3]; dmpc_transition_scripted): M scripted vehicles behind the commanded agents of po / pf (same agent count in
         both), sample t of a path = the vehicle's position at history column t, held at its last sample once the path has ended."""
         po, pf = _f(po), _f(pf)
+        if isinstance(assign, str) or assign not in (True, False):
+            if assign != "rect":
+                raise DmpcError(f"transition: assign is False, True or 'rect', not {assign!r}")
+            if pf.ndim != po.ndim or pf.ndim not in (2, 3) or pf.shape[-1] != 3 or po.shape[-1] != 3 or pf.shape[:-2] != po.shape[:-2]:
+                raise DmpcError(f"transition: with assign='rect', po {tuple(po.shape)} must be [S,N,3] and the goals {tuple(pf.shape)} [S,M,3]")
+            a = self._assigned("transition", po, pf, rect=True)
+            out = self.transition(po, a["pf"], K_T_max, error_tol, histories, path, on_fail, max_hold)
+            out["perm"], out["owner"] = a["perm"], a["owner"]
+            return out
         if assign:
             if pf.size == po.size:
                 pf = pf.reshape(po.shape)
@@ -520,12 +555,28 @@ class Dmpc:
         transition(); path [S,M,P,3]: scripted vehicles, po then covers the commanded agents.  Returns what transition() returns, and stage_col
         [S,Q]: the column each stage ended on (-1: it never did).  on_fail, max_hold: as transition() (a held plan counts as a solved one in the
         stage rule).  assign=True: every goal set is a formation: the commanded agents are assigned to goals[0] from po, then stage by stage -- the
-        assigned goals of stage q are the starts of stage q+1 -- and the dict also has perm [S,Q,N_cmd]."""
+        assigned goals of stage q are the starts of stage q+1 -- and the dict also has perm [S,Q,N_cmd].  assign="rect": goals [S,Q,M,3] with any
+        M >= 1, all N agents of po commanded; assign_rect() stage by stage from the previous stage's assigned targets (po for stage 0), an agent
+        without a goal in a stage keeps its previous target; the dict also has perm [S,Q,N] and owner [S,Q,M]."""
         po, goals = _f(po), _f(goals)
         if on_fail not in ("stop", "hold"):
             raise DmpcError(f"mission: on_fail is 'stop' or 'hold', not {on_fail!r}")
         if po.ndim not in (2, 3) or goals.ndim != po.ndim + 1 or po.shape[-1] != 3 or goals.shape[-1] != 3 or goals.shape[:-3] != po.shape[:-2]:
             raise DmpcError(f"mission: goals {tuple(goals.shape)} must be [Q,N_cmd,3] next to po [N,3], or [S,Q,N_cmd,3] next to po [S,N,3]: po is {tuple(po.shape)}")
+        if isinstance(assign, str) or assign not in (True, False):
+            if assign != "rect":
+                raise DmpcError(f"mission: assign is False, True or 'rect', not {assign!r}")
+            if goals.shape[-2] < 1:
+                raise DmpcError(f"mission: with assign='rect', goals {tuple(goals.shape)} must hold at least one point per stage")
+            start, flown, perms, owners = po, np.empty(po.shape[:-2] + (goals.shape[-3],) + po.shape[-2:]), [], []
+            for q in range(goals.shape[-3]):
+                a = self._assigned("mission", start, goals[..., q, :, :], rect=True)
+                start = flown[..., q, :, :] = a["pf"]
+                perms.append(a["perm"])
+                owners.append(a["owner"])
+            out = self.mission(po, flown, K_T_max, error_tol, histories, deadline, path, on_fail, max_hold)
+            out["perm"], out["owner"] = np.stack(perms, axis=-2), np.stack(owners, axis=-2)
+            return out
         if assign:
             if not 1 <= goals.shape[-2] <= po.shape[-2]:
                 raise DmpcError(f"mission: goals have {goals.shape[-2]} agents, po {po.shape[-2]}: the commanded agents are the FIRST N_cmd <= N vehicles")
@@ -985,6 +1036,11 @@ class Dmpc:
         """dmpc_assign_goals_device: po, goals [S,N,3] fp64 and the outputs (0: not wanted; perm, rounds int32) on the device"""
         self._chk(self._L.dmpc_assign_goals_device(self._ctx, S, N, po, goals, float(eps), int(max_rounds), perm or None, pf or None, price or None,
                                                    cost or None, rounds or None, stream or None))
+
+    def assign_rect_device(self, S, N, M, po, goals, eps, max_rounds=0, perm=0, owner=0, pf=0, price=0, cost=0, rounds=0, stream=0):
+        """dmpc_assign_rect_device: po [S,N,3], goals [S,M,3] fp64 and the outputs (0: not wanted; perm, owner, rounds int32) on the device"""
+        self._chk(self._L.dmpc_assign_rect_device(self._ctx, S, N, M, po, goals, float(eps), int(max_rounds), perm or None, owner or None, pf or None,
+                                                  price or None, cost or None, rounds or None, stream or None))
 
     def plan_routes_device(self, S, n_cmd, M, W, po_cmd, goals, obst, cell, margin, waypoints=0, n_wp=0, plan_status=0, hops=0, stream=0):
         """dmpc_plan_routes_device: po_cmd, goals [S,n_cmd,3], obst [S,M,3] fp64 and the outputs (0: not wanted; all but waypoints int32) on the device"""

@@ -151,6 +151,7 @@ struct dmpc_ctx {
     int32_t *asg_host = nullptr; size_t asg_host_cap = 0;                  // pinned: the scenes' done flags of two windows of rounds
     hipEvent_t asg_ev[2] = {nullptr, nullptr};
     int max_lds_assign = 0;  // dynamic-LDS limit assign_one_kernel was last raised to
+    int max_lds_assign_rect[2] = {0, 0};   // ... and assign_rect_one_kernel<SWAP> (dmpc_assign_rect)
     DevBuf plan_io, plan_mask;                                             // dmpc_plan_routes: staged inputs / outputs of the host form; the scenes' blocked bitmasks
     int max_lds_plan = 0;    // dynamic-LDS limit plan_route_kernel was last raised to
     DevBuf replan_work, replan_obst, replan_goals;                         // re-planning: blocked bitmasks | flagged list | count; the obstacle points of a column; dmpc_transition_replan's goals

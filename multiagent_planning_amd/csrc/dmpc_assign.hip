@@ -13,6 +13,8 @@
 // workgroup barriers between the stages of a round).  Larger scenes take two launches per round (assign_bid_kernel streams the goals through
 // LDS tile by tile, 16 bidders share a tile; assign_settle_kernel, one workgroup per scene, resolves, applies and keeps the phase state) and
 // the host reads the scenes' done flags one window of rounds behind, as dmpc_transition reads its verdicts.
+// dmpc_assign_rect (N agents, M goals; tests/assign_rect.py restates it) adds reverse rounds -- unowned objects offer themselves down to the
+// smallest owned price -- to the same forward rounds: assign_rect_one_kernel, one launch, max(N, M) <= DMPC_ASSIGN_ONE_LAUNCH_MAX only.
 //
 // Included into dmpc_api.hip (single translation unit).  Every kernel rounds each operation on its own (fp contraction off).
 #include <hip/hip_runtime.h>
@@ -52,12 +54,14 @@ __device__ inline double pair_cost(double px, double py, double pz, double gx, d
 }
 
 // lanes stride over goals jbase .. jbase + n - 1 (ascending per lane: a strict < keeps the smallest j of equal values)
+// (SWAP, dmpc_assign_rect with more agents than goals: the scanned arrays hold agents and (px, py, pz) is a goal; pair_cost still gets the agent first)
+template <bool SWAP = false>
 __device__ inline void scan_goals(Best &b, int lane, int n, int jbase, const double *gx, const double *gy, const double *gz, const double *pr,
                                   double px, double py, double pz, double cinv)
 {
 #pragma clang fp contract(off)
     for (int j = lane; j < n; j += 64) {
-        const double m = pair_cost(px, py, pz, gx[j], gy[j], gz[j], cinv) + pr[j];
+        const double m = (SWAP ? pair_cost(gx[j], gy[j], gz[j], px, py, pz, cinv) : pair_cost(px, py, pz, gx[j], gy[j], gz[j], cinv)) + pr[j];
         if (m < b.m1) { b.m2 = b.m1; b.m1 = m; b.j1 = jbase + j; }
         else if (m < b.m2) b.m2 = m;
     }
@@ -222,6 +226,235 @@ __global__ __launch_bounds__(1024) void assign_one_kernel(int N, const double *_
     if (tid == 0) {
         double sum = 0.0;
         for (int i = 0; i < N; ++i) sum = sum + bidv[i];   // in increasing i, one addition at a time
+        if (cost) cost[s] = sum;
+        if (rounds_out) rounds_out[s] = rounds;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// dmpc_assign_rect, N agents and M goals with max(N, M) <= ONE_MAX: the forward/reverse auction of a scene in one workgroup
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// The smaller side are the n persons, the larger side the m objects (SWAP: more agents than goals, the goals are the persons).  Forward rounds
+// are assign_one_kernel's on person and object arrays.  Reverse rounds are their mirror image: one wave per offering object (a compacted list),
+// lanes stride over the persons with a per-lane top-2 of g = u - c, a butterfly that merges by the total order (g descending, p ascending);
+// offers are positive doubles, so atomicMax on their bit patterns per person finds the winning offer and atomicMin over the objects that
+// made it the smallest object.  LDS: 76 B per object, 60 B per person.
+constexpr size_t RECT_LDS_PER_OBJECT = 7 * 8 + 5 * 4;   // ox oy oz pr offd offb bidval | owner bidwin offp list[2]
+constexpr size_t RECT_LDS_PER_PERSON = 6 * 8 + 3 * 4;   // px py pz bidv u offval | assigned bidj offwin
+
+struct Top { double g1, g2; int p1; };    // largest g, largest g over p != p1, the person of g1
+
+template <bool SWAP>
+__device__ inline double rect_cost(double px, double py, double pz, double ox, double oy, double oz, double cinv)
+{
+    return SWAP ? pair_cost(ox, oy, oz, px, py, pz, cinv) : pair_cost(px, py, pz, ox, oy, oz, cinv);   // (agent, goal)
+}
+
+// the merge is defined by the order (g descending, p ascending), so every lane ends with the same bits whatever the tree
+__device__ inline Top wave_top(Top b)
+{
+    for (int off = 1; off < 64; off <<= 1) {
+        const double o1 = __shfl_xor(b.g1, off), o2 = __shfl_xor(b.g2, off);
+        const int op = __shfl_xor(b.p1, off);
+        if (o1 > b.g1 || (o1 == b.g1 && op < b.p1)) {
+            b.g2 = o2 > b.g1 ? o2 : b.g1;
+            b.g1 = o1; b.p1 = op;
+        } else {
+            b.g2 = b.g2 > o1 ? b.g2 : o1;
+        }
+    }
+    return b;
+}
+
+__device__ inline double wave_min(double v)
+{
+    for (int off = 1; off < 64; off <<= 1) { const double o = __shfl_xor(v, off); v = o < v ? o : v; }
+    return v;
+}
+
+template <bool SWAP>
+__global__ __launch_bounds__(1024) void assign_rect_one_kernel(int N, int M, const double *__restrict__ po, const double *__restrict__ goals,
+                                                               double cinv, double eps, int max_rounds, int32_t *__restrict__ perm,
+                                                               int32_t *__restrict__ owner_out, double *__restrict__ pf,
+                                                               double *__restrict__ price_out, double *__restrict__ cost,
+                                                               int32_t *__restrict__ rounds_out)
+{
+#pragma clang fp contract(off)
+    const int n = SWAP ? M : N, m = SWAP ? N : M;     // persons, objects
+    extern __shared__ double sh[];
+    double *ox = sh, *oy = ox + m, *oz = oy + m, *pr = oz + m, *offd = pr + m, *offb = offd + m;
+    unsigned long long *bidval = (unsigned long long *)(offb + m);
+    double *px = (double *)(bidval + m), *py = px + n, *pz = py + n, *bidv = pz + n, *u = bidv + n;
+    unsigned long long *offval = (unsigned long long *)(u + n);
+    int *owner = (int *)(offval + n), *bidwin = owner + m, *offp = bidwin + m;
+    int *list[2] = {offp + m, offp + 2 * (size_t)m};  // bidding persons (forward) or offering objects (reverse)
+    int *assigned = offp + 3 * (size_t)m, *bidj = assigned + n, *offwin = bidj + n;
+    __shared__ unsigned long long s_cmax;
+    __shared__ int s_cnt[2];
+    __shared__ double s_red[16];
+    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
+    const size_t s = blockIdx.x;
+    po += s * N * 3; goals += s * M * 3;
+    const double *psrc = SWAP ? goals : po, *osrc = SWAP ? po : goals;
+
+    for (int o = tid; o < m; o += nt) {
+        ox[o] = osrc[3 * o]; oy[o] = osrc[3 * o + 1]; oz[o] = osrc[3 * o + 2];
+        pr[o] = 0.0; bidval[o] = 0ull; bidwin[o] = NONE;
+    }
+    for (int p = tid; p < n; p += nt) {
+        px[p] = psrc[3 * p]; py[p] = psrc[3 * p + 1]; pz[p] = psrc[3 * p + 2];
+        offval[p] = 0ull; offwin[p] = NONE;
+    }
+    if (tid == 0) { s_cmax = 0ull; s_cnt[0] = s_cnt[1] = 0; }
+    __syncthreads();
+    double mx = 0.0;
+    for (int p = wave; p < n; p += nw)
+        for (int o = lane; o < m; o += 64) {
+            const double c = rect_cost<SWAP>(px[p], py[p], pz[p], ox[o], oy[o], oz[o], cinv);
+            mx = c > mx ? c : mx;
+        }
+    mx = wave_max(mx);
+    if (lane == 0) atomicMax(&s_cmax, (unsigned long long)__double_as_longlong(mx));   // non-negative doubles order like their bit patterns
+    __syncthreads();
+    const double cmax = __longlong_as_double((long long)s_cmax);
+
+    double e; int last;
+    next_e(cmax / 4.0, eps, e, last);
+    int rounds = 0, cur = 0;
+    bool capped = false;
+    for (;;) {                                        // forward(e); reverse(e)
+        for (int o = tid; o < m; o += nt) owner[o] = -1;
+        for (int p = tid; p < n; p += nt) { assigned[p] = -1; list[cur][p] = p; }
+        int cnt = n;
+        __syncthreads();
+        while (cnt > 0) {                             // forward rounds: assign_one_kernel's
+            if (rounds == max_rounds) { capped = true; break; }
+            ++rounds;
+            const int *lc = list[cur];
+            int *ln = list[cur ^ 1];
+            if (tid == 0) s_cnt[cur ^ 1] = 0;
+            for (int t = wave; t < cnt; t += nw) {
+                const int p = lc[t];
+                Best b = {__builtin_inf(), __builtin_inf(), NONE};
+                scan_goals<SWAP>(b, lane, m, 0, ox, oy, oz, pr, px[p], py[p], pz[p], cinv);
+                b = wave_best(b);
+                if (lane == 0) {
+                    const int o1 = b.j1 < m ? b.j1 : 0;   // (no finite value anywhere: a scene of NaNs ends at the round cap, inside the arrays)
+                    const double bid = make_bid(b, pr[o1], e, m);
+                    bidj[p] = o1; bidv[p] = bid;
+                    atomicMax(&bidval[o1], (unsigned long long)__double_as_longlong(bid));
+                }
+            }
+            __syncthreads();
+            resolve_round(cnt, lc, ln, &s_cnt[cur ^ 1], bidj, bidv, bidval, bidwin, owner, assigned, pr);
+            cur ^= 1;
+            cnt = s_cnt[cur];
+        }
+        if (!capped && n < m) {                       // reverse(e): every person owns an object here, s_cnt[cur] is zero
+            double lo = __builtin_inf();
+            for (int p = tid; p < n; p += nt) {
+                const int o = assigned[p];
+                u[p] = rect_cost<SWAP>(px[p], py[p], pz[p], ox[o], oy[o], oz[o], cinv) + pr[o];
+                lo = pr[o] < lo ? pr[o] : lo;
+            }
+            lo = wave_min(lo);
+            if (lane == 0) s_red[wave] = lo;
+            __syncthreads();
+            double lam = s_red[0];                    // the smallest price of an owned object (a minimum: whatever the order)
+            for (int w = 1; w < nw; ++w) lam = s_red[w] < lam ? s_red[w] : lam;
+            for (int o = tid; o < m; o += nt)
+                if (owner[o] < 0 && pr[o] > lam) list[cur][atomicAdd(&s_cnt[cur], 1)] = o;
+            __syncthreads();
+            cnt = s_cnt[cur];
+            while (cnt > 0) {                         // reverse rounds; the list: the unowned objects priced above lam
+                if (rounds == max_rounds) { capped = true; break; }
+                ++rounds;
+                const int *lc = list[cur];
+                int *ln = list[cur ^ 1];
+                int *n_next = &s_cnt[cur ^ 1];
+                if (tid == 0) *n_next = 0;
+                for (int t = wave; t < cnt; t += nw) {    // offers
+                    const int o = lc[t];
+                    const double x = ox[o], y = oy[o], z = oz[o];
+                    Top b = {-__builtin_inf(), -__builtin_inf(), NONE};
+                    for (int p = lane; p < n; p += 64) {   // (ascending per lane: a strict > keeps the smallest p of equal values)
+                        const double g = u[p] - rect_cost<SWAP>(px[p], py[p], pz[p], x, y, z, cinv);
+                        if (g > b.g1) { b.g2 = b.g1; b.g1 = g; b.p1 = p; }
+                        else if (g > b.g2) b.g2 = g;
+                    }
+                    b = wave_top(b);
+                    if (lane == 0) {
+                        const int p1 = b.p1 < n ? b.p1 : 0;   // (no finite value anywhere: as above)
+                        const double beta = b.g1;
+                        if (lam >= beta - e) { pr[o] = lam; offp[o] = -1; }   // done: nobody wants it above the floor
+                        else {
+                            const double d1 = beta - lam, d2 = (beta - b.g2) + e;   // (n == 1: g2 = -inf, d2 = inf)
+                            const double delta = d1 < d2 ? d1 : d2;
+                            offp[o] = p1; offd[o] = delta; offb[o] = beta;
+                            atomicMax(&offval[p1], (unsigned long long)__double_as_longlong(delta));
+                        }
+                    }
+                }
+                __syncthreads();
+                for (int t = tid; t < cnt; t += nt) {     // the smallest object among a person's largest offers
+                    const int o = lc[t], p = offp[o];
+                    if (p >= 0 && (unsigned long long)__double_as_longlong(offd[o]) == offval[p]) atomicMin(&offwin[p], o);
+                }
+                __syncthreads();
+                for (int t = tid; t < cnt; t += nt) {     // an offer that was not taken is made again next round
+                    const int o = lc[t], p = offp[o];
+                    if (p >= 0 && __hip_atomic_load(&offwin[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != o) { offp[o] = -1; ln[atomicAdd(n_next, 1)] = o; }
+                }
+                __syncthreads();
+                for (int t = tid; t < cnt; t += nt) {     // persons take their offers; what they owned is unowned at its price
+                    const int o = lc[t], p = offp[o];
+                    if (p >= 0) {
+                        const int prev = assigned[p];
+                        owner[prev] = -1;
+                        if (pr[prev] > lam) ln[atomicAdd(n_next, 1)] = prev;
+                        pr[o] = offb[o] - offd[o]; u[p] = u[p] - offd[o];
+                        owner[o] = p; assigned[p] = o;
+                        offval[p] = 0ull; offwin[p] = NONE;
+                    }
+                }
+                __syncthreads();
+                cur ^= 1;
+                cnt = s_cnt[cur];
+            }
+        }
+        if (capped || last) break;
+        next_e(e / 4.0, eps, e, last);
+    }
+
+    const int *agent_goal = SWAP ? owner : assigned, *goal_agent = SWAP ? assigned : owner;
+    for (int o = tid; o < m; o += nt)
+        if (price_out) price_out[s * m + o] = pr[o];
+    for (int j = tid; j < M; j += nt)
+        if (owner_out) owner_out[s * M + j] = capped ? -1 : goal_agent[j];
+    if (capped) {                                     // (price: as the rounds left it)
+        for (int i = tid; i < N; i += nt) {
+            if (perm) perm[s * N + i] = -1;
+            if (pf) { pf[(s * N + i) * 3] = 0.0; pf[(s * N + i) * 3 + 1] = 0.0; pf[(s * N + i) * 3 + 2] = 0.0; }
+        }
+        if (tid == 0) { if (cost) cost[s] = __builtin_nan(""); if (rounds_out) rounds_out[s] = -1; }
+        return;
+    }
+    double *term = SWAP ? offd : bidv;                // per agent
+    const double *ax = SWAP ? ox : px, *ay = SWAP ? oy : py, *az = SWAP ? oz : pz, *gx = SWAP ? px : ox, *gy = SWAP ? py : oy, *gz = SWAP ? pz : oz;
+    for (int i = tid; i < N; i += nt) {
+        const int j = agent_goal[i];
+        if (perm) perm[s * N + i] = j;
+        if (pf) {                                     // an agent without a goal is sent nowhere: its start, bit for bit
+            pf[(s * N + i) * 3] = j >= 0 ? gx[j] : ax[i]; pf[(s * N + i) * 3 + 1] = j >= 0 ? gy[j] : ay[i];
+            pf[(s * N + i) * 3 + 2] = j >= 0 ? gz[j] : az[i];
+        }
+        if (j >= 0) term[i] = pair_cost(ax[i], ay[i], az[i], gx[j], gy[j], gz[j], cinv);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double sum = 0.0;
+        for (int i = 0; i < N; ++i)
+            if (agent_goal[i] >= 0) sum = sum + term[i];   // in increasing i, one addition at a time
         if (cost) cost[s] = sum;
         if (rounds_out) rounds_out[s] = rounds;
     }
@@ -483,6 +716,81 @@ extern "C" int dmpc_assign_goals(dmpc_ctx *ctx, int S, int N, const double *po, 
     if (perm) HIPCHK(ctx, hipMemcpyAsync(perm, d_perm, SN * 4, hipMemcpyDeviceToHost, st));
     if (pf_assigned) HIPCHK(ctx, hipMemcpyAsync(pf_assigned, d_pf, SN * 24, hipMemcpyDeviceToHost, st));
     if (price) HIPCHK(ctx, hipMemcpyAsync(price, d_price, SN * 8, hipMemcpyDeviceToHost, st));
+    if (cost) HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+    if (rounds) HIPCHK(ctx, hipMemcpyAsync(rounds, d_rounds, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// dmpc_assign_rect: N agents, M goals
+// ---------------------------------------------------------------------------------------------------------------------------------------
+static int assign_rect_check(dmpc_ctx *ctx, const char *who, int S, int N, int M, const void *po, const void *goals, double eps)
+{
+    if (!ctx) { g_err = std::string(who) + ": ctx is NULL"; return -1; }
+    if (S < 1 || N < 1 || M < 1) FAIL(ctx, std::string(who) + ": S, N and M must be at least 1");
+    if (!po || !goals) FAIL(ctx, std::string(who) + ": po and goals must be given");
+    if (!(eps > 0) || !std::isfinite(eps)) FAIL(ctx, std::string(who) + ": eps must be a finite positive number");
+    if (std::max(N, M) > asg::ONE_MAX)
+        FAIL(ctx, std::string(who) + ": N = " + std::to_string(N) + " agents and M = " + std::to_string(M) + " goals: max(N, M) must not exceed " +
+                      std::to_string(asg::ONE_MAX) + " (DMPC_ASSIGN_ONE_LAUNCH_MAX; larger square scenes: dmpc_assign_goals)");
+    return 0;
+}
+
+template <bool SWAP>
+static int assign_rect_launch(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int cap, int32_t *perm,
+                              int32_t *owner, double *pf, double *price, double *cost, int32_t *rounds, hipStream_t st)
+{
+    const int n = std::min(N, M), m = std::max(N, M);
+    const int lds = (int)(asg::RECT_LDS_PER_OBJECT * (size_t)m + asg::RECT_LDS_PER_PERSON * (size_t)n);
+    if (lds > ctx->max_lds_assign_rect[SWAP]) {
+        HIPCHK(ctx, hipFuncSetAttribute((const void *)asg::assign_rect_one_kernel<SWAP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        ctx->max_lds_assign_rect[SWAP] = lds;
+    }
+    hipLaunchKernelGGL(asg::assign_rect_one_kernel<SWAP>, dim3((unsigned)S), dim3(m <= 256 ? 256 : 1024), (size_t)lds, st, N, M, po, goals,
+                       1.0 / ctx->prm.c, eps, cap, perm, owner, pf, price, cost, rounds);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+// the auction on device arrays, enqueued on st: agents are the persons when N <= M, goals otherwise
+static int assign_rect_run(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int max_rounds, int32_t *perm,
+                           int32_t *owner, double *pf, double *price, double *cost, int32_t *rounds, hipStream_t st)
+{
+    const int cap = max_rounds <= 0 ? asg::DEFAULT_ROUNDS : max_rounds;
+    return N <= M ? assign_rect_launch<false>(ctx, S, N, M, po, goals, eps, cap, perm, owner, pf, price, cost, rounds, st)
+                  : assign_rect_launch<true>(ctx, S, N, M, po, goals, eps, cap, perm, owner, pf, price, cost, rounds, st);
+}
+
+extern "C" int dmpc_assign_rect_device(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int max_rounds,
+                                       int32_t *perm, int32_t *owner, double *pf_assigned, double *price, double *cost, int32_t *rounds,
+                                       void *stream)
+{
+    if (assign_rect_check(ctx, "dmpc_assign_rect_device", S, N, M, po, goals, eps)) return -1;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return assign_rect_run(ctx, S, N, M, po, goals, eps, max_rounds, perm, owner, pf_assigned, price, cost, rounds, (hipStream_t)stream);
+}
+
+extern "C" int dmpc_assign_rect(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int max_rounds,
+                                int32_t *perm, int32_t *owner, double *pf_assigned, double *price, double *cost, int32_t *rounds)
+{
+    if (assign_rect_check(ctx, "dmpc_assign_rect", S, N, M, po, goals, eps)) return -1;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t SN = (size_t)S * N, SM = (size_t)S * M, SX = (size_t)S * std::max(N, M);
+    // po, pf [SN][3] | goals [SM][3] | price [SX] | cost [S] | perm [SN] | owner [SM] | rounds [S]
+    if (ctx->asg_io.ensure(SN * 52 + SM * 28 + SX * 8 + (size_t)S * 12)) FAIL(ctx, "device allocation failed");
+    double *d_po = ctx->asg_io.as<double>(), *d_pf = d_po + 3 * SN, *d_g = d_pf + 3 * SN, *d_price = d_g + 3 * SM, *d_cost = d_price + SX;
+    int32_t *d_perm = (int32_t *)(d_cost + S), *d_owner = d_perm + SN, *d_rounds = d_owner + SM;
+    HIPCHK(ctx, hipMemcpyAsync(d_po, po, SN * 24, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(d_g, goals, SM * 24, hipMemcpyHostToDevice, st));
+    if (assign_rect_run(ctx, S, N, M, d_po, d_g, eps, max_rounds, perm ? d_perm : nullptr, owner ? d_owner : nullptr, pf_assigned ? d_pf : nullptr,
+                        price ? d_price : nullptr, cost ? d_cost : nullptr, rounds ? d_rounds : nullptr, st))
+        return -1;
+    if (perm) HIPCHK(ctx, hipMemcpyAsync(perm, d_perm, SN * 4, hipMemcpyDeviceToHost, st));
+    if (owner) HIPCHK(ctx, hipMemcpyAsync(owner, d_owner, SM * 4, hipMemcpyDeviceToHost, st));
+    if (pf_assigned) HIPCHK(ctx, hipMemcpyAsync(pf_assigned, d_pf, SN * 24, hipMemcpyDeviceToHost, st));
+    if (price) HIPCHK(ctx, hipMemcpyAsync(price, d_price, SX * 8, hipMemcpyDeviceToHost, st));
     if (cost) HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, (size_t)S * 8, hipMemcpyDeviceToHost, st));
     if (rounds) HIPCHK(ctx, hipMemcpyAsync(rounds, d_rounds, (size_t)S * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));

@@ -25,6 +25,8 @@
 //   [pk,vk,ak,K_T_used,scene_status,wp_col] = dmpc_mex('route', params, po, waypoints, K_T_max, error_tol, capture[, n_wp[, timeout]])   waypoints 3 x W x N_cmd: see below
 //   [perm,pf,cost,rounds] = dmpc_mex('assign', params, po, goals[, eps[, max_rounds]])  goal assignment (dmpc_assign_goals): po, goals 3 x N; perm 1 x N, 1-based:
 //                                                                                    agent i takes goals(:,perm(i)) = pf(:,i); eps default 1e-4 / N
+//   [perm,pf,owner,cost,rounds] = dmpc_mex('assign_rect', params, po, goals[, eps[, max_rounds]])  N agents, M goals (dmpc_assign_rect): po 3 x N, goals 3 x M;
+//                                                                                    perm 1 x N, owner 1 x M, 1-based, 0: none (pf(:,i) = po(:,i) then); eps default 1e-4 / max(N,M)
 //   [waypoints,n_wp,plan_status,hops] = dmpc_mex('plan', params, po, goals, cell[, margin[, W[, obstacles]]])   route planning (dmpc_plan_routes): see below
 //   [pk,vk,ak,K_T_used,scene_status,waypoints,n_wp,replan_count,replan_col,wp_col,plan_status] = dmpc_mex('replan', params, po, goals, K_T_max, error_tol, cell,
 //                    capture[, margin[, W[, every[, ahead[, path[, timeout]]]]]])        re-planned routes (dmpc_transition_replan): see below
@@ -525,6 +527,31 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 1) plhs[1] = pf;
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(cost);
         if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)rounds);
+        return;
+    }
+    if (!std::strcmp(cmd, "assign_rect")) {   // N agents, M goals (dmpc_assign_rect); 0: "none"; a scene that met the round cap: perm and owner 0, cost NaN, rounds -1
+        need(nrhs >= 4 && nrhs <= 6, "assign_rect: (cmd, params, po, goals[, eps[, max_rounds]])");
+        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3), M = (int)(mxGetNumberOfElements(prhs[3]) / 3);
+        need(N >= 1 && M >= 1 && mxGetM(prhs[2]) == 3 && mxGetM(prhs[3]) == 3 && mxGetNumberOfElements(prhs[2]) == (size_t)3 * N &&
+             mxGetNumberOfElements(prhs[3]) == (size_t)3 * M, "po must be 3 x N and goals 3 x M");
+        const double eps = nrhs > 4 && mxGetNumberOfElements(prhs[4]) > 0 ? mxGetScalar(prhs[4]) : 1e-4 / (N > M ? N : M);
+        const int max_rounds = nrhs > 5 ? (int)mxGetScalar(prhs[5]) : 0;
+        std::vector<int32_t> perm((size_t)N, 0), owner((size_t)M, 0);
+        mxArray *pf = mxCreateDoubleMatrix(3, (mwSize)N, mxREAL);
+        double cost = 0.0;
+        int32_t rounds = 0;
+        if (dmpc_assign_rect(ctx, 1, N, M, mxGetPr(prhs[2]), mxGetPr(prhs[3]), eps, max_rounds, perm.data(), owner.data(), mxGetPr(pf), nullptr, &cost,
+                             &rounds))
+            mexErrMsgIdAndTxt("dmpc:assign_rect", "%s", dmpc_last_error(ctx));
+        plhs[0] = mxCreateDoubleMatrix(1, (mwSize)N, mxREAL);
+        for (int i = 0; i < N; ++i) mxGetPr(plhs[0])[i] = (double)(perm[(size_t)i] + 1);
+        if (nlhs > 1) plhs[1] = pf;
+        if (nlhs > 2) {
+            plhs[2] = mxCreateDoubleMatrix(1, (mwSize)M, mxREAL);
+            for (int j = 0; j < M; ++j) mxGetPr(plhs[2])[j] = (double)(owner[(size_t)j] + 1);
+        }
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar(cost);
+        if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)rounds);
         return;
     }
     if (!std::strcmp(cmd, "plan")) {   // which way round the static vehicles (dmpc_plan_routes): the waypoints 'route' takes
