@@ -147,11 +147,10 @@ struct dmpc_ctx {
     int hist_S = 0, hist_N = 0, hist_KT = 0;   // shape of the histories left resident by the last dmpc_transition
     int32_t *flags_host = nullptr; size_t flags_host_cap = 0;   // pinned: per-step verdicts of dmpc_transition
     hipEvent_t flag_ev[2] = {nullptr, nullptr};
-    DevBuf asg_io, asg_work;                                               // dmpc_assign_goals: staged inputs / outputs of the host form; scratch of the round launches
+    DevBuf asg_io, asg_work;                                               // dmpc_assign_goals / _rect: staged inputs / outputs of the host forms; scratch of the round launches
     int32_t *asg_host = nullptr; size_t asg_host_cap = 0;                  // pinned: the scenes' done flags of two windows of rounds
     hipEvent_t asg_ev[2] = {nullptr, nullptr};
-    int max_lds_assign = 0;  // dynamic-LDS limit assign_one_kernel was last raised to
-    int max_lds_assign_rect[2] = {0, 0};   // ... and assign_rect_one_kernel<SWAP> (dmpc_assign_rect)
+    int max_lds_assign[2] = {0, 0};   // dynamic-LDS limit assign_one_kernel<SWAP> was last raised to
     DevBuf plan_io, plan_mask;                                             // dmpc_plan_routes: staged inputs / outputs of the host form; the scenes' blocked bitmasks
     int max_lds_plan = 0;    // dynamic-LDS limit plan_route_kernel was last raised to
     DevBuf replan_work, replan_obst, replan_goals;                         // re-planning: blocked bitmasks | flagged list | count; the obstacle points of a column; dmpc_transition_replan's goals
@@ -994,7 +993,7 @@ extern "C" int dmpc_random_sets_device(dmpc_ctx *ctx, int S, int N, const double
                        (hipStream_t)stream);
 }
 
-#include "dmpc_assign.hip"   // goal assignment: the auction's kernels and the two entries
+#include "dmpc_assign.hip"   // goal assignment: the auction's kernels and the four entries
 
 
 // ---------------------------------------------------------------------------------------------

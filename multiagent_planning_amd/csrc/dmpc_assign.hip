@@ -1,20 +1,20 @@
-// dmpc_assign.hip -- goal assignment ahead of a transition: which agent takes which point of the next formation (dmpc_assign_goals).
+// dmpc_assign.hip -- goal assignment ahead of a transition: which agent takes which point of the next formation (dmpc_assign_goals: N agents,
+// N goals; dmpc_assign_rect: N agents, M goals).
 //
 // There is no reference counterpart (randomTest.m / randomExchange.m hand out labelled goals).  The rule is pinned in include/dmpc_hip.h and
-// restated in numpy by tests/assign.py, which the device must equal bit for bit: the forward auction with eps-scaling in synchronous
-// (Jacobi) rounds over the cost c(i,j) = |E1 (po_i - g_j)|^2, E1 = diag(1,1,1/c).  Nothing in the result depends on launch geometry, batch
-// size or the order the device visits anything in:
+// restated in numpy by tests/assign.py (square) and tests/assign_rect.py, which the device must equal bit for bit: the forward auction with
+// eps-scaling in synchronous (Jacobi) rounds over the cost c(i,j) = |E1 (po_i - g_j)|^2, E1 = diag(1,1,1/c); with N != M, reverse rounds
+// -- unowned objects offer themselves down to the smallest owned price -- behind the forward rounds of every eps.  Nothing in the result
+// depends on launch geometry, batch size or the order the device visits anything in:
 //   bidding     one wave per unassigned agent (a compacted list), lanes stride over the goals (SoA in LDS: coordinates + price, 32 B per
 //               goal), per-lane top-2 of m = c + price, then a wave butterfly that merges by the total order (m ascending, j ascending)
 //   resolution  bids are positive doubles, their bit patterns order as unsigned integers: atomicMax per goal finds the winning bid,
 //               atomicMin over the bidders that made it finds the smallest agent
 //   no dense cost matrix: costs are recomputed from the 3 + 1 doubles per goal
-// Scenes of up to DMPC_ASSIGN_ONE_LAUNCH_MAX agents run in ONE launch (assign_one_kernel: one workgroup per scene, everything in LDS,
-// workgroup barriers between the stages of a round).  Larger scenes take two launches per round (assign_bid_kernel streams the goals through
-// LDS tile by tile, 16 bidders share a tile; assign_settle_kernel, one workgroup per scene, resolves, applies and keeps the phase state) and
-// the host reads the scenes' done flags one window of rounds behind, as dmpc_transition reads its verdicts.
-// dmpc_assign_rect (N agents, M goals; tests/assign_rect.py restates it) adds reverse rounds -- unowned objects offer themselves down to the
-// smallest owned price -- to the same forward rounds: assign_rect_one_kernel, one launch, max(N, M) <= DMPC_ASSIGN_ONE_LAUNCH_MAX only.
+// Scenes of max(N, M) <= DMPC_ASSIGN_ONE_LAUNCH_MAX run in ONE launch, square or not (assign_one_kernel: one workgroup per scene, everything
+// in LDS, workgroup barriers between the stages of a round).  Larger scenes, square only, take two launches per round (assign_bid_kernel
+// streams the goals through LDS tile by tile, 16 bidders share a tile; assign_settle_kernel, one workgroup per scene, resolves, applies and
+// keeps the phase state) and the host reads the scenes' done flags one window of rounds behind, as dmpc_transition reads its verdicts.
 //
 // Included into dmpc_api.hip (single translation unit).  Every kernel rounds each operation on its own (fp contraction off).
 #include <hip/hip_runtime.h>
@@ -28,9 +28,9 @@ constexpr int BID_WAVES = 16;       // bidders that share a tile
 constexpr int WINDOW = 64;          // rounds the host launches between two looks at the done flags
 constexpr int NONE = 0x7fffffff;
 constexpr int DEFAULT_ROUNDS = 1 << 20;
-constexpr size_t ONE_LDS_PER_AGENT = 9 * 8 + 6 * 4;   // assign_one_kernel: 9 doubles and 6 ints per agent
 
 struct Best { double m1, m2; int j1; };   // smallest m, smallest m over j != j1, the goal of m1
+struct Top { double g1, g2; int p1; };    // largest g, largest g over p != p1, the person of g1
 
 struct State {                      // of one scene, between the round launches
     unsigned long long cmax_bits;
@@ -53,15 +53,22 @@ __device__ inline double pair_cost(double px, double py, double pz, double gx, d
     return (dx * dx + dy * dy) + dz * dz;
 }
 
-// lanes stride over goals jbase .. jbase + n - 1 (ascending per lane: a strict < keeps the smallest j of equal values)
-// (SWAP, dmpc_assign_rect with more agents than goals: the scanned arrays hold agents and (px, py, pz) is a goal; pair_cost still gets the agent first)
+// the cost of a person and an object -- the smaller and the larger side of a scene; SWAP, more agents than goals: the persons are the goals.
+// The agent goes first into pair_cost.
+template <bool SWAP>
+__device__ inline double rect_cost(double px, double py, double pz, double ox, double oy, double oz, double cinv)
+{
+    return SWAP ? pair_cost(ox, oy, oz, px, py, pz, cinv) : pair_cost(px, py, pz, ox, oy, oz, cinv);
+}
+
+// lanes stride over goals (objects) jbase .. jbase + n - 1 (ascending per lane: a strict < keeps the smallest j of equal values)
 template <bool SWAP = false>
 __device__ inline void scan_goals(Best &b, int lane, int n, int jbase, const double *gx, const double *gy, const double *gz, const double *pr,
                                   double px, double py, double pz, double cinv)
 {
 #pragma clang fp contract(off)
     for (int j = lane; j < n; j += 64) {
-        const double m = (SWAP ? pair_cost(gx[j], gy[j], gz[j], px, py, pz, cinv) : pair_cost(px, py, pz, gx[j], gy[j], gz[j], cinv)) + pr[j];
+        const double m = rect_cost<SWAP>(px, py, pz, gx[j], gy[j], gz[j], cinv) + pr[j];
         if (m < b.m1) { b.m2 = b.m1; b.m1 = m; b.j1 = jbase + j; }
         else if (m < b.m2) b.m2 = m;
     }
@@ -130,124 +137,96 @@ __device__ inline void resolve_round(int cnt, const int *lc, int *ln, int *n_nex
     __syncthreads();
 }
 
-// what a scene stopped at the round cap reports (one workgroup; price: as the rounds left it)
-__device__ inline void write_capped(int N, size_t s, const double *price, int32_t *perm, double *pf, double *price_out, double *cost,
-                                    int32_t *rounds_out)
+// what a scene stopped at the round cap reports (one workgroup; owner_out: dmpc_assign_rect's, null otherwise; the caller writes the prices,
+// as the rounds left them)
+__device__ inline void write_capped(int N, int M, size_t s, int32_t *perm, int32_t *owner_out, double *pf, double *cost, int32_t *rounds_out)
 {
     for (int i = threadIdx.x; i < N; i += blockDim.x) {
         if (perm) perm[s * N + i] = -1;
         if (pf) { pf[(s * N + i) * 3] = 0.0; pf[(s * N + i) * 3 + 1] = 0.0; pf[(s * N + i) * 3 + 2] = 0.0; }
-        if (price_out) price_out[s * N + i] = price[i];
     }
+    for (int j = threadIdx.x; j < M; j += blockDim.x)
+        if (owner_out) owner_out[s * M + j] = -1;
     if (threadIdx.x == 0) { if (cost) cost[s] = __builtin_nan(""); if (rounds_out) rounds_out[s] = -1; }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
-// N <= ONE_MAX: the whole auction of a scene in one workgroup
+// max(N, M) <= ONE_MAX: the whole forward/reverse auction of a scene in one workgroup
 // ---------------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void assign_one_kernel(int N, const double *__restrict__ po, const double *__restrict__ goals, double cinv,
-                                                          double eps, int max_rounds, int32_t *__restrict__ perm, double *__restrict__ pf,
-                                                          double *__restrict__ price_out, double *__restrict__ cost, int32_t *__restrict__ rounds_out)
+// The smaller side are the n persons, the larger side the m objects (SWAP: more agents than goals, the goals are the persons; a square scene
+// is n == m without SWAP and runs no reverse round).  Forward rounds: one wave per bidding person.  Reverse rounds are their mirror image: one
+// wave per offering object (a compacted list), lanes stride over the persons with a per-lane top-2 of g = u - c, a butterfly that merges by
+// the total order (g descending, p ascending); offers are positive doubles, so atomicMax on their bit patterns per person finds the winning
+// offer and atomicMin over the objects that made it the smallest object.
+
+// The kernel's dynamic LDS: where every column starts, in bytes, and what they take together -- the host sizes the launch from it, the kernel
+// carves its pointers from it.  Every 8-byte column lies ahead of every 4-byte column, so odd n, m keep every double and every 64-bit atomic
+// 8-byte aligned.  The columns that only reverse rounds use have no rows when n == m: 56 B per object + 40 B per person (96 B per agent) then,
+// 76 B per object + 60 B per person otherwise.
+struct OneLds {
+    unsigned ox, oy, oz, pr, offd, offb, bidval, px, py, pz, bidv, u, offval;   // 8-byte columns
+    unsigned owner, bidwin, offp, list, assigned, bidj, offwin;                 // 4-byte columns (list: 2 m rows)
+    unsigned bytes;
+    __host__ __device__ OneLds(int n, int m)
+    {
+        const unsigned rm = n < m ? m : 0, rn = n < m ? n : 0;   // rows of the reverse-only columns, per object and per person
+        unsigned at = 0;
+        auto col = [&at](unsigned rows, unsigned width) { const unsigned o = at; at += rows * width; return o; };
+        ox = col(m, 8); oy = col(m, 8); oz = col(m, 8); pr = col(m, 8); offd = col(rm, 8); offb = col(rm, 8); bidval = col(m, 8);
+        px = col(n, 8); py = col(n, 8); pz = col(n, 8); bidv = col(n, 8); u = col(rn, 8); offval = col(rn, 8);
+        owner = col(m, 4); bidwin = col(m, 4); offp = col(rm, 4); list = col(2 * m, 4);
+        assigned = col(n, 4); bidj = col(n, 4); offwin = col(rn, 4);
+        bytes = at;
+    }
+};
+
+struct Scene {                      // of one workgroup of assign_one_kernel
+    int n, m, max_rounds;
+    double cinv;
+    double *ox, *oy, *oz, *pr, *offd, *offb, *px, *py, *pz, *bidv, *u;   // OneLds' columns (offd, offb, offp, u, offval, offwin: n < m only)
+    unsigned long long *bidval, *offval;
+    int *owner, *bidwin, *offp, *lists, *assigned, *bidj, *offwin;
+    int *cnt;                       // [2] the lengths of the two lists
+    double *red;                    // [16] one slot per wave
+    int rounds, cur;                // rounds so far, forward and reverse; which list holds the bidding persons or offering objects
+    __device__ int *list(int k) const { return lists + (size_t)k * m; }
+};
+
+// forward(e): everybody unassigned at the prices as they are, then rounds until no person is -- one wave per bidder.  False: the round cap.
+template <bool SWAP>
+__device__ inline bool forward_rounds(Scene &sc, double e)
 {
 #pragma clang fp contract(off)
-    extern __shared__ double sh[];
-    double *gx = sh, *gy = gx + N, *gz = gy + N, *pr = gz + N, *px = pr + N, *py = px + N, *pz = py + N, *bidv = pz + N;
-    unsigned long long *bidval = (unsigned long long *)(bidv + N);
-    int *owner = (int *)(bidval + N), *assigned = owner + N, *bidwin = assigned + N, *bidj = bidwin + N;
-    int *list[2] = {bidj + N, bidj + 2 * (size_t)N};
-    __shared__ unsigned long long s_cmax;
-    __shared__ int s_cnt[2];
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
-    const size_t s = blockIdx.x;
-    po += s * N * 3; goals += s * N * 3;
-
-    for (int i = tid; i < N; i += nt) {
-        px[i] = po[3 * i]; py[i] = po[3 * i + 1]; pz[i] = po[3 * i + 2];
-        gx[i] = goals[3 * i]; gy[i] = goals[3 * i + 1]; gz[i] = goals[3 * i + 2];
-        pr[i] = 0.0; bidval[i] = 0ull; bidwin[i] = NONE;
-    }
-    if (tid == 0) { s_cmax = 0ull; s_cnt[0] = s_cnt[1] = 0; }
+    const int n = sc.n, m = sc.m;
+    for (int o = tid; o < m; o += nt) sc.owner[o] = -1;
+    for (int p = tid; p < n; p += nt) { sc.assigned[p] = -1; sc.list(sc.cur)[p] = p; }
+    int cnt = n;
     __syncthreads();
-    double mx = 0.0;
-    for (int i = wave; i < N; i += nw)
-        for (int j = lane; j < N; j += 64) {
-            const double c = pair_cost(px[i], py[i], pz[i], gx[j], gy[j], gz[j], cinv);
-            mx = c > mx ? c : mx;
-        }
-    mx = wave_max(mx);
-    if (lane == 0) atomicMax(&s_cmax, (unsigned long long)__double_as_longlong(mx));   // non-negative doubles order like their bit patterns
-    __syncthreads();
-    const double cmax = __longlong_as_double((long long)s_cmax);
-
-    double e; int last;
-    next_e(cmax / 4.0, eps, e, last);
-    int rounds = 0, cur = 0;
-    bool capped = false;
-    for (;;) {                                        // phases
-        for (int i = tid; i < N; i += nt) { assigned[i] = -1; owner[i] = -1; list[cur][i] = i; }
-        int cnt = N;
-        __syncthreads();
-        while (cnt > 0) {                             // rounds
-            if (rounds == max_rounds) { capped = true; break; }
-            ++rounds;
-            const int *lc = list[cur];
-            int *ln = list[cur ^ 1];
-            if (tid == 0) s_cnt[cur ^ 1] = 0;
-            for (int t = wave; t < cnt; t += nw) {    // bids
-                const int i = lc[t];
-                Best b = {__builtin_inf(), __builtin_inf(), NONE};
-                scan_goals(b, lane, N, 0, gx, gy, gz, pr, px[i], py[i], pz[i], cinv);
-                b = wave_best(b);
-                if (lane == 0) {
-                    const int j1 = b.j1 < N ? b.j1 : 0;   // (no finite value anywhere: a scene of NaNs ends at the round cap, inside the arrays)
-                    const double bid = make_bid(b, pr[j1], e, N);
-                    bidj[i] = j1; bidv[i] = bid;
-                    atomicMax(&bidval[j1], (unsigned long long)__double_as_longlong(bid));
-                }
+    while (cnt > 0) {
+        if (sc.rounds == sc.max_rounds) return false;
+        ++sc.rounds;
+        const int *lc = sc.list(sc.cur);
+        int *ln = sc.list(sc.cur ^ 1);
+        if (tid == 0) sc.cnt[sc.cur ^ 1] = 0;
+        for (int t = wave; t < cnt; t += nw) {        // bids
+            const int p = lc[t];
+            Best b = {__builtin_inf(), __builtin_inf(), NONE};
+            scan_goals<SWAP>(b, lane, m, 0, sc.ox, sc.oy, sc.oz, sc.pr, sc.px[p], sc.py[p], sc.pz[p], sc.cinv);
+            b = wave_best(b);
+            if (lane == 0) {
+                const int o1 = b.j1 < m ? b.j1 : 0;   // (no finite value anywhere: a scene of NaNs ends at the round cap, inside the arrays)
+                const double bid = make_bid(b, sc.pr[o1], e, m);
+                sc.bidj[p] = o1; sc.bidv[p] = bid;
+                atomicMax(&sc.bidval[o1], (unsigned long long)__double_as_longlong(bid));
             }
-            __syncthreads();
-            resolve_round(cnt, lc, ln, &s_cnt[cur ^ 1], bidj, bidv, bidval, bidwin, owner, assigned, pr);
-            cur ^= 1;
-            cnt = s_cnt[cur];
         }
-        if (capped || last) break;
-        next_e(e / 4.0, eps, e, last);
+        __syncthreads();
+        resolve_round(cnt, lc, ln, &sc.cnt[sc.cur ^ 1], sc.bidj, sc.bidv, sc.bidval, sc.bidwin, sc.owner, sc.assigned, sc.pr);
+        sc.cur ^= 1;
+        cnt = sc.cnt[sc.cur];
     }
-
-    if (capped) { write_capped(N, s, pr, perm, pf, price_out, cost, rounds_out); return; }
-    for (int i = tid; i < N; i += nt) {
-        const int j = assigned[i];
-        if (perm) perm[s * N + i] = j;
-        if (price_out) price_out[s * N + i] = pr[i];
-        if (pf) { pf[(s * N + i) * 3] = gx[j]; pf[(s * N + i) * 3 + 1] = gy[j]; pf[(s * N + i) * 3 + 2] = gz[j]; }
-        bidv[i] = pair_cost(px[i], py[i], pz[i], gx[j], gy[j], gz[j], cinv);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double sum = 0.0;
-        for (int i = 0; i < N; ++i) sum = sum + bidv[i];   // in increasing i, one addition at a time
-        if (cost) cost[s] = sum;
-        if (rounds_out) rounds_out[s] = rounds;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------------
-// dmpc_assign_rect, N agents and M goals with max(N, M) <= ONE_MAX: the forward/reverse auction of a scene in one workgroup
-// ---------------------------------------------------------------------------------------------------------------------------------------
-// The smaller side are the n persons, the larger side the m objects (SWAP: more agents than goals, the goals are the persons).  Forward rounds
-// are assign_one_kernel's on person and object arrays.  Reverse rounds are their mirror image: one wave per offering object (a compacted list),
-// lanes stride over the persons with a per-lane top-2 of g = u - c, a butterfly that merges by the total order (g descending, p ascending);
-// offers are positive doubles, so atomicMax on their bit patterns per person finds the winning offer and atomicMin over the objects that
-// made it the smallest object.  LDS: 76 B per object, 60 B per person.
-constexpr size_t RECT_LDS_PER_OBJECT = 7 * 8 + 5 * 4;   // ox oy oz pr offd offb bidval | owner bidwin offp list[2]
-constexpr size_t RECT_LDS_PER_PERSON = 6 * 8 + 3 * 4;   // px py pz bidv u offval | assigned bidj offwin
-
-struct Top { double g1, g2; int p1; };    // largest g, largest g over p != p1, the person of g1
-
-template <bool SWAP>
-__device__ inline double rect_cost(double px, double py, double pz, double ox, double oy, double oz, double cinv)
-{
-    return SWAP ? pair_cost(ox, oy, oz, px, py, pz, cinv) : pair_cost(px, py, pz, ox, oy, oz, cinv);   // (agent, goal)
+    return true;
 }
 
 // the merge is defined by the order (g descending, p ascending), so every lane ends with the same bits whatever the tree
@@ -272,45 +251,127 @@ __device__ inline double wave_min(double v)
     return v;
 }
 
+// reverse(e), n < m, behind forward(e): every person owns an object and sc.cnt[sc.cur] is zero on entry.  False: the round cap.
 template <bool SWAP>
-__global__ __launch_bounds__(1024) void assign_rect_one_kernel(int N, int M, const double *__restrict__ po, const double *__restrict__ goals,
-                                                               double cinv, double eps, int max_rounds, int32_t *__restrict__ perm,
-                                                               int32_t *__restrict__ owner_out, double *__restrict__ pf,
-                                                               double *__restrict__ price_out, double *__restrict__ cost,
-                                                               int32_t *__restrict__ rounds_out)
+__device__ inline bool reverse_rounds(Scene &sc, double e)
+{
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
+    const int n = sc.n, m = sc.m;
+    double lo = __builtin_inf();
+    for (int p = tid; p < n; p += nt) {
+        const int o = sc.assigned[p];
+        sc.u[p] = rect_cost<SWAP>(sc.px[p], sc.py[p], sc.pz[p], sc.ox[o], sc.oy[o], sc.oz[o], sc.cinv) + sc.pr[o];
+        lo = sc.pr[o] < lo ? sc.pr[o] : lo;
+    }
+    lo = wave_min(lo);
+    if (lane == 0) sc.red[wave] = lo;
+    __syncthreads();
+    double lam = sc.red[0];                           // the smallest price of an owned object (a minimum: whatever the order)
+    for (int w = 1; w < nw; ++w) lam = sc.red[w] < lam ? sc.red[w] : lam;
+    for (int o = tid; o < m; o += nt)
+        if (sc.owner[o] < 0 && sc.pr[o] > lam) sc.list(sc.cur)[atomicAdd(&sc.cnt[sc.cur], 1)] = o;
+    __syncthreads();
+    int cnt = sc.cnt[sc.cur];
+    while (cnt > 0) {                                 // the list: the unowned objects priced above lam
+        if (sc.rounds == sc.max_rounds) return false;
+        ++sc.rounds;
+        const int *lc = sc.list(sc.cur);
+        int *ln = sc.list(sc.cur ^ 1);
+        int *n_next = &sc.cnt[sc.cur ^ 1];
+        if (tid == 0) *n_next = 0;
+        for (int t = wave; t < cnt; t += nw) {        // offers
+            const int o = lc[t];
+            const double x = sc.ox[o], y = sc.oy[o], z = sc.oz[o];
+            Top b = {-__builtin_inf(), -__builtin_inf(), NONE};
+            for (int p = lane; p < n; p += 64) {      // (ascending per lane: a strict > keeps the smallest p of equal values)
+                const double g = sc.u[p] - rect_cost<SWAP>(sc.px[p], sc.py[p], sc.pz[p], x, y, z, sc.cinv);
+                if (g > b.g1) { b.g2 = b.g1; b.g1 = g; b.p1 = p; }
+                else if (g > b.g2) b.g2 = g;
+            }
+            b = wave_top(b);
+            if (lane == 0) {
+                const int p1 = b.p1 < n ? b.p1 : 0;   // (no finite value anywhere: as in forward_rounds)
+                const double beta = b.g1;
+                if (lam >= beta - e) { sc.pr[o] = lam; sc.offp[o] = -1; }   // done: nobody wants it above the floor
+                else {
+                    const double d1 = beta - lam, d2 = (beta - b.g2) + e;   // (n == 1: g2 = -inf, d2 = inf)
+                    const double delta = d1 < d2 ? d1 : d2;
+                    sc.offp[o] = p1; sc.offd[o] = delta; sc.offb[o] = beta;
+                    atomicMax(&sc.offval[p1], (unsigned long long)__double_as_longlong(delta));
+                }
+            }
+        }
+        __syncthreads();
+        for (int t = tid; t < cnt; t += nt) {         // the smallest object among a person's largest offers
+            const int o = lc[t], p = sc.offp[o];
+            if (p >= 0 && (unsigned long long)__double_as_longlong(sc.offd[o]) == sc.offval[p]) atomicMin(&sc.offwin[p], o);
+        }
+        __syncthreads();
+        for (int t = tid; t < cnt; t += nt) {         // an offer that was not taken is made again next round
+            const int o = lc[t], p = sc.offp[o];
+            if (p >= 0 && __hip_atomic_load(&sc.offwin[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != o) { sc.offp[o] = -1; ln[atomicAdd(n_next, 1)] = o; }
+        }
+        __syncthreads();
+        for (int t = tid; t < cnt; t += nt) {         // persons take their offers; what they owned is unowned at its price
+            const int o = lc[t], p = sc.offp[o];
+            if (p >= 0) {
+                const int prev = sc.assigned[p];
+                sc.owner[prev] = -1;
+                if (sc.pr[prev] > lam) ln[atomicAdd(n_next, 1)] = prev;
+                sc.pr[o] = sc.offb[o] - sc.offd[o]; sc.u[p] = sc.u[p] - sc.offd[o];
+                sc.owner[o] = p; sc.assigned[p] = o;
+                sc.offval[p] = 0ull; sc.offwin[p] = NONE;
+            }
+        }
+        __syncthreads();
+        sc.cur ^= 1;
+        cnt = sc.cnt[sc.cur];
+    }
+    return true;
+}
+
+template <bool SWAP>
+__global__ __launch_bounds__(1024) void assign_one_kernel(int N, int M, const double *__restrict__ po, const double *__restrict__ goals, double cinv,
+                                                          double eps, int max_rounds, int32_t *__restrict__ perm,
+                                                          int32_t *__restrict__ owner_out, double *__restrict__ pf,
+                                                          double *__restrict__ price_out, double *__restrict__ cost,
+                                                          int32_t *__restrict__ rounds_out)
 {
 #pragma clang fp contract(off)
     const int n = SWAP ? M : N, m = SWAP ? N : M;     // persons, objects
     extern __shared__ double sh[];
-    double *ox = sh, *oy = ox + m, *oz = oy + m, *pr = oz + m, *offd = pr + m, *offb = offd + m;
-    unsigned long long *bidval = (unsigned long long *)(offb + m);
-    double *px = (double *)(bidval + m), *py = px + n, *pz = py + n, *bidv = pz + n, *u = bidv + n;
-    unsigned long long *offval = (unsigned long long *)(u + n);
-    int *owner = (int *)(offval + n), *bidwin = owner + m, *offp = bidwin + m;
-    int *list[2] = {offp + m, offp + 2 * (size_t)m};  // bidding persons (forward) or offering objects (reverse)
-    int *assigned = offp + 3 * (size_t)m, *bidj = assigned + n, *offwin = bidj + n;
     __shared__ unsigned long long s_cmax;
     __shared__ int s_cnt[2];
     __shared__ double s_red[16];
+    const OneLds at(n, m);
+    const auto f64 = [](unsigned off) { return (double *)((char *)sh + off); };
+    const auto u64 = [](unsigned off) { return (unsigned long long *)((char *)sh + off); };
+    const auto i32 = [](unsigned off) { return (int *)((char *)sh + off); };
+    Scene sc = {n, m, max_rounds, cinv,
+                f64(at.ox), f64(at.oy), f64(at.oz), f64(at.pr), f64(at.offd), f64(at.offb), f64(at.px), f64(at.py), f64(at.pz), f64(at.bidv), f64(at.u),
+                u64(at.bidval), u64(at.offval),
+                i32(at.owner), i32(at.bidwin), i32(at.offp), i32(at.list), i32(at.assigned), i32(at.bidj), i32(at.offwin),
+                s_cnt, s_red, 0, 0};
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
     const size_t s = blockIdx.x;
     po += s * N * 3; goals += s * M * 3;
     const double *psrc = SWAP ? goals : po, *osrc = SWAP ? po : goals;
 
     for (int o = tid; o < m; o += nt) {
-        ox[o] = osrc[3 * o]; oy[o] = osrc[3 * o + 1]; oz[o] = osrc[3 * o + 2];
-        pr[o] = 0.0; bidval[o] = 0ull; bidwin[o] = NONE;
+        sc.ox[o] = osrc[3 * o]; sc.oy[o] = osrc[3 * o + 1]; sc.oz[o] = osrc[3 * o + 2];
+        sc.pr[o] = 0.0; sc.bidval[o] = 0ull; sc.bidwin[o] = NONE;
     }
     for (int p = tid; p < n; p += nt) {
-        px[p] = psrc[3 * p]; py[p] = psrc[3 * p + 1]; pz[p] = psrc[3 * p + 2];
-        offval[p] = 0ull; offwin[p] = NONE;
+        sc.px[p] = psrc[3 * p]; sc.py[p] = psrc[3 * p + 1]; sc.pz[p] = psrc[3 * p + 2];
+        if (n < m) { sc.offval[p] = 0ull; sc.offwin[p] = NONE; }
     }
     if (tid == 0) { s_cmax = 0ull; s_cnt[0] = s_cnt[1] = 0; }
     __syncthreads();
     double mx = 0.0;
     for (int p = wave; p < n; p += nw)
         for (int o = lane; o < m; o += 64) {
-            const double c = rect_cost<SWAP>(px[p], py[p], pz[p], ox[o], oy[o], oz[o], cinv);
+            const double c = rect_cost<SWAP>(sc.px[p], sc.py[p], sc.pz[p], sc.ox[o], sc.oy[o], sc.oz[o], cinv);
             mx = c > mx ? c : mx;
         }
     mx = wave_max(mx);
@@ -320,127 +381,22 @@ __global__ __launch_bounds__(1024) void assign_rect_one_kernel(int N, int M, con
 
     double e; int last;
     next_e(cmax / 4.0, eps, e, last);
-    int rounds = 0, cur = 0;
-    bool capped = false;
-    for (;;) {                                        // forward(e); reverse(e)
-        for (int o = tid; o < m; o += nt) owner[o] = -1;
-        for (int p = tid; p < n; p += nt) { assigned[p] = -1; list[cur][p] = p; }
-        int cnt = n;
-        __syncthreads();
-        while (cnt > 0) {                             // forward rounds: assign_one_kernel's
-            if (rounds == max_rounds) { capped = true; break; }
-            ++rounds;
-            const int *lc = list[cur];
-            int *ln = list[cur ^ 1];
-            if (tid == 0) s_cnt[cur ^ 1] = 0;
-            for (int t = wave; t < cnt; t += nw) {
-                const int p = lc[t];
-                Best b = {__builtin_inf(), __builtin_inf(), NONE};
-                scan_goals<SWAP>(b, lane, m, 0, ox, oy, oz, pr, px[p], py[p], pz[p], cinv);
-                b = wave_best(b);
-                if (lane == 0) {
-                    const int o1 = b.j1 < m ? b.j1 : 0;   // (no finite value anywhere: a scene of NaNs ends at the round cap, inside the arrays)
-                    const double bid = make_bid(b, pr[o1], e, m);
-                    bidj[p] = o1; bidv[p] = bid;
-                    atomicMax(&bidval[o1], (unsigned long long)__double_as_longlong(bid));
-                }
-            }
-            __syncthreads();
-            resolve_round(cnt, lc, ln, &s_cnt[cur ^ 1], bidj, bidv, bidval, bidwin, owner, assigned, pr);
-            cur ^= 1;
-            cnt = s_cnt[cur];
-        }
-        if (!capped && n < m) {                       // reverse(e): every person owns an object here, s_cnt[cur] is zero
-            double lo = __builtin_inf();
-            for (int p = tid; p < n; p += nt) {
-                const int o = assigned[p];
-                u[p] = rect_cost<SWAP>(px[p], py[p], pz[p], ox[o], oy[o], oz[o], cinv) + pr[o];
-                lo = pr[o] < lo ? pr[o] : lo;
-            }
-            lo = wave_min(lo);
-            if (lane == 0) s_red[wave] = lo;
-            __syncthreads();
-            double lam = s_red[0];                    // the smallest price of an owned object (a minimum: whatever the order)
-            for (int w = 1; w < nw; ++w) lam = s_red[w] < lam ? s_red[w] : lam;
-            for (int o = tid; o < m; o += nt)
-                if (owner[o] < 0 && pr[o] > lam) list[cur][atomicAdd(&s_cnt[cur], 1)] = o;
-            __syncthreads();
-            cnt = s_cnt[cur];
-            while (cnt > 0) {                         // reverse rounds; the list: the unowned objects priced above lam
-                if (rounds == max_rounds) { capped = true; break; }
-                ++rounds;
-                const int *lc = list[cur];
-                int *ln = list[cur ^ 1];
-                int *n_next = &s_cnt[cur ^ 1];
-                if (tid == 0) *n_next = 0;
-                for (int t = wave; t < cnt; t += nw) {    // offers
-                    const int o = lc[t];
-                    const double x = ox[o], y = oy[o], z = oz[o];
-                    Top b = {-__builtin_inf(), -__builtin_inf(), NONE};
-                    for (int p = lane; p < n; p += 64) {   // (ascending per lane: a strict > keeps the smallest p of equal values)
-                        const double g = u[p] - rect_cost<SWAP>(px[p], py[p], pz[p], x, y, z, cinv);
-                        if (g > b.g1) { b.g2 = b.g1; b.g1 = g; b.p1 = p; }
-                        else if (g > b.g2) b.g2 = g;
-                    }
-                    b = wave_top(b);
-                    if (lane == 0) {
-                        const int p1 = b.p1 < n ? b.p1 : 0;   // (no finite value anywhere: as above)
-                        const double beta = b.g1;
-                        if (lam >= beta - e) { pr[o] = lam; offp[o] = -1; }   // done: nobody wants it above the floor
-                        else {
-                            const double d1 = beta - lam, d2 = (beta - b.g2) + e;   // (n == 1: g2 = -inf, d2 = inf)
-                            const double delta = d1 < d2 ? d1 : d2;
-                            offp[o] = p1; offd[o] = delta; offb[o] = beta;
-                            atomicMax(&offval[p1], (unsigned long long)__double_as_longlong(delta));
-                        }
-                    }
-                }
-                __syncthreads();
-                for (int t = tid; t < cnt; t += nt) {     // the smallest object among a person's largest offers
-                    const int o = lc[t], p = offp[o];
-                    if (p >= 0 && (unsigned long long)__double_as_longlong(offd[o]) == offval[p]) atomicMin(&offwin[p], o);
-                }
-                __syncthreads();
-                for (int t = tid; t < cnt; t += nt) {     // an offer that was not taken is made again next round
-                    const int o = lc[t], p = offp[o];
-                    if (p >= 0 && __hip_atomic_load(&offwin[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != o) { offp[o] = -1; ln[atomicAdd(n_next, 1)] = o; }
-                }
-                __syncthreads();
-                for (int t = tid; t < cnt; t += nt) {     // persons take their offers; what they owned is unowned at its price
-                    const int o = lc[t], p = offp[o];
-                    if (p >= 0) {
-                        const int prev = assigned[p];
-                        owner[prev] = -1;
-                        if (pr[prev] > lam) ln[atomicAdd(n_next, 1)] = prev;
-                        pr[o] = offb[o] - offd[o]; u[p] = u[p] - offd[o];
-                        owner[o] = p; assigned[p] = o;
-                        offval[p] = 0ull; offwin[p] = NONE;
-                    }
-                }
-                __syncthreads();
-                cur ^= 1;
-                cnt = s_cnt[cur];
-            }
-        }
+    bool capped;
+    for (;;) {
+        capped = !forward_rounds<SWAP>(sc, e) || (n < m && !reverse_rounds<SWAP>(sc, e));
         if (capped || last) break;
         next_e(e / 4.0, eps, e, last);
     }
 
-    const int *agent_goal = SWAP ? owner : assigned, *goal_agent = SWAP ? assigned : owner;
     for (int o = tid; o < m; o += nt)
-        if (price_out) price_out[s * m + o] = pr[o];
+        if (price_out) price_out[s * m + o] = sc.pr[o];
+    if (capped) { write_capped(N, M, s, perm, owner_out, pf, cost, rounds_out); return; }
+    const int *agent_goal = SWAP ? sc.owner : sc.assigned, *goal_agent = SWAP ? sc.assigned : sc.owner;
     for (int j = tid; j < M; j += nt)
-        if (owner_out) owner_out[s * M + j] = capped ? -1 : goal_agent[j];
-    if (capped) {                                     // (price: as the rounds left it)
-        for (int i = tid; i < N; i += nt) {
-            if (perm) perm[s * N + i] = -1;
-            if (pf) { pf[(s * N + i) * 3] = 0.0; pf[(s * N + i) * 3 + 1] = 0.0; pf[(s * N + i) * 3 + 2] = 0.0; }
-        }
-        if (tid == 0) { if (cost) cost[s] = __builtin_nan(""); if (rounds_out) rounds_out[s] = -1; }
-        return;
-    }
-    double *term = SWAP ? offd : bidv;                // per agent
-    const double *ax = SWAP ? ox : px, *ay = SWAP ? oy : py, *az = SWAP ? oz : pz, *gx = SWAP ? px : ox, *gy = SWAP ? py : oy, *gz = SWAP ? pz : oz;
+        if (owner_out) owner_out[s * M + j] = goal_agent[j];
+    double *term = SWAP ? sc.offd : sc.bidv;          // per agent.  SWAP: the agents are the m objects, and n < m, so offd has its m rows
+    const double *ax = SWAP ? sc.ox : sc.px, *ay = SWAP ? sc.oy : sc.py, *az = SWAP ? sc.oz : sc.pz;
+    const double *gx = SWAP ? sc.px : sc.ox, *gy = SWAP ? sc.py : sc.oy, *gz = SWAP ? sc.pz : sc.oz;
     for (int i = tid; i < N; i += nt) {
         const int j = agent_goal[i];
         if (perm) perm[s * N + i] = j;
@@ -453,10 +409,10 @@ __global__ __launch_bounds__(1024) void assign_rect_one_kernel(int N, int M, con
     __syncthreads();
     if (tid == 0) {
         double sum = 0.0;
-        for (int i = 0; i < N; ++i)
-            if (agent_goal[i] >= 0) sum = sum + term[i];   // in increasing i, one addition at a time
+        for (int i = 0; i < N; ++i)                   // in increasing i, one addition at a time (without SWAP every agent is a person and has a goal)
+            if (!SWAP || agent_goal[i] >= 0) sum = sum + term[i];
         if (cost) cost[s] = sum;
-        if (rounds_out) rounds_out[s] = rounds;
+        if (rounds_out) rounds_out[s] = sc.rounds;
     }
 }
 
@@ -575,7 +531,11 @@ __global__ __launch_bounds__(1024) void assign_settle_kernel(int N, const double
             phase_reset(N, s, w, cur);
             next_cnt = N;
         }
-        if (capped) write_capped(N, s, price, perm, pf, price_out, cost, rounds_out);
+        if (capped) {
+            for (int i = tid; i < N; i += blockDim.x)
+                if (price_out) price_out[s * N + i] = price[i];
+            write_capped(N, N, s, perm, nullptr, pf, cost, rounds_out);
+        }
         if (tid == 0) {
             State &o = w.state[s];
             o.e = e; o.last = last; o.cur = cur; o.cnt = next_cnt; o.rounds = rounds;
@@ -614,33 +574,47 @@ __global__ __launch_bounds__(1024) void assign_settle_kernel(int N, const double
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------------------------------
-static int assign_check(dmpc_ctx *ctx, const char *who, int S, int N, const void *po, const void *goals, double eps)
+// rect: the dmpc_assign_rect entries (M goals of their own; the one launch only).  The square entries pass M = N.
+static int assign_check(dmpc_ctx *ctx, const char *who, int S, int N, int M, const void *po, const void *goals, double eps, bool rect)
 {
     if (!ctx) { g_err = std::string(who) + ": ctx is NULL"; return -1; }
-    if (S < 1 || N < 1) FAIL(ctx, std::string(who) + ": S and N must be at least 1");
+    if (S < 1 || N < 1 || M < 1) FAIL(ctx, std::string(who) + (rect ? ": S, N and M must be at least 1" : ": S and N must be at least 1"));
     if (!po || !goals) FAIL(ctx, std::string(who) + ": po and goals must be given");
     if (!(eps > 0) || !std::isfinite(eps)) FAIL(ctx, std::string(who) + ": eps must be a finite positive number");
+    if (rect && std::max(N, M) > asg::ONE_MAX)
+        FAIL(ctx, std::string(who) + ": N = " + std::to_string(N) + " agents and M = " + std::to_string(M) + " goals: max(N, M) must not exceed " +
+                      std::to_string(asg::ONE_MAX) + " (DMPC_ASSIGN_ONE_LAUNCH_MAX; larger square scenes: dmpc_assign_goals)");
     return 0;
 }
 
-// the auction on device arrays, enqueued on st.  Scenes above the one-launch boundary: the host waits for the done flags of each window of
-// rounds while the next window is already enqueued, so the call returns with at most the last window's (idle) launches still in flight.
-static int assign_run(dmpc_ctx *ctx, int S, int N, const double *po, const double *goals, double eps, int max_rounds, int32_t *perm, double *pf,
-                      double *price, double *cost, int32_t *rounds, hipStream_t st)
+// agents are the persons when N <= M, goals otherwise (SWAP)
+template <bool SWAP>
+static int assign_one_launch(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int cap, int32_t *perm,
+                             int32_t *owner, double *pf, double *price, double *cost, int32_t *rounds, hipStream_t st)
 {
-    const double cinv = 1.0 / ctx->prm.c;
-    const int cap = max_rounds <= 0 ? asg::DEFAULT_ROUNDS : max_rounds;
-    if (N <= asg::ONE_MAX) {
-        const int lds = (int)(asg::ONE_LDS_PER_AGENT * (size_t)N);
-        if (lds > ctx->max_lds_assign) {
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)asg::assign_one_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            ctx->max_lds_assign = lds;
-        }
-        hipLaunchKernelGGL(asg::assign_one_kernel, dim3((unsigned)S), dim3(N <= 256 ? 256 : 1024), (size_t)lds, st, N, po, goals, cinv, eps, cap,
-                           perm, pf, price, cost, rounds);
-        HIPCHK(ctx, hipGetLastError());
-        return 0;
+    const int n = std::min(N, M), m = std::max(N, M);
+    const int lds = (int)asg::OneLds(n, m).bytes;
+    if (lds > ctx->max_lds_assign[SWAP]) {
+        HIPCHK(ctx, hipFuncSetAttribute((const void *)asg::assign_one_kernel<SWAP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        ctx->max_lds_assign[SWAP] = lds;
     }
+    hipLaunchKernelGGL(asg::assign_one_kernel<SWAP>, dim3((unsigned)S), dim3(m <= 256 ? 256 : 1024), (size_t)lds, st, N, M, po, goals,
+                       1.0 / ctx->prm.c, eps, cap, perm, owner, pf, price, cost, rounds);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+// the auction on device arrays, enqueued on st (owner: dmpc_assign_rect's output, null otherwise).  Scenes above the one-launch boundary --
+// square, assign_check has refused the others --: the host waits for the done flags of each window of rounds while the next window is
+// already enqueued, so the call returns with at most the last window's (idle) launches still in flight.
+static int assign_run(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int max_rounds, int32_t *perm,
+                      int32_t *owner, double *pf, double *price, double *cost, int32_t *rounds, hipStream_t st)
+{
+    const int cap = max_rounds <= 0 ? asg::DEFAULT_ROUNDS : max_rounds;
+    if (std::max(N, M) <= asg::ONE_MAX)
+        return N <= M ? assign_one_launch<false>(ctx, S, N, M, po, goals, eps, cap, perm, owner, pf, price, cost, rounds, st)
+                      : assign_one_launch<true>(ctx, S, N, M, po, goals, eps, cap, perm, owner, pf, price, cost, rounds, st);
+    const double cinv = 1.0 / ctx->prm.c;
     const size_t SN = (size_t)S * N;
     // price, bidv, bidval [SN] x 8 | owner, assigned, bidwin, bidj [SN] x 4, list [2 SN] x 4 | state [S] | done [S]
     const size_t bytes = SN * 48 + (size_t)S * sizeof(asg::State) + (size_t)S * 4;
@@ -689,110 +663,64 @@ static int assign_run(dmpc_ctx *ctx, int S, int N, const double *po, const doubl
     return 0;
 }
 
+// the host-pointer entries: po and goals staged into asg_io, the auction, the requested outputs copied back (owner: dmpc_assign_rect's, null
+// otherwise), one synchronise
+static int assign_staged(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int max_rounds, int32_t *perm,
+                         int32_t *owner, double *pf, double *price, double *cost, int32_t *rounds)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t SN = (size_t)S * N, SM = (size_t)S * M, SX = (size_t)S * std::max(N, M);
+    const size_t b_po = SN * 3 * sizeof(double), b_goals = SM * 3 * sizeof(double), b_pf = b_po, b_price = SX * sizeof(double),
+                 b_cost = S * sizeof(double), b_perm = SN * sizeof(int32_t), b_owner = owner ? SM * sizeof(int32_t) : 0, b_rounds = S * sizeof(int32_t);
+    if (ctx->asg_io.ensure(b_po + b_goals + b_pf + b_price + b_cost + b_perm + b_owner + b_rounds)) FAIL(ctx, "device allocation failed");
+    char *at = (char *)ctx->asg_io.p;                 // the 8-byte arrays ahead of the 4-byte ones
+    auto take = [&at](size_t bytes) { char *p = at; at += bytes; return p; };
+    double *d_po = (double *)take(b_po), *d_g = (double *)take(b_goals), *d_pf = (double *)take(b_pf), *d_price = (double *)take(b_price),
+           *d_cost = (double *)take(b_cost);
+    int32_t *d_perm = (int32_t *)take(b_perm), *d_owner = (int32_t *)take(b_owner), *d_rounds = (int32_t *)take(b_rounds);
+    HIPCHK(ctx, hipMemcpyAsync(d_po, po, b_po, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(d_g, goals, b_goals, hipMemcpyHostToDevice, st));
+    if (assign_run(ctx, S, N, M, d_po, d_g, eps, max_rounds, perm ? d_perm : nullptr, owner ? d_owner : nullptr, pf ? d_pf : nullptr,
+                   price ? d_price : nullptr, cost ? d_cost : nullptr, rounds ? d_rounds : nullptr, st))
+        return -1;
+    if (perm) HIPCHK(ctx, hipMemcpyAsync(perm, d_perm, b_perm, hipMemcpyDeviceToHost, st));
+    if (owner) HIPCHK(ctx, hipMemcpyAsync(owner, d_owner, b_owner, hipMemcpyDeviceToHost, st));
+    if (pf) HIPCHK(ctx, hipMemcpyAsync(pf, d_pf, b_pf, hipMemcpyDeviceToHost, st));
+    if (price) HIPCHK(ctx, hipMemcpyAsync(price, d_price, b_price, hipMemcpyDeviceToHost, st));
+    if (cost) HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, b_cost, hipMemcpyDeviceToHost, st));
+    if (rounds) HIPCHK(ctx, hipMemcpyAsync(rounds, d_rounds, b_rounds, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" int dmpc_assign_goals_device(dmpc_ctx *ctx, int S, int N, const double *po, const double *goals, double eps, int max_rounds,
                                         int32_t *perm, double *pf_assigned, double *price, double *cost, int32_t *rounds, void *stream)
 {
-    if (assign_check(ctx, "dmpc_assign_goals_device", S, N, po, goals, eps)) return -1;
+    if (assign_check(ctx, "dmpc_assign_goals_device", S, N, N, po, goals, eps, false)) return -1;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return assign_run(ctx, S, N, po, goals, eps, max_rounds, perm, pf_assigned, price, cost, rounds, (hipStream_t)stream);
+    return assign_run(ctx, S, N, N, po, goals, eps, max_rounds, perm, nullptr, pf_assigned, price, cost, rounds, (hipStream_t)stream);
 }
 
 extern "C" int dmpc_assign_goals(dmpc_ctx *ctx, int S, int N, const double *po, const double *goals, double eps, int max_rounds, int32_t *perm,
                                  double *pf_assigned, double *price, double *cost, int32_t *rounds)
 {
-    if (assign_check(ctx, "dmpc_assign_goals", S, N, po, goals, eps)) return -1;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t SN = (size_t)S * N;
-    // po, goals, pf [SN][3] | price [SN] | cost [S] | perm [SN] | rounds [S]
-    if (ctx->asg_io.ensure(SN * 84 + (size_t)S * 12)) FAIL(ctx, "device allocation failed");
-    double *d_po = ctx->asg_io.as<double>(), *d_g = d_po + 3 * SN, *d_pf = d_g + 3 * SN, *d_price = d_pf + 3 * SN, *d_cost = d_price + SN;
-    int32_t *d_perm = (int32_t *)(d_cost + S), *d_rounds = d_perm + SN;
-    HIPCHK(ctx, hipMemcpyAsync(d_po, po, SN * 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(d_g, goals, SN * 24, hipMemcpyHostToDevice, st));
-    if (assign_run(ctx, S, N, d_po, d_g, eps, max_rounds, perm ? d_perm : nullptr, pf_assigned ? d_pf : nullptr, price ? d_price : nullptr,
-                   cost ? d_cost : nullptr, rounds ? d_rounds : nullptr, st))
-        return -1;
-    if (perm) HIPCHK(ctx, hipMemcpyAsync(perm, d_perm, SN * 4, hipMemcpyDeviceToHost, st));
-    if (pf_assigned) HIPCHK(ctx, hipMemcpyAsync(pf_assigned, d_pf, SN * 24, hipMemcpyDeviceToHost, st));
-    if (price) HIPCHK(ctx, hipMemcpyAsync(price, d_price, SN * 8, hipMemcpyDeviceToHost, st));
-    if (cost) HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-    if (rounds) HIPCHK(ctx, hipMemcpyAsync(rounds, d_rounds, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------------
-// dmpc_assign_rect: N agents, M goals
-// ---------------------------------------------------------------------------------------------------------------------------------------
-static int assign_rect_check(dmpc_ctx *ctx, const char *who, int S, int N, int M, const void *po, const void *goals, double eps)
-{
-    if (!ctx) { g_err = std::string(who) + ": ctx is NULL"; return -1; }
-    if (S < 1 || N < 1 || M < 1) FAIL(ctx, std::string(who) + ": S, N and M must be at least 1");
-    if (!po || !goals) FAIL(ctx, std::string(who) + ": po and goals must be given");
-    if (!(eps > 0) || !std::isfinite(eps)) FAIL(ctx, std::string(who) + ": eps must be a finite positive number");
-    if (std::max(N, M) > asg::ONE_MAX)
-        FAIL(ctx, std::string(who) + ": N = " + std::to_string(N) + " agents and M = " + std::to_string(M) + " goals: max(N, M) must not exceed " +
-                      std::to_string(asg::ONE_MAX) + " (DMPC_ASSIGN_ONE_LAUNCH_MAX; larger square scenes: dmpc_assign_goals)");
-    return 0;
-}
-
-template <bool SWAP>
-static int assign_rect_launch(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int cap, int32_t *perm,
-                              int32_t *owner, double *pf, double *price, double *cost, int32_t *rounds, hipStream_t st)
-{
-    const int n = std::min(N, M), m = std::max(N, M);
-    const int lds = (int)(asg::RECT_LDS_PER_OBJECT * (size_t)m + asg::RECT_LDS_PER_PERSON * (size_t)n);
-    if (lds > ctx->max_lds_assign_rect[SWAP]) {
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)asg::assign_rect_one_kernel<SWAP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        ctx->max_lds_assign_rect[SWAP] = lds;
-    }
-    hipLaunchKernelGGL(asg::assign_rect_one_kernel<SWAP>, dim3((unsigned)S), dim3(m <= 256 ? 256 : 1024), (size_t)lds, st, N, M, po, goals,
-                       1.0 / ctx->prm.c, eps, cap, perm, owner, pf, price, cost, rounds);
-    HIPCHK(ctx, hipGetLastError());
-    return 0;
-}
-
-// the auction on device arrays, enqueued on st: agents are the persons when N <= M, goals otherwise
-static int assign_rect_run(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int max_rounds, int32_t *perm,
-                           int32_t *owner, double *pf, double *price, double *cost, int32_t *rounds, hipStream_t st)
-{
-    const int cap = max_rounds <= 0 ? asg::DEFAULT_ROUNDS : max_rounds;
-    return N <= M ? assign_rect_launch<false>(ctx, S, N, M, po, goals, eps, cap, perm, owner, pf, price, cost, rounds, st)
-                  : assign_rect_launch<true>(ctx, S, N, M, po, goals, eps, cap, perm, owner, pf, price, cost, rounds, st);
+    if (assign_check(ctx, "dmpc_assign_goals", S, N, N, po, goals, eps, false)) return -1;
+    return assign_staged(ctx, S, N, N, po, goals, eps, max_rounds, perm, nullptr, pf_assigned, price, cost, rounds);
 }
 
 extern "C" int dmpc_assign_rect_device(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int max_rounds,
                                        int32_t *perm, int32_t *owner, double *pf_assigned, double *price, double *cost, int32_t *rounds,
                                        void *stream)
 {
-    if (assign_rect_check(ctx, "dmpc_assign_rect_device", S, N, M, po, goals, eps)) return -1;
+    if (assign_check(ctx, "dmpc_assign_rect_device", S, N, M, po, goals, eps, true)) return -1;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return assign_rect_run(ctx, S, N, M, po, goals, eps, max_rounds, perm, owner, pf_assigned, price, cost, rounds, (hipStream_t)stream);
+    return assign_run(ctx, S, N, M, po, goals, eps, max_rounds, perm, owner, pf_assigned, price, cost, rounds, (hipStream_t)stream);
 }
 
 extern "C" int dmpc_assign_rect(dmpc_ctx *ctx, int S, int N, int M, const double *po, const double *goals, double eps, int max_rounds,
                                 int32_t *perm, int32_t *owner, double *pf_assigned, double *price, double *cost, int32_t *rounds)
 {
-    if (assign_rect_check(ctx, "dmpc_assign_rect", S, N, M, po, goals, eps)) return -1;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t SN = (size_t)S * N, SM = (size_t)S * M, SX = (size_t)S * std::max(N, M);
-    // po, pf [SN][3] | goals [SM][3] | price [SX] | cost [S] | perm [SN] | owner [SM] | rounds [S]
-    if (ctx->asg_io.ensure(SN * 52 + SM * 28 + SX * 8 + (size_t)S * 12)) FAIL(ctx, "device allocation failed");
-    double *d_po = ctx->asg_io.as<double>(), *d_pf = d_po + 3 * SN, *d_g = d_pf + 3 * SN, *d_price = d_g + 3 * SM, *d_cost = d_price + SX;
-    int32_t *d_perm = (int32_t *)(d_cost + S), *d_owner = d_perm + SN, *d_rounds = d_owner + SM;
-    HIPCHK(ctx, hipMemcpyAsync(d_po, po, SN * 24, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(d_g, goals, SM * 24, hipMemcpyHostToDevice, st));
-    if (assign_rect_run(ctx, S, N, M, d_po, d_g, eps, max_rounds, perm ? d_perm : nullptr, owner ? d_owner : nullptr, pf_assigned ? d_pf : nullptr,
-                        price ? d_price : nullptr, cost ? d_cost : nullptr, rounds ? d_rounds : nullptr, st))
-        return -1;
-    if (perm) HIPCHK(ctx, hipMemcpyAsync(perm, d_perm, SN * 4, hipMemcpyDeviceToHost, st));
-    if (owner) HIPCHK(ctx, hipMemcpyAsync(owner, d_owner, SM * 4, hipMemcpyDeviceToHost, st));
-    if (pf_assigned) HIPCHK(ctx, hipMemcpyAsync(pf_assigned, d_pf, SN * 24, hipMemcpyDeviceToHost, st));
-    if (price) HIPCHK(ctx, hipMemcpyAsync(price, d_price, SX * 8, hipMemcpyDeviceToHost, st));
-    if (cost) HIPCHK(ctx, hipMemcpyAsync(cost, d_cost, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-    if (rounds) HIPCHK(ctx, hipMemcpyAsync(rounds, d_rounds, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return 0;
+    if (assign_check(ctx, "dmpc_assign_rect", S, N, M, po, goals, eps, true)) return -1;
+    return assign_staged(ctx, S, N, M, po, goals, eps, max_rounds, perm, owner, pf_assigned, price, cost, rounds);
 }

@@ -14,8 +14,10 @@ pytestmark = pytest.mark.gpu
 
 PMIN, PMAX, RMIN = (-2.5, -2.5, 0.2), (2.5, 2.5, 2.2), 0.35
 ONE_MAX = int(re.search(r"#define\s+DMPC_ASSIGN_ONE_LAUNCH_MAX\s+(\d+)", open(ROOT + "/include/dmpc_hip_dev.h").read()).group(1))
-# one person; one object; one more object than persons; both orientations; a wave boundary on each side; the LDS cap
-SHAPES = [(1, 1), (1, 4), (4, 1), (2, 3), (3, 2), (63, 64), (64, 65), (65, 64), (60, 100), (100, 60), (1, 1024), (1024, 1), (900, 1024)]
+# one person; one object; one more object than persons; both orientations; a wave boundary on each side; the 256 -> 1024-thread switch with the
+# reverse columns in LDS; the LDS cap; one short of square at the cap: the largest launch there is (76 * 1024 + 60 * 1023 = 139 204 B)
+SHAPES = [(1, 1), (1, 4), (4, 1), (2, 3), (3, 2), (63, 64), (64, 65), (65, 64), (60, 100), (100, 60), (256, 257), (257, 256), (1, 1024), (1024, 1),
+          (900, 1024), (1023, 1024), (1024, 1023)]
 
 
 @pytest.fixture(scope="module")
@@ -66,6 +68,59 @@ def test_square_scenes_equal_dmpc_assign_goals_bit_for_bit(d, N):
         inv = np.empty(N, dtype=np.int32)
         inv[sq["perm"][s]] = np.arange(N)
         assert np.array_equal(re_["owner"][s], inv)
+
+
+def _square_batch(N, seeds):
+    sc = [asg.lattice(N, s) for s in seeds]
+    return np.stack([x[0] for x in sc]), np.stack([x[1] for x in sc])
+
+
+@pytest.mark.parametrize("N", [1, 64, 257, ONE_MAX])
+def test_square_scenes_equal_the_square_restatement_bit_for_bit(d, N):
+    """N == M leaves the reverse-only columns out of LDS; against tests/assign.py, which knows no reverse round: one agent, a full wave, the
+    256 -> 1024-thread switch, the cap"""
+    po, g = _square_batch(N, range(2))
+    out = d.assign_rect(po, g, eps=asg.lattice_eps(N))
+    for s in range(2):
+        ref = asg.lattice_result(N, s)
+        assert ref["rounds"] > 0
+        assert asg.same(out, ref, s) is None, (N, s, asg.same(out, ref, s), int(out["rounds"][s]), ref["rounds"])
+        inv = np.empty(N, dtype=np.int32)
+        inv[ref["perm"]] = np.arange(N)
+        assert np.array_equal(out["owner"][s], inv)
+
+
+def test_the_lds_limit_is_raised_whatever_the_order_of_the_calls():
+    """both entries share one limit per instantiation of the kernel: on a fresh context every launch is larger or smaller than what was set before"""
+    import multiagent_planning_amd as mp
+    ctx = mp.Dmpc("bound", c=asg.C_LATTICE)
+    try:
+        for N, M in ((900, 1024), (3, None), (ONE_MAX, None), (100, 60), (1024, 1023), (300, None)):
+            if M is None:
+                po, g = asg.lattice(N)
+                assert asg.same(ctx.assign(po[None], g[None], eps=asg.lattice_eps(N)), asg.lattice_result(N), 0) is None, N
+            else:
+                po, g = ar.lattice_batch(N, M, [0])
+                assert ar.same(ctx.assign_rect(po, g, eps=ar.lattice_eps(N, M)), ar.lattice_result(N, M), 0) is None, (N, M)
+    finally:
+        ctx.close()
+
+
+def test_round_cap_on_a_square_scene_is_the_same_through_both_entries(d):
+    """a cap of exactly the rounds the first scene needs, next to a scene that needs many more"""
+    N = 64
+    ex, lat, eps = asg.exchange(N), asg.lattice(N), asg.lattice_eps(N)
+    cap = asg.auction(ex[0], ex[1], asg.C_LATTICE, eps)["rounds"]
+    assert 0 < cap < 16 and asg.lattice_result(N)["rounds"] > cap
+    po, g = np.stack([ex[0], lat[0]]), np.stack([ex[1], lat[1]])
+    sq, re_ = d.assign(po, g, eps=eps, max_rounds=cap), d.assign_rect(po, g, eps=eps, max_rounds=cap)
+    for k in sq:
+        assert re_[k].tobytes() == sq[k].tobytes(), k
+    for out in (sq, re_):
+        assert out["rounds"][0] == cap and sorted(out["perm"][0].tolist()) == list(range(N))
+        assert out["rounds"][1] == -1 and (out["perm"][1] == -1).all() and np.isnan(out["cost"][1]) and not out["pf"][1].any()
+        assert out["price"][1].tobytes() == asg.auction(lat[0], lat[1], asg.C_LATTICE, eps, max_rounds=cap)["price"].tobytes()
+    assert (re_["owner"][1] == -1).all() and sorted(re_["owner"][0].tolist()) == list(range(N))
 
 
 @pytest.mark.parametrize("N,M", [(60, 100), (100, 60)])
