@@ -808,6 +808,52 @@ DMPC_API int dmpc_replan_routes_device(dmpc_ctx *ctx, int S, int N_cmd, int M, i
                               int32_t *wp_col, double *pf, int32_t *plan_status, int32_t *replan_count, int32_t *replan_col,
                               const int32_t *scene_done, void *stream);
 
+/* Disturbed transitions (additive, the ABI revision stays 8): WIND, NOISE AND PUSHES ON THE STATE, IN THE LOOP.  NO REFERENCE COUNTERPART: in
+ * every closed loop of this header the state of column k is, bit for bit, entry 0 of the plan solved on column k-1 -- the vehicle is never
+ * anywhere but where the model put it.  A disturbance is a SETTING OF THE CONTEXT: while one is set, dmpc_transition, _cmd, _scripted, _mission,
+ * _hold, _route and _replan add it to the state of every commanded agent between the state advance and the history record of every column
+ * k >= 1; with none set every entry launches what it launched before and returns the same bytes.  tests/disturb.py restates the rule; the
+ * device, dmpc_disturbance_sample on the host and that restatement agree bit for bit.
+ *   the rule  for scene s (its index IN THE CALL, also when the batch is split over contexts), commanded agent i, column k >= 1, component
+ *             c = 0, 1, 2, in fp64, every operation rounded on its own (no fused multiply-add); uniform(seed, sid, ctr) is the counter-based
+ *             stream of dmpc_random_test (53 bits in [0, 1)), h the context's step:
+ *               sid  = (uint64) s << 32 | i
+ *               u_j  = 2.0 * uniform(seed, sid, 6 * k + j) - 1.0                      j = 0 .. 5
+ *               w    = wind[s] (wind_scenes == 1: wind[0]; no wind: 0)
+ *               dp_c = ((0.5 * h) * h) * w_c;  if amp_p > 0: dp_c = dp_c + amp_p * u_c;
+ *                      then, in list order, every push with (scene, agent, column) == (s, i, k): dp_c = dp_c + push.dp[c]
+ *               dv_c = h * w_c;                if amp_v > 0: dv_c = dv_c + amp_v * u_(3+c);   then the same pushes' dv[c]
+ *               x_p_c = x_p_c + dp_c;   x_v_c = x_v_c + dv_c
+ *             Column 0 is never disturbed; x_a never is.  Nothing depends on launch geometry or on the batch split.
+ *   the place in column k >= 1: solve; hold rule; state advance; DISTURBANCE; history record; verdict; mission / route / re-plan rule.  So the
+ *             histories hold the disturbed state, ReachedGoal and the waypoint rule are evaluated on it, and the next solve starts from it.  THE
+ *             PREDICTION TABLE IS NOT TOUCHED: a neighbour's view of the agent is stale for one column.  Every commanded agent of a scene that
+ *             was running when the column began is disturbed, whether its solve succeeded, was held or failed (a failed agent's state is the
+ *             previous column's, plus the disturbance); scenes that are over are skipped.
+ *   dmpc_set_disturbance copies everything (the pushes sorted by scene, agent and column, list order kept among equal keys); d == NULL, or a
+ *             descriptor that is all zero, clears.  A push on a column at or behind K_T_max is legal and never applied.
+ *   dmpc_disturbance_sample: dp, dv [S][N_cmd][3] of column k by the rule, on the host -- no context, no GPU; k == 0 gives zeros.
+ *   dmpc_disturb_device: the disturbance of column k on device arrays x_p, x_v [S][N_cmd][3], enqueued on the caller's stream, for callers that
+ *             loop over dmpc_step_device_cmd themselves (behind dmpc_advance_device); scene_done [S] or NULL: scenes with a non-zero word are
+ *             skipped.  With no disturbance set it returns 0 and launches nothing.
+ * Batch split as dmpc_transition.  A DMPC_DEVICE_ALL context with a disturbance set runs the call unsharded on its first GPU;
+ * dmpc_transition_sharded[_gather] refuse while one is set; there is no RCCL form.  Not modelled: a "measured" state apart from the true one,
+ * re-anchoring of the agent's table column, disturbed uncommanded or scripted vehicles.
+ * Refused (-1, nothing launched, a message that starts with the entry's name) by dmpc_set_disturbance and dmpc_disturbance_sample: a negative or
+ * non-finite amp_p or amp_v, a non-finite wind or push value, n_push < 0, wind_scenes < 0, a NULL array with a positive count, a push with
+ * scene < 0, agent < 0 or column < 1.  By a transition entry, dmpc_disturbance_sample and dmpc_disturb_device: wind_scenes neither 0, 1 nor S, a
+ * push with scene >= S or agent >= N_cmd.  dmpc_disturb_device also: k < 1, a NULL x_p or x_v, a DMPC_DEVICE_ALL context. */
+typedef struct dmpc_push { int32_t scene, agent, column; double dp[3], dv[3]; } dmpc_push;
+typedef struct dmpc_disturbance {
+    uint64_t seed;
+    double amp_p, amp_v;                   /* half-widths of the uniform noise on position (m) and velocity (m/s); >= 0, finite */
+    const double *wind; int wind_scenes;   /* acceleration [wind_scenes][3] (m/s^2) or NULL / 0; 1: the same for every scene, else == S of the call */
+    const dmpc_push *push; int n_push;     /* listed impulses or NULL / 0 */
+} dmpc_disturbance;
+DMPC_API int dmpc_set_disturbance(dmpc_ctx *ctx, const dmpc_disturbance *d);
+DMPC_API int dmpc_disturbance_sample(const dmpc_disturbance *d, double h, int S, int N_cmd, int k, double *dp, double *dv);
+DMPC_API int dmpc_disturb_device(dmpc_ctx *ctx, int S, int N_cmd, int k, double *x_p, double *x_v, const int32_t *scene_done, void *stream);
+
 /* Standalone forms of the path's small helpers (fused into the step kernels inside the solvers), for callers that
  * invoke them on their own as the reference's scripts do.  Host pointers, synchronous.
  *   dmpc_prop_state   propStatedmpc.m:1-8 (A_initp given): p = A_p a + A_initp [po;vo], v = A_v a + 1 (x) vo  -> pass

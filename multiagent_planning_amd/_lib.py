@@ -4,6 +4,7 @@ The shared library is built in-tree (multiagent_planning_amd/libdmpc_hip.so) by
 `__graft_entry__.build()` / `make -C multiagent_planning_amd/csrc`.  There is no fallback of any
 kind: if the library is missing, or no HIP device is present, the calls raise.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -46,6 +47,7 @@ ABI_SYMBOLS = [
     "dmpc_transition_route",
     "dmpc_plan_routes", "dmpc_plan_routes_device",
     "dmpc_transition_replan", "dmpc_replan_routes_device",
+    "dmpc_set_disturbance", "dmpc_disturbance_sample", "dmpc_disturb_device",
 ]
 
 
@@ -58,6 +60,15 @@ class DmpcParams(C.Structure):
         ("Qfar", C.c_double), ("Qnear", C.c_double), ("Sfree", C.c_double),
         ("tol", C.c_double),
     ]
+
+
+class DmpcPush(C.Structure):
+    _fields_ = [("scene", C.c_int32), ("agent", C.c_int32), ("column", C.c_int32), ("dp", C.c_double * 3), ("dv", C.c_double * 3)]
+
+
+class DmpcDisturbance(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("amp_p", C.c_double), ("amp_v", C.c_double), ("wind", C.POINTER(C.c_double)), ("wind_scenes", C.c_int),
+                ("push", C.POINTER(DmpcPush)), ("n_push", C.c_int)]
 
 
 class DmpcError(RuntimeError):
@@ -166,6 +177,11 @@ def load():
                                          C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, dp, ip, ip, dp, ip, ip, ip, ip, ip, ip, ip, ip, ip]
     L.dmpc_replan_routes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp,
                                             vp, vp, vp, vp, vp]
+    # disturbed transitions: wind, noise and pushes on the state, in the loop (additive, still revision 8)
+    if hasattr(L, "dmpc_set_disturbance"):   # (absent from the older builds tools/with_lib.py may load)
+        L.dmpc_set_disturbance.argtypes = [vp, C.POINTER(DmpcDisturbance)]
+        L.dmpc_disturbance_sample.argtypes = [C.POINTER(DmpcDisturbance), C.c_double, C.c_int, C.c_int, C.c_int, dp, dp]
+        L.dmpc_disturb_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -249,6 +265,44 @@ def _path(path, lead_cmd, what):
     if M < 1 or P < 1:
         raise DmpcError(f"{what}: path {tuple(path.shape)} needs at least one vehicle and one sample")
     return path, int(M), int(P)
+
+
+def _disturbance(noise_p=0.0, noise_v=0.0, wind=None, pushes=None, seed=0):
+    """The dmpc_disturbance descriptor of set_disturbance()'s arguments -> (descriptor, the arrays it points into).  wind [3] or [S,3]; pushes
+    [n,9], rows of scene, agent, column, dp (3), dv (3).  Shapes are checked here, values by the library."""
+    d, keep = DmpcDisturbance(), []
+    d.seed, d.amp_p, d.amp_v = int(seed), float(noise_p), float(noise_v)
+    if wind is not None:
+        wind = _f(wind)
+        if wind.ndim not in (1, 2) or wind.shape[-1] != 3:
+            raise DmpcError(f"disturbance: wind {tuple(wind.shape)} must be [3] or [S,3]")
+        d.wind, d.wind_scenes = _dp(wind), wind.size // 3
+        keep.append(wind)
+    if pushes is not None and np.size(pushes):
+        pushes = _f(pushes)
+        if pushes.ndim != 2 or pushes.shape[1] != 9:
+            raise DmpcError(f"disturbance: pushes {tuple(pushes.shape)} must be [n,9]: scene, agent, column, dp (3), dv (3)")
+        if not np.array_equal(pushes[:, :3], np.trunc(pushes[:, :3])) or np.abs(pushes[:, :3]).max() > 0x7fffffff:
+            raise DmpcError("disturbance: scene, agent and column of a push must be integers")
+        arr = (DmpcPush * len(pushes))()
+        for q, row in zip(arr, pushes):
+            q.scene, q.agent, q.column = int(row[0]), int(row[1]), int(row[2])
+            q.dp[:], q.dv[:] = row[3:6], row[6:9]
+        d.push, d.n_push = arr, len(pushes)
+        keep.append(arr)
+    return d, keep
+
+
+def disturbance_sample(h, S, n_cmd, k, **kw):
+    """dmpc_disturbance_sample (host, no context, no GPU): (dp, dv), [S,n_cmd,3] each, of column k by the rule include/dmpc_hip.h pins, for
+    Dmpc.set_disturbance()'s arguments and the step h"""
+    L = load()
+    d, keep = _disturbance(**kw)
+    dp, dv = np.zeros((int(S), int(n_cmd), 3)), np.zeros((int(S), int(n_cmd), 3))
+    if L.dmpc_disturbance_sample(C.byref(d), float(h), int(S), int(n_cmd), int(k), _dp(dp), _dp(dv)):
+        raise DmpcError(L.dmpc_last_error(None).decode())
+    del keep
+    return dp, dv
 
 
 def model_matrices(h, K=K_HOR):
@@ -359,6 +413,36 @@ class Dmpc:
         base.update(kw)
         self.prm = make_params(self.prm.variant if variant is None else variant, **base)
         self._chk(self._L.dmpc_set_params(self._ctx, C.byref(self.prm)))
+
+    # ---- disturbed transitions -----------------------------------------------------------------
+    def set_disturbance(self, noise_p=0.0, noise_v=0.0, wind=None, pushes=None, seed=0):
+        """dmpc_set_disturbance: from now on transition(), mission(), route() and replan() add wind, noise and pushes to the state of every
+        commanded agent between the state advance and the history record of every column k >= 1 (the rule include/dmpc_hip.h pins).  noise_p
+        (metres), noise_v (m/s): half-widths of the uniform noise drawn from stream `seed`; wind [3] (every scene) or [S,3]: a constant
+        acceleration (m/s^2); pushes [n,9]: rows of scene, agent, column, dp (3), dv (3).  Everything zero / None clears."""
+        d, keep = _disturbance(noise_p, noise_v, wind, pushes, seed)
+        self._chk(self._L.dmpc_set_disturbance(self._ctx, C.byref(d)))
+        del keep   # (the library has copied everything)
+        return self
+
+    def clear_disturbance(self):
+        self._chk(self._L.dmpc_set_disturbance(self._ctx, None))
+        return self
+
+    def disturbance_sample(self, S, n_cmd, k, **kw):
+        """disturbance_sample() of this module with the context's h"""
+        return disturbance_sample(float(self.prm.h), S, n_cmd, k, **kw)
+
+    @contextlib.contextmanager
+    def _disturbed(self, disturb):
+        """disturb= of the transition methods: set before the call, cleared after it, also on an error"""
+        if not isinstance(disturb, dict):
+            raise DmpcError(f"disturb is None or a dict of set_disturbance()'s arguments, not {disturb!r}")
+        self.set_disturbance(**disturb)
+        try:
+            yield
+        finally:
+            self.clear_disturbance()
 
     # ---- host-array entry points -------------------------------------------------------------
     def init_batch(self, po, pf):
@@ -473,8 +557,9 @@ class Dmpc:
             raise DmpcError(f"{what}: the goal assignment met its round cap")
         return a
 
-    def transition(self, po, pf, K_T_max, error_tol=0.01, histories=True, path=None, on_fail="stop", max_hold=14, assign=False):
-        """histories=False: pk/vk/ak are not downloaded (they stay on the device for postcheck()).
+    def transition(self, po, pf, K_T_max, error_tol=0.01, histories=True, path=None, on_fail="stop", max_hold=14, assign=False, disturb=None):
+        """disturb: a dict of set_disturbance()'s arguments, in force for this call alone (with assign too); None: the context's standing setting.
+        histories=False: pk/vk/ak are not downloaded (they stay on the device for postcheck()).
         assign=True: the goals are a formation, not a labelling: the commanded agents are assigned to them first (assign(), default eps), agent i
         flies to pf[perm[i]], and the dict also has perm.
         assign="rect": ALL N agents of po are commanded and pf holds any M >= 1 points [S,M,3]: assign_rect() (default eps) chooses who flies
@@ -486,6 +571,9 @@ class Dmpc:
         behind the first N_cmd are not commanded and stay at po as static obstacles; histories, K_T_used and scene_status cover the commanded ones.
         path [S,M,P,3] (or [M,P,3]; dmpc_transition_scripted): M scripted vehicles behind the commanded agents of po / pf (same agent count in
         both), sample t of a path = the vehicle's position at history column t, held at its last sample once the path has ended."""
+        if disturb is not None:
+            with self._disturbed(disturb):
+                return self.transition(po, pf, K_T_max, error_tol, histories, path, on_fail, max_hold, assign)
         po, pf = _f(po), _f(pf)
         if isinstance(assign, str) or assign not in (True, False):
             if assign != "rect":
@@ -548,8 +636,10 @@ class Dmpc:
                                                   _ip(used), _ip(sst)))
         return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst)
 
-    def mission(self, po, goals, K_T_max, error_tol=0.01, histories=True, deadline=None, path=None, on_fail="stop", max_hold=14, assign=False):
-        """dmpc_transition_mission: one transition through the Q goal sets goals [Q,N_cmd,3] (next to an unbatched po) or [S,Q,N_cmd,3].  A stage
+    def mission(self, po, goals, K_T_max, error_tol=0.01, histories=True, deadline=None, path=None, on_fail="stop", max_hold=14, assign=False,
+                disturb=None):
+        """disturb: as transition().
+        dmpc_transition_mission: one transition through the Q goal sets goals [Q,N_cmd,3] (next to an unbatched po) or [S,Q,N_cmd,3].  A stage
         ends at the first column where its goals are reached or -- deadline [Q] / [S,Q], 0 = none, the last 0 -- its deadline has passed; the
         next step is solved with the next goal set, the last stage ends the trial.  po with MORE vehicles than the goals: static vehicles, as
         transition(); path [S,M,P,3]: scripted vehicles, po then covers the commanded agents.  Returns what transition() returns, and stage_col
@@ -558,6 +648,9 @@ class Dmpc:
         assigned goals of stage q are the starts of stage q+1 -- and the dict also has perm [S,Q,N_cmd].  assign="rect": goals [S,Q,M,3] with any
         M >= 1, all N agents of po commanded; assign_rect() stage by stage from the previous stage's assigned targets (po for stage 0), an agent
         without a goal in a stage keeps its previous target; the dict also has perm [S,Q,N] and owner [S,Q,M]."""
+        if disturb is not None:
+            with self._disturbed(disturb):
+                return self.mission(po, goals, K_T_max, error_tol, histories, deadline, path, on_fail, max_hold, assign)
         po, goals = _f(po), _f(goals)
         if on_fail not in ("stop", "hold"):
             raise DmpcError(f"mission: on_fail is 'stop' or 'hold', not {on_fail!r}")
@@ -614,8 +707,10 @@ class Dmpc:
                                                   _ip(used), _ip(sst), _ip(stage_col)))
         return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, stage_col=stage_col)
 
-    def route(self, po, waypoints, K_T_max, capture, n_wp=None, timeout=0, error_tol=0.01, histories=True, path=None, on_fail="stop", max_hold=14):
-        """dmpc_transition_route: one transition in which every commanded agent flies through waypoints of its own, waypoints [N_cmd,W,3] (next
+    def route(self, po, waypoints, K_T_max, capture, n_wp=None, timeout=0, error_tol=0.01, histories=True, path=None, on_fail="stop", max_hold=14,
+              disturb=None):
+        """disturb: as transition().
+        dmpc_transition_route: one transition in which every commanded agent flies through waypoints of its own, waypoints [N_cmd,W,3] (next
         to an unbatched po) or [S,N_cmd,W,3]; n_wp [N_cmd] / [S,N_cmd] (1 .. W; None: every agent has W) counts an agent's waypoints, the last
         of them is its goal.  An agent leaves a waypoint that is not its last at the first column where it is closer to it than capture (metres)
         or -- timeout > 0, in columns -- has flown towards it for timeout columns; the next step is solved with its next waypoint.  The trial ends
@@ -623,6 +718,9 @@ class Dmpc:
         transition(); path [S,M,P,3]: scripted vehicles, po then covers the commanded agents.  Returns what transition() returns, and wp_col
         [S,N_cmd,W]: the column on which the agent left each waypoint (-1: it never did), wp_index [S,N_cmd]: the waypoint it was flying to when
         the scene ended.  on_fail, max_hold: as transition() (a held plan counts as a solved one in the waypoint rule)."""
+        if disturb is not None:
+            with self._disturbed(disturb):
+                return self.route(po, waypoints, K_T_max, capture, n_wp, timeout, error_tol, histories, path, on_fail, max_hold)
         po, waypoints = _f(po), _f(waypoints)
         if on_fail not in ("stop", "hold"):
             raise DmpcError(f"route: on_fail is 'stop' or 'hold', not {on_fail!r}")
@@ -697,13 +795,17 @@ class Dmpc:
         return dict(waypoints=wp, n_wp=n_wp, plan_status=st, hops=hops)
 
     def replan(self, po, goals, K_T_max, cell, capture, margin=0.0, W=4, every=5, ahead=0, timeout=0, error_tol=0.01, histories=True, path=None,
-               on_fail="stop", max_hold=14):
-        """dmpc_transition_replan: plan() before column 0, route() from there, and every `every` columns (0: never) the agents whose remaining
+               on_fail="stop", max_hold=14, disturb=None):
+        """disturb: as transition().
+        dmpc_transition_replan: plan() before column 0, route() from there, and every `every` columns (0: never) the agents whose remaining
         legs are no longer clear are planned again on the device, from where they are, round the vehicles where they are on that column and on
         the `ahead` columns behind it.  goals [N_cmd,3] next to an unbatched po, or [S,N_cmd,3]; po with MORE vehicles than goals: static
         vehicles; path [S,M,P,3]: scripted ones, po then covers the commanded agents.  cell, margin, W: plan()'s; capture, timeout, on_fail,
         max_hold: route()'s.  Returns what route() returns, and waypoints [S,N_cmd,W,3], n_wp, plan_status [S,N_cmd]: the plan in force when the
         scene ended (wp_col and wp_index refer to it), replan_count [S,N_cmd], replan_col [S,N_cmd]: the last re-plan's column (-1: none)."""
+        if disturb is not None:
+            with self._disturbed(disturb):
+                return self.replan(po, goals, K_T_max, cell, capture, margin, W, every, ahead, timeout, error_tol, histories, path, on_fail, max_hold)
         po, goals = _f(po), _f(goals)
         if on_fail not in ("stop", "hold"):
             raise DmpcError(f"replan: on_fail is 'stop' or 'hold', not {on_fail!r}")
@@ -1021,6 +1123,10 @@ class Dmpc:
         """dmpc_scripted_cols_device: columns n_cmd .. N-1 of lT [S,45,N] (and of the fp32 table lTf, if given) for MPC step k >= 1 from the
         device-resident path [S,N-n_cmd,P,3]: horizon entry kk of a vehicle = its sample min(k-1+kk, P-1)"""
         self._chk(self._L.dmpc_scripted_cols_device(self._ctx, S, N, n_cmd, P, path, int(k), lT, lTf or None, stream or None))
+
+    def disturb_device(self, S, n_cmd, k, x_p, x_v, scene_done=0, stream=0):
+        """dmpc_disturb_device: the disturbance in force, of column k, on device arrays x_p, x_v [S,n_cmd,3] (behind advance_device)"""
+        self._chk(self._L.dmpc_disturb_device(self._ctx, S, n_cmd, k, x_p, x_v, scene_done, stream))
 
     def step_device(self, S, G, Cn, g_local, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out, lT_next, status, info, stream=0):
         self._chk(self._L.dmpc_step_device(self._ctx, S, G, Cn, g_local, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out,

@@ -120,6 +120,17 @@ struct DevOptions {
     int setpoint_batch = 0;  // development option setpoint_batch: 100 Hz samples per staging pass of dmpc_postcheck_setpoints (0: the 256 MB rule; tests)
 };
 
+// dmpc_set_disturbance's copy of the descriptor (dmpc_disturb.hip); the pushes sorted by (scene, agent, column), stable
+struct Disturbance {
+    bool on = false;
+    uint64_t seed = 0;
+    double amp_p = 0.0, amp_v = 0.0;
+    int wind_scenes = 0;
+    std::vector<double> wind;      // [wind_scenes][3]
+    std::vector<dmpc_push> push;
+    void set(const dmpc_disturbance &d);
+};
+
 struct dmpc_ctx {
     int device = 0;
     int precision = DMPC_PREC_F64;   // DMPC_PREC_MIXED: fp32 table / scan / rows, fp64 QP (host-pointer entry points)
@@ -175,6 +186,8 @@ struct dmpc_ctx {
     DevBuf path;                                                           // dmpc_transition_scripted: the scripted vehicles' paths [S][M][P][3], resident for the call
     DevBuf hold_out, hold_state;                                           // dmpc_transition_hold: the second set of p / v / a output rows 3 x [S][N_cmd][3K]; ints: run, hold_count, hold_first [S][N_cmd] each, agent_status [S][N_cmd][K_T_max]
     DevBuf mis_goals, mis_state;                                           // dmpc_transition_mission: goal sets [S][Q][N_cmd][3]; ints: stage [S], k_start [S], stage_col [S][Q], deadline [S][Q]
+    Disturbance dist;                                                      // dmpc_set_disturbance: the disturbance in force (children of a split batch get a copy per call)
+    DevBuf dist_buf; std::vector<unsigned char> dist_stage; long dist_key = -1;   // ... of a call on the device: wind | sorted pushes | offsets [S * N_cmd + 1]; its host staging; the shape dmpc_disturb_device uploaded for
     DevBuf route_wp, route_state;                                          // dmpc_transition_route: waypoints [S][N_cmd][W][3]; ints: n_wp, cur, since [S][N_cmd] each, wp_col [S][N_cmd][W]
     DevBuf pc_sc_path, pc_sc_y, pc_sc_M, pc_sc_w, pc_sc_pts, pc_sc_interp; // dmpc_postcheck_scripted: paths, knots, second derivatives, scratch, sample batch, p_scripted
     DevBuf pc_pts, pc_cell, pc_fill, pc_start, pc_sorted, pc_on;           // post-check, large scenes: cell grid of a batch of samples
@@ -786,6 +799,7 @@ static std::vector<int> batch_parts(int S, int want, bool sharded)
 }
 
 #include "dmpc_plan.hip"     // route planning round static vehicles, before and during a flight: the wavefront planner's kernels, the three entries
+#include "dmpc_disturb.hip"  // disturbed transitions: the rule on the host and the device, the descriptor's check and upload, the three entries
 #include "dmpc_transition.hip"   // the closed loop: the record of a call, transition_one, transition_any, the seven entries
 
 #include "dmpc_postcheck_host.hip"   // the post-checks on the host: the record of a call, PcPrep, the three checks, pc_run, the five entries

@@ -1585,10 +1585,16 @@ __global__ void record_kernel(int S, int N, int KT, int k, const double *__restr
 // The three small kernels that follow a solve in a transition, in one launch (one block per scene; a 100-agent step is
 // latency bound, and three launches cost more than their work): x <- first horizon column of the solved agents
 // (dmpc_soft_bound.m:132-134), the history column k (pk/vk/ak(:,k,n)), then the scene verdict as scene_reduce_kernel.
-__global__ void post_step_kernel(int N, int KT, int k, double tol, const double *__restrict__ p, const double *__restrict__ v,
-                                 const double *__restrict__ a, const int *__restrict__ status, double *x_p, double *x_v, double *x_a,
-                                 const double *__restrict__ pf, double *pk, double *vk, double *ak, int *flags, int *scene_done,
-                                 const int *__restrict__ stopped)
+// `disturb` is the hook between the state advance and the history record: NoDisturb here, dmpc_disturb.hip's rule in post_step_disturbed_kernel.
+struct NoDisturb {
+    static constexpr bool on = false;
+    __device__ void operator()(int, int, int, int, double *, double *) const {}
+};
+template <class Disturb>
+__device__ __forceinline__ void post_step_body(int N, int KT, int k, double tol, const double *__restrict__ p, const double *__restrict__ v,
+                                               const double *__restrict__ a, const int *__restrict__ status, double *x_p, double *x_v, double *x_a,
+                                               const double *__restrict__ pf, double *pk, double *vk, double *ak, int *flags, int *scene_done,
+                                               const int *__restrict__ stopped, const Disturb &disturb)
 {
     __shared__ double smax[256];
     __shared__ int sor[256];
@@ -1600,11 +1606,17 @@ __global__ void post_step_kernel(int N, int KT, int k, double tol, const double 
     for (int i = threadIdx.x; i < N; i += blockDim.x) {
         const size_t ag = (size_t)s * N + i, b = ag * 3;
         const int st = status[ag];
+        const bool advance = (st & ST_SOLVED) != 0;
         double xp[3], xv[3], xa[3];
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            if (st & ST_SOLVED) { xp[d] = p[ag * N3 + d]; xv[d] = v[ag * N3 + d]; xa[d] = a[ag * N3 + d]; x_p[b + d] = xp[d]; x_v[b + d] = xv[d]; x_a[b + d] = xa[d]; }
+            if (advance) { xp[d] = p[ag * N3 + d]; xv[d] = v[ag * N3 + d]; xa[d] = a[ag * N3 + d]; }
             else { xp[d] = x_p[b + d]; xv[d] = x_v[b + d]; xa[d] = x_a[b + d]; }
+        }
+        disturb(s, i, N, k, xp, xv);   // (every agent of a running scene, whether it advanced or not)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            if (advance || Disturb::on) { x_p[b + d] = xp[d]; x_v[b + d] = xv[d]; x_a[b + d] = xa[d]; }
             const size_t ho = (ag * KT + k) * 3 + d;
             pk[ho] = xp[d]; vk[ho] = xv[d]; ak[ho] = xa[d];
         }
@@ -1623,6 +1635,13 @@ __global__ void post_step_kernel(int N, int KT, int k, double tol, const double 
         flags[(size_t)s * 2] = reached; flags[(size_t)s * 2 + 1] = sor[0];
         if (scene_done && (reached || (sor[0] & ~ST_SOLVED))) scene_done[s] = 1;
     }
+}
+__global__ void post_step_kernel(int N, int KT, int k, double tol, const double *__restrict__ p, const double *__restrict__ v,
+                                 const double *__restrict__ a, const int *__restrict__ status, double *x_p, double *x_v, double *x_a,
+                                 const double *__restrict__ pf, double *pk, double *vk, double *ak, int *flags, int *scene_done,
+                                 const int *__restrict__ stopped)
+{
+    post_step_body(N, KT, k, tol, p, v, a, status, x_p, x_v, x_a, pf, pk, vk, ak, flags, scene_done, stopped, NoDisturb{});
 }
 
 // one block per scene: flags[0] = ReachedGoal.m:3-11 (max_i ||p_i - pf_i|| < tol), flags[1] = OR of status bits

@@ -55,11 +55,12 @@ struct TransitionCall {
     int32_t *K_T_used, *scene_status;
     const double *path = nullptr; int P = 0;
     Mission mission; Hold hold; Route route;
+    int s0 = 0;              // the index in the caller's batch of scene 0 (a part of a split batch; the disturbance rule counts scenes of the call)
     // the same call for scenes [s0, s0 + sn): the one place that knows each array's stride per scene
     TransitionCall scenes(int s0, int sn) const {
         auto at = [](auto *p, size_t off) { return p ? p + off : nullptr; };
         const size_t a0 = (size_t)s0 * N_cmd, q0 = (size_t)s0 * mission.Q, h0 = a0 * (size_t)K_T_max, w0 = a0 * (size_t)route.W;
-        TransitionCall c = *this; c.S = sn;
+        TransitionCall c = *this; c.S = sn; c.s0 = this->s0 + s0;
         c.po = at(po, (path ? a0 : (size_t)s0 * N) * 3);   // (scripted vehicles: po covers the commanded agents)
         c.path = at(path, (size_t)s0 * (N - N_cmd) * P * 3);
         c.pk = at(pk, h0 * 3); c.vk = at(vk, h0 * 3); c.ak = at(ak, h0 * 3);
@@ -80,7 +81,7 @@ static int check_call(dmpc_ctx *ctx, const std::string &who, const TransitionCal
 {
     if (c.S < 1 || c.N < 1 || c.N_cmd < 1 || c.N_cmd > c.N || c.K_T_max < 2 || !c.po || !c.pf || !c.K_T_used || !c.scene_status || ((c.pk || c.vk || c.ak) && !(c.pk && c.vk && c.ak)))
         FAIL(ctx, who + ": bad arguments");
-    return 0;
+    return check_disturb_shape(ctx, who, ctx->dist, c.S, c.N_cmd);
 }
 
 // The verdicts of every column and scene -- flags [K_T_max][S][2]: (reached, OR of the status bits) -- folded into what the caller gets.  The host
@@ -284,6 +285,20 @@ struct HoldDev {
     }
 };
 
+// the device side of a disturbance (dmpc_disturb.hip): the wind, the sorted pushes and the offsets of this call's scenes go up once per call
+struct DisturbDev {
+    dmpc_ctx *ctx; const TransitionCall &c; hipStream_t st;
+    DisturbArgs args{};
+    explicit operator bool() const { return ctx->dist.on; }
+    int begin() {
+        if (!ctx->dist.on) return 0;
+        ctx->dist_key = -1;   // (dmpc_disturb_device's upload does not survive this one)
+        if (disturb_upload(ctx, c.s0, c.S, c.N_cmd, st)) return -1;
+        args = disturb_args(ctx, c.s0);
+        return 0;
+    }
+};
+
 static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
 {
     const int S = c.S, N = c.N, N_cmd = c.N_cmd, K_T_max = c.K_T_max;
@@ -303,8 +318,8 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
         HIPCHK(ctx, hipMemcpyAsync(ctx->path.p, c.path, path_bytes, hipMemcpyHostToDevice, st));
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, c.po, (scripted ? A : T) * 24, hipMemcpyHostToDevice, st));
-    MissionDev mission{ctx, c, st}; HoldDev hold{ctx, c, st}; RouteDev route{ctx, c, st};
-    if (mission.begin() || route.begin()) return -1;
+    MissionDev mission{ctx, c, st}; HoldDev hold{ctx, c, st}; RouteDev route{ctx, c, st}; DisturbDev disturb{ctx, c, st};
+    if (mission.begin() || route.begin() || disturb.begin()) return -1;
     if (reset_run_buffers(ctx, S, K_T_max, hist, st)) return -1;
     // ---- column 0: initDMPC (dmpc_soft_bound.m:117-121): state = (po, 0, 0), table = straight lines
     if (N_cmd == N || scripted) HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
@@ -367,12 +382,17 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
         StepIO io = scratch_io(ctx);   // (xp, xv, xa, the goals and the status are the scratch's; a closed loop takes no info)
         io.lT = cur; io.lT_next = nxt; io.info = nullptr;
         io.p_out = out[0]; io.v_out = out[1]; io.a_out = out[2];
-        io.scene_done = ctx->scene_done.as<int>(); io.lTf = mixed ? ctx->lTf.as<float>() : nullptr; io.post = c.hold ? nullptr : &post;
+        io.scene_done = ctx->scene_done.as<int>(); io.lTf = mixed ? ctx->lTf.as<float>() : nullptr; io.post = c.hold || disturb ? nullptr : &post;   // (hold, a disturbance: the post step is a launch of its own)
         const StepShape sh{S, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ 0, /*c_count*/ N_cmd};
         if (launch_step(ctx, sh, io, st)) return -1;
         hold.apply(k, cur, nxt);
         // state advance + history column + scene verdict in one launch (unless the solve kernel did them: tiny launches)
-        if (!ctx->post_fused)
+        if (disturb)   // ... with the disturbance of column k between the advance and the record
+            hipLaunchKernelGGL(post_step_disturbed_kernel, dim3((unsigned)S), dim3(N_cmd >= 256 ? 256 : 128), 0, st, disturb.args, N_cmd, K_T_max, k, c.error_tol,
+                               (const double *)out[0], (const double *)out[1], (const double *)out[2],
+                               (const int *)ctx->status.as<int32_t>(), xp, xv, xa, (const double *)ctx->pf.as<double>(), ctx->hist_p.as<double>(),
+                               ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), verdict_k, ctx->scene_done.as<int>(), (const int *)ctx->scene_done.as<int>());
+        else if (!ctx->post_fused)
             hipLaunchKernelGGL(post_step_kernel, dim3((unsigned)S), dim3(N_cmd >= 256 ? 256 : 128), 0, st, N_cmd, K_T_max, k, c.error_tol,
                                (const double *)out[0], (const double *)out[1], (const double *)out[2],
                                (const int *)ctx->status.as<int32_t>(), xp, xv, xa, (const double *)ctx->pf.as<double>(), ctx->hist_p.as<double>(),
@@ -425,6 +445,7 @@ static int part_context(dmpc_ctx *ctx, size_t i, int device)
         ch->opt.no_split = 1; ctx->children.push_back(ch);
     }
     dmpc_ctx *ch = ctx->children[i];
+    ch->dist = ctx->dist;
     if (std::memcmp(&ch->prm, &ctx->prm, sizeof(dmpc_params)) != 0 && dmpc_set_params(ch, &ctx->prm)) FAIL(ctx, what + ch->err);
     return 0;
 }
@@ -448,13 +469,13 @@ static int run_parts(dmpc_ctx *ctx, const TransitionCall &c, const std::vector<i
 }
 
 // A batch in parts (batch_parts), each on a context, HIP stream and host thread of its own.  A DMPC_DEVICE_ALL context shards the agents of each scene
-// over every visible GPU (dmpc_multigpu.hip) -- unless there are uncommanded vehicles, a mission or a route, or fewer agents than twice the GPUs (the
+// over every visible GPU (dmpc_multigpu.hip) -- unless there are uncommanded vehicles, a mission, a route or a disturbance, or fewer agents than twice the GPUs (the
 // reference's small swarms on an 8-GPU node: sharding N = 4 agents over 8 GPUs is impossible and over 2-3 of them nothing but barriers and peer
 // copies): the first GPU alone then, unsplit, as dmpc_step_batch does.
 static int transition_any(dmpc_ctx *ctx, const TransitionCall &c)
 {
     ctx->split_at.clear();
-    const bool sharded = ctx->grp && c.N_cmd == c.N && !c.mission && !c.route;
+    const bool sharded = ctx->grp && c.N_cmd == c.N && !c.mission && !c.route && !ctx->dist.on;
     if (sharded && c.N < 2 * ctx->grp->G) return transition_one(ctx, c);
     int (*const body)(dmpc_ctx *, const TransitionCall &) = sharded ? group_transition : transition_one;
     const std::vector<int> at = batch_parts(c.S, ctx->opt.split_parts, sharded);

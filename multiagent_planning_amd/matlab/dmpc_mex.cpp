@@ -21,6 +21,7 @@
 //   [xi,rhs,dist,kc,viol_k,coll] = dmpc_mex('rows_one', params, l, n, po, vo)           CheckCollSoftDMPC + CollConstr*DMPC rows
 //   Ain            = dmpc_mex('rows_dense', params, xi, kc, A)                          -diff_mat*A of structured rows
 //   [pk,vk,ak,K_T_used,scene_status] = dmpc_mex('transition', params, po, pf, K_T_max, error_tol)   the whole k-loop on the GPU
+//   [pk,vk,ak,K_T_used,scene_status] = dmpc_mex('transition_disturbed', params, po, pf, K_T_max, error_tol, noise_p, noise_v, seed, wind, pushes)   see below
 //   [pk,vk,ak,K_T_used,scene_status,stage_col] = dmpc_mex('mission', params, po, goals, K_T_max, error_tol[, deadline])   goals 3 x N_cmd x Q: see below
 //   [pk,vk,ak,K_T_used,scene_status,wp_col] = dmpc_mex('route', params, po, waypoints, K_T_max, error_tol, capture[, n_wp[, timeout]])   waypoints 3 x W x N_cmd: see below
 //   [perm,pf,cost,rounds] = dmpc_mex('assign', params, po, goals[, eps[, max_rounds]])  goal assignment (dmpc_assign_goals): po, goals 3 x N; perm 1 x N, 1-based:
@@ -55,6 +56,10 @@
 // are on that column and on the `ahead` (default 0) columns behind it.  path (3 x P x M, optional): scripted vehicles, po is then 3 x N_cmd; without
 // it the vehicles of po behind the goals are static obstacles.  waypoints, n_wp, plan_status: the plan in force at the end; replan_count, replan_col
 // (1 x N_cmd): re-plans per agent and the 0-based column of the last one, -1 for none; wp_col refers to the last plan.
+// Disturbed transitions (dmpc_set_disturbance, no reference counterpart): 'transition_disturbed' is 'transition' with a disturbance added to the state
+// of every commanded agent on every column from 1 on, by the rule include/dmpc_hip.h pins: uniform noise of half-width noise_p (metres) on the
+// position and noise_v (m/s) on the velocity from the stream `seed` (an integer below 2^53), a constant wind (3 x 1, m/s^2, or []) and pushes
+// (8 x n or []: agent, 1-based; history column, 0-based, >= 1; dp (3); dv (3)).  The command sets the disturbance, flies and clears it.
 // `params` is a struct with the fields of dmpc_params (variant as the DMPC_VAR_* integer).
 // The signature-preserving wrappers (solveSoftDMPCbound.m, ...) in this directory call 'solve_one'
 // and convert status bits into the reference's [] + flag conventions.
@@ -446,6 +451,38 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
                     : dmpc_transition_cmd(ctx, 1, N, Nc, mxGetPr(prhs[2]), mxGetPr(prhs[3]), KT, mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v),
                                           mxGetPr(a), &used, &sst))
             mexErrMsgIdAndTxt("dmpc:transition", "%s", dmpc_last_error(ctx));
+        if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);
+        if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
+        return;
+    }
+    if (!std::strcmp(cmd, "transition_disturbed")) {   // 'transition' with wind, noise and pushes on the state (dmpc_set_disturbance): set, fly, clear
+        need(nrhs == 11, "transition_disturbed: (cmd, params, po, pf, K_T_max, error_tol, noise_p, noise_v, seed, wind, pushes)");
+        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3), Nc = (int)(mxGetNumberOfElements(prhs[3]) / 3), KT = (int)mxGetScalar(prhs[4]);
+        need(N >= 1 && Nc >= 1 && Nc <= N && mxGetNumberOfElements(prhs[3]) == (size_t)3 * Nc && KT >= 2, "po must be 3 x N, pf 3 x N_cmd (N_cmd <= N), K_T_max >= 2");
+        const size_t nw = mxGetNumberOfElements(prhs[9]), np8 = mxGetNumberOfElements(prhs[10]);
+        need(nw == 0 || nw == 3, "wind must have 3 elements (or be empty)");
+        need(np8 == 0 || (mxGetM(prhs[10]) == 8 && np8 % 8 == 0), "pushes must be 8 x n: agent (1-based), column (0-based), dp (3), dv (3) (or empty)");
+        std::vector<dmpc_push> push(np8 / 8);
+        for (size_t j = 0; j < push.size(); ++j) {
+            const double *q = mxGetPr(prhs[10]) + 8 * j;
+            push[j].scene = 0; push[j].agent = (int32_t)q[0] - 1; push[j].column = (int32_t)q[1];
+            for (int c = 0; c < 3; ++c) { push[j].dp[c] = q[2 + c]; push[j].dv[c] = q[5 + c]; }
+        }
+        const dmpc_disturbance dist{(uint64_t)mxGetScalar(prhs[8]), mxGetScalar(prhs[6]), mxGetScalar(prhs[7]), nw ? mxGetPr(prhs[9]) : nullptr, nw ? 1 : 0,
+                                    push.empty() ? nullptr : push.data(), (int)push.size()};
+        const mwSize d3[3] = {3, (mwSize)KT, (mwSize)Nc};
+        plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        mxArray *v = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), *a = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        int32_t used = 0, sst = 0;
+        if (dmpc_set_disturbance(ctx, &dist)) mexErrMsgIdAndTxt("dmpc:transition_disturbed", "%s", dmpc_last_error(ctx));
+        const int rc = Nc == N ? dmpc_transition(ctx, 1, N, mxGetPr(prhs[2]), mxGetPr(prhs[3]), KT, mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v),
+                                                 mxGetPr(a), &used, &sst)
+                               : dmpc_transition_cmd(ctx, 1, N, Nc, mxGetPr(prhs[2]), mxGetPr(prhs[3]), KT, mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v),
+                                                     mxGetPr(a), &used, &sst);
+        const std::string why = rc ? dmpc_last_error(ctx) : "";
+        dmpc_set_disturbance(ctx, nullptr);   // the contexts are kept between calls: the setting must not outlive this one
+        if (rc) mexErrMsgIdAndTxt("dmpc:transition_disturbed", "%s", why.c_str());
         if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
         if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);
         if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
