@@ -174,7 +174,9 @@ DMPC_API int dmpc_group_size(const dmpc_ctx *ctx);
 DMPC_API void dmpc_destroy(dmpc_ctx *ctx);
 DMPC_API const char *dmpc_last_error(const dmpc_ctx *ctx);
 
-/* Change parameters (variant, weights, bounds ...) of an existing context. */
+/* Change parameters (variant, weights, bounds ...) of an existing context.  Every later call answers, bit for bit, as on a context
+ * created with `prm` (same device and precision); what survives is what is not a parameter: development options, the disturbance of
+ * dmpc_set_disturbance and the resident histories of the last transition.  A refused block (-1) leaves the context as it was. */
 DMPC_API int dmpc_set_params(dmpc_ctx *ctx, const dmpc_params *prm);
 
 /* a1-a3: getPosMat.m:1 (Lambda = A = A_p), A_v / A_initp loop dmpc_soft_bound.m:92-108,

@@ -408,11 +408,14 @@ class Dmpc:
             raise DmpcError(self._L.dmpc_last_error(self._ctx).decode())
 
     def set_params(self, variant=None, **kw):
-        base = {f: getattr(self.prm, f) for f in ("h", "rmin", "c", "alim", "Q1", "S1", "term", "max_tries")}
+        """dmpc_set_params: re-tune this context.  Every parameter not named keeps its value (K, order, Qfar, Qnear, Sfree and tol included);
+        a refused block leaves the context, and self.prm, as they were."""
+        base = {f: getattr(self.prm, f) for f in ("K", "h", "rmin", "c", "alim", "Q1", "S1", "term", "max_tries", "order", "Qfar", "Qnear", "Sfree", "tol")}
         base["pmin"], base["pmax"] = tuple(self.prm.pmin), tuple(self.prm.pmax)
         base.update(kw)
-        self.prm = make_params(self.prm.variant if variant is None else variant, **base)
-        self._chk(self._L.dmpc_set_params(self._ctx, C.byref(self.prm)))
+        prm = make_params(self.prm.variant if variant is None else variant, **base)
+        self._chk(self._L.dmpc_set_params(self._ctx, C.byref(prm)))
+        self.prm = prm
 
     # ---- disturbed transitions -----------------------------------------------------------------
     def set_disturbance(self, noise_p=0.0, noise_v=0.0, wind=None, pushes=None, seed=0):

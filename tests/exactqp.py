@@ -7,7 +7,9 @@ its minimiser is determined by its active set.  Given a candidate answer `a` (th
   1. the slack is completed in closed form (certificates.complete_slack);
   2. the rows with residual >= -1e-7 x scale are the candidates, the support of their Lawson-Hanson NNLS multipliers is the working
      set W (as certificates.kkt_certificate recovers its multipliers);
-  3. [H C_W'; C_W 0] [x; lam] = [-f; d_W] is solved in double (LU) and refined four times with residuals in np.longdouble.
+  3. [H C_W'; C_W 0] [x; lam] = [-f; d_W] is solved in double (LU) and refined four times with residuals in np.longdouble; a system
+     whose pivots look dependent only because its variables differ in scale by many decades (softall_c's slack weights) is solved
+     again with the variables scaled to a unit diagonal of H.
 
 If every refined multiplier is >= 0 and C x* - d <= 1e-11 on every row, x* satisfies the KKT conditions and is THE minimiser, to about
 1e-15: the candidate only had to be near enough to name the right working set.  Anything else is `unresolved` -- counted by the
@@ -37,8 +39,9 @@ def working_set(qp, a, tol_act=1e-7):
     return act[lam_s > 0.0]
 
 
-def kkt_point(qp, W):
-    """the stationary point of the QP with the rows W as equalities, refined in extended precision: (x, lam, singular)"""
+def kkt_point(qp, W, equilibrate=False):
+    """the stationary point of the QP with the rows W as equalities, refined in extended precision: (x, lam, singular).
+    equilibrate: the variables are scaled to a unit diagonal of H first (see exact_minimiser)"""
     H, f, C, d = qp["H"], qp["f"], qp["C"], qp["d"]
     n, m = H.shape[0], len(W)
     Kd = np.zeros((n + m, n + m))
@@ -48,7 +51,9 @@ def kkt_point(qp, W):
     rhs = np.concatenate([-f, d[W]])
     # rows and columns of the constraints scaled to unit norm: the pivots of the LU then tell dependence from mere scale
     s = np.ones(n + m)
-    s[n:] = 1.0 / np.maximum(1e-300, np.linalg.norm(C[W], axis=1))
+    if equilibrate:
+        s[:n] = 1.0 / np.sqrt(np.diag(H))
+    s[n:] = 1.0 / np.maximum(1e-300, np.linalg.norm(C[W] * s[None, :n], axis=1))
     Ks = Kd * s[:, None] * s[None, :]
     if not np.isfinite(Ks).all():
         return None, None, True
@@ -76,6 +81,13 @@ def exact_minimiser(qp, a):
     are then None / nan): a singular KKT matrix, a refined multiplier below -1e-9 max(1, |lam|max), a row of C x* - d above 1e-11."""
     W = working_set(qp, a)
     x, lam, singular = kkt_point(qp, W)
+    if singular:
+        # The pivot test of kkt_point compares pivots of the KKT matrix with only its constraint rows scaled.  A QP whose variables differ
+        # in scale by many decades fails it without being dependent: softall_c weighs a slack with 1e6 (K/k)^2 against about 1e3 on an
+        # acceleration, the pivot of a slack's bound row is 1 / H_ii of that slack, and 1 / H_ii^2 lies below the test's 1e-13.  Such a
+        # system is solved again with the variables scaled to a unit diagonal of H, where a small pivot again means dependence.  The
+        # unscaled attempt stays first: every x* it resolves (all figures of DESIGN.md section 2) is unchanged to the bit.
+        x, lam, singular = kkt_point(qp, W, equilibrate=True)
     bad = dict(x=None, lam_max=float("nan"), resolved=False, n_active=int(len(W)))
     if singular:
         return dict(bad, why="singular")

@@ -25,10 +25,7 @@ def build():
     return EXE
 
 
-def call(cmd, prm, args=(), nlhs=1, emulate_devices=0):
-    """dmpc_mex(cmd, prm, args...) -> list of nlhs numpy arrays (column-major like MATLAB); raises RuntimeError with the
-    MATLAB error text on mexErrMsgIdAndTxt.  prm: dict with K, variant, order, h, rmin, c, alim, Q1, S1, term, pmin, pmax."""
-    exe = build()
+def _request(cmd, prm, args, nlhs):
     req = struct.pack("<i", len(cmd)) + cmd.encode()
     req += struct.pack("<3i", int(prm["K"]), int(prm["variant"]), int(prm["order"]))
     req += struct.pack("<14d", prm["h"], prm["rmin"], prm["c"], prm["alim"], prm["Q1"], prm["S1"], prm["term"], *prm["pmin"], *prm["pmax"], prm.get("tol", 0.0))
@@ -38,20 +35,16 @@ def call(cmd, prm, args=(), nlhs=1, emulate_devices=0):
         if a.ndim < 2:
             a = a.reshape(1, -1) if a.ndim == 1 else a.reshape(1, 1)
         req += struct.pack("<i", a.ndim) + struct.pack(f"<{a.ndim}q", *a.shape) + a.tobytes(order="F")
-    req += struct.pack("<i", nlhs)
-    with tempfile.TemporaryDirectory() as td:
-        rq, rp = os.path.join(td, "req.bin"), os.path.join(td, "rep.bin")
-        open(rq, "wb").write(req)
-        env = dict(os.environ)
-        if emulate_devices:
-            env["DMPC_TEST_EMULATE_DEVICES"] = str(int(emulate_devices))
-        subprocess.check_call([exe, rq, rp], env=env)
-        buf = open(rp, "rb").read()
-    rc, = struct.unpack_from("<i", buf, 0)
-    off = 4
+    return req + struct.pack("<i", nlhs)
+
+
+def _reply(buf, off):
+    """one reply at buf[off:] -> (list of arrays, or the RuntimeError of a MATLAB error; the offset behind it)"""
+    rc, = struct.unpack_from("<i", buf, off)
+    off += 4
     if rc:
         n, = struct.unpack_from("<i", buf, off)
-        raise RuntimeError(buf[off + 4: off + 4 + n].decode())
+        return RuntimeError(buf[off + 4: off + 4 + n].decode()), off + 4 + n
     nout, = struct.unpack_from("<i", buf, off); off += 4
     outs = []
     for _ in range(nout):
@@ -61,6 +54,40 @@ def call(cmd, prm, args=(), nlhs=1, emulate_devices=0):
         cnt = int(np.prod(dims))
         outs.append(np.frombuffer(buf, dtype=dt, count=cnt, offset=off).reshape(dims, order="F").copy())
         off += cnt * np.dtype(dt).itemsize
+    return outs, off
+
+
+def _run(req, many, emulate_devices):
+    exe = build()
+    with tempfile.TemporaryDirectory() as td:
+        rq, rp = os.path.join(td, "req.bin"), os.path.join(td, "rep.bin")
+        open(rq, "wb").write(req)
+        env = dict(os.environ)
+        if emulate_devices:
+            env["DMPC_TEST_EMULATE_DEVICES"] = str(int(emulate_devices))
+        subprocess.check_call([exe] + (["--many"] if many else []) + [rq, rp], env=env)
+        return open(rp, "rb").read()
+
+
+def call(cmd, prm, args=(), nlhs=1, emulate_devices=0):
+    """dmpc_mex(cmd, prm, args...) -> list of nlhs numpy arrays (column-major like MATLAB); raises RuntimeError with the
+    MATLAB error text on mexErrMsgIdAndTxt.  prm: dict with K, variant, order, h, rmin, c, alim, Q1, S1, term, pmin, pmax."""
+    out, _ = _reply(_run(_request(cmd, prm, args, nlhs), False, emulate_devices), 0)
+    if isinstance(out, RuntimeError):
+        raise out
+    return out
+
+
+def session(calls, emulate_devices=0):
+    """several gateway calls in ONE process, as a MATLAB session makes them: the gateway's persistent contexts live across the calls.
+    calls: (cmd, prm, args, nlhs) each; returns per call the list call() returns, or the RuntimeError a MATLAB error would be (the session
+    goes on after it)."""
+    buf = _run(struct.pack("<i", len(calls)) + b"".join(_request(*c) for c in calls), True, emulate_devices)
+    outs, off = [], 0
+    for _ in calls:
+        out, off = _reply(buf, off)
+        outs.append(out)
+    assert off == len(buf)
     return outs
 
 

@@ -135,3 +135,31 @@ def test_gateway_transition_and_step_on_all_gpus_of_one_process(G):
     assert np.array_equal(st.ravel(), out["status"])
     assert np.array_equal(P.transpose(2, 1, 0).reshape(Ng, 45), out["p"]) and np.array_equal(A.transpose(2, 1, 0).reshape(Ng, 45), out["a"])
     assert np.array_equal(V.transpose(2, 1, 0).reshape(Ng, 45), out["v"])
+
+
+@pytest.mark.gpu
+def test_gateway_context_cache_retunes_and_returns_to_an_evicted_struct():
+    """A MATLAB session with more parameter structs than the gateway keeps contexts (four; dmpc_mex.cpp context()): six 'step_batch' calls with
+    five distinct structs in ONE process.  The fifth call re-tunes the least recently used context (dmpc_set_params), the sixth returns to
+    the struct that was evicted and re-tunes the next one.  Each call must give, bit for bit, what the same call gives alone in its own
+    process, where the context is created with its struct."""
+    import offconst as oc
+    _, po, pf = oc.scene("base")
+    N = len(po)
+    names = ["base", "h=0.1", "Q1=1e5", "alim=0.3", "h=0.3", "base"]
+    calls = []
+    for name in names:
+        kw = oc.solver_kw(name)
+        l, xp, xv, xa, _ = oc.init(po, pf, kw["h"])
+        calls.append(("step_batch", mh.params("bound", kw), [np.ascontiguousarray(l.reshape(N, 15, 3).transpose(2, 1, 0)), xp.T, xv.T, xa.T, pf.T], 5))
+    together = mh.session(calls)
+    for i, (name, got, c) in enumerate(zip(names, together, calls)):
+        assert not isinstance(got, RuntimeError), f"call {i + 1} ({name}): {got}"
+        alone = mh.call(c[0], c[1], c[2], nlhs=c[3])
+        assert len(got) == len(alone) == 5
+        for j, (g, w) in enumerate(zip(got, alone)):
+            assert g.dtype == w.dtype and np.array_equal(g, w), f"call {i + 1} ({name}) of the session: output {j + 1} differs from the call made alone"
+        assert (got[3].ravel() == 1).all() and (got[4][1] > 0).any(), "every agent solved, rows were built"
+    for j in range(5):
+        assert np.array_equal(together[5][j], together[0][j])                # the evicted struct answers as it did before
+    assert not np.array_equal(together[4][0], together[0][0])                # ... and the context re-tuned in between did not answer with the old one
