@@ -6,6 +6,8 @@ kind: if the library is missing, or no HIP device is present, the calls raise.
 """
 import contextlib
 import ctypes as C
+import functools
+import inspect
 import os
 
 import numpy as np
@@ -238,6 +240,15 @@ def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _dpn(a):
+    """_dp, or the null pointer for None"""
+    return _dp(a) if a is not None else C.POINTER(C.c_double)()
+
+
+def _ipn(a):
+    return _ip(a) if a is not None else C.POINTER(C.c_int32)()
+
+
 def _n_cmd(lead_table, cmd, what):
     """The reference's rule (DMPC::solveParallelDMPCv2, dmpc/cpp/dmpc.cpp:1572-1573): N = _po.cols(), N_cmd = _pf.cols().
     lead_table: leading shape ([N] or [S,N]) of the table-sized array (l, po); cmd: a commanded-sized array (pf [..,3]).
@@ -265,6 +276,123 @@ def _path(path, lead_cmd, what):
     if M < 1 or P < 1:
         raise DmpcError(f"{what}: path {tuple(path.shape)} needs at least one vehicle and one sample")
     return path, int(M), int(P)
+
+
+# ---- the flight methods (transition, mission, route, replan, transition_sharded) and the check methods (postcheck, clearance, setpoints) of
+# Dmpc share the functions from here to _other_vehicles.  They are functions of the module, not methods: every refusal fires before anything
+# touches the context (tests/bindingcalls.py records what the methods pass down)
+def _disturbable(method):
+    """disturb= of a flight method: the method runs inside _disturbed(disturb) and is itself called without it"""
+    sig = inspect.signature(method)
+
+    @functools.wraps(method)
+    def wrapped(*args, **kw):
+        call = sig.bind(*args, **kw)
+        disturb = call.arguments.pop("disturb", None)
+        if disturb is None:
+            return method(*call.args, **call.kwargs)
+        with call.arguments["self"]._disturbed(disturb):
+            return method(*call.args, **call.kwargs)
+    return wrapped
+
+
+def _on_fail(what, on_fail):
+    """on_fail= of a flight method -> whether failed agents hold"""
+    if on_fail not in ("stop", "hold"):
+        raise DmpcError(f"{what}: on_fail is 'stop' or 'hold', not {on_fail!r}")
+    return on_fail == "hold"
+
+
+def _assign_mode(what, assign):
+    """assign= of transition() / mission() -> (whether to assign, whether by assign_rect())"""
+    if isinstance(assign, str) or assign not in (True, False):
+        if assign != "rect":
+            raise DmpcError(f"{what}: assign is False, True or 'rect', not {assign!r}")
+        return True, True
+    return bool(assign), False
+
+
+def _cmd_shape(what, po, cmd, axes, noun, last=True):
+    """The shape rule of mission(), route() and replan(), first half: po is [N,3] or [S,N,3] and cmd -- the goals or waypoints, `noun` in the
+    messages -- has the axes `axes` ("Q,N_cmd,3", "N_cmd,W,3" or "N_cmd,3") behind po's batch axis, the last of them before the 3 not empty
+    (last=False: not asked here).  Returns N_cmd."""
+    names = axes.split(",")
+    if (po.ndim not in (2, 3) or cmd.ndim != po.ndim + len(names) - 2 or po.shape[-1] != 3 or cmd.shape[-1] != 3
+            or cmd.shape[:-len(names)] != po.shape[:-2] or (last and cmd.shape[-2] < 1)):
+        raise DmpcError(f"{what}: {noun} {tuple(cmd.shape)} must be [{axes}] next to po [N,3], or [S,{axes}] next to po [S,N,3]: po is {tuple(po.shape)}")
+    return cmd.shape[names.index("N_cmd") - len(names)]
+
+
+def _commanded(what, po, cmd, axes, noun, path, last=True):
+    """The shape rule of mission(), route() and replan(): _cmd_shape, then N_cmd <= N = po's vehicles means static vehicles behind the commanded
+    ones, and a path means M scripted ones behind N == N_cmd commanded ones.  Returns (S, N, N_cmd, lead: the leading shape of the per-agent
+    outputs, path, M, P), M = P = 0 without a path."""
+    n_cmd = _cmd_shape(what, po, cmd, axes, noun, last)
+    S, N = (1 if po.ndim == 2 else po.shape[0]), po.shape[-2]
+    lead = po.shape[:-2] + (n_cmd,)
+    M = P = 0
+    if path is not None:
+        if N != n_cmd:
+            raise DmpcError(f"{what}: with path, po {tuple(po.shape)} and {noun} {tuple(cmd.shape)} must cover the same commanded agents")
+        path, M, P = _path(path, lead, what)
+    elif n_cmd < 1 or n_cmd > N:
+        raise DmpcError(f"{what}: {noun} have {n_cmd} agents, po {N}: the commanded agents are the FIRST N_cmd <= N vehicles")
+    return S, N, n_cmd, lead, path, M, P
+
+
+def _flight_outputs(S, lead, K_T_max, histories, hold=None):
+    """The outputs every flight has, as (out, common, held, trio).  out: K_T_used, scene_status [S] and the histories pk, vk, ak
+    [lead, K_T_max, 3] (histories=False: None, they stay on the device); common: the pointers to them in every entry's order, pk vk ak K_T_used
+    scene_status.  hold=None: the entry has no hold record (held and trio are empty); otherwise it has one: held holds hold_count, hold_first
+    [lead] and agent_status [lead, K_T_max] and trio points to them when hold is true, held is empty and trio null when it is false."""
+    out = dict(pk=None, vk=None, ak=None, K_T_used=np.zeros(S, dtype=np.int32), scene_status=np.zeros(S, dtype=np.int32))
+    if histories:
+        out.update((k, np.zeros(lead + (K_T_max, 3))) for k in ("pk", "vk", "ak"))
+    common = [_dpn(out[k]) for k in ("pk", "vk", "ak")] + [_ip(out["K_T_used"]), _ip(out["scene_status"])]
+    held = {}
+    if hold:
+        held = dict(hold_count=np.zeros(lead, dtype=np.int32), hold_first=np.zeros(lead, dtype=np.int32),
+                    agent_status=np.zeros(lead + (K_T_max,), dtype=np.int32))
+    trio = [] if hold is None else [_ip(a) for a in held.values()] if hold else [_ipn(None)] * 3
+    return out, common, held, trio
+
+
+def _stage_head(shape, Q, po, goals, deadline, K_T_max, error_tol):
+    """what dmpc_transition_mission and dmpc_transition_hold take between the context and the histories (the latter: and max_hold); shape: what
+    _commanded returns"""
+    S, N, n_cmd, _, path, M, P = shape
+    return [S, N + M, n_cmd, Q, _dp(po), _dp(goals), _ipn(deadline), _dpn(path), P, int(K_T_max), float(error_tol)]
+
+
+def _check_inputs(K_T_used, hist, KT_alloc, mask):
+    """What postcheck(), clearance() and setpoints() check.  hist = (pk, vk, ak): given histories, or pk None for the ones the last transition
+    left on the device, whose K_T_max KT_alloc then says.  Returns (K_T_used as int32, the histories as contiguous arrays, KT_alloc, run), run:
+    the arguments every post-check entry has in a row -- KT_alloc, K_T_used, mask, pk, vk, ak."""
+    used = np.ascontiguousarray(np.atleast_1d(K_T_used), dtype=np.int32)
+    if hist[0] is not None:
+        hist = [None if x is None else _f(x) for x in hist]
+        KT_alloc = hist[0].shape[-2]
+    else:
+        hist = [None] * 3
+    assert KT_alloc is not None
+    msk = None if mask is None else np.ascontiguousarray(np.atleast_1d(mask), dtype=np.int32)
+    return used, hist, KT_alloc, [int(KT_alloc), _ip(used), _ipn(msk)] + [_dpn(x) for x in hist]
+
+
+def _other_vehicles(what, pf_shape, po_static, path):
+    """The vehicles postcheck() and clearance() check the commanded agents of pf against: po_static [S,M,3] (or [M,3]), resting, or path
+    [S,M,P,3], scripted, never both.  Returns (po_static, None where M = 0; path; M; P)."""
+    if path is not None and po_static is not None:
+        raise DmpcError(f"{what}: path and po_static exclude each other (scripted vehicles move, static ones rest)")
+    lead = tuple(pf_shape[:-1])
+    if path is not None:
+        return (None,) + _path(path, lead, what)
+    if po_static is None:
+        return None, None, 0, 0
+    pos = _f(po_static)
+    if pos.shape[:-2] != lead[:-1] or pos.shape[-1] != 3:
+        raise DmpcError(f"{what}: po_static {pos.shape} does not batch like pf {tuple(pf_shape)}")
+    return (pos if pos.shape[-2] else None), None, pos.shape[-2], 0
 
 
 def _disturbance(noise_p=0.0, noise_v=0.0, wind=None, pushes=None, seed=0):
@@ -498,23 +626,6 @@ class Dmpc:
         k = min(int(nr[0]), max_rows)
         return dict(xi=xi[:k], rhs=rhs[:k], slack_coef=sc[:k], kc=kc[:k], nrows=int(nr[0]), viol_k=int(vk[0]), status=int(st[0]))
 
-    def _transition_hold(self, S, N, n_cmd, Q, po, goals, deadline, path, P, K_T_max, error_tol, max_hold, lead, histories):
-        """dmpc_transition_hold on prepared arrays (lead: the leading shape of the per-agent outputs); what mission() returns, and hold_count,
-        hold_first [lead], agent_status [lead, K_T_max]"""
-        nul, inul = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
-        used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
-        stage_col = np.zeros((S, Q), dtype=np.int32)
-        cnt, first = np.zeros(lead, dtype=np.int32), np.zeros(lead, dtype=np.int32)
-        log = np.zeros(lead + (K_T_max,), dtype=np.int32)
-        pk = vk = ak = None
-        if histories:
-            pk, vk, ak = (np.zeros(lead + (K_T_max, 3)) for _ in range(3))
-        self._chk(self._L.dmpc_transition_hold(self._ctx, S, N, n_cmd, Q, _dp(po), _dp(goals), _ip(deadline) if deadline is not None else inul,
-                                               _dp(path) if path is not None else nul, P, int(K_T_max), float(error_tol), int(max_hold),
-                                               _dp(pk) if histories else nul, _dp(vk) if histories else nul, _dp(ak) if histories else nul,
-                                               _ip(used), _ip(sst), _ip(stage_col), _ip(cnt), _ip(first), _ip(log)))
-        return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, stage_col=stage_col, hold_count=cnt, hold_first=first, agent_status=log)
-
     def assign(self, po, goals, eps=None, max_rounds=0):
         """dmpc_assign_goals: which agent takes which goal.  po, goals [S,N,3] (or [N,3]); the permutation that minimises the sum of
         |E1 (po_i - goals_perm[i])|^2, E1 = diag(1,1,1/c) of the context's parameters, by the forward auction include/dmpc_hip.h pins, to within
@@ -553,13 +664,30 @@ class Dmpc:
                                            _dp(pf), _dp(price), _dp(cost), _ip(rounds)))
         return dict(perm=perm, owner=owner, pf=pf, price=price, cost=cost, rounds=rounds)
 
-    def _assigned(self, what, start, goals, rect=False):
-        """assign() -- rect: assign_rect() -- for transition() / mission(): a scene that met the round cap has no labelling to fly"""
-        a = self.assign_rect(start, goals) if rect else self.assign(start, goals)
-        if (np.asarray(a["rounds"]) < 0).any():
-            raise DmpcError(f"{what}: the goal assignment met its round cap")
-        return a
+    def _assigned(self, what, start, stages, rect):
+        """The assignment pre-pass of transition() / mission(): assign() -- rect: assign_rect() -- of the agents at start [..,n,3] to each goal set
+        of `stages` in turn, the assigned goals of one stage being the starts of the next.  Returns (the goals to fly per stage, {perm: per stage,
+        and owner: per stage when rect}); a scene that met the round cap has no labelling to fly."""
+        flown, labels = [], {k: [] for k in (("perm", "owner") if rect else ("perm",))}
+        for goals in stages:
+            a = self.assign_rect(start, goals) if rect else self.assign(start, goals)
+            if (np.asarray(a["rounds"]) < 0).any():
+                raise DmpcError(f"{what}: the goal assignment met its round cap")
+            start = a["pf"]
+            flown.append(start)
+            for k in labels:
+                labels[k].append(a[k])
+        return flown, labels
 
+    def _fly(self, entry, head, outputs, tail=(), extra=()):
+        """The one flight call: entry(context, *head, pk, vk, ak, K_T_used, scene_status, *tail, and the hold record where the entry has one), on
+        outputs = _flight_outputs(...); head and tail: the entry's own arguments before and behind those.  Returns the result dict: the common
+        outputs, then extra (the method's own keys), then the hold record."""
+        out, common, held, trio = outputs
+        self._chk(entry(self._ctx, *head, *common, *tail, *trio))
+        return {**out, **dict(extra), **held}
+
+    @_disturbable
     def transition(self, po, pf, K_T_max, error_tol=0.01, histories=True, path=None, on_fail="stop", max_hold=14, assign=False, disturb=None):
         """disturb: a dict of set_disturbance()'s arguments, in force for this call alone (with assign too); None: the context's standing setting.
         histories=False: pk/vk/ak are not downloaded (they stay on the device for postcheck()).
@@ -574,71 +702,47 @@ class Dmpc:
         behind the first N_cmd are not commanded and stay at po as static obstacles; histories, K_T_used and scene_status cover the commanded ones.
         path [S,M,P,3] (or [M,P,3]; dmpc_transition_scripted): M scripted vehicles behind the commanded agents of po / pf (same agent count in
         both), sample t of a path = the vehicle's position at history column t, held at its last sample once the path has ended."""
-        if disturb is not None:
-            with self._disturbed(disturb):
-                return self.transition(po, pf, K_T_max, error_tol, histories, path, on_fail, max_hold, assign)
         po, pf = _f(po), _f(pf)
-        if isinstance(assign, str) or assign not in (True, False):
-            if assign != "rect":
-                raise DmpcError(f"transition: assign is False, True or 'rect', not {assign!r}")
-            if pf.ndim != po.ndim or pf.ndim not in (2, 3) or pf.shape[-1] != 3 or po.shape[-1] != 3 or pf.shape[:-2] != po.shape[:-2]:
-                raise DmpcError(f"transition: with assign='rect', po {tuple(po.shape)} must be [S,N,3] and the goals {tuple(pf.shape)} [S,M,3]")
-            a = self._assigned("transition", po, pf, rect=True)
-            out = self.transition(po, a["pf"], K_T_max, error_tol, histories, path, on_fail, max_hold)
-            out["perm"], out["owner"] = a["perm"], a["owner"]
-            return out
+        assign, rect = _assign_mode("transition", assign)
         if assign:
-            if pf.size == po.size:
-                pf = pf.reshape(po.shape)
-            if pf.ndim != po.ndim or pf.ndim not in (2, 3) or pf.shape[-1] != 3 or pf.shape[-2] > po.shape[-2]:
-                raise DmpcError(f"transition: with assign, pf {tuple(pf.shape)} must cover the first agents of po {tuple(po.shape)}")
-            a = self._assigned("transition", po[..., :pf.shape[-2], :], pf)
-            out = self.transition(po, a["pf"], K_T_max, error_tol, histories, path, on_fail, max_hold)
-            out["perm"] = a["perm"]
+            if rect:
+                if pf.ndim != po.ndim or pf.ndim not in (2, 3) or pf.shape[-1] != 3 or po.shape[-1] != 3 or pf.shape[:-2] != po.shape[:-2]:
+                    raise DmpcError(f"transition: with assign='rect', po {tuple(po.shape)} must be [S,N,3] and the goals {tuple(pf.shape)} [S,M,3]")
+                start = po
+            else:
+                if pf.size == po.size:
+                    pf = pf.reshape(po.shape)
+                if pf.ndim != po.ndim or pf.ndim not in (2, 3) or pf.shape[-1] != 3 or pf.shape[-2] > po.shape[-2]:
+                    raise DmpcError(f"transition: with assign, pf {tuple(pf.shape)} must cover the first agents of po {tuple(po.shape)}")
+                start = po[..., :pf.shape[-2], :]
+            flown, labels = self._assigned("transition", start, [pf], rect)
+            out = self.transition(po, flown[0], K_T_max, error_tol, histories, path, on_fail, max_hold)
+            out.update((k, v[0]) for k, v in labels.items())
             return out
-        if on_fail not in ("stop", "hold"):
-            raise DmpcError(f"transition: on_fail is 'stop' or 'hold', not {on_fail!r}")
+        hold = _on_fail("transition", on_fail)
         if path is not None:
             if po.shape != pf.shape or po.ndim not in (2, 3) or po.shape[-1] != 3:
                 raise DmpcError(f"transition: with path, po {tuple(po.shape)} and pf {tuple(pf.shape)} must cover the same commanded agents")
-            shp = po.shape[:-1]
-            path, M, P = _path(path, shp, "transition")
-            S, n_cmd = (1, shp[0]) if len(shp) == 1 else shp
-            if on_fail == "hold":   # (pf [S][N_cmd][3] is goals [S][1][N_cmd][3])
-                out = self._transition_hold(S, n_cmd + M, n_cmd, 1, po, pf, None, path, P, K_T_max, error_tol, max_hold, shp, histories)
-                del out["stage_col"]
-                return out
-            used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
-            nul = C.POINTER(C.c_double)()
-            pk = vk = ak = None
-            if histories:
-                pk, vk, ak = (np.zeros(shp + (K_T_max, 3)) for _ in range(3))
-            self._chk(self._L.dmpc_transition_scripted(self._ctx, S, n_cmd, M, P, _dp(po), _dp(pf), _dp(path), int(K_T_max), float(error_tol),
-                                                       _dp(pk) if histories else nul, _dp(vk) if histories else nul, _dp(ak) if histories else nul,
-                                                       _ip(used), _ip(sst)))
-            return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst)
-        S, N, n_cmd, shp = _n_cmd(po.shape[:-1], pf, "transition")
-        if on_fail == "hold":
-            out = self._transition_hold(S, N, n_cmd, 1, po, pf, None, None, 0, K_T_max, error_tol, max_hold, shp, histories)
-            del out["stage_col"]
-            return out
-        used = np.zeros(S, dtype=np.int32)
-        sst = np.zeros(S, dtype=np.int32)
-        if histories:
-            pk = np.zeros(shp + (K_T_max, 3))
-            vk, ak = np.zeros_like(pk), np.zeros_like(pk)
-            hp = (_dp(pk), _dp(vk), _dp(ak))
+            lead = po.shape[:-1]
+            path, M, P = _path(path, lead, "transition")
+            S, n_cmd = (1, lead[0]) if len(lead) == 1 else lead
+            N = n_cmd
         else:
-            pk = vk = ak = None
-            hp = (C.POINTER(C.c_double)(),) * 3
-        if n_cmd == N:
-            self._chk(self._L.dmpc_transition(self._ctx, S, N, _dp(po), _dp(pf), int(K_T_max), float(error_tol), hp[0], hp[1], hp[2],
-                                              _ip(used), _ip(sst)))
+            S, N, n_cmd, lead = _n_cmd(po.shape[:-1], pf, "transition")
+            M = P = 0
+        outputs = _flight_outputs(S, lead, K_T_max, histories, True if hold else None)
+        if hold:   # (pf [S][N_cmd][3] is goals [S][1][N_cmd][3]; stage_col is mission()'s to return)
+            head = _stage_head((S, N, n_cmd, lead, path, M, P), 1, po, pf, None, K_T_max, error_tol)
+            return self._fly(self._L.dmpc_transition_hold, head + [int(max_hold)], outputs, [_ip(np.zeros((S, 1), dtype=np.int32))])
+        if path is not None:
+            entry, head = self._L.dmpc_transition_scripted, [S, n_cmd, M, P, _dp(po), _dp(pf), _dp(path)]
+        elif n_cmd < N:
+            entry, head = self._L.dmpc_transition_cmd, [S, N, n_cmd, _dp(po), _dp(pf)]
         else:
-            self._chk(self._L.dmpc_transition_cmd(self._ctx, S, N, n_cmd, _dp(po), _dp(pf), int(K_T_max), float(error_tol), hp[0], hp[1], hp[2],
-                                                  _ip(used), _ip(sst)))
-        return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst)
+            entry, head = self._L.dmpc_transition, [S, N, _dp(po), _dp(pf)]
+        return self._fly(entry, head + [int(K_T_max), float(error_tol)], outputs)
 
+    @_disturbable
     def mission(self, po, goals, K_T_max, error_tol=0.01, histories=True, deadline=None, path=None, on_fail="stop", max_hold=14, assign=False,
                 disturb=None):
         """disturb: as transition().
@@ -651,65 +755,31 @@ class Dmpc:
         assigned goals of stage q are the starts of stage q+1 -- and the dict also has perm [S,Q,N_cmd].  assign="rect": goals [S,Q,M,3] with any
         M >= 1, all N agents of po commanded; assign_rect() stage by stage from the previous stage's assigned targets (po for stage 0), an agent
         without a goal in a stage keeps its previous target; the dict also has perm [S,Q,N] and owner [S,Q,M]."""
-        if disturb is not None:
-            with self._disturbed(disturb):
-                return self.mission(po, goals, K_T_max, error_tol, histories, deadline, path, on_fail, max_hold, assign)
         po, goals = _f(po), _f(goals)
-        if on_fail not in ("stop", "hold"):
-            raise DmpcError(f"mission: on_fail is 'stop' or 'hold', not {on_fail!r}")
-        if po.ndim not in (2, 3) or goals.ndim != po.ndim + 1 or po.shape[-1] != 3 or goals.shape[-1] != 3 or goals.shape[:-3] != po.shape[:-2]:
-            raise DmpcError(f"mission: goals {tuple(goals.shape)} must be [Q,N_cmd,3] next to po [N,3], or [S,Q,N_cmd,3] next to po [S,N,3]: po is {tuple(po.shape)}")
-        if isinstance(assign, str) or assign not in (True, False):
-            if assign != "rect":
-                raise DmpcError(f"mission: assign is False, True or 'rect', not {assign!r}")
-            if goals.shape[-2] < 1:
-                raise DmpcError(f"mission: with assign='rect', goals {tuple(goals.shape)} must hold at least one point per stage")
-            start, flown, perms, owners = po, np.empty(po.shape[:-2] + (goals.shape[-3],) + po.shape[-2:]), [], []
-            for q in range(goals.shape[-3]):
-                a = self._assigned("mission", start, goals[..., q, :, :], rect=True)
-                start = flown[..., q, :, :] = a["pf"]
-                perms.append(a["perm"])
-                owners.append(a["owner"])
-            out = self.mission(po, flown, K_T_max, error_tol, histories, deadline, path, on_fail, max_hold)
-            out["perm"], out["owner"] = np.stack(perms, axis=-2), np.stack(owners, axis=-2)
-            return out
+        hold = _on_fail("mission", on_fail)
+        _cmd_shape("mission", po, goals, "Q,N_cmd,3", "goals", last=False)   # (last: a mission without agents is refused by their count, below)
+        assign, rect = _assign_mode("mission", assign)
         if assign:
-            if not 1 <= goals.shape[-2] <= po.shape[-2]:
+            if rect and goals.shape[-2] < 1:
+                raise DmpcError(f"mission: with assign='rect', goals {tuple(goals.shape)} must hold at least one point per stage")
+            if not rect and not 1 <= goals.shape[-2] <= po.shape[-2]:
                 raise DmpcError(f"mission: goals have {goals.shape[-2]} agents, po {po.shape[-2]}: the commanded agents are the FIRST N_cmd <= N vehicles")
-            start, flown, perms = po[..., :goals.shape[-2], :], np.empty_like(goals), []
-            for q in range(goals.shape[-3]):
-                a = self._assigned("mission", start, goals[..., q, :, :])
-                start = flown[..., q, :, :] = a["pf"]
-                perms.append(a["perm"])
-            out = self.mission(po, flown, K_T_max, error_tol, histories, deadline, path, on_fail, max_hold)
-            out["perm"] = np.stack(perms, axis=-2)
+            start = po if rect else po[..., :goals.shape[-2], :]
+            flown, labels = self._assigned("mission", start, [goals[..., q, :, :] for q in range(goals.shape[-3])], rect)
+            out = self.mission(po, np.stack(flown, axis=-3), K_T_max, error_tol, histories, deadline, path, on_fail, max_hold)
+            out.update((k, np.stack(v, axis=-2)) for k, v in labels.items())
             return out
-        S = 1 if po.ndim == 2 else po.shape[0]
-        Q, n_cmd, N = goals.shape[-3], goals.shape[-2], po.shape[-2]
-        lead = po.shape[:-2] + (n_cmd,)
-        M = P = 0
-        if path is not None:
-            if N != n_cmd:
-                raise DmpcError(f"mission: with path, po {tuple(po.shape)} and goals {tuple(goals.shape)} must cover the same commanded agents")
-            path, M, P = _path(path, lead, "mission")
-        elif n_cmd < 1 or n_cmd > N:
-            raise DmpcError(f"mission: goals have {n_cmd} agents, po {N}: the commanded agents are the FIRST N_cmd <= N vehicles")
-        nul, inul = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
+        shape = S, _, _, lead, _, _, _ = _commanded("mission", po, goals, "Q,N_cmd,3", "goals", path, last=False)
+        Q = goals.shape[-3]
         if deadline is not None:
             deadline = np.ascontiguousarray(np.broadcast_to(np.asarray(deadline, dtype=np.int32), (S, Q)))
-        if on_fail == "hold":
-            return self._transition_hold(S, N + M, n_cmd, Q, po, goals, deadline, path, P, K_T_max, error_tol, max_hold, lead, histories)
-        used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
         stage_col = np.zeros((S, Q), dtype=np.int32)
-        pk = vk = ak = None
-        if histories:
-            pk, vk, ak = (np.zeros(lead + (K_T_max, 3)) for _ in range(3))
-        self._chk(self._L.dmpc_transition_mission(self._ctx, S, N + M, n_cmd, Q, _dp(po), _dp(goals), _ip(deadline) if deadline is not None else inul,
-                                                  _dp(path) if path is not None else nul, P, int(K_T_max), float(error_tol),
-                                                  _dp(pk) if histories else nul, _dp(vk) if histories else nul, _dp(ak) if histories else nul,
-                                                  _ip(used), _ip(sst), _ip(stage_col)))
-        return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, stage_col=stage_col)
+        head = _stage_head(shape, Q, po, goals, deadline, K_T_max, error_tol)
+        entry = self._L.dmpc_transition_hold if hold else self._L.dmpc_transition_mission
+        return self._fly(entry, head + [int(max_hold)] * hold, _flight_outputs(S, lead, K_T_max, histories, hold or None), [_ip(stage_col)],
+                         dict(stage_col=stage_col))
 
+    @_disturbable
     def route(self, po, waypoints, K_T_max, capture, n_wp=None, timeout=0, error_tol=0.01, histories=True, path=None, on_fail="stop", max_hold=14,
               disturb=None):
         """disturb: as transition().
@@ -721,25 +791,10 @@ class Dmpc:
         transition(); path [S,M,P,3]: scripted vehicles, po then covers the commanded agents.  Returns what transition() returns, and wp_col
         [S,N_cmd,W]: the column on which the agent left each waypoint (-1: it never did), wp_index [S,N_cmd]: the waypoint it was flying to when
         the scene ended.  on_fail, max_hold: as transition() (a held plan counts as a solved one in the waypoint rule)."""
-        if disturb is not None:
-            with self._disturbed(disturb):
-                return self.route(po, waypoints, K_T_max, capture, n_wp, timeout, error_tol, histories, path, on_fail, max_hold)
         po, waypoints = _f(po), _f(waypoints)
-        if on_fail not in ("stop", "hold"):
-            raise DmpcError(f"route: on_fail is 'stop' or 'hold', not {on_fail!r}")
-        if (po.ndim not in (2, 3) or waypoints.ndim != po.ndim + 1 or po.shape[-1] != 3 or waypoints.shape[-1] != 3 or waypoints.shape[:-3] != po.shape[:-2]
-                or waypoints.shape[-2] < 1):
-            raise DmpcError(f"route: waypoints {tuple(waypoints.shape)} must be [N_cmd,W,3] next to po [N,3], or [S,N_cmd,W,3] next to po [S,N,3]: po is {tuple(po.shape)}")
-        S = 1 if po.ndim == 2 else po.shape[0]
-        n_cmd, W, N = waypoints.shape[-3], waypoints.shape[-2], po.shape[-2]
-        lead = po.shape[:-2] + (n_cmd,)
-        M = P = 0
-        if path is not None:
-            if N != n_cmd:
-                raise DmpcError(f"route: with path, po {tuple(po.shape)} and waypoints {tuple(waypoints.shape)} must cover the same commanded agents")
-            path, M, P = _path(path, lead, "route")
-        elif n_cmd < 1 or n_cmd > N:
-            raise DmpcError(f"route: waypoints have {n_cmd} agents, po {N}: the commanded agents are the FIRST N_cmd <= N vehicles")
+        hold = _on_fail("route", on_fail)
+        S, N, n_cmd, lead, path, M, P = _commanded("route", po, waypoints, "N_cmd,W,3", "waypoints", path)
+        W = waypoints.shape[-2]
         if n_wp is not None:
             n_wp = np.asarray(n_wp)
             if n_wp.shape != lead or not np.issubdtype(n_wp.dtype, np.integer) or n_wp.min() < 1 or n_wp.max() > W:
@@ -749,23 +804,10 @@ class Dmpc:
             raise DmpcError(f"route: capture must be > 0 (metres), not {capture!r}")
         if int(timeout) < 0:
             raise DmpcError(f"route: timeout must be >= 0 (columns; 0: none), not {timeout!r}")
-        hold = on_fail == "hold"
-        nul, inul = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
-        used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
-        wp_col, wp_index = np.zeros(lead + (W,), dtype=np.int32), np.zeros(lead, dtype=np.int32)
-        cnt, first, log = np.zeros(lead, dtype=np.int32), np.zeros(lead, dtype=np.int32), np.zeros(lead + (K_T_max,), dtype=np.int32)
-        pk = vk = ak = None
-        if histories:
-            pk, vk, ak = (np.zeros(lead + (K_T_max, 3)) for _ in range(3))
-        self._chk(self._L.dmpc_transition_route(self._ctx, S, N + M, n_cmd, W, _dp(po), _dp(waypoints), _ip(n_wp) if n_wp is not None else inul,
-                                                float(capture), int(timeout), _dp(path) if path is not None else nul, P, int(K_T_max), float(error_tol),
-                                                int(max_hold) if hold else 0, _dp(pk) if histories else nul, _dp(vk) if histories else nul,
-                                                _dp(ak) if histories else nul, _ip(used), _ip(sst), _ip(wp_col), _ip(wp_index),
-                                                _ip(cnt) if hold else inul, _ip(first) if hold else inul, _ip(log) if hold else inul))
-        out = dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, wp_col=wp_col, wp_index=wp_index)
-        if hold:
-            out.update(hold_count=cnt, hold_first=first, agent_status=log)
-        return out
+        extra = dict(wp_col=np.zeros(lead + (W,), dtype=np.int32), wp_index=np.zeros(lead, dtype=np.int32))
+        head = [S, N + M, n_cmd, W, _dp(po), _dp(waypoints), _ipn(n_wp), float(capture), int(timeout), _dpn(path), P, int(K_T_max), float(error_tol),
+                int(max_hold) if hold else 0]
+        return self._fly(self._L.dmpc_transition_route, head, _flight_outputs(S, lead, K_T_max, histories, hold), map(_ip, extra.values()), extra)
 
     def plan(self, po, goals, cell, margin=0.0, W=4, obstacles=None):
         """dmpc_plan_routes: which way round the static vehicles every commanded agent goes.  goals [S,N_cmd,3] (or [N_cmd,3]); po [S,N,3] with
@@ -797,6 +839,7 @@ class Dmpc:
                                            _ip(hops)))
         return dict(waypoints=wp, n_wp=n_wp, plan_status=st, hops=hops)
 
+    @_disturbable
     def replan(self, po, goals, K_T_max, cell, capture, margin=0.0, W=4, every=5, ahead=0, timeout=0, error_tol=0.01, histories=True, path=None,
                on_fail="stop", max_hold=14, disturb=None):
         """disturb: as transition().
@@ -806,50 +849,22 @@ class Dmpc:
         vehicles; path [S,M,P,3]: scripted ones, po then covers the commanded agents.  cell, margin, W: plan()'s; capture, timeout, on_fail,
         max_hold: route()'s.  Returns what route() returns, and waypoints [S,N_cmd,W,3], n_wp, plan_status [S,N_cmd]: the plan in force when the
         scene ended (wp_col and wp_index refer to it), replan_count [S,N_cmd], replan_col [S,N_cmd]: the last re-plan's column (-1: none)."""
-        if disturb is not None:
-            with self._disturbed(disturb):
-                return self.replan(po, goals, K_T_max, cell, capture, margin, W, every, ahead, timeout, error_tol, histories, path, on_fail, max_hold)
-        po, goals = _f(po), _f(goals)
-        if on_fail not in ("stop", "hold"):
-            raise DmpcError(f"replan: on_fail is 'stop' or 'hold', not {on_fail!r}")
-        if (po.ndim not in (2, 3) or goals.ndim != po.ndim or po.shape[-1] != 3 or goals.shape[-1] != 3 or goals.shape[:-2] != po.shape[:-2]
-                or goals.shape[-2] < 1):
-            raise DmpcError(f"replan: goals {tuple(goals.shape)} must be [N_cmd,3] next to po [N,3], or [S,N_cmd,3] next to po [S,N,3]: po is {tuple(po.shape)}")
-        S = 1 if po.ndim == 2 else po.shape[0]
-        n_cmd, N, W = goals.shape[-2], po.shape[-2], int(W)
-        lead = goals.shape[:-1]
-        M = P = 0
-        if path is not None:
-            if N != n_cmd:
-                raise DmpcError(f"replan: with path, po {tuple(po.shape)} and goals {tuple(goals.shape)} must cover the same commanded agents")
-            path, M, P = _path(path, lead, "replan")
-        elif n_cmd > N:
-            raise DmpcError(f"replan: goals have {n_cmd} agents, po {N}: the commanded agents are the FIRST N_cmd <= N vehicles")
+        po, goals, W = _f(po), _f(goals), int(W)
+        hold = _on_fail("replan", on_fail)
+        S, N, n_cmd, lead, path, M, P = _commanded("replan", po, goals, "N_cmd,3", "goals", path)
         if W < 1:
             raise DmpcError(f"replan: W must be >= 1, not {W!r}")
         if not float(capture) > 0.0:
             raise DmpcError(f"replan: capture must be > 0 (metres), not {capture!r}")
         if int(timeout) < 0 or int(every) < 0 or int(ahead) < 0:
             raise DmpcError(f"replan: timeout, every and ahead must be >= 0 (columns), not {timeout!r}, {every!r}, {ahead!r}")
-        hold = on_fail == "hold"
-        nul, inul = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
-        used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
         wp, wp_col = np.zeros(lead + (W, 3)), np.zeros(lead + (W,), dtype=np.int32)
         n_wp, pst, wp_index, rcnt, rcol = (np.zeros(lead, dtype=np.int32) for _ in range(5))
-        cnt, first, log = np.zeros(lead, dtype=np.int32), np.zeros(lead, dtype=np.int32), np.zeros(lead + (K_T_max,), dtype=np.int32)
-        pk = vk = ak = None
-        if histories:
-            pk, vk, ak = (np.zeros(lead + (K_T_max, 3)) for _ in range(3))
-        self._chk(self._L.dmpc_transition_replan(self._ctx, S, N + M, n_cmd, W, _dp(po), _dp(goals), float(cell), float(margin), int(every), int(ahead),
-                                                 float(capture), int(timeout), _dp(path) if path is not None else nul, P, int(K_T_max), float(error_tol),
-                                                 int(max_hold) if hold else 0, _dp(pk) if histories else nul, _dp(vk) if histories else nul,
-                                                 _dp(ak) if histories else nul, _ip(used), _ip(sst), _dp(wp), _ip(n_wp), _ip(pst), _ip(wp_col), _ip(wp_index),
-                                                 _ip(rcnt), _ip(rcol), _ip(cnt) if hold else inul, _ip(first) if hold else inul, _ip(log) if hold else inul))
-        out = dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, wp_col=wp_col, wp_index=wp_index, waypoints=wp, n_wp=n_wp, plan_status=pst,
-                   replan_count=rcnt, replan_col=rcol)
-        if hold:
-            out.update(hold_count=cnt, hold_first=first, agent_status=log)
-        return out
+        head = [S, N + M, n_cmd, W, _dp(po), _dp(goals), float(cell), float(margin), int(every), int(ahead), float(capture), int(timeout), _dpn(path), P,
+                int(K_T_max), float(error_tol), int(max_hold) if hold else 0]
+        tail = [_dp(wp), _ip(n_wp), _ip(pst), _ip(wp_col), _ip(wp_index), _ip(rcnt), _ip(rcol)]
+        extra = dict(wp_col=wp_col, wp_index=wp_index, waypoints=wp, n_wp=n_wp, plan_status=pst, replan_count=rcnt, replan_col=rcol)
+        return self._fly(self._L.dmpc_transition_replan, head, _flight_outputs(S, lead, K_T_max, histories, hold), tail, extra)
 
     # ---- multi-GPU (one process per GPU): dmpc_multigpu.hip ----
     @staticmethod
@@ -882,16 +897,9 @@ class Dmpc:
         po, pf = _f(po), _f(pf)
         S, N = po.shape[0], po.shape[1]
         lo, cnt, cmax = partition(N, getattr(self, "nranks", 1), getattr(self, "rank", 0))
-        used, sst = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
-        if histories:
-            pk = np.zeros((S, cnt, K_T_max, 3)); vk, ak = np.zeros_like(pk), np.zeros_like(pk)
-            hp = (_dp(pk), _dp(vk), _dp(ak))
-        else:
-            pk = vk = ak = None
-            hp = (C.POINTER(C.c_double)(),) * 3
-        fn = self._L.dmpc_transition_sharded_gather if gather else self._L.dmpc_transition_sharded
-        self._chk(fn(self._ctx, S, N, _dp(po), _dp(pf), int(K_T_max), float(error_tol), hp[0], hp[1], hp[2], _ip(used), _ip(sst)))
-        return dict(pk=pk, vk=vk, ak=ak, K_T_used=used, scene_status=sst, lo=lo, count=cnt)
+        entry = self._L.dmpc_transition_sharded_gather if gather else self._L.dmpc_transition_sharded
+        return self._fly(entry, [S, N, _dp(po), _dp(pf), int(K_T_max), float(error_tol)], _flight_outputs(S, (S, cnt), K_T_max, histories),
+                         extra=dict(lo=lo, count=cnt))
 
     def postcheck(self, K_T_used, pf, pk=None, vk=None, ak=None, KT_alloc=None, vmax=2.0, amax=1.0, Ts=0.01, interp=False,
                   mask=None, po_static=None, path=None):
@@ -901,63 +909,35 @@ class Dmpc:
         agents'): the result gains min_dist_static / violation_static, the commanded-against-static check; everything else is unchanged.
         path [S,M,P,3] (or [M,P,3]; dmpc_postcheck_scripted, not together with po_static): M scripted vehicles, splined on the commanded agents'
         knots; the result gains min_dist_scripted / violation_scripted and, with interp, p_scripted [S,M,ns,3]."""
-        if path is not None and po_static is not None:
-            raise DmpcError("postcheck: path and po_static exclude each other (scripted vehicles move, static ones rest)")
         pf = _f(pf)
-        shp = pf.shape[:-1]
-        S, N = (1, shp[0]) if len(shp) == 1 else shp
-        used = np.ascontiguousarray(np.atleast_1d(K_T_used), dtype=np.int32)
-        if pk is not None:
-            pk, vk, ak = _f(pk), _f(vk), _f(ak)
-            KT_alloc = pk.shape[-2]
-        assert KT_alloc is not None
+        pos, path, M, P = _other_vehicles("postcheck", pf.shape, po_static, path)
+        used, hist, KT_alloc, run = _check_inputs(K_T_used, (pk, vk, ak), KT_alloc, mask)
+        S, N = (1, pf.shape[0]) if pf.ndim == 2 else pf.shape[:-1]
         out = dict(r_factor=np.zeros(S), h_scaled=np.zeros(S), n_samples=np.zeros(S, dtype=np.int32), min_dist=np.zeros(S),
                    violation=np.zeros(S, dtype=np.int32), totdist=np.zeros(S), traj_time=np.zeros(S))
-        ns_alloc, p_i = 0, None
+        ns_alloc, p_i, p_s = 0, None, None
         if interp:   # upper bound of the sample count: r_factor is not known yet, so run once without and size from it
-            pre = self.postcheck(K_T_used, pf, pk, vk, ak, KT_alloc, vmax, amax, Ts, False, mask)   # (sizes only: no static pass)
+            pre = self.postcheck(used, pf, *hist, KT_alloc, vmax, amax, Ts, False, mask)   # (sizes only: no static pass)
             ns_alloc = max(int(pre["n_samples"].max()), 1)
             p_i = np.zeros((S, N, ns_alloc, 3))
-        nul = C.POINTER(C.c_double)()
-        msk = None if mask is None else np.ascontiguousarray(np.atleast_1d(mask), dtype=np.int32)
         if path is not None:
-            path, M, P = _path(path, shp, "postcheck")
             out["min_dist_scripted"], out["violation_scripted"] = np.zeros(S), np.zeros(S, dtype=np.int32)
-            p_s = np.zeros((S, M, ns_alloc, 3)) if p_i is not None else None
-            self._chk(self._L.dmpc_postcheck_scripted(self._ctx, S, N + M, N, int(KT_alloc), _ip(used),
-                                                      _ip(msk) if msk is not None else C.POINTER(C.c_int32)(), _dp(pk) if pk is not None else nul,
-                                                      _dp(vk) if pk is not None else nul, _dp(ak) if pk is not None else nul, _dp(pf), _dp(path), P,
-                                                      float(vmax), float(amax), float(Ts), _dp(out["r_factor"]), _dp(out["h_scaled"]),
-                                                      _ip(out["n_samples"]), _dp(out["min_dist"]), _ip(out["violation"]), _dp(out["totdist"]),
-                                                      _dp(out["traj_time"]), _dp(p_i) if p_i is not None else nul, ns_alloc,
-                                                      _dp(out["min_dist_scripted"]), _ip(out["violation_scripted"]), _dp(p_s) if p_s is not None else nul))
-            if p_i is not None:
-                out["p"], out["p_scripted"] = p_i, p_s
-            return out
-        if po_static is not None:
-            pos = _f(po_static)
-            if pos.shape[:-2] != shp[:-1] or pos.shape[-1] != 3:
-                raise DmpcError(f"postcheck: po_static {pos.shape} does not batch like pf {pf.shape}")
-            M = pos.shape[-2]
+            p_s = np.zeros((S, M, ns_alloc, 3)) if interp else None
+            entry, dims, others = self._L.dmpc_postcheck_scripted, [S, N + M, N], [_dp(path), P]
+            tail = [_dp(out["min_dist_scripted"]), _ip(out["violation_scripted"]), _dpn(p_s)]
+        elif po_static is not None:
             out["min_dist_static"], out["violation_static"] = np.zeros(S), np.zeros(S, dtype=np.int32)
-            self._chk(self._L.dmpc_postcheck_cmd(self._ctx, S, N + M, N, int(KT_alloc), _ip(used),
-                                                 _ip(msk) if msk is not None else C.POINTER(C.c_int32)(), _dp(pk) if pk is not None else nul,
-                                                 _dp(vk) if pk is not None else nul, _dp(ak) if pk is not None else nul, _dp(pf),
-                                                 _dp(pos) if M else nul, float(vmax), float(amax), float(Ts), _dp(out["r_factor"]), _dp(out["h_scaled"]),
-                                                 _ip(out["n_samples"]), _dp(out["min_dist"]), _ip(out["violation"]), _dp(out["totdist"]),
-                                                 _dp(out["traj_time"]), _dp(p_i) if p_i is not None else nul, ns_alloc,
-                                                 _dp(out["min_dist_static"]), _ip(out["violation_static"])))
-            if p_i is not None:
-                out["p"] = p_i
-            return out
-        self._chk(self._L.dmpc_postcheck(self._ctx, S, N, int(KT_alloc), _ip(used),
-                                         _ip(msk) if msk is not None else C.POINTER(C.c_int32)(), _dp(pk) if pk is not None else nul,
-                                         _dp(vk) if pk is not None else nul, _dp(ak) if pk is not None else nul, _dp(pf),
-                                         float(vmax), float(amax), float(Ts), _dp(out["r_factor"]), _dp(out["h_scaled"]),
-                                         _ip(out["n_samples"]), _dp(out["min_dist"]), _ip(out["violation"]), _dp(out["totdist"]),
-                                         _dp(out["traj_time"]), _dp(p_i) if p_i is not None else nul, ns_alloc))
-        if p_i is not None:
+            entry, dims, others = self._L.dmpc_postcheck_cmd, [S, N + M, N], [_dpn(pos)]
+            tail = [_dp(out["min_dist_static"]), _ip(out["violation_static"])]
+        else:
+            entry, dims, others, tail = self._L.dmpc_postcheck, [S, N], [], []
+        self._chk(entry(self._ctx, *dims, *run, _dp(pf), *others, float(vmax), float(amax), float(Ts), _dp(out["r_factor"]), _dp(out["h_scaled"]),
+                        _ip(out["n_samples"]), _dp(out["min_dist"]), _ip(out["violation"]), _dp(out["totdist"]), _dp(out["traj_time"]), _dpn(p_i),
+                        ns_alloc, *tail))
+        if interp:
             out["p"] = p_i
+            if path is not None:
+                out["p_scripted"] = p_s
         return out
 
     def clearance(self, K_T_used, pf, pk=None, vk=None, ak=None, KT_alloc=None, vmax=2.0, amax=1.0, Ts=0.01, mask=None, po_static=None,
@@ -966,32 +946,14 @@ class Dmpc:
         the 100 Hz samples of postcheck(), and when.  The leading arguments are postcheck()'s (pf gives the shape only).  Returns
         dict(dist [S,N_cmd,2], partner (0-based in the table: commanded agents first), sample, time = sample * Ts, NaN where there is no sample).
         reach: slots with a distance < reach are exact, the others report inf / -1 / -1 (inf: all exact); masked scenes NaN / -1 / -1."""
-        if path is not None and po_static is not None:
-            raise DmpcError("clearance: path and po_static exclude each other (scripted vehicles move, static ones rest)")
-        shp = np.shape(pf)[:-1]
-        S, N = (1, shp[0]) if len(shp) == 1 else shp
-        used = np.ascontiguousarray(np.atleast_1d(K_T_used), dtype=np.int32)
-        if pk is not None:
-            pk, vk, ak = _f(pk), _f(vk), _f(ak)
-            KT_alloc = pk.shape[-2]
-        assert KT_alloc is not None
-        nul = C.POINTER(C.c_double)()
-        msk = None if mask is None else np.ascontiguousarray(np.atleast_1d(mask), dtype=np.int32)
-        M, P, pos = 0, 0, None
-        if path is not None:
-            path, M, P = _path(path, shp, "clearance")
-        elif po_static is not None:
-            pos = _f(po_static)
-            if pos.shape[:-2] != tuple(shp[:-1]) or pos.shape[-1] != 3:
-                raise DmpcError(f"clearance: po_static {pos.shape} does not batch like pf {np.shape(pf)}")
-            M = pos.shape[-2]
+        shp = np.shape(pf)
+        pos, path, M, P = _other_vehicles("clearance", shp, po_static, path)
+        used, hist, KT_alloc, run = _check_inputs(K_T_used, (pk, vk, ak), KT_alloc, mask)
+        S, N = (1, shp[0]) if len(shp) == 2 else shp[:-1]
         dist = np.zeros((S, N, 2))
         partner, sample = np.zeros((S, N, 2), dtype=np.int32), np.zeros((S, N, 2), dtype=np.int32)
-        self._chk(self._L.dmpc_postcheck_clearance(self._ctx, S, N + M, N, int(KT_alloc), _ip(used),
-                                                   _ip(msk) if msk is not None else C.POINTER(C.c_int32)(), _dp(pk) if pk is not None else nul,
-                                                   _dp(vk) if pk is not None else nul, _dp(ak) if pk is not None else nul,
-                                                   _dp(pos) if pos is not None and M else nul, _dp(path) if path is not None else nul, P,
-                                                   float(vmax), float(amax), float(Ts), float(reach), _dp(dist), _ip(partner), _ip(sample)))
+        self._chk(self._L.dmpc_postcheck_clearance(self._ctx, S, N + M, N, *run, _dpn(pos), _dpn(path), P, float(vmax), float(amax), float(Ts),
+                                                   float(reach), _dp(dist), _ip(partner), _ip(sample)))
         return dict(dist=dist, partner=partner, sample=sample, time=np.where(sample >= 0, sample * float(Ts), np.nan))
 
     def setpoints(self, K_T_used, N=None, pk=None, vk=None, ak=None, KT_alloc=None, vmax=2.0, amax=1.0, Ts=0.01, mask=None, first=0, count=None,
@@ -1001,29 +963,24 @@ class Dmpc:
         h_scaled, n_samples [S] of postcheck().  pk/vk/ak [S,N,KT_alloc,3] (or [N,KT,3]); None: the resident histories of the last transition
         (then N and KT_alloc say their shape).  count=None: the window runs from `first` to the largest n_samples (sized by a report-only
         call, as postcheck(interp=True) sizes p).  report_only: no p, v, a."""
-        used = np.ascontiguousarray(np.atleast_1d(K_T_used), dtype=np.int32)
+        used, hist, KT_alloc, run = _check_inputs(K_T_used, (pk, vk, ak), KT_alloc, mask)
         S = used.size
-        if pk is not None:
-            pk, vk, ak = (None if x is None else _f(x) for x in (pk, vk, ak))
-            N, KT_alloc = pk.shape[-3], pk.shape[-2]
-        assert N is not None and KT_alloc is not None
-        nul, inul = C.POINTER(C.c_double)(), C.POINTER(C.c_int32)()
-        msk = None if mask is None else np.ascontiguousarray(np.atleast_1d(mask), dtype=np.int32)
+        if hist[0] is not None:
+            N = hist[0].shape[-3]
+        assert N is not None
         if report_only:
             count = 0
         elif count is None:
-            pre = self.setpoints(used, N, pk, vk, ak, KT_alloc, vmax, amax, Ts, mask, report_only=True)
+            pre = self.setpoints(used, N, *hist, KT_alloc, vmax, amax, Ts, mask, report_only=True)
             count = max(int(pre["n_samples"].max()) - int(first), 1)
         count = int(count)
         out = dict(v_peak=np.zeros((S, N)), v_peak_sample=np.zeros((S, N), dtype=np.int32), a_peak=np.zeros((S, N)),
                    a_peak_sample=np.zeros((S, N), dtype=np.int32), r_factor=np.zeros(S), h_scaled=np.zeros(S), n_samples=np.zeros(S, dtype=np.int32))
-        sp = None if report_only else [np.zeros((S, N, count, 3)) for _ in range(3)]
-        opt = lambda x: _dp(x) if x is not None else nul
-        self._chk(self._L.dmpc_postcheck_setpoints(self._ctx, S, int(N), int(KT_alloc), _ip(used), _ip(msk) if msk is not None else inul, opt(pk), opt(vk),
-                                                   opt(ak), float(vmax), float(amax), float(Ts), int(first), count, *(3 * [nul] if sp is None else map(_dp, sp)),
+        sp = [None] * 3 if report_only else [np.zeros((S, N, count, 3)) for _ in range(3)]
+        self._chk(self._L.dmpc_postcheck_setpoints(self._ctx, S, int(N), *run, float(vmax), float(amax), float(Ts), int(first), count, *map(_dpn, sp),
                                                    _dp(out["v_peak"]), _ip(out["v_peak_sample"]), _dp(out["a_peak"]), _ip(out["a_peak_sample"]),
                                                    _dp(out["r_factor"]), _dp(out["h_scaled"]), _ip(out["n_samples"])))
-        if sp is not None:
+        if not report_only:
             out["p"], out["v"], out["a"] = sp
         return out
 
