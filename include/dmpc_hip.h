@@ -856,6 +856,57 @@ DMPC_API int dmpc_set_disturbance(dmpc_ctx *ctx, const dmpc_disturbance *d);
 DMPC_API int dmpc_disturbance_sample(const dmpc_disturbance *d, double h, int S, int N_cmd, int k, double *dp, double *dv);
 DMPC_API int dmpc_disturb_device(dmpc_ctx *ctx, int S, int N_cmd, int k, double *x_p, double *x_v, const int32_t *scene_done, void *stream);
 
+/* Start in motion (additive, the ABI revision stays 8): A FLIGHT FROM A GIVEN OR CARRIED STATE AND PLAN.  NO REFERENCE COUNTERPART: the
+ * reference flies one leg, every agent at rest at the start.  A start is a one-shot SETTING OF THE CONTEXT.
+ * THE START IS CONSUMED BY ONE FLIGHT: the next of dmpc_transition, _cmd, _scripted, _mission, _hold, _route, _replan that passes its own
+ * argument checks uses it and clears it; a refused call leaves it armed; with none armed every entry launches what it launched before and
+ * returns the same bytes.
+ *   column 0  of that flight, instead of initDMPC: for every commanded agent x_p = its row of the call's po, x_v = vo, x_a = ao (history column
+ *             0 records these); its column of the first table = plan_p [3K], entry kk where it expects to be on column kk (entry 0 is not
+ *             checked against x_p: a disturbed state is not on its plan).  Hold mode: the "previous plan" of column 1 is (plan_p, plan_v,
+ *             plan_a); plan_v / plan_a absent: zeros; the run counters start at 0.  Uncommanded vehicles as ever.
+ *   no plan   (plan_p NULL): THE BRAKING PLAN, made on the device, per agent and axis, in fp64, every operation rounded on its own (no fused
+ *             multiply-add) -- the hold policy's braking tail K-1 times:
+ *               p[0] = x_p, v[0] = x_v, a[0] = x_a;   for kk = 1 .. K-1:
+ *               a[kk] = min(max(-v[kk-1] / h, -alim), alim);  v[kk] = v[kk-1] + h * a[kk];  p[kk] = (p[kk-1] + h * v[kk-1]) + ((0.5 * h) * h) * a[kk]
+ *             dmpc_start_plan is the rule on the host (no context, no GPU), dmpc_start_plan_device its kernel on device rows [n][3K] for
+ *             callers of dmpc_step_device_cmd; tests/start.py restates it; the three agree bit for bit.  n states [n][3]; any output NULL.
+ *   col0      COLUMN 0 IS THE CALLER'S COLUMN col0: local column k is the caller's column col0 + k in exactly two places -- the scripted window
+ *             is sample(j, col0 + k-1+kk), and the disturbance rule uses col0 + k for the stream counter and for a push's column.  Local column
+ *             0 is never disturbed.  Deadlines, timeouts, K_T_used, stage_col, wp_col, hold_first and the histories count local columns.
+ *   behind column 0 everything is the entry's own loop: ReachedGoal on column 0 against the new goals (a scene can end there), the stop rule,
+ *             the mission / route / re-plan rules (dmpc_transition_replan plans its first routes from the start's positions), hold, disturbance.
+ *   the end   of a flight: scene s ends on column e = K_T_used[s] - 1; its end is x_p, x_v, x_a of column e, every commanded agent's plan of
+ *             the step that produced column e (e = 0: the plan column 0 was built from) and col = col0 + e.  Kept for scenes that ended
+ *             DMPC_ST_SOLVED (with or without _REACHED, _HELD), until the next call on the context that uses the step scratch (any step or
+ *             transition entry; not the post-checks).  dmpc_flight_end copies it to the host ([S][N_cmd][3],
+ *             [S][N_cmd][3K], [S]; any output NULL).
+ *   from_end  = 1: the start is the end of this context's last flight, gathered ON THE DEVICE when dmpc_set_start is called (so later calls may
+ *             reuse the scratch): scene s starts where scene src_scene[s] of that flight ended (NULL: identity, S equal), col0 is added to
+ *             that end's col.  vo, ao and the plans must be NULL; the commanded rows of the flight's po are ignored (they must still be
+ *             passed), the uncommanded rows are read as ever.
+ * Batch split as dmpc_transition (results do not depend on it); src_scene on the end of a split flight is refused.  A DMPC_DEVICE_ALL context
+ * runs a flight with a start on its first GPU; from_end and dmpc_flight_end after a sharded flight are refused;
+ * dmpc_transition_sharded[_gather] refuse while a start is armed; there is no RCCL form.
+ * Refused (-1, nothing launched, a message that starts with the entry's name): S or N_cmd < 1, col0 < 0, plan_v without plan_a or without
+ * plan_p, host arrays together with from_end, src_scene without from_end or with an entry out of range, a source scene that did not end
+ * SOLVED (named by index), no valid flight end on the context, a non-finite value; by a flight: S / N_cmd other than the armed start's. */
+typedef struct dmpc_start {
+    int32_t S, N_cmd;                        /* of the flight it arms; that flight must match or is refused */
+    int32_t from_end;                        /* 0: the host arrays below; 1: the end of this context's last flight, on the device */
+    const int32_t *src_scene;                /* from_end only, [S]: scene s starts where scene src_scene[s] of that flight ended; NULL: identity, S equal */
+    const double *vo, *ao;                   /* [S][N_cmd][3] or NULL = zeros                                  (from_end: must be NULL) */
+    const double *plan_p, *plan_v, *plan_a;  /* [S][N_cmd][3K]; plan_p NULL: the braking plan; plan_v and plan_a both or neither, only with plan_p */
+    int32_t col0;                            /* >= 0; from_end: added to the end's col */
+} dmpc_start;
+DMPC_API int dmpc_set_start(dmpc_ctx *ctx, const dmpc_start *start);   /* NULL clears */
+DMPC_API int dmpc_flight_end(dmpc_ctx *ctx, int S, int N_cmd, double *x_p, double *x_v, double *x_a, double *plan_p, double *plan_v, double *plan_a,
+                    int32_t *col);
+DMPC_API int dmpc_start_plan(const dmpc_params *prm, int n, const double *x_p, const double *x_v, const double *x_a, double *plan_p, double *plan_v,
+                    double *plan_a);
+DMPC_API int dmpc_start_plan_device(dmpc_ctx *ctx, int n, const double *x_p, const double *x_v, const double *x_a, double *plan_p, double *plan_v,
+                           double *plan_a, void *stream);
+
 /* Standalone forms of the path's small helpers (fused into the step kernels inside the solvers), for callers that
  * invoke them on their own as the reference's scripts do.  Host pointers, synchronous.
  *   dmpc_prop_state   propStatedmpc.m:1-8 (A_initp given): p = A_p a + A_initp [po;vo], v = A_v a + 1 (x) vo  -> pass

@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "dmpc_plan_routes", "dmpc_plan_routes_device",
     "dmpc_transition_replan", "dmpc_replan_routes_device",
     "dmpc_set_disturbance", "dmpc_disturbance_sample", "dmpc_disturb_device",
+    "dmpc_set_start", "dmpc_flight_end", "dmpc_start_plan", "dmpc_start_plan_device",
 ]
 
 
@@ -71,6 +72,12 @@ class DmpcPush(C.Structure):
 class DmpcDisturbance(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("amp_p", C.c_double), ("amp_v", C.c_double), ("wind", C.POINTER(C.c_double)), ("wind_scenes", C.c_int),
                 ("push", C.POINTER(DmpcPush)), ("n_push", C.c_int)]
+
+
+class DmpcStart(C.Structure):
+    _fields_ = [("S", C.c_int32), ("N_cmd", C.c_int32), ("from_end", C.c_int32), ("src_scene", C.POINTER(C.c_int32)),
+                ("vo", C.POINTER(C.c_double)), ("ao", C.POINTER(C.c_double)), ("plan_p", C.POINTER(C.c_double)), ("plan_v", C.POINTER(C.c_double)),
+                ("plan_a", C.POINTER(C.c_double)), ("col0", C.c_int32)]
 
 
 class DmpcError(RuntimeError):
@@ -184,6 +191,12 @@ def load():
         L.dmpc_set_disturbance.argtypes = [vp, C.POINTER(DmpcDisturbance)]
         L.dmpc_disturbance_sample.argtypes = [C.POINTER(DmpcDisturbance), C.c_double, C.c_int, C.c_int, C.c_int, dp, dp]
         L.dmpc_disturb_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    # start in motion: a flight from a given or carried state and plan (additive, still revision 8)
+    if hasattr(L, "dmpc_set_start"):   # (absent from the older builds tools/with_lib.py may load)
+        L.dmpc_set_start.argtypes = [vp, C.POINTER(DmpcStart)]
+        L.dmpc_flight_end.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, ip]
+        L.dmpc_start_plan.argtypes = [pp, C.c_int, dp, dp, dp, dp, dp, dp]
+        L.dmpc_start_plan_device.argtypes = [vp, C.c_int] + [vp] * 7
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -574,6 +587,83 @@ class Dmpc:
             yield
         finally:
             self.clear_disturbance()
+
+    # ---- start in motion ------------------------------------------------------------------------
+    def set_start(self, vo=None, ao=None, plan=None, col0=0, from_end=False, src_scene=None, S=None, N_cmd=None):
+        """dmpc_set_start: THE START IS CONSUMED BY ONE FLIGHT -- the next transition(), mission(), route() or replan() that passes its own
+        checks starts from it instead of from rest, and clears it.  Host form: vo, ao [S,N_cmd,3] (or [N_cmd,3]; None: zeros) next to the
+        flight's po; plan: None (the braking plan, made on the device), plan_p [S,N_cmd,45], or (plan_p, plan_v, plan_a).  from_end=True: the
+        end of this context's last flight, gathered on the device now; src_scene [S]: scene s starts where scene src_scene[s] ended (None:
+        identity).  COLUMN 0 IS THE CALLER'S COLUMN col0 (scripted windows, the disturbance's counter and pushes; from_end: added to the end's
+        col).  S, N_cmd: the flight's shape; taken from the arrays (from_end: from src_scene / the last flight_end) where they are not given."""
+        what = "set_start"
+        arrs = dict(vo=vo, ao=ao)
+        if plan is not None and not isinstance(plan, (tuple, list)):
+            plan = (plan,)
+        if plan is not None:
+            if len(plan) not in (1, 3):
+                raise DmpcError(f"{what}: plan is plan_p or (plan_p, plan_v, plan_a)")
+            arrs.update(zip(("plan_p", "plan_v", "plan_a"), plan))
+        arrs = {k: _f(a) for k, a in arrs.items() if a is not None}
+        if from_end and arrs:
+            raise DmpcError(f"{what}: from_end takes no host arrays ({', '.join(arrs)})")
+        if src_scene is not None:
+            if not from_end:
+                raise DmpcError(f"{what}: src_scene needs from_end=True")
+            src_scene = np.ascontiguousarray(src_scene, dtype=np.int32).reshape(-1)
+            S = src_scene.size if S is None else S
+        for k, a in arrs.items():
+            w = 3 if k in ("vo", "ao") else 3 * K_HOR
+            if a.ndim not in (2, 3) or a.shape[-1] != w:
+                raise DmpcError(f"{what}: {k} {tuple(a.shape)} must be [S,N_cmd,{w}] or [N_cmd,{w}]")
+            s_, n_ = (1, a.shape[0]) if a.ndim == 2 else a.shape[:2]
+            S, N_cmd = (s_ if S is None else S), (n_ if N_cmd is None else N_cmd)
+            if (s_, n_) != (S, N_cmd):
+                raise DmpcError(f"{what}: {k} {tuple(a.shape)} is not for S = {S}, N_cmd = {N_cmd}")
+        if S is None or N_cmd is None:
+            raise DmpcError(f"{what}: S and N_cmd are needed (no array gives them)")
+        d = DmpcStart(int(S), int(N_cmd), int(bool(from_end)), _ipn(src_scene), _dpn(arrs.get("vo")), _dpn(arrs.get("ao")), _dpn(arrs.get("plan_p")),
+                      _dpn(arrs.get("plan_v")), _dpn(arrs.get("plan_a")), int(col0))
+        self._chk(self._L.dmpc_set_start(self._ctx, C.byref(d)))
+        del arrs   # (the library has copied everything)
+        return self
+
+    def clear_start(self):
+        self._chk(self._L.dmpc_set_start(self._ctx, None))
+        return self
+
+    @contextlib.contextmanager
+    def starting(self, **kw):
+        """set_start(**kw) on entry; cleared on exit if no flight consumed it (also on an error)"""
+        self.set_start(**kw)
+        try:
+            yield self
+        finally:
+            self.clear_start()
+
+    def flight_end(self, S, N_cmd):
+        """dmpc_flight_end: where the S scenes of this context's last flight ended -- dict(x_p, x_v, x_a [S,N_cmd,3], plan_p, plan_v, plan_a
+        [S,N_cmd,45]: every agent's plan of the step that produced its scene's last column, col [S]: that column in the caller's count).
+        Valid until the next step or flight on the context; refused if a scene did not end SOLVED."""
+        S, N_cmd = int(S), int(N_cmd)
+        if S < 1 or N_cmd < 1:
+            raise DmpcError("flight_end: S and N_cmd must be >= 1")
+        o = {k: np.zeros((S, N_cmd, 3)) for k in ("x_p", "x_v", "x_a")}
+        o.update({k: np.zeros((S, N_cmd, 3 * K_HOR)) for k in ("plan_p", "plan_v", "plan_a")})
+        o["col"] = np.zeros(S, dtype=np.int32)
+        self._chk(self._L.dmpc_flight_end(self._ctx, S, N_cmd, _dp(o["x_p"]), _dp(o["x_v"]), _dp(o["x_a"]), _dp(o["plan_p"]), _dp(o["plan_v"]),
+                                          _dp(o["plan_a"]), _ip(o["col"])))
+        return o
+
+    def start_plan(self, x_p, x_v, x_a):
+        """dmpc_start_plan: the braking plan of states [..,3] on the host (no GPU) -> (plan_p, plan_v, plan_a) [..,45]"""
+        x_p, x_v, x_a = _f(x_p), _f(x_v), _f(x_a)
+        if x_p.shape != x_v.shape or x_p.shape != x_a.shape or x_p.ndim < 1 or x_p.shape[-1] != 3 or x_p.size < 3:
+            raise DmpcError(f"start_plan: x_p, x_v, x_a must share a shape [..,3]: {tuple(x_p.shape)}, {tuple(x_v.shape)}, {tuple(x_a.shape)}")
+        out = [np.zeros(x_p.shape[:-1] + (3 * K_HOR,)) for _ in range(3)]
+        if self._L.dmpc_start_plan(C.byref(self.prm), x_p.size // 3, _dp(x_p), _dp(x_v), _dp(x_a), _dp(out[0]), _dp(out[1]), _dp(out[2])):
+            raise DmpcError(self._L.dmpc_last_error(None).decode())
+        return tuple(out)
 
     # ---- host-array entry points -------------------------------------------------------------
     def init_batch(self, po, pf):

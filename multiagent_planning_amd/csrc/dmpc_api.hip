@@ -131,6 +131,22 @@ struct Disturbance {
     void set(const dmpc_disturbance &d);
 };
 
+// dmpc_set_start's armed start (dmpc_start.hip).  Host form: copies of the caller's arrays, uploaded by the flight that consumes it.  from_end: the
+// snapshot stands in the context's start_x / start_plan already (a split flight: in every part's context), `col` is each scene's column 0
+struct StartState {
+    bool armed = false, from_end = false;
+    int S = 0, N_cmd = 0, col0 = 0;
+    std::vector<double> vo, ao, plan_p, plan_v, plan_a;   // [S][N_cmd][3], [S][N_cmd][3K]; empty: absent
+    std::vector<int32_t> col;                             // from_end: [S] of this context's scenes
+    std::vector<int> at;                                  // from_end of a split flight: the parts it was snapshotted in
+};
+// the end of the context's last flight (transition_one): what dmpc_flight_end and a from_end start read of the step scratch
+struct FlightEnd {
+    bool valid = false, hold = false, e0_zero = false;    // e0_zero: a scene that ended on column 0 has the initDMPC plan's v = a = 0 (nothing wrote them)
+    int S = 0, N = 0, N_cmd = 0;
+    std::vector<int32_t> last, status, col0;              // [S]: K_T_used - 1, scene_status, the caller's number of column 0
+};
+
 struct dmpc_ctx {
     int device = 0;
     int precision = DMPC_PREC_F64;   // DMPC_PREC_MIXED: fp32 table / scan / rows, fp64 QP (host-pointer entry points)
@@ -188,6 +204,8 @@ struct dmpc_ctx {
     DevBuf mis_goals, mis_state;                                           // dmpc_transition_mission: goal sets [S][Q][N_cmd][3]; ints: stage [S], k_start [S], stage_col [S][Q], deadline [S][Q]
     Disturbance dist;                                                      // dmpc_set_disturbance: the disturbance in force (children of a split batch get a copy per call)
     DevBuf dist_buf; std::vector<unsigned char> dist_stage; long dist_key = -1;   // ... of a call on the device: wind | sorted pushes | offsets [S * N_cmd + 1]; its host staging; the shape dmpc_disturb_device uploaded for
+    StartState start; FlightEnd end; std::vector<int32_t> start_src_host;                                       // dmpc_set_start: the armed start; the end of the last flight, valid until the step scratch is used again
+    DevBuf start_x, start_plan, start_col, end_x, end_plan, end_src;       // a start on the device: x_p | x_v | x_a, plan_p | plan_v | plan_a rows, col0 [S]; dmpc_flight_end's gather; (source scene, last column) [S][2]
     DevBuf route_wp, route_state;                                          // dmpc_transition_route: waypoints [S][N_cmd][W][3]; ints: n_wp, cur, since [S][N_cmd] each, wp_col [S][N_cmd][W]
     DevBuf pc_sc_path, pc_sc_y, pc_sc_M, pc_sc_w, pc_sc_pts, pc_sc_interp; // dmpc_postcheck_scripted: paths, knots, second derivatives, scratch, sample batch, p_scripted
     DevBuf pc_pts, pc_cell, pc_fill, pc_start, pc_sorted, pc_on;           // post-check, large scenes: cell grid of a batch of samples
@@ -800,6 +818,7 @@ static std::vector<int> batch_parts(int S, int want, bool sharded)
 
 #include "dmpc_plan.hip"     // route planning round static vehicles, before and during a flight: the wavefront planner's kernels, the three entries
 #include "dmpc_disturb.hip"  // disturbed transitions: the rule on the host and the device, the descriptor's check and upload, the three entries
+#include "dmpc_start.hip"    // a flight from a given or carried state and plan: the braking plan, the gather of a flight's end, the four entries
 #include "dmpc_transition.hip"   // the closed loop: the record of a call, transition_one, transition_any, the seven entries
 
 #include "dmpc_postcheck_host.hip"   // the post-checks on the host: the record of a call, PcPrep, the three checks, pc_run, the five entries

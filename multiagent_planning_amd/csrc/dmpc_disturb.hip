@@ -16,6 +16,7 @@ struct DisturbArgs {
     int s0;                  // the index in the call of scene 0 of this launch (a split batch)
     const dmpc_push *push;   // sorted by (scene, agent, column), list order among equal keys
     const int *off;          // [S * N_cmd + 1]: the pushes of agent a of this launch are push[off[a]] .. push[off[a + 1] - 1]
+    const int *col0 = nullptr;   // a flight with a start (dmpc_start.hip): [S] the caller's number of every scene's column 0, added to k; null: 0
     // the hook of post_step_body: scene s and agent i of the launch, column k
     __device__ void operator()(int s, int i, int N, int k, double *xp, double *xv) const;
 };
@@ -45,7 +46,7 @@ __host__ __device__ inline void disturb_delta(const DisturbArgs &D, int s, int i
 __device__ inline void DisturbArgs::operator()(int s, int i, int N, int k, double *xp, double *xv) const
 {
     double dp[3], dv[3];
-    disturb_delta(*this, s, i, (size_t)s * N + i, k, dp, dv);
+    disturb_delta(*this, s, i, (size_t)s * N + i, col0 ? col0[s] + k : k, dp, dv);
     for (int c = 0; c < 3; ++c) { xp[c] = xp[c] + dp[c]; xv[c] = xv[c] + dv[c]; }
 }
 

@@ -14,6 +14,7 @@ static int check_cmd(dmpc_ctx *ctx, const char *entry, int S, int N, int N_cmd)
 static int ensure_step_scratch(dmpc_ctx *ctx, size_t agents_table, size_t agents_solved)
 {
     int rc = 0;
+    ctx->end.valid = false;   // the end of the last flight stands in this scratch (dmpc_start.hip); transition_one sets it again
     rc |= ctx->rows.ensure(agents_table * N3 * 8);
     rc |= ctx->lT.ensure(agents_table * N3 * 8);
     rc |= ctx->xp.ensure(agents_solved * 24);

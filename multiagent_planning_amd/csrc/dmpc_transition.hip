@@ -55,6 +55,7 @@ struct TransitionCall {
     int32_t *K_T_used, *scene_status;
     const double *path = nullptr; int P = 0;
     Mission mission; Hold hold; Route route;
+    Start start;             // the armed start, as transition_any took it from the context (dmpc_start.hip)
     int s0 = 0;              // the index in the caller's batch of scene 0 (a part of a split batch; the disturbance rule counts scenes of the call)
     // the same call for scenes [s0, s0 + sn): the one place that knows each array's stride per scene
     TransitionCall scenes(int s0, int sn) const {
@@ -71,6 +72,8 @@ struct TransitionCall {
         c.route.plan_status = at(route.plan_status, a0); c.route.replan_count = at(route.replan_count, a0); c.route.replan_col = at(route.replan_col, a0);
         c.pf = mission ? c.mission.goals : route ? (route.goals ? c.route.goals : c.route.waypoints) : at(pf, a0 * 3);
         c.hold.hold_count = at(hold.hold_count, a0); c.hold.hold_first = at(hold.hold_first, a0); c.hold.agent_status = at(hold.agent_status, h0);
+        c.start.vo = at(start.vo, a0 * 3); c.start.ao = at(start.ao, a0 * 3);
+        c.start.plan_p = at(start.plan_p, a0 * N3); c.start.plan_v = at(start.plan_v, a0 * N3); c.start.plan_a = at(start.plan_a, a0 * N3);
         return c;
     }
 };
@@ -81,6 +84,7 @@ static int check_call(dmpc_ctx *ctx, const std::string &who, const TransitionCal
 {
     if (c.S < 1 || c.N < 1 || c.N_cmd < 1 || c.N_cmd > c.N || c.K_T_max < 2 || !c.po || !c.pf || !c.K_T_used || !c.scene_status || ((c.pk || c.vk || c.ak) && !(c.pk && c.vk && c.ak)))
         FAIL(ctx, who + ": bad arguments");
+    if (check_start_shape(ctx, who, c.S, c.N_cmd)) return -1;
     return check_disturb_shape(ctx, who, ctx->dist, c.S, c.N_cmd);
 }
 
@@ -183,7 +187,8 @@ struct RouteDev {
         n_wp = ctx->route_state.as<int>(); cur = n_wp + A; since = cur + A; col = since + A;
         HIPCHK(ctx, hipMemcpyAsync(ctx->replan_goals.p, r.goals, A * 24, hipMemcpyHostToDevice, st));
         double *xp = ctx->xp.as<double>();
-        if (c.N_cmd == c.N || c.path) HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
+        if (c.start.from_end) ;   // (the carried positions stand in ctx->xp already: the commanded rows of po are ignored)
+        else if (c.N_cmd == c.N || c.path) HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
         else HIPCHK(ctx, hipMemcpy2DAsync(xp, (size_t)c.N_cmd * 24, ctx->po.p, (size_t)c.N * 24, (size_t)c.N_cmd * 24, (size_t)c.S, hipMemcpyDeviceToDevice, st));
         rp.g = r.grid; rp.S = c.S; rp.N_cmd = c.N_cmd; rp.W = r.W; rp.M = (int)pts; rp.margin = r.margin;
         rp.x_p = xp; rp.goals = ctx->replan_goals.as<double>(); rp.obst = ctx->replan_obst.as<double>(); rp.wp = ctx->route_wp.as<double>();
@@ -245,6 +250,7 @@ struct HoldDev {
     double *outs[2][3] = {};
     int *run = nullptr, *cnt = nullptr, *first = nullptr, *log = nullptr;
     std::vector<int32_t> held;
+    const double *start_va = nullptr;   // a start: its plan_v | plan_a rows, the "previous plan" of column 1
     int begin() {
         for (auto &set : outs) { set[0] = ctx->pout.as<double>(); set[1] = ctx->vout.as<double>(); set[2] = ctx->aout.as<double>(); }
         if (!c.hold) return 0;
@@ -254,7 +260,8 @@ struct HoldDev {
         if (ctx->hold_out.ensure(3 * row_bytes) || ctx->hold_state.ensure((3 * A + A * (size_t)c.K_T_max) * 4)) FAIL(ctx, "device allocation failed");
         for (int j = 0; j < 3; ++j) outs[0][j] = ctx->hold_out.as<double>() + (size_t)j * A * N3;   // (the first step writes the context's own rows)
         run = ctx->hold_state.as<int>(); cnt = run + A; first = cnt + A; log = first + A;
-        HIPCHK(ctx, hipMemsetAsync(outs[0][1], 0, 2 * row_bytes, st));   // the initDMPC plan: v = a = 0 (its positions are the first table)
+        if (start_va) HIPCHK(ctx, hipMemcpyAsync(outs[0][1], start_va, 2 * row_bytes, hipMemcpyDeviceToDevice, st));
+        else HIPCHK(ctx, hipMemsetAsync(outs[0][1], 0, 2 * row_bytes, st));   // the initDMPC plan: v = a = 0 (its positions are the first table)
         HIPCHK(ctx, hipMemsetAsync(cnt, 0, A * 4, st));
         HIPCHK(ctx, hipMemsetAsync(first, 0xff, A * 4, st));
         HIPCHK(ctx, hipMemsetAsync(log, 0, A * (size_t)c.K_T_max * 4, st));
@@ -319,20 +326,37 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, c.po, (scripted ? A : T) * 24, hipMemcpyHostToDevice, st));
     MissionDev mission{ctx, c, st}; HoldDev hold{ctx, c, st}; RouteDev route{ctx, c, st}; DisturbDev disturb{ctx, c, st};
+    StartDev start{ctx, c.start, st};
+    if (start && start.begin(S, N_cmd)) return -1;
+    if (c.start.from_end) HIPCHK(ctx, hipMemcpyAsync(xp, start.x(0), A * 24, hipMemcpyDeviceToDevice, st));   // (in front of a re-planned route's first plan)
     if (mission.begin() || route.begin() || disturb.begin()) return -1;
+    if (start && disturb) disturb.args.col0 = start.col0();
     if (reset_run_buffers(ctx, S, K_T_max, hist, st)) return -1;
     // ---- column 0: initDMPC (dmpc_soft_bound.m:117-121): state = (po, 0, 0), table = straight lines
-    if (N_cmd == N || scripted) HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
+    // (a start, dmpc_start.hip: state = (po, vo, ao) or the carried one, the commanded columns of the table = the start's plan rows)
+    if (c.start.from_end) ;   // (the carried positions: copied above)
+    else if (N_cmd == N || scripted) HIPCHK(ctx, hipMemcpyAsync(xp, ctx->po.p, A * 24, hipMemcpyDeviceToDevice, st));
     else HIPCHK(ctx, hipMemcpy2DAsync(xp, (size_t)N_cmd * 24, ctx->po.p, (size_t)N * 24, (size_t)N_cmd * 24, (size_t)S, hipMemcpyDeviceToDevice, st));   // the commanded agents' starts, packed
-    for (double *x : {xv, xa}) HIPCHK(ctx, hipMemsetAsync(x, 0, A * 24, st));
-    hipLaunchKernelGGL(init_rows_kernel, dim3((unsigned)((A * N3 + 255) / 256)), dim3(256), 0, st, (int)A, ctx->prm.h,
-                       (const double *)(N_cmd == N ? ctx->po.as<double>() : xp), ctx->pf.as<double>(), ctx->rows.as<double>());
+    const double *rows0 = ctx->rows.as<double>();
+    if (start) {
+        if (start.states(xv, xa) || start.plans(xp, xv, xa)) return -1;
+        rows0 = start.plan(0);
+        if (c.hold) hold.start_va = start.plan(1);
+        else {   // the plan column 0 was built from, where a step's would stand: the end of a scene that ends here
+            HIPCHK(ctx, hipMemcpyAsync(ctx->vout.p, start.plan(1), A * N3 * 8, hipMemcpyDeviceToDevice, st));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->aout.p, start.plan(2), A * N3 * 8, hipMemcpyDeviceToDevice, st));
+        }
+    } else {
+        for (double *x : {xv, xa}) HIPCHK(ctx, hipMemsetAsync(x, 0, A * 24, st));
+        hipLaunchKernelGGL(init_rows_kernel, dim3((unsigned)((A * N3 + 255) / 256)), dim3(256), 0, st, (int)A, ctx->prm.h,
+                           (const double *)(N_cmd == N ? ctx->po.as<double>() : xp), ctx->pf.as<double>(), ctx->rows.as<double>());
+    }
     if (N_cmd == N) {
-        if (dmpc_table_from_rows_device(ctx, S, 1, N, ctx->rows.as<double>(), ctx->lT.as<double>(), st)) return -1;
+        if (dmpc_table_from_rows_device(ctx, S, 1, N, rows0, ctx->lT.as<double>(), st)) return -1;
     } else {
         // the commanded columns of the first table from the initDMPC rows; the static columns -- po replicated over the horizon (dmpc.cpp:1633-1649)
         // -- into BOTH tables of the ping-pong pair, once: the solve kernels write the columns of the agents they solved and nothing else
-        hipLaunchKernelGGL(cmd_cols_from_rows_kernel, dim3(grid_1d(A * N3, 4096)), dim3(256), 0, st, S, N, N_cmd, (const double *)ctx->rows.as<double>(), ctx->lT.as<double>());
+        hipLaunchKernelGGL(cmd_cols_from_rows_kernel, dim3(grid_1d(A * N3, 4096)), dim3(256), 0, st, S, N, N_cmd, rows0, ctx->lT.as<double>());
         if (!scripted)   // (scripted vehicles: their columns are written before every step, the first included -- window k = 1 of the first table)
             hipLaunchKernelGGL(static_cols_kernel, dim3(grid_1d((T - A) * N3, 4096)), dim3(256), 0, st, S, N, N_cmd, (const double *)ctx->po.as<double>(),
                                ctx->lT.as<double>(), ctx->lT2.as<double>());
@@ -373,7 +397,9 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
     };
     // ---- columns 1 .. K_T_max - 1
     for (int k = 1; k < K_T_max && verdict.ndone < S; ++k) {
-        if (scripted)   // the scripted columns of the current table: window k-1 .. k+K-2 of every path (before the fp32 copy, which then covers them)
+        if (scripted && start)   // (a start: the window of scene s begins at its column col0[s] + k-1)
+            hipLaunchKernelGGL(scripted_cols_from_kernel, dim3(grid_1d((T - A) * N3, 4096)), dim3(256), 0, st, S, N, N_cmd, c.P, k, start.col0(), (const double *)ctx->path.as<double>(), cur);
+        else if (scripted)   // the scripted columns of the current table: window k-1 .. k+K-2 of every path (before the fp32 copy, which then covers them)
             hipLaunchKernelGGL(scripted_cols_kernel, dim3(grid_1d((T - A) * N3, 4096)), dim3(256), 0, st, S, N, N_cmd, c.P, k, (const double *)ctx->path.as<double>(), cur, (float *)nullptr);
         if (mixed && table_f32(ctx, cur, ctx->lTf, T * N3, st)) return -1;   // (all N columns, the static ones included)
         int *const verdict_k = ctx->flags.as<int>() + (size_t)k * S * 2;
@@ -416,6 +442,12 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
     HIPCHK(ctx, hipStreamSynchronize(st));
     hold.report();
     ctx->hist_S = S; ctx->hist_N = N_cmd; ctx->hist_KT = K_T_max;   // (the resident histories are the commanded agents')
+    // the end of this flight stands in the step scratch until something else uses it (dmpc_flight_end, a from_end start)
+    FlightEnd &end = ctx->end;
+    end.S = S; end.N = N; end.N_cmd = N_cmd; end.hold = (bool)c.hold; end.e0_zero = !c.hold && !start;
+    end.last.resize((size_t)S); end.status.assign(c.scene_status, c.scene_status + S); start.cols(end.col0, S);
+    for (int s = 0; s < S; ++s) end.last[s] = c.K_T_used[s] - 1;
+    end.valid = true;
     return 0;
 }
 
@@ -469,20 +501,33 @@ static int run_parts(dmpc_ctx *ctx, const TransitionCall &c, const std::vector<i
 }
 
 // A batch in parts (batch_parts), each on a context, HIP stream and host thread of its own.  A DMPC_DEVICE_ALL context shards the agents of each scene
-// over every visible GPU (dmpc_multigpu.hip) -- unless there are uncommanded vehicles, a mission, a route or a disturbance, or fewer agents than twice the GPUs (the
+// over every visible GPU (dmpc_multigpu.hip) -- unless there are uncommanded vehicles, a mission, a route, a disturbance or a start, or fewer agents than twice the GPUs (the
 // reference's small swarms on an 8-GPU node: sharding N = 4 agents over 8 GPUs is impossible and over 2-3 of them nothing but barriers and peer
 // copies): the first GPU alone then, unsplit, as dmpc_step_batch does.
-static int transition_any(dmpc_ctx *ctx, const TransitionCall &c)
+static int transition_any(dmpc_ctx *ctx, const TransitionCall &call)
 {
     ctx->split_at.clear();
-    const bool sharded = ctx->grp && c.N_cmd == c.N && !c.mission && !c.route && !ctx->dist.on;
+    ctx->end.valid = false;   // (transition_one sets it again; a sharded flight leaves no end)
+    TransitionCall c = call;
+    // the armed start is consumed here: every entry has passed its own checks (a from_end start was snapshotted in the parts of the flight it
+    // continues, so it is flown in those parts -- or, snapshotted whole, unsplit)
+    StartState &a = ctx->start;
+    std::vector<int> start_at;
+    if (a.armed) {
+        auto ptr = [](const std::vector<double> &v) { return v.empty() ? nullptr : v.data(); };
+        c.start = Start{true, a.from_end, a.col0, ptr(a.vo), ptr(a.ao), ptr(a.plan_p), ptr(a.plan_v), ptr(a.plan_a)};
+        if (a.from_end) start_at = a.at.empty() ? std::vector<int>{0, c.S} : a.at;
+        a.armed = false;
+    }
+    const bool sharded = ctx->grp && c.N_cmd == c.N && !c.mission && !c.route && !ctx->dist.on && !c.start;
     if (sharded && c.N < 2 * ctx->grp->G) return transition_one(ctx, c);
     int (*const body)(dmpc_ctx *, const TransitionCall &) = sharded ? group_transition : transition_one;
-    const std::vector<int> at = batch_parts(c.S, ctx->opt.split_parts, sharded);
-    if (at.size() < 3 || ctx->opt.no_split || (ctx->grp && !sharded)) return body(ctx, c);
+    const std::vector<int> at = start_at.empty() ? batch_parts(c.S, ctx->opt.split_parts, sharded) : start_at;
+    if (at.size() < 3 || (ctx->opt.no_split && start_at.empty()) || (ctx->grp && !sharded)) return body(ctx, c);
     for (size_t i = 0; i + 2 < at.size(); ++i)
         if (part_context(ctx, i, sharded ? DMPC_DEVICE_ALL : ctx->device)) return -1;
-    return run_parts(ctx, c, at, body);
+    if (run_parts(ctx, c, at, body)) { ctx->end.valid = false; return -1; }
+    return 0;
 }
 
 extern "C" int dmpc_transition(dmpc_ctx *ctx, int S, int N, const double *po, const double *pf, int K_T_max, double error_tol, double *pk, double *vk,

@@ -36,6 +36,8 @@
 //   tol            = dmpc_mex('max_deviation', params, p, prev_p)                      maxDeviation.m (p, prev_p: 3 x K)
 //   [po,pf]        = dmpc_mex('random_test', params, N, pmin, pmax, rmin, c, seed)      randomTest.m
 //   [po,pf]        = dmpc_mex('random_exchange', params, N, pmin, pmax, rmin, seed)     randomExchange.m
+//   [x_p,x_v,x_a,plan_p,plan_v,plan_a,col] = dmpc_mex('flight_end', params, N_cmd)
+//   [pk,vk,ak,K_T_used,status] = dmpc_mex('transition_from', params, po, pf, K_T_max, error_tol, vo, ao, plan_p, plan_v, plan_a, col0[, from_end])
 // Uncommanded vehicles (DMPC::solveParallelDMPCv2, dmpc/cpp/dmpc.cpp:1572-1573: N = _po.cols(), N_cmd = _pf.cols()): 'transition' and
 // 'step_batch' take pf (and the states) with FEWER columns than po / l -- the first N_cmd vehicles are commanded, the others stay at po as
 // static obstacles, and the outputs cover the commanded ones; 'postcheck' takes po_static (3 x M) behind Ts.
@@ -60,6 +62,12 @@
 // of every commanded agent on every column from 1 on, by the rule include/dmpc_hip.h pins: uniform noise of half-width noise_p (metres) on the
 // position and noise_v (m/s) on the velocity from the stream `seed` (an integer below 2^53), a constant wind (3 x 1, m/s^2, or []) and pushes
 // (8 x n or []: agent, 1-based; history column, 0-based, >= 1; dp (3); dv (3)).  The command sets the disturbance, flies and clears it.
+// Start in motion (dmpc_set_start, no reference counterpart): 'flight_end' returns where the last 'transition*' of the context ended -- x_p, x_v,
+// x_a (3 x N_cmd), every agent's plan of the step that produced the last column, plan_p, plan_v, plan_a (3 x K x N_cmd), and col, that column in the
+// caller's count; 'transition_from' is 'transition' whose column 0 is the state (po, vo, ao) and the plan given instead of initDMPC: vo, ao
+// (3 x N_cmd or [] = zeros), plan_p ([]: the braking plan), plan_v, plan_a (both or []), col0 (the caller's number of column 0: scripted windows,
+// the disturbance's counter); from_end = 1 (all five arrays []): the end of the context's last flight, carried on the device, col0 added to its col.
+// The command sets the start, flies dmpc_transition_cmd and clears the start on any error.
 // `params` is a struct with the fields of dmpc_params (variant as the DMPC_VAR_* integer).
 // The signature-preserving wrappers (solveSoftDMPCbound.m, ...) in this directory call 'solve_one'
 // and convert status bits into the reference's [] + flag conventions.
@@ -483,6 +491,47 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         const std::string why = rc ? dmpc_last_error(ctx) : "";
         dmpc_set_disturbance(ctx, nullptr);   // the contexts are kept between calls: the setting must not outlive this one
         if (rc) mexErrMsgIdAndTxt("dmpc:transition_disturbed", "%s", why.c_str());
+        if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);
+        if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
+        return;
+    }
+    if (!std::strcmp(cmd, "flight_end")) {   // where the last 'transition*' of this context ended (dmpc_flight_end): what 'transition_from' takes
+        need(nrhs == 3, "flight_end: (cmd, params, N_cmd)");
+        const int Nc = (int)mxGetScalar(prhs[2]);
+        need(Nc >= 1, "N_cmd must be >= 1");
+        const mwSize d3[3] = {3, (mwSize)p.K, (mwSize)Nc};
+        mxArray *o[6];
+        for (int u = 0; u < 6; ++u) o[u] = u < 3 ? mxCreateDoubleMatrix(3, Nc, mxREAL) : mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        int32_t col = 0;
+        if (dmpc_flight_end(ctx, 1, Nc, mxGetPr(o[0]), mxGetPr(o[1]), mxGetPr(o[2]), mxGetPr(o[3]), mxGetPr(o[4]), mxGetPr(o[5]), &col))
+            mexErrMsgIdAndTxt("dmpc:flight_end", "%s", dmpc_last_error(ctx));
+        plhs[0] = o[0];
+        for (int u = 1; u < 6; ++u) if (nlhs > u) plhs[u] = o[u];
+        if (nlhs > 6) plhs[6] = mxCreateDoubleScalar((double)col);
+        return;
+    }
+    if (!std::strcmp(cmd, "transition_from")) {   // 'transition' from a given or carried state and plan (dmpc_set_start): set, fly, clear on any error
+        need(nrhs == 12 || nrhs == 13, "transition_from: (cmd, params, po, pf, K_T_max, error_tol, vo, ao, plan_p, plan_v, plan_a, col0[, from_end])");
+        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3), Nc = (int)(mxGetNumberOfElements(prhs[3]) / 3), KT = (int)mxGetScalar(prhs[4]);
+        need(N >= 1 && Nc >= 1 && Nc <= N && mxGetNumberOfElements(prhs[3]) == (size_t)3 * Nc && KT >= 2, "po must be 3 x N, pf 3 x N_cmd (N_cmd <= N), K_T_max >= 2");
+        const double *arr[5];
+        for (int u = 0; u < 5; ++u) {   // vo, ao: 3 x N_cmd; plan_p, plan_v, plan_a: 3 x K x N_cmd; or []
+            const size_t n = mxGetNumberOfElements(prhs[6 + u]), want = (size_t)(u < 2 ? 3 : n3) * Nc;
+            need(n == 0 || n == want, "vo, ao must be 3 x N_cmd, plan_p, plan_v, plan_a 3 x K x N_cmd (or empty)");
+            arr[u] = n ? mxGetPr(prhs[6 + u]) : nullptr;
+        }
+        const dmpc_start start{1, Nc, nrhs == 13 && mxGetScalar(prhs[12]) != 0.0, nullptr, arr[0], arr[1], arr[2], arr[3], arr[4], (int32_t)mxGetScalar(prhs[11])};
+        const mwSize d3[3] = {3, (mwSize)KT, (mwSize)Nc};
+        plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        mxArray *v = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), *a = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        int32_t used = 0, sst = 0;
+        if (dmpc_set_start(ctx, &start)) mexErrMsgIdAndTxt("dmpc:transition_from", "%s", dmpc_last_error(ctx));
+        const int rc = dmpc_transition_cmd(ctx, 1, N, Nc, mxGetPr(prhs[2]), mxGetPr(prhs[3]), KT, mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v), mxGetPr(a),
+                                           &used, &sst);
+        const std::string why = rc ? dmpc_last_error(ctx) : "";
+        if (rc) dmpc_set_start(ctx, nullptr);   // the contexts are kept between calls: a start that was not consumed must not outlive this one
+        if (rc) mexErrMsgIdAndTxt("dmpc:transition_from", "%s", why.c_str());
         if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
         if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);
         if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
