@@ -623,14 +623,7 @@ static int assign_run(dmpc_ctx *ctx, int S, int N, int M, const double *po, cons
     w.price = ctx->asg_work.as<double>(); w.bidv = w.price + SN; w.bidval = (unsigned long long *)(w.bidv + SN);
     w.owner = (int *)(w.bidval + SN); w.assigned = w.owner + SN; w.bidwin = w.assigned + SN; w.bidj = w.bidwin + SN; w.list = w.bidj + SN;
     w.state = (asg::State *)(w.list + 2 * SN); w.done = (int *)(w.state + S);
-    if (ctx->asg_host_cap < (size_t)2 * S) {
-        if (ctx->asg_host) (void)hipHostFree(ctx->asg_host);
-        ctx->asg_host = nullptr; ctx->asg_host_cap = 0;
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->asg_host, (size_t)2 * S * 4, hipHostMallocDefault));
-        ctx->asg_host_cap = (size_t)2 * S;
-    }
-    for (int u = 0; u < 2; ++u)
-        if (!ctx->asg_ev[u]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->asg_ev[u], hipEventDisableTiming));
+    HIPCHK(ctx, ctx->asg_win.ensure((size_t)2 * S));
     HIPCHK(ctx, hipMemsetAsync(w.state, 0, (size_t)S * sizeof(asg::State), st));
     const unsigned g_rows = (unsigned)std::min((N + 3) / 4, 1024), g_bid = (unsigned)std::min((N + asg::BID_WAVES - 1) / asg::BID_WAVES, 512);
     hipLaunchKernelGGL(asg::assign_cmax_kernel, dim3(g_rows, (unsigned)S), dim3(256), 0, st, N, po, goals, cinv, w);
@@ -645,18 +638,18 @@ static int assign_run(dmpc_ctx *ctx, int S, int N, int M, const double *po, cons
         }
         HIPCHK(ctx, hipGetLastError());
         launched += asg::WINDOW;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->asg_host + (size_t)(k & 1) * S, w.done, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipEventRecord(ctx->asg_ev[k & 1], st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->asg_win.p + (size_t)(k & 1) * S, w.done, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipEventRecord(ctx->asg_win.ev[k & 1], st));
         bool over = launched >= (long)cap;            // every scene has finished or met the cap by now
         if (!over && k >= 1) {                        // the window before this one
-            HIPCHK(ctx, hipEventSynchronize(ctx->asg_ev[(k - 1) & 1]));
-            const int32_t *d = ctx->asg_host + (size_t)((k - 1) & 1) * S;
+            HIPCHK(ctx, hipEventSynchronize(ctx->asg_win.ev[(k - 1) & 1]));
+            const int32_t *d = ctx->asg_win.p + (size_t)((k - 1) & 1) * S;
             over = true;
             for (int s = 0; s < S; ++s) over = over && d[s] != 0;
         }
         if (over) {
-            HIPCHK(ctx, hipEventSynchronize(ctx->asg_ev[k & 1]));   // the pinned flags are at rest when the call returns
-            if (k >= 1) HIPCHK(ctx, hipEventSynchronize(ctx->asg_ev[(k - 1) & 1]));
+            HIPCHK(ctx, hipEventSynchronize(ctx->asg_win.ev[k & 1]));   // the pinned flags are at rest when the call returns
+            if (k >= 1) HIPCHK(ctx, hipEventSynchronize(ctx->asg_win.ev[(k - 1) & 1]));
             break;
         }
     }

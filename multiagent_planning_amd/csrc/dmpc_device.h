@@ -1,4 +1,4 @@
-// dmpc_device.h -- constants and the kernel parameter block shared by dmpc_kernels.hip and dmpc_api.hip
+// dmpc_device.h -- constants and the kernel parameter block shared by the kernels (dmpc_kernels.hip) and the host code (dmpc_context.hip, dmpc_tables.hip, dmpc_launch.hip)
 #pragma once
 #include <stdint.h>
 
@@ -86,7 +86,7 @@ struct StepParams {
     int queue_chunk;        // persistent solve kernel: adjacent queue positions a ticket of the light bulk stands for (1 or 2, launch_step)
     int n_ext;              // persistent solve kernel with a split T: extensions in the workgroup's pool (behind the waves' blocks)
     int *cost_out;          // [S*c_count] or null: work estimate of this agent's solve (quarter microseconds: iterations weighted by the working-set size,
-                            // certificate calls) -- the NEXT step's launch order is built from it (order_kernel; dmpc_api.hip: order hint)
+                            // certificate calls) -- the NEXT step's launch order is built from it (order_kernel; dmpc_launch.hip: order hint)
     double scp_tol;         // VAR_SCP: `tol` of solveDMPC.m:1,17 (the loop stops when maxDeviation(p, prev_p) <= tol)
     int *gzero;             // scan kernel: the cell grid's counters (cell counts, largest half extents), set to zero for the NEXT step's grid_prep_kernel (no memset launch), or null
     int gzero_n;
@@ -103,7 +103,7 @@ struct StepParams {
 
 constexpr int SCAN_CAND_CAP = 1024;   // (neighbour, step) candidates buffered per flush of the hard-row scan
 
-// Precomputed tables (host: build_case_tables, dmpc_api.hip).  Per cost case one symmetric 30x30 Gram table over the
+// Precomputed tables (host: build_tables, dmpc_tables.hip).  Per cost case one symmetric 30x30 Gram table over the
 // index (space, step), space A = acceleration components (0..14), space W = position components (15..29):
 //   G[A i][A j] = H1^-1(i,j),  G[A i][W j] = (H1^-1 L')(i,j),  G[W i][W j] = (L H1^-1 L')(i,j);
 // then Lt[k][kk] = Lambda(kk,k) (15x15, the same for every case).

@@ -119,9 +119,8 @@ struct ListPlan {
     double R = 0, Rsel = 0;  // radius of the boxes' test / of the scan's selection
     size_t gq_lds = 0;
     bool close = false;      // the query also leaves the (neighbour, step) pairs inside rmin: the scan tests those instead of walking its list
-    int close_cap = 0;       // records per agent
     GridGeom gg{};
-    int ncell = 1;
+    int ncell = 1, close_cap = 0;   // cells of the grid; close records per agent (the context's default is DevOptions::close_cap)
 };
 // the cell grid's buffer (carve_grid)
 struct GridBuffers {
@@ -438,7 +437,7 @@ static void fill_constants(const dmpc_ctx *ctx, StepParams &P)
     P.alim = p.alim; P.Q1 = p.Q1; P.S1 = p.S1; P.term = p.term;
     P.Qfar = p.Qfar > 0 ? p.Qfar : 1000.0; P.Qnear = p.Qnear > 0 ? p.Qnear : 10000.0; P.Sfree = p.Sfree > 0 ? p.Sfree : 10.0;
     for (int d = 0; d < 3; ++d) { P.pmin[d] = p.pmin[d]; P.pmax[d] = p.pmax[d]; }
-    P.tables = ctx->d_tables;
+    P.tables = ctx->d_tables.as<double>();
     for (int i = 0; i < 3; ++i) P.hsum[i] = ctx->hsum[i];
     P.scp_tol = p.tol;
 }
@@ -467,7 +466,7 @@ static int fill_params(dmpc_ctx *ctx, const StepPlan &pl, const StepIO &io, Step
             FAIL(ctx, "device allocation failed (row scratch)");
         P.rowbuf = ctx->rowbuf.as<double>(); P.rowkc = ctx->rowkc.as<int>(); P.hdr = ctx->hdr.as<int>();
     }
-    P.dbg = ctx->dbg; P.dbg_agent = ctx->dbg_agent; P.dbg_cap = ctx->dbg_cap;
+    P.dbg = ctx->dbg.as<double>(); P.dbg_agent = ctx->dbg_agent; P.dbg_cap = ctx->dbg_cap;
     P.iter_cap = o.iter_cap;
     P.rsolve_cap = o.rsolve_cap;
     P.dep_tol_f32 = std::pow(10.0, -(double)o.f32_dep_exp);
@@ -745,7 +744,7 @@ static int launch_step(dmpc_ctx *ctx, const StepShape &sh, const StepIO &io, hip
     const StepPlan pl = plan_step(ctx, sh);
     StepParams P;
     if (fill_params(ctx, pl, io, P, st)) return -1;
-    dmpc_ctx::Ev ev{nullptr, nullptr, nullptr};
+    Ev ev{nullptr, nullptr, nullptr};
     if (ctx->profile) {   // event triples are recycled (dmpc_profile_read2 returns them to the pool): no event is created inside a timed loop
         if (!ctx->ev_pool.empty()) { ev = ctx->ev_pool.back(); ctx->ev_pool.pop_back(); }
         else {

@@ -1,5 +1,5 @@
 // dmpc_transition.hip -- the closed loop on one GPU (included by dmpc_api.hip; the sharded loop is in dmpc_multigpu.hip): the record of a call and
-// its argument check, the MPC loop (transition_one), the split of a batch over contexts (transition_any), the entries.
+// its argument check, the MPC loop (transition_one), the split of a batch over contexts (batch_parts, transition_any), the entries.
 //
 // The whole `for k = 1:K_T` loop on the device (dmpc_soft_bound.m:115-148, failure_rate.m:99-127) for the N_cmd commanded agents of N vehicles
 // (DMPC::solveParallelDMPCv2, dmpc.cpp:1570-1730: N = _po.cols(), N_cmd = _pf.cols()).  State, goals, outputs, histories, status and the
@@ -378,21 +378,13 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
     // event of window c.  The device never idles while the host reads flags (a stream synchronisation per window cost 40-45 us of idle GPU per
     // 8 steps: 8 % of a single-scene transition); the steps enqueued past the end of a trial are skipped on the device (scene_done), so
     // what a scene records and reports does not change.
-    const size_t flag_ints = (size_t)K_T_max * S * 2;
-    if (ctx->flags_host_cap < flag_ints) {
-        if (ctx->flags_host) (void)hipHostFree(ctx->flags_host);
-        ctx->flags_host = nullptr; ctx->flags_host_cap = 0;
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->flags_host, flag_ints * 4, hipHostMallocDefault));
-        ctx->flags_host_cap = flag_ints;
-    }
-    for (int u = 0; u < 2; ++u)
-        if (!ctx->flag_ev[u]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->flag_ev[u], hipEventDisableTiming));
+    HIPCHK(ctx, ctx->flag_win.ensure((size_t)K_T_max * S * 2));
     VerdictFold verdict; verdict.init(c);
     int pend_k0 = -1, pend_k1 = -1, pend_ev = 0, nwin = 0;   // the window whose verdicts are in flight to the host
     auto digest = [&]() -> int {   // wait for the pending window and fold its verdicts
         if (pend_k0 < 0) return 0;
-        HIPCHK(ctx, hipEventSynchronize(ctx->flag_ev[pend_ev]));
-        verdict.fold(ctx->flags_host, pend_k0, pend_k1); pend_k0 = -1;
+        HIPCHK(ctx, hipEventSynchronize(ctx->flag_win.ev[pend_ev]));
+        verdict.fold(ctx->flag_win.p, pend_k0, pend_k1); pend_k0 = -1;
         return 0;
     };
     // ---- columns 1 .. K_T_max - 1
@@ -430,9 +422,9 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
         if (VerdictFold::window_ends(k, K_T_max)) {
             if (digest()) return -1;   // the window before this one (its steps ran while this one was enqueued)
             const int k0 = VerdictFold::window_start(k);
-            HIPCHK(ctx, hipMemcpyAsync(&ctx->flags_host[(size_t)k0 * S * 2], ctx->flags.as<int>() + (size_t)k0 * S * 2, (size_t)(k - k0 + 1) * S * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipMemcpyAsync(&ctx->flag_win.p[(size_t)k0 * S * 2], ctx->flags.as<int>() + (size_t)k0 * S * 2, (size_t)(k - k0 + 1) * S * 8, hipMemcpyDeviceToHost, st));
             pend_ev = nwin++ & 1;
-            HIPCHK(ctx, hipEventRecord(ctx->flag_ev[pend_ev], st));
+            HIPCHK(ctx, hipEventRecord(ctx->flag_win.ev[pend_ev], st));
             pend_k0 = k0; pend_k1 = k;
         }
     }
@@ -498,6 +490,19 @@ static int run_parts(dmpc_ctx *ctx, const TransitionCall &c, const std::vector<i
     if (rc[0]) return -1;
     ctx->split_at = at; ctx->hist_S = c.S;   // the resident histories are split over the contexts (dmpc_postcheck knows)
     return 0;
+}
+
+// Batched transitions are bound, MPC step by MPC step, by the slowest agent of the whole batch while most of the GPU idles.  Scenes are independent,
+// so a large batch is run in parts side by side: the tail of one part overlaps the bulk of another (512 transitions of 100 agents, two halves: 103 ->
+// 60 ms).  Launches of fewer than ~2000 agents are one-agent workgroups, which the hardware interleaves across streams freely (persistent launches
+// hold a CU's whole LDS), so many small parts overlap best.  sharded (a DMPC_DEVICE_ALL context): batches of 64 or more scenes as TWO groups -- while
+// one half's ranks exchange their predictions the other half's solve kernels keep the GPUs busy.  want: option split_parts.  Returns every part's first scene, and S.
+static std::vector<int> batch_parts(int S, int want, bool sharded)
+{
+    const int parts = sharded ? (want > 0 ? std::min(want, 2) : (S >= 64 ? 2 : 1)) : std::min(S, want > 0 ? want : (S >= 128 ? 4 : (S >= 32 ? 2 : 1)));
+    std::vector<int> at((size_t)parts + 1);
+    for (int i = 0; i <= parts; ++i) at[(size_t)i] = (int)((long)S * i / parts);
+    return at;
 }
 
 // A batch in parts (batch_parts), each on a context, HIP stream and host thread of its own.  A DMPC_DEVICE_ALL context shards the agents of each scene

@@ -147,7 +147,7 @@ def corner_hard_rows(fourth=False, rmin=RMIN, c=2.0):
 
 
 def row_capacity(variant, N):
-    """rows per agent the scan builds (dmpc_api.hip row_capacity): want = rows of the worst case, capped per variant, at least 8,
+    """rows per agent the scan builds (row_capacity in dmpc_launch.hip): want = rows of the worst case, capped per variant, at least 8,
     rounded up to an even number; one row more sets DMPC_ST_CAPACITY"""
     nb = N - 1 if N > 1 else 1
     if variant in ("hard", "scp"):

@@ -11,6 +11,13 @@ ALL_VARIANTS = ["bound", "bound2", "all3", "hard", "ondemand", "ellip", "softall
 CAMPAIGN_VARIANTS = ALL_VARIANTS[:11]   # the variant list of rounds 2-5: the recorded scenes of the randomized campaigns are positions in ITS random stream
 
 
+def lib_source():
+    """the library's source text, every csrc/*.hip and csrc/*.h in sorted order: for the tests that read a default or a rule out of it"""
+    import glob
+    csrc = os.path.join(ROOT, "multiagent_planning_amd", "csrc")
+    return "".join(open(p).read() for p in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))))
+
+
 def load_golden(name):
     g = np.load(os.path.join(GOLD, name + ".npz"))
     kw = dict(rmin=float(g["rmin"]), c=float(g["c"]), alim=float(g["alim"]), Q1=float(g["Q"]), S1=float(g["S"]),

@@ -86,7 +86,7 @@ def test_corner_probe_has_three_hard_rows_and_three_walls(fourth):
 
 
 def test_row_capacity_restated():
-    """the capacity the GPU tests assume (dmpc_api.hip row_capacity): per-variant want/cap, at least 8, rounded up to even"""
+    """the capacity the GPU tests assume (row_capacity in dmpc_launch.hip): per-variant want/cap, at least 8, rounded up to even"""
     row_capacity = cr.row_capacity
     assert [row_capacity("bound", n) for n in (2, 6, 9, 10, 129, 130, 5000)] == [8, 8, 8, 10, 128, 128, 128]
     assert [row_capacity("all3", n) for n in (3, 4, 128, 129, 130)] == [8, 10, 382, 384, 384]

@@ -50,7 +50,7 @@ def _qp(variant, sc, kw=KW):
 
 def _agree_or_capacity(out, ref, reduced, skip=(), qp=None):
     """every agent the GPU flags with ST_CAPACITY -- past the row capacity, or with a working set that outgrows the solver's 64 slots
-    (full_qcap, dmpc_api.hip:626) -- has zero outputs and is not "solved"; every other agent agrees with the oracle (_agree of
+    (full_qcap in dmpc_launch.hip) -- has zero outputs and is not "solved"; every other agent agrees with the oracle (_agree of
     test_gpu_reduced for the reduced solver's variants, helpers.compare_to_oracle otherwise).  Returns the flag mask."""
     flag = (out["status"] & ST_CAPACITY) != 0
     assert not (out["status"][flag] & ST_SOLVED).any()
@@ -164,7 +164,7 @@ def _matlab_call(variant, sc, n):
 @pytest.mark.parametrize("variant,cap", [("bound", 128), ("all3", 384), ("hard", 640)])
 @pytest.mark.parametrize("past", [False, True], ids=["at", "past"])
 def test_row_capacity(variant, cap, past):
-    """dmpc_api.hip:600-614 row_capacity (bound family 128, all3 384, hard 640) and dmpc_kernels.hip:817 (`nr > nrmax` ->
+    """row_capacity in dmpc_launch.hip (bound family 128, all3 384, hard 640) and dmpc_kernels.hip:817 (`nr > nrmax` ->
     DMPC_ST_CAPACITY): a probe with exactly `cap` rows agrees with the oracle; with one row more (all3: one neighbour, three rows)
     it carries ST_CAPACITY with zero outputs, the MATLAB-signature wrapper raises DmpcError for it, and every other agent of the
     scene still agrees with the oracle.  The rows sit on late horizon steps, where none is pruned."""
@@ -186,7 +186,7 @@ def test_row_capacity(variant, cap, past):
 
 @pytest.mark.parametrize("N", [4, 6, 10])
 def test_row_capacity_of_small_scenes(N):
-    """small scenes, where row_capacity's floor of 8 and rounding to an even number (dmpc_api.hip:612-613) set the buffer: N - 1 = 3, 5
+    """small scenes, where row_capacity's floor of 8 and rounding to an even number (the last lines of row_capacity) set the buffer: N - 1 = 3, 5
     (below 8) and 9 (odd, rounded to 10) neighbours, a probe with a row for each agrees with the oracle, without ST_CAPACITY (bound,
     all3, hard).  The floor and the rounding are not observable from outputs: a probe has at most N - 1 rows (all3: 3 (N - 1), hard:
     15 (N - 1)), never more than the unrounded capacity, so this test would pass without them; it guards the small buffers only"""
@@ -214,7 +214,7 @@ def test_row_capacity_of_small_scenes(N):
 
 @pytest.mark.parametrize("variant,rows", [("bound", 128), ("all3", 384)])
 def test_tier_forms_are_bit_identical_on_crowds(variant, rows):
-    """tier1_qcap / full_qcap (dmpc_api.hip:626-649, 718): the working-set capacity of the first solve launch (32, 48, 56, 64) only
+    """tier1_qcap / full_qcap (dmpc_launch.hip, and plan_step that calls them): the working-set capacity of the first solve launch (32, 48, 56, 64) only
     decides which agents are re-solved from scratch in the second launch -- the crowd's outputs are the same bits in every form, and
     (bound) agree with the oracle, agents flagged ST_CAPACITY (working set past 64 slots) with zero outputs.  Some agent's working set
     outgrows 32 slots, so the 32-slot form does hand agents to the second launch.  Not covered: the 48/49/56/57 peaks one by one and
@@ -339,7 +339,7 @@ def test_threshold_ties(kind, axis, c):
 
 @pytest.mark.parametrize("N", [274, 275])
 def test_scp_crossing_crowd_around_the_row_cap_size(N):
-    """DMPC_VAR_SCP (dmpc_scp_kernel) at the scene sizes where 15 (N - 1) crosses its row cap of 4096 (row_capacity, dmpc_api.hip:606):
+    """DMPC_VAR_SCP (dmpc_scp_kernel) at the scene sizes where 15 (N - 1) crosses its row cap of 4096 (row_capacity):
     a crossing crowd (every agent heads for the mirror of its start).  Every agent either matches the oracle or carries ST_CAPACITY
     with zero outputs, and dmpc_last_solve_kernel names the SCP kernel.  The cap itself is NOT reached here: these agents add at most
     four steps (about 1100 rows); an agent needs all 15 steps, with more than 4096 rows that can become active, to overflow"""

@@ -15,7 +15,7 @@ import pytest
 
 import multiagent_planning_amd as mp
 from multiagent_planning_amd import _lib, workload as wl
-from helpers import ROOT
+from helpers import ROOT, lib_source
 import obstacles as ob
 import test_gpu_paths as paths
 import test_gpu_obstacles as obstacle_tests
@@ -50,7 +50,7 @@ def _same(a, b, what):
 
 def default_close_cap():
     """the context default as the library's source states it"""
-    src = open(os.path.join(ROOT, "multiagent_planning_amd", "csrc", "dmpc_api.hip")).read()
+    src = lib_source()
     return int(re.search(r"\bint close_cap = (\d+);", src).group(1))
 
 

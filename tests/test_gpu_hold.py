@@ -11,7 +11,7 @@ import pytest
 
 import multiagent_planning_amd as mp
 from multiagent_planning_amd import workload as wl
-from helpers import ROOT
+from helpers import ROOT, lib_source
 import hold as ho
 import mission as ms
 import obstacles as ob
@@ -71,7 +71,7 @@ def test_without_a_failure_hold_equals_stop_byte_for_byte(shape, kind):
     scene (stop fuses the post step into the solve launch, hold never does), 40 scenes (two parts on contexts of their own) and mixed precision"""
     n = 40 if shape == "split40" else (3 if shape == "mixed" else 1)
     if n == 40:
-        src = open(os.path.join(ROOT, "multiagent_planning_amd", "csrc", "dmpc_api.hip")).read()
+        src = lib_source()
         assert "(S >= 128 ? 4 : (S >= 32 ? 2 : 1))" in src
     b = ho.batch([(kind, i % 3) for i in range(n)])
     d = mp.Dmpc("bound", precision="mixed" if shape == "mixed" else "f64", **ho.KW)

@@ -11,7 +11,7 @@ import pytest
 
 import multiagent_planning_amd as mp
 from multiagent_planning_amd import workload as wl
-from helpers import ROOT
+from helpers import ROOT, lib_source
 import obstacles as ob
 import mission as ms
 
@@ -49,7 +49,7 @@ def test_one_stage_equals_the_one_leg_entries_byte_for_byte(shape):
     kt = 30
     r, s, p = _tiny(n)
     if n == 40:
-        src = open(os.path.join(ROOT, "multiagent_planning_amd", "csrc", "dmpc_api.hip")).read()
+        src = lib_source()
         assert "(S >= 128 ? 4 : (S >= 32 ? 2 : 1))" in src
         for b in (r, s, p):
             b["goals"][7, 0, :, 0] += 2.0                                             # too far for 30 columns

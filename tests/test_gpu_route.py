@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import multiagent_planning_amd as mp
-from helpers import ROOT
+from helpers import ROOT, lib_source
 import mission as ms
 import route as rt
 
@@ -45,7 +45,7 @@ def test_one_waypoint_equals_transition_and_hold_byte_for_byte(shape):
     kt, tol = 30, ms.ERROR_TOL
     batches = [ms.batch([name] * n, list(range(n))) for name in ("reached", "static", "path")]
     if n == 40:
-        src = open(os.path.join(ROOT, "multiagent_planning_amd", "csrc", "dmpc_api.hip")).read()
+        src = lib_source()
         assert "(S >= 128 ? 4 : (S >= 32 ? 2 : 1))" in src
         for b in batches:
             b["goals"][7, 0, :, 0] += 2.0                                             # too far for 30 columns

@@ -14,7 +14,7 @@ from scipy.interpolate import CubicSpline
 import multiagent_planning_amd as mp
 from multiagent_planning_amd import driver
 from oracle import postcheck as PC
-from helpers import ROOT
+from helpers import ROOT, lib_source
 import obstacles as ob
 import scripted as sc
 
@@ -147,7 +147,7 @@ def test_transition_scripted_batch_split_and_device_all_context():
     A DMPC_DEVICE_ALL context runs the call on its first GPU."""
     po, pf, path = sc.mixed_batch(36)
     assert all(not np.array_equal(path[i], path[j]) for i in range(36) for j in range(i))
-    src = open(os.path.join(ROOT, "multiagent_planning_amd", "csrc", "dmpc_api.hip")).read()
+    src = lib_source()
     assert "(S >= 128 ? 4 : (S >= 32 ? 2 : 1))" in src and "at[(size_t)i] = (int)((long)S * i / parts)" in src      # 36 scenes: parts of 18
     assert np.abs(path[18 + 17] - path[17]).max() > 0.03 and np.abs(path[12 + 5] - path[5]).max() > 0.02      # same place in another part: another path
     d = mp.Dmpc("bound", **sc.KW)

@@ -14,7 +14,7 @@ import multiagent_planning_amd as mp
 from multiagent_planning_amd import resultio, workload as wl
 import mission as ms
 import setpoints as sp
-from helpers import GOLD, unrescale
+from helpers import GOLD, lib_source, unrescale
 
 pytestmark = pytest.mark.gpu
 
@@ -203,7 +203,7 @@ def test_resident_histories_after_a_transition_equal_host_arrays():
 def test_resident_histories_of_a_split_batch_and_of_a_mission():
     b = ms.batch(["reached"] * 40, list(range(40)))
     d = mp.Dmpc("bound", **ms.KW)
-    src = open(os.path.join(os.path.dirname(GOLD), os.pardir, "multiagent_planning_amd", "csrc", "dmpc_api.hip")).read()
+    src = lib_source()
     assert "(S >= 128 ? 4 : (S >= 32 ? 2 : 1))" in src                        # (40 scenes: two parts on contexts of their own)
     tr = d.transition(b["po"], b["goals"][:, 0], 30, ms.ERROR_TOL)
     res = d.setpoints(tr["K_T_used"], N=4, KT_alloc=30)
