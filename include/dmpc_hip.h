@@ -839,8 +839,8 @@ DMPC_API int dmpc_replan_routes_device(dmpc_ctx *ctx, int S, int N_cmd, int M, i
  *             loop over dmpc_step_device_cmd themselves (behind dmpc_advance_device); scene_done [S] or NULL: scenes with a non-zero word are
  *             skipped.  With no disturbance set it returns 0 and launches nothing.
  * Batch split as dmpc_transition.  A DMPC_DEVICE_ALL context with a disturbance set runs the call unsharded on its first GPU;
- * dmpc_transition_sharded[_gather] refuse while one is set; there is no RCCL form.  Not modelled: a "measured" state apart from the true one,
- * re-anchoring of the agent's table column, disturbed uncommanded or scripted vehicles.
+ * dmpc_transition_sharded[_gather] refuse while one is set; there is no RCCL form.  Not modelled here: disturbed uncommanded or scripted
+ * vehicles.  A planning state apart from the true one and re-anchoring of the agent's table column: dmpc_set_feedback, below.
  * Refused (-1, nothing launched, a message that starts with the entry's name) by dmpc_set_disturbance and dmpc_disturbance_sample: a negative or
  * non-finite amp_p or amp_v, a non-finite wind or push value, n_push < 0, wind_scenes < 0, a NULL array with a positive count, a push with
  * scene < 0, agent < 0 or column < 1.  By a transition entry, dmpc_disturbance_sample and dmpc_disturb_device: wind_scenes neither 0, 1 nor S, a
@@ -906,6 +906,69 @@ DMPC_API int dmpc_start_plan(const dmpc_params *prm, int n, const double *x_p, c
                     double *plan_a);
 DMPC_API int dmpc_start_plan_device(dmpc_ctx *ctx, int n, const double *x_p, const double *x_v, const double *x_a, double *plan_p, double *plan_v,
                            double *plan_a, void *stream);
+
+/* Event-triggered feedback (additive, the ABI revision stays 8): THE PLANNING STATE APART FROM THE TRUE STATE.  NO REFERENCE COUNTERPART (the rule
+ * is the one the reference author's follow-up describes: plan from your own prediction while the vehicle tracks it, re-initialise from the
+ * vehicle's state only when the tracking error passes a threshold).  A feedback policy is a SETTING OF THE CONTEXT, persistent like the
+ * disturbance: dmpc_set_feedback(ctx, fb); NULL clears.  It is honoured by dmpc_transition, _cmd, _scripted, _mission, _hold, _route and
+ * _replan.  WITHOUT A DISTURBANCE THE POLICY IS INERT (e == 0 for ever): such a flight, like one with no policy, enqueues what it enqueued before
+ * and returns the same bytes.  tests/feedback.py restates the rule; the loop, dmpc_feedback_device, dmpc_feedback_apply_host and that
+ * restatement agree bit for bit.
+ *   per commanded agent: the TRUE state x = (x_p, x_v) -- recorded in the histories, judged by ReachedGoal, read by the route, re-plan and mission
+ *             rules, exactly as before; the PLANNING state xh the solver starts from; the tracking error e = (e_p, e_v).
+ *   column 0: xh = x, e = 0 -- also in a flight with a start (dmpc_set_start), WHATEVER THE PREVIOUS FLIGHT ENDED WITH: e is not carried
+ *             across dmpc_flight_end.  So with trigger = (0, 0) every column ends with e == 0 and cut-and-continue stays bit-identical; with other
+ *             thresholds it need not.
+ *   column k >= 1, for every commanded agent of a scene that was running when the column began, behind the solve and the hold rule.  Its plan
+ *             rows are p, v, a [3K]; d = (dp, dv) is the disturbance of the column by the rule above (none set: 0).  fp64, every operation
+ *             rounded on its own (no fused multiply-add), per component c:
+ *               advanced (its status after the hold rule has DMPC_ST_SOLVED):
+ *                     q_p = p[c], q_v = v[c];   g_p = (e_p + h * e_v) + dp;   g_v = e_v + dv
+ *               not advanced:
+ *                     q = xh unchanged;         g_p = e_p + dp;               g_v = e_v + dv
+ *               x_p = q_p + g_p;   x_v = q_v + g_v;   x_a = a[c] (advanced only)
+ *               n_p = sqrt((g_px*g_px + g_py*g_py) + g_pz*g_pz);   n_v likewise
+ *               event = (n_p > trigger_p) || (n_v > trigger_v)
+ *               event:    xh = x;  e = 0;  and if reanchor, for kk = 0 .. K-1:
+ *                             table_next[3kk+c] = table_next[3kk+c] + (g_p + ((double)kk * h) * g_v)        (the agent's column of the next table)
+ *                             v[3kk+c]          = v[3kk+c] + g_v
+ *               no event: xh = q;  e = g
+ *             With e == 0 the state is q + d: trigger = (0, 0), reanchor = 0 is the disturbed loop of before, byte for byte.  trigger = +inf
+ *             never feeds back (open loop).  Entry 0 of a re-anchored column is x_p.  The v rows are re-anchored too: they are what the hold
+ *             rule and dmpc_flight_end read as "the previous plan's velocities", so a held or carried plan continues the re-anchored one.
+ *             Nothing depends on launch geometry, batch split or visiting order.
+ *   dmpc_feedback_device: one column on device arrays, enqueued on the caller's stream, for callers that loop over dmpc_step_device_cmd themselves
+ *             (INSTEAD of dmpc_advance_device and dmpc_disturb_device): p_rows, v_rows, a_rows [S][N_cmd][3K] and status [S][N_cmd] of the step;
+ *             x_p, x_v, x_a, xh_p, xh_v, e_p, e_v [S][N_cmd][3]; lT_next [S][3K][N] the table the step wrote; event [S][N_cmd] (out: 0 | 1).
+ *             v_rows and lT_next are in/out.  It applies the context's disturbance of column k, if one is set, and the policy; with no policy
+ *             set it launches nothing.  Scenes with scene_done[s] != 0 (scene_done [S] or NULL) are left alone.
+ *   dmpc_feedback_apply_host: the same column on host arrays with an explicit policy `fb`, an optional disturbance `d` (NULL: none) and the step
+ *             h -- no context, no GPU.
+ *   dmpc_feedback_log: a report on the context's last flight, resident until the next one (a split batch: gathered part by part); any output
+ *             NULL.  event_count, event_first, event_last [S][N_cmd]: first and last are local columns, -1 when there was none.  dev_p_max,
+ *             dev_v_max [S][N_cmd]: the largest n_p / n_v seen, events included (column 0 counts with 0); dev_p_col, dev_v_col their columns,
+ *             ties to the smallest.  xh_p, xh_v, e_p, e_v [S][N_cmd][3]: the planning state and the error at the scene's last column.
+ * Batch split as dmpc_transition (results do not depend on it).  A DMPC_DEVICE_ALL context with a policy set runs the call unsharded on its
+ * first GPU; dmpc_transition_sharded[_gather] refuse while one is set; there is no RCCL form.  Not modelled: measurement noise apart from
+ * process noise (an estimate that does not move the vehicle), e carried across dmpc_flight_end, events forced by the caller.
+ * Refused (-1, nothing launched, a message that starts with the entry's name) by dmpc_set_feedback and dmpc_feedback_apply_host: a NaN or
+ * negative trigger_p or trigger_v, reanchor outside {0, 1}; by dmpc_feedback_device and dmpc_feedback_apply_host: S, N_cmd < 1, N_cmd > N,
+ * k < 1, a NULL array other than scene_done, a disturbance that does not fit the call; dmpc_feedback_device: a DMPC_DEVICE_ALL context;
+ * dmpc_feedback_log: no flight on the context yet, a flight without a policy, a sharded one, S or N_cmd other than the flight's. */
+typedef struct dmpc_feedback {
+    double  trigger_p, trigger_v;   /* thresholds on |g_p| (m) and |g_v| (m/s); >= 0, +inf allowed, NaN refused */
+    int32_t reanchor;               /* 0 | 1: on an event, shift the agent's column of the next table and its v rows onto the true state */
+} dmpc_feedback;
+DMPC_API int dmpc_set_feedback(dmpc_ctx *ctx, const dmpc_feedback *fb);   /* NULL clears */
+DMPC_API int dmpc_feedback_device(dmpc_ctx *ctx, int S, int N, int N_cmd, int k, const double *p_rows, double *v_rows, const double *a_rows,
+                         const int32_t *status, double *x_p, double *x_v, double *x_a, double *xh_p, double *xh_v, double *e_p, double *e_v,
+                         double *lT_next, int32_t *event, const int32_t *scene_done, void *stream);
+DMPC_API int dmpc_feedback_apply_host(const dmpc_feedback *fb, const dmpc_disturbance *d, double h, int S, int N, int N_cmd, int k,
+                             const double *p_rows, double *v_rows, const double *a_rows, const int32_t *status, double *x_p, double *x_v,
+                             double *x_a, double *xh_p, double *xh_v, double *e_p, double *e_v, double *lT_next, int32_t *event,
+                             const int32_t *scene_done);
+DMPC_API int dmpc_feedback_log(dmpc_ctx *ctx, int S, int N_cmd, int32_t *event_count, int32_t *event_first, int32_t *event_last, double *dev_p_max,
+                      int32_t *dev_p_col, double *dev_v_max, int32_t *dev_v_col, double *xh_p, double *xh_v, double *e_p, double *e_v);
 
 /* Standalone forms of the path's small helpers (fused into the step kernels inside the solvers), for callers that
  * invoke them on their own as the reference's scripts do.  Host pointers, synchronous.

@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "dmpc_transition_replan", "dmpc_replan_routes_device",
     "dmpc_set_disturbance", "dmpc_disturbance_sample", "dmpc_disturb_device",
     "dmpc_set_start", "dmpc_flight_end", "dmpc_start_plan", "dmpc_start_plan_device",
+    "dmpc_set_feedback", "dmpc_feedback_device", "dmpc_feedback_apply_host", "dmpc_feedback_log",
 ]
 
 
@@ -78,6 +79,10 @@ class DmpcStart(C.Structure):
     _fields_ = [("S", C.c_int32), ("N_cmd", C.c_int32), ("from_end", C.c_int32), ("src_scene", C.POINTER(C.c_int32)),
                 ("vo", C.POINTER(C.c_double)), ("ao", C.POINTER(C.c_double)), ("plan_p", C.POINTER(C.c_double)), ("plan_v", C.POINTER(C.c_double)),
                 ("plan_a", C.POINTER(C.c_double)), ("col0", C.c_int32)]
+
+
+class DmpcFeedback(C.Structure):
+    _fields_ = [("trigger_p", C.c_double), ("trigger_v", C.c_double), ("reanchor", C.c_int32)]
 
 
 class DmpcError(RuntimeError):
@@ -197,6 +202,13 @@ def load():
         L.dmpc_flight_end.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, ip]
         L.dmpc_start_plan.argtypes = [pp, C.c_int, dp, dp, dp, dp, dp, dp]
         L.dmpc_start_plan_device.argtypes = [vp, C.c_int] + [vp] * 7
+    # event-triggered feedback: the planning state apart from the true state (additive, still revision 8)
+    if hasattr(L, "dmpc_set_feedback"):   # (absent from the older builds tools/with_lib.py may load)
+        L.dmpc_set_feedback.argtypes = [vp, C.POINTER(DmpcFeedback)]
+        L.dmpc_feedback_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 15
+        L.dmpc_feedback_apply_host.argtypes = [C.POINTER(DmpcFeedback), C.POINTER(DmpcDisturbance), C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               dp, dp, dp, ip, dp, dp, dp, dp, dp, dp, dp, dp, ip, ip]
+        L.dmpc_feedback_log.argtypes = [vp, C.c_int, C.c_int, ip, ip, ip, dp, ip, dp, ip, dp, dp, dp, dp]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -446,6 +458,47 @@ def disturbance_sample(h, S, n_cmd, k, **kw):
     return dp, dv
 
 
+def _feedback(trigger_p, trigger_v, reanchor):
+    """the dmpc_feedback descriptor of set_feedback()'s arguments; values are checked by the library"""
+    return DmpcFeedback(float(trigger_p), float(trigger_v), int(reanchor))
+
+
+def feedback_apply(trigger_p, trigger_v, reanchor, h, k, p_rows, v_rows, a_rows, status, x_p, x_v, x_a, xh_p, xh_v, e_p, e_v, lT_next, scene_done=None,
+                   disturb=None):
+    """dmpc_feedback_apply_host (host, no context, no GPU): one column of the feedback rule include/dmpc_hip.h pins.  p_rows, v_rows, a_rows
+    [S,n_cmd,45] and status [S,n_cmd] of the step; x_p .. e_v [S,n_cmd,3]; lT_next [S,45,N]; scene_done [S] or None; disturb: a dict of
+    Dmpc.set_disturbance()'s arguments or None.  Nothing is changed in place: returns dict(x_p, x_v, x_a, xh_p, xh_v, e_p, e_v, v_rows, lT_next,
+    event [S,n_cmd])."""
+    L = load()
+    p_rows, a_rows = _f(p_rows), _f(a_rows)
+    o = {key: _f(a).copy() for key, a in dict(x_p=x_p, x_v=x_v, x_a=x_a, xh_p=xh_p, xh_v=xh_v, e_p=e_p, e_v=e_v, v_rows=v_rows, lT_next=lT_next).items()}
+    status = np.ascontiguousarray(status, dtype=np.int32)
+    if p_rows.ndim != 3 or p_rows.shape[2] != 3 * K_HOR or o["lT_next"].ndim != 3 or o["lT_next"].shape[:2] != (p_rows.shape[0], 3 * K_HOR):
+        raise DmpcError(f"feedback_apply: p_rows {tuple(p_rows.shape)} must be [S,n_cmd,{3 * K_HOR}] and lT_next {tuple(o['lT_next'].shape)} [S,{3 * K_HOR},N]")
+    S, n_cmd = p_rows.shape[:2]
+    for key, a in dict(a_rows=a_rows, v_rows=o["v_rows"]).items():
+        if a.shape != p_rows.shape:
+            raise DmpcError(f"feedback_apply: {key} {tuple(a.shape)} is not shaped like p_rows {tuple(p_rows.shape)}")
+    for key in ("x_p", "x_v", "x_a", "xh_p", "xh_v", "e_p", "e_v"):
+        if o[key].shape != (S, n_cmd, 3):
+            raise DmpcError(f"feedback_apply: {key} {tuple(o[key].shape)} must be [{S},{n_cmd},3]")
+    if status.shape != (S, n_cmd):
+        raise DmpcError(f"feedback_apply: status {tuple(status.shape)} must be [{S},{n_cmd}]")
+    if scene_done is not None:
+        scene_done = np.ascontiguousarray(scene_done, dtype=np.int32)
+        if scene_done.shape != (S,):
+            raise DmpcError(f"feedback_apply: scene_done {tuple(scene_done.shape)} must be [{S}]")
+    fb = _feedback(trigger_p, trigger_v, reanchor)
+    d, keep = _disturbance(**disturb) if disturb is not None else (None, None)
+    o["event"] = np.zeros((S, n_cmd), dtype=np.int32)
+    if L.dmpc_feedback_apply_host(C.byref(fb), C.byref(d) if d is not None else None, float(h), S, o["lT_next"].shape[2], n_cmd, int(k), _dp(p_rows),
+                                  _dp(o["v_rows"]), _dp(a_rows), _ip(status), _dp(o["x_p"]), _dp(o["x_v"]), _dp(o["x_a"]), _dp(o["xh_p"]), _dp(o["xh_v"]),
+                                  _dp(o["e_p"]), _dp(o["e_v"]), _dp(o["lT_next"]), _ip(o["event"]), _ipn(scene_done)):
+        raise DmpcError(L.dmpc_last_error(None).decode())
+    del keep
+    return o
+
+
 def model_matrices(h, K=K_HOR):
     """(Lambda, A_v, A_initp, Delta) -- getPosMat.m / dmpc_soft_bound.m:92-108 / getDeltaMat.m (host, no GPU needed)."""
     L = load()
@@ -587,6 +640,36 @@ class Dmpc:
             yield
         finally:
             self.clear_disturbance()
+
+    # ---- event-triggered feedback --------------------------------------------------------------
+    def set_feedback(self, trigger_p, trigger_v, reanchor=True):
+        """dmpc_set_feedback: from now on transition(), mission(), route() and replan() keep a planning state apart from the true state of every
+        commanded agent (the rule include/dmpc_hip.h pins): the solver starts from its own prediction, and from the true state again only on
+        an EVENT -- the tracking error |g_p| > trigger_p (metres) or |g_v| > trigger_v (m/s).  (0, 0): feed back on every column (the disturbed
+        loop as it was); inf: never.  reanchor: on an event, shift the agent's announced plan onto the true state.  The setting is persistent,
+        like set_disturbance(); without a disturbance it is inert."""
+        fb = _feedback(trigger_p, trigger_v, reanchor)
+        self._chk(self._L.dmpc_set_feedback(self._ctx, C.byref(fb)))
+        return self
+
+    def clear_feedback(self):
+        self._chk(self._L.dmpc_set_feedback(self._ctx, None))
+        return self
+
+    def feedback_log(self, S, n_cmd):
+        """dmpc_feedback_log: the report on this context's last flight with a policy -- dict(event_count, event_first, event_last [S,n_cmd]
+        (local columns, -1: none), dev_p_max, dev_v_max [S,n_cmd] (the largest tracking error seen, events included), dev_p_col, dev_v_col,
+        xh_p, xh_v, e_p, e_v [S,n_cmd,3]: the planning state and the error at the scene's last column)"""
+        S, n_cmd = int(S), int(n_cmd)
+        if S < 1 or n_cmd < 1:
+            raise DmpcError("feedback_log: S and n_cmd must be >= 1")
+        o = {k: np.zeros((S, n_cmd), dtype=np.int32) for k in ("event_count", "event_first", "event_last", "dev_p_col", "dev_v_col")}
+        o.update({k: np.zeros((S, n_cmd)) for k in ("dev_p_max", "dev_v_max")})
+        o.update({k: np.zeros((S, n_cmd, 3)) for k in ("xh_p", "xh_v", "e_p", "e_v")})
+        self._chk(self._L.dmpc_feedback_log(self._ctx, S, n_cmd, _ip(o["event_count"]), _ip(o["event_first"]), _ip(o["event_last"]), _dp(o["dev_p_max"]),
+                                            _ip(o["dev_p_col"]), _dp(o["dev_v_max"]), _ip(o["dev_v_col"]), _dp(o["xh_p"]), _dp(o["xh_v"]), _dp(o["e_p"]),
+                                            _dp(o["e_v"])))
+        return o
 
     # ---- start in motion ------------------------------------------------------------------------
     def set_start(self, vo=None, ao=None, plan=None, col0=0, from_end=False, src_scene=None, S=None, N_cmd=None):
@@ -1177,6 +1260,12 @@ class Dmpc:
     def disturb_device(self, S, n_cmd, k, x_p, x_v, scene_done=0, stream=0):
         """dmpc_disturb_device: the disturbance in force, of column k, on device arrays x_p, x_v [S,n_cmd,3] (behind advance_device)"""
         self._chk(self._L.dmpc_disturb_device(self._ctx, S, n_cmd, k, x_p, x_v, scene_done, stream))
+
+    def feedback_device(self, S, N, n_cmd, k, p_rows, v_rows, a_rows, status, x_p, x_v, x_a, xh_p, xh_v, e_p, e_v, lT_next, event, scene_done=0, stream=0):
+        """dmpc_feedback_device: one column of the feedback rule (the disturbance in force inside it) on device arrays, behind step_device_cmd and
+        INSTEAD of advance_device / disturb_device; v_rows and lT_next are in/out, event [S,n_cmd] is written"""
+        self._chk(self._L.dmpc_feedback_device(self._ctx, S, N, n_cmd, k, p_rows, v_rows, a_rows, status, x_p, x_v, x_a, xh_p, xh_v, e_p, e_v, lT_next, event,
+                                               scene_done, stream))
 
     def step_device(self, S, G, Cn, g_local, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out, lT_next, status, info, stream=0):
         self._chk(self._L.dmpc_step_device(self._ctx, S, G, Cn, g_local, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out,

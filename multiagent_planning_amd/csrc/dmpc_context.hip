@@ -144,6 +144,17 @@ struct Disturbance {
     void set(const dmpc_disturbance &d);
 };
 
+// dmpc_set_feedback's copy of the policy (dmpc_feedback.hip), and what the last flight left for dmpc_feedback_log
+struct Feedback {
+    bool on = false;
+    double trigger_p = 0.0, trigger_v = 0.0;
+    int reanchor = 0;
+};
+struct FeedbackFlight {
+    bool valid = false, live = false;   // valid: the flight had a policy; live: ... and a disturbance, so the loop kept xh, e and the log (else xh = x, e = 0, no event)
+    int S = 0, N_cmd = 0;
+};
+
 // dmpc_set_start's armed start (dmpc_start.hip).  Host form: copies of the caller's arrays, uploaded by the flight that consumes it.  from_end: the
 // snapshot stands in the context's start_x / start_plan already (a split flight: in every part's context), `col` is each scene's column 0
 struct StartState {
@@ -210,6 +221,10 @@ struct dmpc_ctx {
     DevBuf route_wp, route_state;                                          // dmpc_transition_route: waypoints [S][N_cmd][W][3]; ints: n_wp, cur, since [S][N_cmd] each, wp_col [S][N_cmd][W]
     Disturbance dist;                                                      // dmpc_set_disturbance: the disturbance in force (children of a split batch get a copy per call)
     DevBuf dist_buf; std::vector<unsigned char> dist_stage; long dist_key = -1;   // ... of a call on the device: wind | sorted pushes | offsets [S * N_cmd + 1]; its host staging; the shape dmpc_disturb_device uploaded for
+    // event-triggered feedback (dmpc_feedback.hip)
+    Feedback fb;                                                           // dmpc_set_feedback: the policy in force (children of a split batch get a copy per call)
+    FeedbackFlight fb_flight;                                              // what dmpc_feedback_log reads of the last flight
+    DevBuf fb_x, fb_g, fb_ev, fb_logi, fb_logd;                            // of a flight: xh_p | xh_v | e_p | e_v [S][N_cmd][3] each; the event record g_p | g_v [S][N_cmd][6] (also dmpc_feedback_device's) and its flag [S][N_cmd]; the log: count, first, last, p_col, v_col [S][N_cmd] each; p_max, v_max [S][N_cmd] each
     // a flight's start and end (dmpc_start.hip)
     StartState start; FlightEnd end; std::vector<int32_t> start_src_host;                                       // dmpc_set_start: the armed start; the end of the last flight, valid until the step scratch is used again
     DevBuf start_x, start_plan, start_col, end_x, end_plan, end_src;       // a start on the device: x_p | x_v | x_a, plan_p | plan_v | plan_a rows, col0 [S]; dmpc_flight_end's gather; (source scene, last column) [S][2]

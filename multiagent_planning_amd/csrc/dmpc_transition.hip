@@ -306,6 +306,47 @@ struct DisturbDev {
     }
 };
 
+// the device side of a feedback policy (dmpc_feedback.hip), live only next to a disturbance (without one e stays 0 and the flight is the plain
+// one): the planning state and the error in ctx->fb_x, the event record, the log.  The solver's io.x_p / x_v point at xh; everything else keeps
+// reading the true state in ctx->xp / xv / xa.
+struct FeedbackDev {
+    dmpc_ctx *ctx; const TransitionCall &c; hipStream_t st;
+    size_t A = 0;
+    explicit operator bool() const { return ctx->fb.on && ctx->dist.on; }
+    double *x(int u) const { return ctx->fb_x.as<double>() + (size_t)u * A * 3; }   // xh_p, xh_v, e_p, e_v
+    // column 0, behind whatever set its true state: xh = x, e = 0; no event yet; the log's column 0 (deviation 0)
+    int begin(const double *xp, const double *xv) {
+        ctx->fb_flight = FeedbackFlight{ctx->fb.on, (bool)*this, c.S, c.N_cmd};
+        if (!*this) return 0;
+        A = (size_t)c.S * c.N_cmd;
+        if (ctx->fb_x.ensure(4 * A * 24) || ctx->fb_g.ensure(A * 48) || ctx->fb_ev.ensure(A * 4) || ctx->fb_logi.ensure(5 * A * 4) || ctx->fb_logd.ensure(2 * A * 8))
+            FAIL(ctx, "device allocation failed");
+        HIPCHK(ctx, hipMemcpyAsync(x(0), xp, A * 24, hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(x(1), xv, A * 24, hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemsetAsync(x(2), 0, 2 * A * 24, st));
+        HIPCHK(ctx, hipMemsetAsync(ctx->fb_ev.p, 0, A * 4, st));
+        int *li = ctx->fb_logi.as<int>();
+        HIPCHK(ctx, hipMemsetAsync(li, 0, 5 * A * 4, st));             // count, (first, last), p_col, v_col
+        HIPCHK(ctx, hipMemsetAsync(li + A, 0xff, 2 * A * 4, st));      // first = last = -1
+        HIPCHK(ctx, hipMemsetAsync(ctx->fb_logd.p, 0, 2 * A * 8, st));
+        return 0;
+    }
+    // the post step of column k on the step's rows `out`, then the re-anchoring of `nxt` and of the v rows
+    void post(const DisturbArgs &D, int k, double **out, double *nxt, double *xp, double *xv, double *xa, int *verdict_k) {
+        const Feedback &f = ctx->fb;
+        int *li = ctx->fb_logi.as<int>(); double *ld = ctx->fb_logd.as<double>();
+        const FeedbackArgs F{D, f.trigger_p, f.trigger_v, (const int *)ctx->status.as<int32_t>(), x(0), x(1), x(2), x(3), ctx->fb_g.as<double>(), ctx->fb_ev.as<int>(),
+                             li, li + A, li + 2 * A, li + 3 * A, li + 4 * A, ld, ld + A};
+        hipLaunchKernelGGL(post_step_feedback_kernel, dim3((unsigned)c.S), dim3(c.N_cmd >= 256 ? 256 : 128), 0, st, F, c.N_cmd, c.K_T_max, k, c.error_tol,
+                           (const double *)out[0], (const double *)out[1], (const double *)out[2], xp, xv, xa, (const double *)ctx->pf.as<double>(),
+                           ctx->hist_p.as<double>(), ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), verdict_k, ctx->scene_done.as<int>(),
+                           (const int *)ctx->scene_done.as<int>());
+        if (f.reanchor)   // (a scene that stopped before this column kept the flag of an earlier one: no scene_done here, which column k has just set)
+            hipLaunchKernelGGL(reanchor_kernel, dim3(grid_1d(A * N3, 4096)), dim3(256), 0, st, c.S, c.N, c.N_cmd, k, ctx->prm.h, (const int *)ctx->fb_ev.as<int>(),
+                               (const double *)ctx->fb_g.as<double>(), (const int *)nullptr, nxt, out[1]);
+    }
+};
+
 static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
 {
     const int S = c.S, N = c.N, N_cmd = c.N_cmd, K_T_max = c.K_T_max;
@@ -325,7 +366,7 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
         HIPCHK(ctx, hipMemcpyAsync(ctx->path.p, c.path, path_bytes, hipMemcpyHostToDevice, st));
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->po.p, c.po, (scripted ? A : T) * 24, hipMemcpyHostToDevice, st));
-    MissionDev mission{ctx, c, st}; HoldDev hold{ctx, c, st}; RouteDev route{ctx, c, st}; DisturbDev disturb{ctx, c, st};
+    MissionDev mission{ctx, c, st}; HoldDev hold{ctx, c, st}; RouteDev route{ctx, c, st}; DisturbDev disturb{ctx, c, st}; FeedbackDev feedback{ctx, c, st};
     StartDev start{ctx, c.start, st};
     if (start && start.begin(S, N_cmd)) return -1;
     if (c.start.from_end) HIPCHK(ctx, hipMemcpyAsync(xp, start.x(0), A * 24, hipMemcpyDeviceToDevice, st));   // (in front of a re-planned route's first plan)
@@ -361,6 +402,7 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
             hipLaunchKernelGGL(static_cols_kernel, dim3(grid_1d((T - A) * N3, 4096)), dim3(256), 0, st, S, N, N_cmd, (const double *)ctx->po.as<double>(),
                                ctx->lT.as<double>(), ctx->lT2.as<double>());
     }
+    if (feedback.begin(xp, xv)) return -1;
     hipLaunchKernelGGL(record_kernel, dim3((unsigned)((A * 3 + 255) / 256)), dim3(256), 0, st, S, N_cmd, K_T_max, 0, xp, xv, xa, ctx->hist_p.as<double>(),
                        ctx->hist_v.as<double>(), ctx->hist_a.as<double>());
     // ReachedGoal is also evaluated on the initDMPC column (failure_rate.m:125 runs after k = 1 as well)
@@ -399,13 +441,16 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
         double **out = hold.outs[k & 1];
         StepIO io = scratch_io(ctx);   // (xp, xv, xa, the goals and the status are the scratch's; a closed loop takes no info)
         io.lT = cur; io.lT_next = nxt; io.info = nullptr;
+        if (feedback) { io.x_p = feedback.x(0); io.x_v = feedback.x(1); }   // (the solver starts from the planning state)
         io.p_out = out[0]; io.v_out = out[1]; io.a_out = out[2];
         io.scene_done = ctx->scene_done.as<int>(); io.lTf = mixed ? ctx->lTf.as<float>() : nullptr; io.post = c.hold || disturb ? nullptr : &post;   // (hold, a disturbance: the post step is a launch of its own)
         const StepShape sh{S, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ 0, /*c_count*/ N_cmd};
         if (launch_step(ctx, sh, io, st)) return -1;
         hold.apply(k, cur, nxt);
         // state advance + history column + scene verdict in one launch (unless the solve kernel did them: tiny launches)
-        if (disturb)   // ... with the disturbance of column k between the advance and the record
+        if (feedback)   // ... with the feedback rule, the disturbance of column k inside it, between the advance and the record
+            feedback.post(disturb.args, k, out, nxt, xp, xv, xa, verdict_k);
+        else if (disturb)   // ... with the disturbance of column k between the advance and the record
             hipLaunchKernelGGL(post_step_disturbed_kernel, dim3((unsigned)S), dim3(N_cmd >= 256 ? 256 : 128), 0, st, disturb.args, N_cmd, K_T_max, k, c.error_tol,
                                (const double *)out[0], (const double *)out[1], (const double *)out[2],
                                (const int *)ctx->status.as<int32_t>(), xp, xv, xa, (const double *)ctx->pf.as<double>(), ctx->hist_p.as<double>(),
@@ -469,7 +514,7 @@ static int part_context(dmpc_ctx *ctx, size_t i, int device)
         ch->opt.no_split = 1; ctx->children.push_back(ch);
     }
     dmpc_ctx *ch = ctx->children[i];
-    ch->dist = ctx->dist;
+    ch->dist = ctx->dist; ch->fb = ctx->fb;
     if (std::memcmp(&ch->prm, &ctx->prm, sizeof(dmpc_params)) != 0 && dmpc_set_params(ch, &ctx->prm)) FAIL(ctx, what + ch->err);
     return 0;
 }
@@ -506,13 +551,14 @@ static std::vector<int> batch_parts(int S, int want, bool sharded)
 }
 
 // A batch in parts (batch_parts), each on a context, HIP stream and host thread of its own.  A DMPC_DEVICE_ALL context shards the agents of each scene
-// over every visible GPU (dmpc_multigpu.hip) -- unless there are uncommanded vehicles, a mission, a route, a disturbance or a start, or fewer agents than twice the GPUs (the
+// over every visible GPU (dmpc_multigpu.hip) -- unless there are uncommanded vehicles, a mission, a route, a disturbance, a feedback policy or a start, or fewer agents than twice the GPUs (the
 // reference's small swarms on an 8-GPU node: sharding N = 4 agents over 8 GPUs is impossible and over 2-3 of them nothing but barriers and peer
 // copies): the first GPU alone then, unsplit, as dmpc_step_batch does.
 static int transition_any(dmpc_ctx *ctx, const TransitionCall &call)
 {
     ctx->split_at.clear();
     ctx->end.valid = false;   // (transition_one sets it again; a sharded flight leaves no end)
+    ctx->fb_flight.valid = false;   // (likewise: dmpc_feedback_log)
     TransitionCall c = call;
     // the armed start is consumed here: every entry has passed its own checks (a from_end start was snapshotted in the parts of the flight it
     // continues, so it is flown in those parts -- or, snapshotted whole, unsplit)
@@ -524,7 +570,7 @@ static int transition_any(dmpc_ctx *ctx, const TransitionCall &call)
         if (a.from_end) start_at = a.at.empty() ? std::vector<int>{0, c.S} : a.at;
         a.armed = false;
     }
-    const bool sharded = ctx->grp && c.N_cmd == c.N && !c.mission && !c.route && !ctx->dist.on && !c.start;
+    const bool sharded = ctx->grp && c.N_cmd == c.N && !c.mission && !c.route && !ctx->dist.on && !ctx->fb.on && !c.start;
     if (sharded && c.N < 2 * ctx->grp->G) return transition_one(ctx, c);
     int (*const body)(dmpc_ctx *, const TransitionCall &) = sharded ? group_transition : transition_one;
     const std::vector<int> at = start_at.empty() ? batch_parts(c.S, ctx->opt.split_parts, sharded) : start_at;

@@ -22,6 +22,8 @@
 //   Ain            = dmpc_mex('rows_dense', params, xi, kc, A)                          -diff_mat*A of structured rows
 //   [pk,vk,ak,K_T_used,scene_status] = dmpc_mex('transition', params, po, pf, K_T_max, error_tol)   the whole k-loop on the GPU
 //   [pk,vk,ak,K_T_used,scene_status] = dmpc_mex('transition_disturbed', params, po, pf, K_T_max, error_tol, noise_p, noise_v, seed, wind, pushes)   see below
+//   [pk,vk,ak,K_T_used,scene_status,event_count,event_first,event_last,dev_p_max,dev_p_col,dev_v_max,dev_v_col,xh_p,xh_v,e_p,e_v] = dmpc_mex('transition_feedback',
+//                    params, po, pf, K_T_max, error_tol, trigger_p, trigger_v, reanchor, noise_p, noise_v, seed, wind, pushes)   see below
 //   [pk,vk,ak,K_T_used,scene_status,stage_col] = dmpc_mex('mission', params, po, goals, K_T_max, error_tol[, deadline])   goals 3 x N_cmd x Q: see below
 //   [pk,vk,ak,K_T_used,scene_status,wp_col] = dmpc_mex('route', params, po, waypoints, K_T_max, error_tol, capture[, n_wp[, timeout]])   waypoints 3 x W x N_cmd: see below
 //   [perm,pf,cost,rounds] = dmpc_mex('assign', params, po, goals[, eps[, max_rounds]])  goal assignment (dmpc_assign_goals): po, goals 3 x N; perm 1 x N, 1-based:
@@ -62,6 +64,11 @@
 // of every commanded agent on every column from 1 on, by the rule include/dmpc_hip.h pins: uniform noise of half-width noise_p (metres) on the
 // position and noise_v (m/s) on the velocity from the stream `seed` (an integer below 2^53), a constant wind (3 x 1, m/s^2, or []) and pushes
 // (8 x n or []: agent, 1-based; history column, 0-based, >= 1; dp (3); dv (3)).  The command sets the disturbance, flies and clears it.
+// Event-triggered feedback (dmpc_set_feedback, no reference counterpart): 'transition_feedback' is 'transition_disturbed' under a feedback policy --
+// the solver starts from its own prediction and from the true state again only on an event, a tracking error above trigger_p (metres) or trigger_v
+// (m/s; Inf: never, 0: on every column); reanchor (0 | 1): an event shifts the agent's announced plan onto the true state.  Behind the flight's
+// outputs come dmpc_feedback_log's, in the order of the list above: event_count, event_first, event_last, dev_p_col, dev_v_col (1 x N_cmd; 0-based history columns,
+// -1: none), dev_p_max, dev_v_max (1 x N_cmd) and xh_p, xh_v, e_p, e_v (3 x N_cmd).  The command sets the policy and the disturbance, flies, reads the log and clears both.
 // Start in motion (dmpc_set_start, no reference counterpart): 'flight_end' returns where the last 'transition*' of the context ended -- x_p, x_v,
 // x_a (3 x N_cmd), every agent's plan of the step that produced the last column, plan_p, plan_v, plan_a (3 x K x N_cmd), and col, that column in the
 // caller's count; 'transition_from' is 'transition' whose column 0 is the state (po, vo, ao) and the plan given instead of initDMPC: vo, ao
@@ -494,6 +501,54 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
         if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);
         if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
+        return;
+    }
+    if (!std::strcmp(cmd, "transition_feedback")) {   // 'transition_disturbed' under a feedback policy (dmpc_set_feedback): set both, fly, read the log, clear both
+        need(nrhs == 14, "transition_feedback: (cmd, params, po, pf, K_T_max, error_tol, trigger_p, trigger_v, reanchor, noise_p, noise_v, seed, wind, pushes)");
+        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3), Nc = (int)(mxGetNumberOfElements(prhs[3]) / 3), KT = (int)mxGetScalar(prhs[4]);
+        need(N >= 1 && Nc >= 1 && Nc <= N && mxGetNumberOfElements(prhs[3]) == (size_t)3 * Nc && KT >= 2, "po must be 3 x N, pf 3 x N_cmd (N_cmd <= N), K_T_max >= 2");
+        const size_t nw = mxGetNumberOfElements(prhs[12]), np8 = mxGetNumberOfElements(prhs[13]);
+        need(nw == 0 || nw == 3, "wind must have 3 elements (or be empty)");
+        need(np8 == 0 || (mxGetM(prhs[13]) == 8 && np8 % 8 == 0), "pushes must be 8 x n: agent (1-based), column (0-based), dp (3), dv (3) (or empty)");
+        std::vector<dmpc_push> push(np8 / 8);
+        for (size_t j = 0; j < push.size(); ++j) {
+            const double *q = mxGetPr(prhs[13]) + 8 * j;
+            push[j].scene = 0; push[j].agent = (int32_t)q[0] - 1; push[j].column = (int32_t)q[1];
+            for (int c = 0; c < 3; ++c) { push[j].dp[c] = q[2 + c]; push[j].dv[c] = q[5 + c]; }
+        }
+        const dmpc_disturbance dist{(uint64_t)mxGetScalar(prhs[11]), mxGetScalar(prhs[9]), mxGetScalar(prhs[10]), nw ? mxGetPr(prhs[12]) : nullptr, nw ? 1 : 0,
+                                    push.empty() ? nullptr : push.data(), (int)push.size()};
+        const dmpc_feedback fbk{mxGetScalar(prhs[6]), mxGetScalar(prhs[7]), (int32_t)mxGetScalar(prhs[8])};
+        const mwSize d3[3] = {3, (mwSize)KT, (mwSize)Nc};
+        plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        mxArray *v = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), *a = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        int32_t used = 0, sst = 0;
+        if (dmpc_set_feedback(ctx, &fbk)) mexErrMsgIdAndTxt("dmpc:transition_feedback", "%s", dmpc_last_error(ctx));
+        if (dmpc_set_disturbance(ctx, &dist)) {
+            const std::string why = dmpc_last_error(ctx);
+            dmpc_set_feedback(ctx, nullptr);
+            mexErrMsgIdAndTxt("dmpc:transition_feedback", "%s", why.c_str());
+        }
+        int rc = Nc == N ? dmpc_transition(ctx, 1, N, mxGetPr(prhs[2]), mxGetPr(prhs[3]), KT, mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v), mxGetPr(a),
+                                           &used, &sst)
+                         : dmpc_transition_cmd(ctx, 1, N, Nc, mxGetPr(prhs[2]), mxGetPr(prhs[3]), KT, mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v),
+                                               mxGetPr(a), &used, &sst);
+        mxArray *f[11];   // event_count, event_first, event_last, dev_p_col, dev_v_col | dev_p_max, dev_v_max | xh_p, xh_v, e_p, e_v
+        for (int u = 0; u < 11; ++u) f[u] = mxCreateDoubleMatrix(u < 7 ? 1 : 3, Nc, mxREAL);
+        std::vector<int32_t> li((size_t)5 * Nc);
+        if (!rc) rc = dmpc_feedback_log(ctx, 1, Nc, &li[0], &li[Nc], &li[2 * (size_t)Nc], mxGetPr(f[5]), &li[3 * (size_t)Nc], mxGetPr(f[6]), &li[4 * (size_t)Nc],
+                                        mxGetPr(f[7]), mxGetPr(f[8]), mxGetPr(f[9]), mxGetPr(f[10]));
+        const std::string why = rc ? dmpc_last_error(ctx) : "";
+        dmpc_set_disturbance(ctx, nullptr);   // the contexts are kept between calls: the settings must not outlive this one
+        dmpc_set_feedback(ctx, nullptr);
+        if (rc) mexErrMsgIdAndTxt("dmpc:transition_feedback", "%s", why.c_str());
+        for (int u = 0; u < 5; ++u)
+            for (int i = 0; i < Nc; ++i) mxGetPr(f[u])[i] = (double)li[(size_t)u * Nc + i];
+        if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);
+        if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
+        static const int order[11] = {0, 1, 2, 5, 3, 6, 4, 7, 8, 9, 10};   // dmpc_feedback_log's order of outputs
+        for (int u = 0; u < 11; ++u) if (nlhs > 5 + u) plhs[5 + u] = f[order[u]];
         return;
     }
     if (!std::strcmp(cmd, "flight_end")) {   // where the last 'transition*' of this context ended (dmpc_flight_end): what 'transition_from' takes
