@@ -134,7 +134,9 @@ enum {
                           * fp32; the QP itself (cost, factor, multipliers, propagation) and all inputs / outputs stay
                           * fp64.  Every entry point takes such a context: the host-pointer ones, the device-pointer steps (they
                           * make the fp32 copy of the caller's fp64 table themselves) and the sharded transitions, where the table
-                          * the ranks exchange per step is the fp32 one (half the payload).  BASELINE configs[4].               */
+                          * the ranks exchange per step is the fp32 one (half the payload).  BASELINE configs[4].  The exact pruning,
+                          * the infeasibility certificate and the ladder start keep a margin of 2e-5 that covers the fp32 rounding for
+                          * coordinates up to about 8 m per axis: DESIGN.md section 6 has the bounds and the domain.          */
     DMPC_PREC_F32FACTOR = 2, /* the QP below fp64 (BASELINE configs[4], "fp32 vs fp64 tolerance sweep"): the inverse factor of the
                           * active-set solver -- its largest object, what every iteration multiplies with -- is STORED in fp32; cost,
                           * multipliers, residuals and the refinement of the result stay fp64 (lambda += T T' rho until the active-set

@@ -33,6 +33,15 @@ DMPC_API int dmpc_debug_read_hdr(dmpc_ctx *ctx, int *host_out, int n_agents);
  * [S][3][ncell + 1], entry records [2][S][3][G C][4] (the two 16-byte halves), nbr_cnt [agents][pieces], nbr_list [agents][capacity],
  * close_cnt [agents], close_list [agents][close capacity][2].  Refused before any list build and when out_bytes is too small. */
 DMPC_API int dmpc_debug_read_grid(dmpc_ctx *ctx, int *shape, void *out, size_t out_bytes);
+/* the scan's own records of ONE agent (column n of the table; host pointers, one wave, as dmpc_rows_one) as a step of this context forms them:
+ * a DMPC_PREC_MIXED context on the fp32 copy of the table, with the float instantiation of the scan and the row builder.  prune = 0: every row
+ * the reference builds; 1: the step's exact pruning.  hdr[8]: rows kept, the reference's row count, viol_k, status (DMPC_ST_INFEAS from the
+ * slack-free variants' certificate), flags (1: violation, 4: the cpp flavour's collision flag), rows_exist, first retry-ladder level that is not
+ * certainly infeasible, launch-order key.  The first min(hdr[0], max_rows) kept rows in the reference's order: xi[3], rhs, kc (1-based), slack
+ * coefficient, slack cost term, slack lower bound (zeros for the slack-free variants).  Order 2 only, not DMPC_VAR_SCP
+ * (tests/test_gpu_mixed_rows.py). */
+DMPC_API int dmpc_debug_scan_rows(dmpc_ctx *ctx, int N, int n, const double *l, const double *po, const double *vo, int prune, int max_rows,
+                                  int32_t *hdr, double *xi, double *rhs, int32_t *kc, double *slack_coef, double *slack_term, double *slack_lb);
 /* force the solve launch order of the next launches (n = 0: the built-in policy) */
 DMPC_API int dmpc_debug_set_order(dmpc_ctx *ctx, const int *host_order, int n);
 /* a coalesced streaming read of `bytes` bytes at 8 or 16 bytes per lane, `reps` launches: the known byte count rocprofv3's FETCH_SIZE is

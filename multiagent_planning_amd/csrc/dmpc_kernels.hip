@@ -703,9 +703,13 @@ __device__ __forceinline__ void scan_body(const StepParams &P, const int lane, c
                 L.r_b[pos] = -rr;
                 L.r_kc[pos] = kc;
                     if (soft) {
-                    real sd = pd, st = P.term, slb = -0.05;
+                    // (cost term and lower bound are constants of the fp64 QP, not results of the row arithmetic: they stay doubles in the float
+                    // instantiation too -- -0.05 and -0.01 are no floats, and a term that is none would lose its low bits;
+                    // tests/test_gpu_mixed_rows.py holds them to the reference's bits)
+                    real sd = pd;
+                    double st = P.term, slb = -0.05;
                     if (var == VAR_BOUND2 || var == VAR_ALL3) slb = -0.01;           // bound2:77, all:92
-                    else if (cppv) slb = -(real)0.01f;                              // dmpc.cpp:907-914,1079: -eps <= lim, float lim = 0.01
+                    else if (cppv) slb = -(double)0.01f;                            // dmpc.cpp:907-914,1079: -eps <= lim, float lim = 0.01
                     else if (var == VAR_SOFTALL) { sd = 1.0; st = -1e5; slb = -INFINITY; }  // solveSoftDMPC.m:21,65
                     else if (var == VAR_SOFTALL_C) {
                         // solveSoftDMPC_c.m:18-20,60-63: rows [Ainr I], cost EPS eps^2 + f_eps eps with EPS = 1e6 (K/k)^2, f_eps = -1e4 (K/k)^2, k the
@@ -717,7 +721,7 @@ __device__ __forceinline__ void scan_body(const StepParams &P, const int lane, c
                         sd = (real)isq; st = (real)(lin * isq); slb = -INFINITY;
                     }
                     else if (var == VAR_CPP1) { sd = 1.0; st = -1e6; slb = -INFINITY; }     // dmpc.cpp:629-633,715: [A I] x <= b, eps <= 0, f_w = -10^6
-                    else if (var == VAR_REPAIR) { st = P.term / pd; slb = -INFINITY; }      // repair:77,81 (term ./ prev_dist)
+                    else if (var == VAR_REPAIR) { st = (real)(P.term / pd); slb = -INFINITY; }   // repair:77,81 (term ./ prev_dist)
                     L.r_sd[pos] = sd; L.r_st[pos] = st; L.r_slb[pos] = slb;
                 }
             }

@@ -245,8 +245,64 @@ extern "C" int dmpc_solve_one(dmpc_ctx *ctx, int N, int n, const double *l, cons
     return step_batch_one(ctx, c);
 }
 
+// the scan + collision rows of ONE agent on one wave, with the step's own parameter block and scan kernel: staged, launched, header and rows
+// fetched.  What is this runner's: the exact row capacity and the order of the rows.  `f32_table`: a mixed-precision context's scan reads the
+// fp32 copy of the table and runs its float instantiation, as a step's does (mixed_table; an fp64 context stays on the fp64 table either way);
+// `prune`: the step's exact pruning instead of every row the reference builds.
+struct ScanRowsOne {
+    int hdr[8];
+    int nrmax = 0;
+    bool soft = false;
+    std::vector<double> buf;     // the agent's slice of the row scratch: xi [nrmax][3], rhs, then (soft) slack coefficient, cost term, lower bound
+    std::vector<int> kbuf, idx;  // constrained step of a row (0-based); the rows in the reference's order
+};
+static int scan_rows_one(dmpc_ctx *ctx, int N, int n, const double *l, const double *po, const double *vo, bool f32_table, bool prune,
+                         bool fetch_rows, ScanRowsOne &R)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const dmpc_params &p = ctx->prm;
+    const bool soft = R.soft = variant_soft(p.variant);
+    const double zero3[3] = {0, 0, 0};   // (the scan reads no acceleration and no goal)
+    StepCall c{};   // (no outputs: the rows come back below)
+    c.S = 1; c.N = N; c.N_cmd = 1; c.l = l; c.x_p = po; c.x_v = vo; c.x_a = c.pf = zero3;
+    if (upload_step(ctx, c, st)) return -1;
+    StepIO io = scratch_io(ctx);
+    if (f32_table && mixed_table(ctx, io, (size_t)N3 * N, st)) return -1;
+    // the step's own parameter block and scan kernel; what is this entry's: the exact row capacity, one wave
+    StepParams P;
+    fill_constants(ctx, P);
+    P.S = 1; P.G = 1; P.C = N; P.g_local = 0; P.c_first = n; P.c_count = 1;
+    const long want = (p.variant == DMPC_VAR_HARD ? (long)K : (p.variant == DMPC_VAR_ALL3 ? 3L : 1L)) * (N > 1 ? N - 1 : 1);
+    P.nrmax = R.nrmax = (int)((want + 1) & ~1L);   // the exact worst case: nothing is truncated here
+    P.lT = io.lTf ? (const double *)io.lTf : io.lT; P.x_p = io.x_p; P.x_v = io.x_v; P.x_a = io.x_a; P.pf = io.pf;
+    P.status = io.status; P.no_prune = prune ? 0 : 1; P.qcap = QMAX; P.qover_bit = ST_CAPACITY;
+    const size_t per = (size_t)P.nrmax * (soft ? 7 : 4);
+    if (ctx->rowbuf.ensure(per * 8) || ctx->rowkc.ensure((size_t)P.nrmax * 4) || ctx->hdr.ensure(32)) FAIL(ctx, "device allocation failed");
+    P.rowbuf = ctx->rowbuf.as<double>(); P.rowkc = ctx->rowkc.as<int>(); P.hdr = ctx->hdr.as<int>();
+    P.lds_per_wave = (int)scan_lds_bytes();
+    launch_params_kernel(scan_kernel(soft, io.lTf != nullptr, /*fast_exit*/ false, p.order == 4), dim3(1), dim3(64), scan_lds_bytes(), st, P);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(R.hdr, ctx->hdr.p, 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const int nr = R.hdr[0];
+    if (nr > 0 && fetch_rows) {
+        R.buf.resize(per);
+        R.kbuf.resize(P.nrmax);
+        HIPCHK(ctx, hipMemcpy(R.buf.data(), ctx->rowbuf.p, per * 8, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(R.kbuf.data(), ctx->rowkc.p, (size_t)P.nrmax * 4, hipMemcpyDeviceToHost));
+        // reference order: horizon step major, neighbour index minor (the hard variant's rows are emitted
+        // neighbour-chunk major on the device): stable sort by constrained step
+        R.idx.resize(nr);
+        for (int i = 0; i < nr; ++i) R.idx[i] = i;
+        if (p.variant == DMPC_VAR_HARD || p.variant == DMPC_VAR_ALL3)
+            std::stable_sort(R.idx.begin(), R.idx.end(), [&](int a_, int b_) { return R.kbuf[a_] < R.kbuf[b_]; });
+    }
+    return 0;
+}
+
 // a5/a6 standalone: scan + collision rows of ONE agent in the reference's row order
-// (CheckCollSoftDMPC.m + CollConstrSoftDMPC.m and variants), without pruning.  Host pointers.
+// (CheckCollSoftDMPC.m + CollConstrSoftDMPC.m and variants), always on the fp64 table, without pruning.  Host pointers.
 extern "C" int dmpc_rows_one(dmpc_ctx *ctx, int N, int n, const double *l, const double *po, const double *vo,
                              int max_rows, double *xi, double *rhs, double *slack_coef, int32_t *kc, int32_t *nrows,
                              int32_t *viol_k, int32_t *status)
@@ -254,53 +310,46 @@ extern "C" int dmpc_rows_one(dmpc_ctx *ctx, int N, int n, const double *l, const
     if (!ctx) { g_err = "dmpc_rows_one: ctx is NULL"; return -1; }
     if (N < 1 || n < 0 || n >= N || max_rows < 0) FAIL(ctx, "dmpc_rows_one: bad arguments");
     if (!l || !po || !vo || !nrows || !viol_k || !status) FAIL(ctx, "dmpc_rows_one: NULL pointer");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const dmpc_params &p = ctx->prm;
-    const bool soft = variant_soft(p.variant);
-    const double zero3[3] = {0, 0, 0};   // (the scan reads no acceleration and no goal)
-    StepCall c{};   // (no outputs: the rows come back below)
-    c.S = 1; c.N = N; c.N_cmd = 1; c.l = l; c.x_p = po; c.x_v = vo; c.x_a = c.pf = zero3;
-    if (upload_step(ctx, c, st)) return -1;
-    // the step's own parameter block and scan kernel, always on the fp64 table; what is this entry's: the exact row capacity, no pruning, one wave
-    StepParams P;
-    fill_constants(ctx, P);
-    P.S = 1; P.G = 1; P.C = N; P.g_local = 0; P.c_first = n; P.c_count = 1;
-    const long want = (p.variant == DMPC_VAR_HARD ? (long)K : (p.variant == DMPC_VAR_ALL3 ? 3L : 1L)) * (N > 1 ? N - 1 : 1);
-    P.nrmax = (int)((want + 1) & ~1L);   // the exact worst case: nothing is pruned or truncated here
-    const StepIO io = scratch_io(ctx);
-    P.lT = io.lT; P.x_p = io.x_p; P.x_v = io.x_v; P.x_a = io.x_a; P.pf = io.pf;
-    P.status = io.status; P.no_prune = 1; P.qcap = QMAX; P.qover_bit = ST_CAPACITY;
-    const size_t per = (size_t)P.nrmax * (soft ? 7 : 4);
-    if (ctx->rowbuf.ensure(per * 8) || ctx->rowkc.ensure((size_t)P.nrmax * 4) || ctx->hdr.ensure(32)) FAIL(ctx, "device allocation failed");
-    P.rowbuf = ctx->rowbuf.as<double>(); P.rowkc = ctx->rowkc.as<int>(); P.hdr = ctx->hdr.as<int>();
-    P.lds_per_wave = (int)scan_lds_bytes();
-    launch_params_kernel(scan_kernel(soft, /*f32_table*/ false, /*fast_exit*/ false, p.order == 4), dim3(1), dim3(64), scan_lds_bytes(), st, P);
-    HIPCHK(ctx, hipGetLastError());
-    int hdr[8];
-    HIPCHK(ctx, hipMemcpyAsync(hdr, ctx->hdr.p, 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    const int nr = hdr[0];
-    *nrows = hdr[1]; *viol_k = hdr[2]; *status = hdr[3] & (DMPC_ST_COLL | DMPC_ST_CAPACITY);
-    const int cnt = nr < max_rows ? nr : max_rows;
-    if (cnt > 0 && xi && rhs && kc) {
-        std::vector<double> buf(per);
-        std::vector<int> kbuf(P.nrmax);
-        HIPCHK(ctx, hipMemcpy(buf.data(), ctx->rowbuf.p, per * 8, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(kbuf.data(), ctx->rowkc.p, (size_t)P.nrmax * 4, hipMemcpyDeviceToHost));
-        // reference order: horizon step major, neighbour index minor (the hard variant's rows are emitted
-        // neighbour-chunk major on the device): stable sort by constrained step
-        std::vector<int> idx(nr);
-        for (int i = 0; i < nr; ++i) idx[i] = i;
-        if (p.variant == DMPC_VAR_HARD || p.variant == DMPC_VAR_ALL3)
-            std::stable_sort(idx.begin(), idx.end(), [&](int a_, int b_) { return kbuf[a_] < kbuf[b_]; });
-        for (int i = 0; i < cnt; ++i) {
-            const int j = idx[i];
-            xi[3 * i] = buf[3 * j]; xi[3 * i + 1] = buf[3 * j + 1]; xi[3 * i + 2] = buf[3 * j + 2];
-            rhs[i] = buf[(size_t)3 * P.nrmax + j];
-            if (slack_coef) slack_coef[i] = soft ? buf[(size_t)4 * P.nrmax + j] : 0.0;
-            kc[i] = kbuf[j] + 1;   // 1-based like the reference's k_ctr
-        }
+    ScanRowsOne R;
+    const bool rows = max_rows > 0 && xi && rhs && kc;
+    if (scan_rows_one(ctx, N, n, l, po, vo, /*f32_table*/ false, /*prune*/ false, rows, R)) return -1;
+    *nrows = R.hdr[1]; *viol_k = R.hdr[2]; *status = R.hdr[3] & (DMPC_ST_COLL | DMPC_ST_CAPACITY);
+    const int cnt = R.hdr[0] < max_rows ? R.hdr[0] : max_rows;
+    for (int i = 0; rows && i < cnt; ++i) {
+        const int j = R.idx[i];
+        xi[3 * i] = R.buf[3 * j]; xi[3 * i + 1] = R.buf[3 * j + 1]; xi[3 * i + 2] = R.buf[3 * j + 2];
+        rhs[i] = R.buf[(size_t)3 * R.nrmax + j];
+        if (slack_coef) slack_coef[i] = R.soft ? R.buf[(size_t)4 * R.nrmax + j] : 0.0;
+        kc[i] = R.kbuf[j] + 1;   // 1-based like the reference's k_ctr
+    }
+    return 0;
+}
+
+// development (include/dmpc_hip_dev.h): the scan's own records of ONE agent as a step of this context forms them -- a mixed-precision context
+// on the fp32 copy of the table with the float instantiation of the scan and the row builder -- with or without the exact pruning
+extern "C" int dmpc_debug_scan_rows(dmpc_ctx *ctx, int N, int n, const double *l, const double *po, const double *vo, int prune,
+                                    int max_rows, int32_t *hdr, double *xi, double *rhs, int32_t *kc, double *slack_coef,
+                                    double *slack_term, double *slack_lb)
+{
+    if (!ctx) { g_err = "dmpc_debug_scan_rows: ctx is NULL"; return -1; }
+    if (N < 1 || n < 0 || n >= N || max_rows < 0) FAIL(ctx, "dmpc_debug_scan_rows: bad arguments");
+    if (!l || !po || !vo || !hdr) FAIL(ctx, "dmpc_debug_scan_rows: NULL pointer");
+    if (max_rows > 0 && (!xi || !rhs || !kc || !slack_coef || !slack_term || !slack_lb)) FAIL(ctx, "dmpc_debug_scan_rows: NULL row array");
+    if (ctx->prm.order == 4) FAIL(ctx, "dmpc_debug_scan_rows: order 2 only (the context's super-ellipsoid is of order 4)");
+    if (ctx->prm.variant == DMPC_VAR_SCP) FAIL(ctx, "dmpc_debug_scan_rows: solveDMPC (DMPC_VAR_SCP) builds its rows inside its own kernel, pass by pass");
+    ScanRowsOne R;
+    if (scan_rows_one(ctx, N, n, l, po, vo, /*f32_table*/ true, prune != 0, max_rows > 0, R)) return -1;
+    for (int i = 0; i < 8; ++i) hdr[i] = R.hdr[i];
+    const int cnt = R.hdr[0] < max_rows ? R.hdr[0] : max_rows;
+    const size_t m = (size_t)R.nrmax;
+    for (int i = 0; i < cnt; ++i) {
+        const int j = R.idx[i];
+        xi[3 * i] = R.buf[3 * j]; xi[3 * i + 1] = R.buf[3 * j + 1]; xi[3 * i + 2] = R.buf[3 * j + 2];
+        rhs[i] = R.buf[3 * m + j];
+        kc[i] = R.kbuf[j] + 1;   // 1-based like the reference's k_ctr
+        slack_coef[i] = R.soft ? R.buf[4 * m + j] : 0.0;
+        slack_term[i] = R.soft ? R.buf[5 * m + j] : 0.0;
+        slack_lb[i] = R.soft ? R.buf[6 * m + j] : 0.0;
     }
     return 0;
 }
