@@ -951,8 +951,9 @@ DMPC_API int dmpc_start_plan_device(dmpc_ctx *ctx, int n, const double *x_p, con
  *             dev_v_max [S][N_cmd]: the largest n_p / n_v seen, events included (column 0 counts with 0); dev_p_col, dev_v_col their columns,
  *             ties to the smallest.  xh_p, xh_v, e_p, e_v [S][N_cmd][3]: the planning state and the error at the scene's last column.
  * Batch split as dmpc_transition (results do not depend on it).  A DMPC_DEVICE_ALL context with a policy set runs the call unsharded on its
- * first GPU; dmpc_transition_sharded[_gather] refuse while one is set; there is no RCCL form.  Not modelled: measurement noise apart from
- * process noise (an estimate that does not move the vehicle), e carried across dmpc_flight_end, events forced by the caller.
+ * first GPU; dmpc_transition_sharded[_gather] refuse while one is set; there is no RCCL form.  Measurement noise apart from process noise (an
+ * estimate that does not move the vehicle): dmpc_set_measurement, below.  Not modelled: e carried across dmpc_flight_end, events forced by the
+ * caller.
  * Refused (-1, nothing launched, a message that starts with the entry's name) by dmpc_set_feedback and dmpc_feedback_apply_host: a NaN or
  * negative trigger_p or trigger_v, reanchor outside {0, 1}; by dmpc_feedback_device and dmpc_feedback_apply_host: S, N_cmd < 1, N_cmd > N,
  * k < 1, a NULL array other than scene_done, a disturbance that does not fit the call; dmpc_feedback_device: a DMPC_DEVICE_ALL context;
@@ -971,6 +972,67 @@ DMPC_API int dmpc_feedback_apply_host(const dmpc_feedback *fb, const dmpc_distur
                              const int32_t *scene_done);
 DMPC_API int dmpc_feedback_log(dmpc_ctx *ctx, int S, int N_cmd, int32_t *event_count, int32_t *event_first, int32_t *event_last, double *dev_p_max,
                       int32_t *dev_p_col, double *dev_v_max, int32_t *dev_v_col, double *xh_p, double *xh_v, double *e_p, double *e_v);
+
+/* Measured state (additive, the ABI revision stays 8): SENSOR NOISE AND A FIXED-GAIN ESTIMATE IN THE LOOP.  NO REFERENCE COUNTERPART.  In the
+ * feedback rule above the planner knows the true deviation g exactly; here it sees g through a noisy measurement and keeps an estimate of it.  A
+ * measurement model is a SETTING OF THE CONTEXT, persistent like the disturbance and the policy: dmpc_set_measurement(ctx, m); NULL clears.  IT
+ * CHANGES WHAT THE FEEDBACK RULE DECIDES ON AND WHAT THE PLANNER IS RE-INITIALISED TO; IT NEVER MOVES THE VEHICLE.  It is honoured only under a
+ * feedback policy: dmpc_transition, _cmd, _scripted, _mission, _hold, _route and _replan refuse a flight with a measurement set and no policy
+ * (set one with dmpc_set_feedback; trigger (0, 0) is "feed the measurement back on every column").  A disturbance is not required: the policy is
+ * live when a disturbance OR a measurement is set; with a measurement alone dp = dv = 0.  With no measurement set every entry enqueues what it
+ * enqueued before and returns the same bytes.  tests/estimate.py restates the rule; the loop, dmpc_estimate_device, dmpc_estimate_apply_host and
+ * that restatement agree bit for bit.
+ *   per commanded agent one more pair of state, beside the true error e: the BELIEF eh = (eh_p, eh_v), the planner's estimate of e.
+ *   column 0: eh = 0 -- also in a flight with a start; like e, it is not carried across dmpc_flight_end.
+ *   column k >= 1: the same agents and the same place in the column as the feedback rule.  fp64, every operation rounded on its own (no fused
+ *             multiply-add), per component c; uniform as in the disturbance rule, col0 the start's (none: 0), s the scene's index in the call:
+ *               sid   = (uint64) 1 << 63 | (uint64) s << 32 | i          (a stream of its own: never the disturbance's, even with equal seeds)
+ *               u_j   = 2.0 * uniform(seed, sid, 6 * (col0 + k) + j) - 1.0          j = 0 .. 5
+ *               m_p   = amp_p * u_c;   m_v = amp_v * u_(3+c)
+ *               q, g_p, g_v, x_p = q_p + g_p, x_v = q_v + g_v, x_a: exactly the feedback rule's (the vehicle: unchanged by the measurement)
+ *               b_p   = advanced ? eh_p + h * eh_v : eh_p;   b_v = eh_v
+ *               y_p   = amp_p > 0 ? g_p + m_p : g_p;         y_v likewise with amp_v          (amp == 0: no addition, -0.0 stays -0.0)
+ *               gh_p  = gain_p == 1.0 ? y_p : b_p + gain_p * (y_p - b_p);   gh_v likewise with gain_v
+ *               n_p   = sqrt((gh_px*gh_px + gh_py*gh_py) + gh_pz*gh_pz);   n_v likewise;   event = (n_p > trigger_p) || (n_v > trigger_v)
+ *               event:    xh = q + gh;  e = g - gh;  eh = 0;  and if reanchor: the re-anchoring above with (gh_p, gh_v) in the place of (g_p, g_v)
+ *               no event: xh = q;       e = g;       eh = gh
+ *             With amp = (0, 0) and gain = (1, 1) this is the feedback rule bit for bit: gh = g, q + g is the expression of x, g - g = +0.
+ *   dmpc_measurement_sample: m_p, m_v [S][N_cmd][3] of column k (col0 = 0) on the host -- no context, no GPU; k == 0 gives zeros.
+ *   dmpc_estimate_device: dmpc_feedback_device with the belief eh_p, eh_v [S][N_cmd][3] (in/out) behind e_v.  It applies the context's
+ *             disturbance of column k if one is set, its measurement and its policy; with no policy or no measurement set it launches nothing.
+ *             dmpc_feedback_device itself never reads the measurement.
+ *   dmpc_estimate_apply_host: the same column on host arrays with an explicit policy `fb`, measurement `m` and optional disturbance `d` (NULL:
+ *             none) -- no context, no GPU.
+ *   dmpc_estimate_log: a report on the context's last flight, on dmpc_feedback_log's model (resident until the next flight, a split batch
+ *             gathered part by part, any output NULL).  err_p_max, err_v_max [S][N_cmd]: the largest estimation error |g_p - gh_p|, |g_v - gh_v|
+ *             (the norm as n_p, of the differences rounded once); dev_p_max, dev_v_max: the largest TRUE |g_p|, |g_v|; *_col their local
+ *             columns, ties to the smallest, column 0 counts with 0.  eh_p, eh_v [S][N_cmd][3]: the belief at the scene's last column.
+ *             ON SUCH A FLIGHT dmpc_feedback_log's dev_* ARE THE NORMS THE EVENTS WERE DECIDED ON (of gh, not of g), and its xh, e are as stored
+ *             by the rule above (e need not be 0 after an event).
+ * Batch split, DMPC_DEVICE_ALL and the sharded entries as for the policy: a DMPC_DEVICE_ALL context flies such a flight on its first GPU,
+ * dmpc_transition_sharded[_gather] refuse while a measurement is set; there is no RCCL form.  Not modelled: a Kalman filter with a covariance
+ * (the gains are fixed), e or eh carried across dmpc_flight_end, events forced by the caller, noisy knowledge of uncommanded or scripted vehicles.
+ * Refused (-1, nothing launched, a message that starts with the entry's name) by dmpc_set_measurement (the descriptor is checked before the
+ * context), dmpc_measurement_sample and dmpc_estimate_apply_host, by the field's name: a negative or non-finite amp_p or amp_v, a gain_p or
+ * gain_v outside (0, 1] or NaN; by dmpc_estimate_device and dmpc_estimate_apply_host what dmpc_feedback_device / _apply_host refuse, and a NULL
+ * eh_p, eh_v or m; by dmpc_estimate_log: no flight yet, a sharded one, a flight without a policy or without a measurement, S or N_cmd other than
+ * the flight's. */
+typedef struct dmpc_measurement {
+    uint64_t seed;
+    double amp_p, amp_v;     /* half-widths of the uniform sensor noise on position (m) and velocity (m/s); >= 0, finite */
+    double gain_p, gain_v;   /* fixed gains of the estimate, in (0, 1]; 1: the estimate is the measurement */
+} dmpc_measurement;          /* 40 bytes, offsets 0 8 16 24 32 */
+DMPC_API int dmpc_set_measurement(dmpc_ctx *ctx, const dmpc_measurement *m);   /* NULL clears */
+DMPC_API int dmpc_measurement_sample(const dmpc_measurement *m, int S, int N_cmd, int k, double *mp, double *mv);
+DMPC_API int dmpc_estimate_device(dmpc_ctx *ctx, int S, int N, int N_cmd, int k, const double *p_rows, double *v_rows, const double *a_rows,
+                         const int32_t *status, double *x_p, double *x_v, double *x_a, double *xh_p, double *xh_v, double *e_p, double *e_v,
+                         double *eh_p, double *eh_v, double *lT_next, int32_t *event, const int32_t *scene_done, void *stream);
+DMPC_API int dmpc_estimate_apply_host(const dmpc_feedback *fb, const dmpc_measurement *m, const dmpc_disturbance *d, double h, int S, int N,
+                             int N_cmd, int k, const double *p_rows, double *v_rows, const double *a_rows, const int32_t *status, double *x_p,
+                             double *x_v, double *x_a, double *xh_p, double *xh_v, double *e_p, double *e_v, double *eh_p, double *eh_v,
+                             double *lT_next, int32_t *event, const int32_t *scene_done);
+DMPC_API int dmpc_estimate_log(dmpc_ctx *ctx, int S, int N_cmd, double *err_p_max, int32_t *err_p_col, double *err_v_max, int32_t *err_v_col,
+                      double *dev_p_max, int32_t *dev_p_col, double *dev_v_max, int32_t *dev_v_col, double *eh_p, double *eh_v);
 
 /* Standalone forms of the path's small helpers (fused into the step kernels inside the solvers), for callers that
  * invoke them on their own as the reference's scripts do.  Host pointers, synchronous.

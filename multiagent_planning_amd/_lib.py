@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "dmpc_set_disturbance", "dmpc_disturbance_sample", "dmpc_disturb_device",
     "dmpc_set_start", "dmpc_flight_end", "dmpc_start_plan", "dmpc_start_plan_device",
     "dmpc_set_feedback", "dmpc_feedback_device", "dmpc_feedback_apply_host", "dmpc_feedback_log",
+    "dmpc_set_measurement", "dmpc_measurement_sample", "dmpc_estimate_device", "dmpc_estimate_apply_host", "dmpc_estimate_log",
 ]
 
 
@@ -83,6 +84,10 @@ class DmpcStart(C.Structure):
 
 class DmpcFeedback(C.Structure):
     _fields_ = [("trigger_p", C.c_double), ("trigger_v", C.c_double), ("reanchor", C.c_int32)]
+
+
+class DmpcMeasurement(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("amp_p", C.c_double), ("amp_v", C.c_double), ("gain_p", C.c_double), ("gain_v", C.c_double)]
 
 
 class DmpcError(RuntimeError):
@@ -209,6 +214,14 @@ def load():
         L.dmpc_feedback_apply_host.argtypes = [C.POINTER(DmpcFeedback), C.POINTER(DmpcDisturbance), C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                                dp, dp, dp, ip, dp, dp, dp, dp, dp, dp, dp, dp, ip, ip]
         L.dmpc_feedback_log.argtypes = [vp, C.c_int, C.c_int, ip, ip, ip, dp, ip, dp, ip, dp, dp, dp, dp]
+    # measured state: sensor noise and a fixed-gain estimate in the loop (additive, still revision 8)
+    if hasattr(L, "dmpc_set_measurement"):   # (absent from the older builds tools/with_lib.py may load)
+        L.dmpc_set_measurement.argtypes = [vp, C.POINTER(DmpcMeasurement)]
+        L.dmpc_measurement_sample.argtypes = [C.POINTER(DmpcMeasurement), C.c_int, C.c_int, C.c_int, dp, dp]
+        L.dmpc_estimate_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 17
+        L.dmpc_estimate_apply_host.argtypes = [C.POINTER(DmpcFeedback), C.POINTER(DmpcMeasurement), C.POINTER(DmpcDisturbance), C.c_double, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, dp, dp, dp, ip, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip, ip]
+        L.dmpc_estimate_log.argtypes = [vp, C.c_int, C.c_int, dp, ip, dp, ip, dp, ip, dp, ip, dp, dp]
     L.dmpc_partition.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip]
     L.dmpc_comm_unique_id.argtypes = [C.c_char_p]
     L.dmpc_comm_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
@@ -499,6 +512,61 @@ def feedback_apply(trigger_p, trigger_v, reanchor, h, k, p_rows, v_rows, a_rows,
     return o
 
 
+def _measurement(noise_p=0.0, noise_v=0.0, gain_p=1.0, gain_v=1.0, seed=0):
+    """the dmpc_measurement descriptor of set_measurement()'s arguments; values are checked by the library"""
+    return DmpcMeasurement(int(seed), float(noise_p), float(noise_v), float(gain_p), float(gain_v))
+
+
+def measurement_sample(S, n_cmd, k, **kw):
+    """dmpc_measurement_sample (host, no context, no GPU): (m_p, m_v), [S,n_cmd,3] each, the sensor noise of column k by the rule
+    include/dmpc_hip.h pins, for Dmpc.set_measurement()'s arguments"""
+    L = load()
+    m = _measurement(**kw)
+    mp, mv = np.zeros((int(S), int(n_cmd), 3)), np.zeros((int(S), int(n_cmd), 3))
+    if L.dmpc_measurement_sample(C.byref(m), int(S), int(n_cmd), int(k), _dp(mp), _dp(mv)):
+        raise DmpcError(L.dmpc_last_error(None).decode())
+    return mp, mv
+
+
+def estimate_apply(trigger_p, trigger_v, reanchor, h, k, p_rows, v_rows, a_rows, status, x_p, x_v, x_a, xh_p, xh_v, e_p, e_v, eh_p, eh_v, lT_next,
+                   scene_done=None, disturb=None, measure=None):
+    """dmpc_estimate_apply_host (host, no context, no GPU): one column of the feedback rule behind a measurement, as include/dmpc_hip.h pins it.
+    feedback_apply()'s arguments with the belief eh_p, eh_v [S,n_cmd,3] behind e_v; measure: a dict of Dmpc.set_measurement()'s arguments (None:
+    no noise, gain 1).  Nothing is changed in place: returns dict(x_p, x_v, x_a, xh_p, xh_v, e_p, e_v, eh_p, eh_v, v_rows, lT_next, event
+    [S,n_cmd])."""
+    L = load()
+    p_rows, a_rows = _f(p_rows), _f(a_rows)
+    o = {key: _f(a).copy() for key, a in dict(x_p=x_p, x_v=x_v, x_a=x_a, xh_p=xh_p, xh_v=xh_v, e_p=e_p, e_v=e_v, eh_p=eh_p, eh_v=eh_v, v_rows=v_rows,
+                                              lT_next=lT_next).items()}
+    status = np.ascontiguousarray(status, dtype=np.int32)
+    if p_rows.ndim != 3 or p_rows.shape[2] != 3 * K_HOR or o["lT_next"].ndim != 3 or o["lT_next"].shape[:2] != (p_rows.shape[0], 3 * K_HOR):
+        raise DmpcError(f"estimate_apply: p_rows {tuple(p_rows.shape)} must be [S,n_cmd,{3 * K_HOR}] and lT_next {tuple(o['lT_next'].shape)} [S,{3 * K_HOR},N]")
+    S, n_cmd = p_rows.shape[:2]
+    for key, a in dict(a_rows=a_rows, v_rows=o["v_rows"]).items():
+        if a.shape != p_rows.shape:
+            raise DmpcError(f"estimate_apply: {key} {tuple(a.shape)} is not shaped like p_rows {tuple(p_rows.shape)}")
+    for key in ("x_p", "x_v", "x_a", "xh_p", "xh_v", "e_p", "e_v", "eh_p", "eh_v"):
+        if o[key].shape != (S, n_cmd, 3):
+            raise DmpcError(f"estimate_apply: {key} {tuple(o[key].shape)} must be [{S},{n_cmd},3]")
+    if status.shape != (S, n_cmd):
+        raise DmpcError(f"estimate_apply: status {tuple(status.shape)} must be [{S},{n_cmd}]")
+    if scene_done is not None:
+        scene_done = np.ascontiguousarray(scene_done, dtype=np.int32)
+        if scene_done.shape != (S,):
+            raise DmpcError(f"estimate_apply: scene_done {tuple(scene_done.shape)} must be [{S}]")
+    fb = _feedback(trigger_p, trigger_v, reanchor)
+    m = _measurement(**(measure or {}))
+    d, keep = _disturbance(**disturb) if disturb is not None else (None, None)
+    o["event"] = np.zeros((S, n_cmd), dtype=np.int32)
+    if L.dmpc_estimate_apply_host(C.byref(fb), C.byref(m), C.byref(d) if d is not None else None, float(h), S, o["lT_next"].shape[2], n_cmd, int(k),
+                                  _dp(p_rows), _dp(o["v_rows"]), _dp(a_rows), _ip(status), _dp(o["x_p"]), _dp(o["x_v"]), _dp(o["x_a"]), _dp(o["xh_p"]),
+                                  _dp(o["xh_v"]), _dp(o["e_p"]), _dp(o["e_v"]), _dp(o["eh_p"]), _dp(o["eh_v"]), _dp(o["lT_next"]), _ip(o["event"]),
+                                  _ipn(scene_done)):
+        raise DmpcError(L.dmpc_last_error(None).decode())
+    del keep
+    return o
+
+
 def model_matrices(h, K=K_HOR):
     """(Lambda, A_v, A_initp, Delta) -- getPosMat.m / dmpc_soft_bound.m:92-108 / getDeltaMat.m (host, no GPU needed)."""
     L = load()
@@ -669,6 +737,34 @@ class Dmpc:
         self._chk(self._L.dmpc_feedback_log(self._ctx, S, n_cmd, _ip(o["event_count"]), _ip(o["event_first"]), _ip(o["event_last"]), _dp(o["dev_p_max"]),
                                             _ip(o["dev_p_col"]), _dp(o["dev_v_max"]), _ip(o["dev_v_col"]), _dp(o["xh_p"]), _dp(o["xh_v"]), _dp(o["e_p"]),
                                             _dp(o["e_v"])))
+        return o
+
+    # ---- measured state --------------------------------------------------------------------------
+    def set_measurement(self, noise_p=0.0, noise_v=0.0, gain_p=1.0, gain_v=1.0, seed=0):
+        """dmpc_set_measurement: from now on the feedback rule of a flight decides on an ESTIMATE of the tracking error -- the true deviation plus
+        uniform sensor noise of half-widths noise_p (m), noise_v (m/s), blended into the planner's belief with the fixed gains gain_p, gain_v in
+        (0, 1] (1: the estimate is the measurement) -- and re-initialises the planner to it (the rule include/dmpc_hip.h pins).  It never moves the
+        vehicle.  Persistent, like set_disturbance() and set_feedback(); a flight with a measurement and no feedback policy is refused."""
+        m = _measurement(noise_p, noise_v, gain_p, gain_v, seed)
+        self._chk(self._L.dmpc_set_measurement(self._ctx, C.byref(m)))
+        return self
+
+    def clear_measurement(self):
+        self._chk(self._L.dmpc_set_measurement(self._ctx, None))
+        return self
+
+    def estimate_log(self, S, n_cmd):
+        """dmpc_estimate_log: the report on this context's last flight with a measurement -- dict(err_p_max, err_v_max [S,n_cmd]: the largest
+        estimation error |g - gh|; dev_p_max, dev_v_max: the largest TRUE tracking error |g|; err_p_col, err_v_col, dev_p_col, dev_v_col their
+        local columns; eh_p, eh_v [S,n_cmd,3]: the belief at the scene's last column)"""
+        S, n_cmd = int(S), int(n_cmd)
+        if S < 1 or n_cmd < 1:
+            raise DmpcError("estimate_log: S and n_cmd must be >= 1")
+        o = {k: np.zeros((S, n_cmd), dtype=np.int32) for k in ("err_p_col", "err_v_col", "dev_p_col", "dev_v_col")}
+        o.update({k: np.zeros((S, n_cmd)) for k in ("err_p_max", "err_v_max", "dev_p_max", "dev_v_max")})
+        o.update({k: np.zeros((S, n_cmd, 3)) for k in ("eh_p", "eh_v")})
+        self._chk(self._L.dmpc_estimate_log(self._ctx, S, n_cmd, _dp(o["err_p_max"]), _ip(o["err_p_col"]), _dp(o["err_v_max"]), _ip(o["err_v_col"]),
+                                            _dp(o["dev_p_max"]), _ip(o["dev_p_col"]), _dp(o["dev_v_max"]), _ip(o["dev_v_col"]), _dp(o["eh_p"]), _dp(o["eh_v"])))
         return o
 
     # ---- start in motion ------------------------------------------------------------------------
@@ -1266,6 +1362,13 @@ class Dmpc:
         INSTEAD of advance_device / disturb_device; v_rows and lT_next are in/out, event [S,n_cmd] is written"""
         self._chk(self._L.dmpc_feedback_device(self._ctx, S, N, n_cmd, k, p_rows, v_rows, a_rows, status, x_p, x_v, x_a, xh_p, xh_v, e_p, e_v, lT_next, event,
                                                scene_done, stream))
+
+    def estimate_device(self, S, N, n_cmd, k, p_rows, v_rows, a_rows, status, x_p, x_v, x_a, xh_p, xh_v, e_p, e_v, eh_p, eh_v, lT_next, event, scene_done=0,
+                        stream=0):
+        """dmpc_estimate_device: feedback_device with the measurement in force between the true deviation and the rule's decision; eh_p, eh_v
+        [S,n_cmd,3] is the belief (in/out).  With no policy or no measurement set it launches nothing."""
+        self._chk(self._L.dmpc_estimate_device(self._ctx, S, N, n_cmd, k, p_rows, v_rows, a_rows, status, x_p, x_v, x_a, xh_p, xh_v, e_p, e_v, eh_p, eh_v,
+                                               lT_next, event, scene_done, stream))
 
     def step_device(self, S, G, Cn, g_local, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out, lT_next, status, info, stream=0):
         self._chk(self._L.dmpc_step_device(self._ctx, S, G, Cn, g_local, lT, x_p, x_v, x_a, pf, p_out, v_out, a_out,

@@ -27,7 +27,7 @@
 #include "dmpc_debug.hip"            // development aids: trace, read probe, header and grid readers, forced order
 #include "dmpc_plan.hip"             // route planning round static vehicles, before and during a flight: the wavefront planner's kernels, the three entries
 #include "dmpc_disturb.hip"          // disturbed transitions: the rule on the host and the device, the descriptor's check and upload, the three entries
-#include "dmpc_feedback.hip"         // event-triggered feedback: the rule on the host and the device, the post step with it, the re-anchoring, the four entries
+#include "dmpc_feedback.hip"         // event-triggered feedback: the rule on the host and the device, the post step with it, the re-anchoring, the four entries; the measurement model (dmpc_set_measurement) and its five
 #include "dmpc_start.hip"            // a flight from a given or carried state and plan: the braking plan, the gather of a flight's end, the four entries
 #include "dmpc_transition.hip"       // the closed loop: batch_parts, the record of a call, transition_one, transition_any, the seven entries
 #include "dmpc_postcheck_host.hip"   // the post-checks on the host: the record of a call, PcPrep, the three checks, pc_run, the five entries

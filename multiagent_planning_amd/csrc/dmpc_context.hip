@@ -151,8 +151,15 @@ struct Feedback {
     int reanchor = 0;
 };
 struct FeedbackFlight {
-    bool valid = false, live = false;   // valid: the flight had a policy; live: ... and a disturbance, so the loop kept xh, e and the log (else xh = x, e = 0, no event)
+    bool valid = false, live = false;   // valid: the flight had a policy; live: ... and a disturbance or a measurement, so the loop kept xh, e and the log (else xh = x, e = 0, no event)
     int S = 0, N_cmd = 0;
+    bool measured = false;              // ... and a measurement: the loop also kept the belief and dmpc_estimate_log's log
+};
+// dmpc_set_measurement's copy of the measurement model (dmpc_feedback.hip)
+struct Measurement {
+    bool on = false;
+    uint64_t seed = 0;
+    double amp_p = 0.0, amp_v = 0.0, gain_p = 1.0, gain_v = 1.0;
 };
 
 // dmpc_set_start's armed start (dmpc_start.hip).  Host form: copies of the caller's arrays, uploaded by the flight that consumes it.  from_end: the
@@ -224,6 +231,8 @@ struct dmpc_ctx {
     // event-triggered feedback (dmpc_feedback.hip)
     Feedback fb;                                                           // dmpc_set_feedback: the policy in force (children of a split batch get a copy per call)
     FeedbackFlight fb_flight;                                              // what dmpc_feedback_log reads of the last flight
+    Measurement meas;                                                      // dmpc_set_measurement: the measurement model in force (children of a split batch get a copy per call)
+    DevBuf est_x, est_logi, est_logd;                                      // of a measured flight: the belief eh_p | eh_v [S][N_cmd][3] each; dmpc_estimate_log's log: err_p_col, err_v_col, dev_p_col, dev_v_col [S][N_cmd] each; err_p_max, err_v_max, dev_p_max, dev_v_max [S][N_cmd] each
     DevBuf fb_x, fb_g, fb_ev, fb_logi, fb_logd;                            // of a flight: xh_p | xh_v | e_p | e_v [S][N_cmd][3] each; the event record g_p | g_v [S][N_cmd][6] (also dmpc_feedback_device's) and its flag [S][N_cmd]; the log: count, first, last, p_col, v_col [S][N_cmd] each; p_max, v_max [S][N_cmd] each
     // a flight's start and end (dmpc_start.hip)
     StartState start; FlightEnd end; std::vector<int32_t> start_src_host;                                       // dmpc_set_start: the armed start; the end of the last flight, valid until the step scratch is used again

@@ -450,6 +450,7 @@ static int transition_sharded_entry(dmpc_ctx *ctx, const char *who, const Transi
     if (!ctx) { g_err = "dmpc_transition_sharded: ctx is NULL"; return -1; }
     if (ctx->dist.on) FAIL(ctx, std::string(who) + ": a disturbance is set (dmpc_set_disturbance); the sharded loop has no disturbed form");
     if (ctx->fb.on) FAIL(ctx, std::string(who) + ": a feedback policy is set (dmpc_set_feedback); the sharded loop keeps no planning state apart from the true one");
+    if (ctx->meas.on) FAIL(ctx, std::string(who) + ": a measurement is set (dmpc_set_measurement); the sharded loop keeps no estimate of the tracking error");
     if (ctx->start.armed) FAIL(ctx, std::string(who) + ": a start is armed (dmpc_set_start); the sharded loop has no form that starts in motion");
     return check_call(ctx, "dmpc_transition_sharded", c) ? -1 : transition_sharded_impl(ctx, c, gather);
 }

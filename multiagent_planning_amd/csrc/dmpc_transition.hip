@@ -85,6 +85,8 @@ static int check_call(dmpc_ctx *ctx, const std::string &who, const TransitionCal
     if (c.S < 1 || c.N < 1 || c.N_cmd < 1 || c.N_cmd > c.N || c.K_T_max < 2 || !c.po || !c.pf || !c.K_T_used || !c.scene_status || ((c.pk || c.vk || c.ak) && !(c.pk && c.vk && c.ak)))
         FAIL(ctx, who + ": bad arguments");
     if (check_start_shape(ctx, who, c.S, c.N_cmd)) return -1;
+    if (ctx->meas.on && !ctx->fb.on)
+        FAIL(ctx, who + ": a measurement is set (dmpc_set_measurement) and no feedback policy: set one with dmpc_set_feedback (trigger (0, 0) feeds the measurement back on every column)");
     return check_disturb_shape(ctx, who, ctx->dist, c.S, c.N_cmd);
 }
 
@@ -306,17 +308,20 @@ struct DisturbDev {
     }
 };
 
-// the device side of a feedback policy (dmpc_feedback.hip), live only next to a disturbance (without one e stays 0 and the flight is the plain
-// one): the planning state and the error in ctx->fb_x, the event record, the log.  The solver's io.x_p / x_v point at xh; everything else keeps
+// the device side of a feedback policy (dmpc_feedback.hip), live only next to a disturbance or a measurement (without either e stays 0 and the
+// flight is the plain one): the planning state and the error in ctx->fb_x, the event record, the log; with a measurement also the belief in
+// ctx->est_x and dmpc_estimate_log's log.  The solver's io.x_p / x_v point at xh; everything else keeps
 // reading the true state in ctx->xp / xv / xa.
 struct FeedbackDev {
     dmpc_ctx *ctx; const TransitionCall &c; hipStream_t st;
     size_t A = 0;
-    explicit operator bool() const { return ctx->fb.on && ctx->dist.on; }
+    const int *col0 = nullptr;   // a start: the caller's number of every scene's column 0 (the measurement's stream counts from it, as the disturbance's does)
+    explicit operator bool() const { return ctx->fb.on && (ctx->dist.on || ctx->meas.on); }
+    bool measured() const { return ctx->fb.on && ctx->meas.on; }
     double *x(int u) const { return ctx->fb_x.as<double>() + (size_t)u * A * 3; }   // xh_p, xh_v, e_p, e_v
     // column 0, behind whatever set its true state: xh = x, e = 0; no event yet; the log's column 0 (deviation 0)
     int begin(const double *xp, const double *xv) {
-        ctx->fb_flight = FeedbackFlight{ctx->fb.on, (bool)*this, c.S, c.N_cmd};
+        ctx->fb_flight = FeedbackFlight{ctx->fb.on, (bool)*this, c.S, c.N_cmd, measured()};
         if (!*this) return 0;
         A = (size_t)c.S * c.N_cmd;
         if (ctx->fb_x.ensure(4 * A * 24) || ctx->fb_g.ensure(A * 48) || ctx->fb_ev.ensure(A * 4) || ctx->fb_logi.ensure(5 * A * 4) || ctx->fb_logd.ensure(2 * A * 8))
@@ -329,18 +334,34 @@ struct FeedbackDev {
         HIPCHK(ctx, hipMemsetAsync(li, 0, 5 * A * 4, st));             // count, (first, last), p_col, v_col
         HIPCHK(ctx, hipMemsetAsync(li + A, 0xff, 2 * A * 4, st));      // first = last = -1
         HIPCHK(ctx, hipMemsetAsync(ctx->fb_logd.p, 0, 2 * A * 8, st));
+        if (!measured()) return 0;
+        if (ctx->est_x.ensure(2 * A * 24) || ctx->est_logi.ensure(4 * A * 4) || ctx->est_logd.ensure(4 * A * 8)) FAIL(ctx, "device allocation failed");
+        HIPCHK(ctx, hipMemsetAsync(ctx->est_x.p, 0, 2 * A * 24, st));   // eh = 0; the log's column 0 (error 0, deviation 0)
+        HIPCHK(ctx, hipMemsetAsync(ctx->est_logi.p, 0, 4 * A * 4, st));
+        HIPCHK(ctx, hipMemsetAsync(ctx->est_logd.p, 0, 4 * A * 8, st));
         return 0;
     }
     // the post step of column k on the step's rows `out`, then the re-anchoring of `nxt` and of the v rows
     void post(const DisturbArgs &D, int k, double **out, double *nxt, double *xp, double *xv, double *xa, int *verdict_k) {
         const Feedback &f = ctx->fb;
         int *li = ctx->fb_logi.as<int>(); double *ld = ctx->fb_logd.as<double>();
-        const FeedbackArgs F{D, f.trigger_p, f.trigger_v, (const int *)ctx->status.as<int32_t>(), x(0), x(1), x(2), x(3), ctx->fb_g.as<double>(), ctx->fb_ev.as<int>(),
-                             li, li + A, li + 2 * A, li + 3 * A, li + 4 * A, ld, ld + A};
-        hipLaunchKernelGGL(post_step_feedback_kernel, dim3((unsigned)c.S), dim3(c.N_cmd >= 256 ? 256 : 128), 0, st, F, c.N_cmd, c.K_T_max, k, c.error_tol,
-                           (const double *)out[0], (const double *)out[1], (const double *)out[2], xp, xv, xa, (const double *)ctx->pf.as<double>(),
-                           ctx->hist_p.as<double>(), ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), verdict_k, ctx->scene_done.as<int>(),
-                           (const int *)ctx->scene_done.as<int>());
+        if (measured()) {   // the rule decides on the estimate; gh stands in the event record
+            const Measurement &m = ctx->meas;
+            const EstimateArgs E{D, ctx->dist.on ? 1 : 0, m.seed, m.amp_p, m.amp_v, m.gain_p, m.gain_v, c.s0, col0, ctx->prm.h, f.trigger_p, f.trigger_v,
+                                 (const int *)ctx->status.as<int32_t>(), A, x(0), ctx->est_x.as<double>(), ctx->fb_g.as<double>(), ctx->fb_ev.as<int>(), li, ld,
+                                 ctx->est_logi.as<int>(), ctx->est_logd.as<double>()};
+            hipLaunchKernelGGL(post_step_estimate_kernel, dim3((unsigned)c.S), dim3(c.N_cmd >= 256 ? 256 : 128), 0, st, E, c.N_cmd, c.K_T_max, k, c.error_tol,
+                               (const double *)out[0], (const double *)out[1], (const double *)out[2], xp, xv, xa, (const double *)ctx->pf.as<double>(),
+                               ctx->hist_p.as<double>(), ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), verdict_k, ctx->scene_done.as<int>(),
+                               (const int *)ctx->scene_done.as<int>());
+        } else {
+            const FeedbackArgs F{D, f.trigger_p, f.trigger_v, (const int *)ctx->status.as<int32_t>(), x(0), x(1), x(2), x(3), ctx->fb_g.as<double>(), ctx->fb_ev.as<int>(),
+                                 li, li + A, li + 2 * A, li + 3 * A, li + 4 * A, ld, ld + A};
+            hipLaunchKernelGGL(post_step_feedback_kernel, dim3((unsigned)c.S), dim3(c.N_cmd >= 256 ? 256 : 128), 0, st, F, c.N_cmd, c.K_T_max, k, c.error_tol,
+                               (const double *)out[0], (const double *)out[1], (const double *)out[2], xp, xv, xa, (const double *)ctx->pf.as<double>(),
+                               ctx->hist_p.as<double>(), ctx->hist_v.as<double>(), ctx->hist_a.as<double>(), verdict_k, ctx->scene_done.as<int>(),
+                               (const int *)ctx->scene_done.as<int>());
+        }
         if (f.reanchor)   // (a scene that stopped before this column kept the flag of an earlier one: no scene_done here, which column k has just set)
             hipLaunchKernelGGL(reanchor_kernel, dim3(grid_1d(A * N3, 4096)), dim3(256), 0, st, c.S, c.N, c.N_cmd, k, ctx->prm.h, (const int *)ctx->fb_ev.as<int>(),
                                (const double *)ctx->fb_g.as<double>(), (const int *)nullptr, nxt, out[1]);
@@ -372,6 +393,7 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
     if (c.start.from_end) HIPCHK(ctx, hipMemcpyAsync(xp, start.x(0), A * 24, hipMemcpyDeviceToDevice, st));   // (in front of a re-planned route's first plan)
     if (mission.begin() || route.begin() || disturb.begin()) return -1;
     if (start && disturb) disturb.args.col0 = start.col0();
+    if (start) feedback.col0 = start.col0();
     if (reset_run_buffers(ctx, S, K_T_max, hist, st)) return -1;
     // ---- column 0: initDMPC (dmpc_soft_bound.m:117-121): state = (po, 0, 0), table = straight lines
     // (a start, dmpc_start.hip: state = (po, vo, ao) or the carried one, the commanded columns of the table = the start's plan rows)
@@ -443,7 +465,7 @@ static int transition_one(dmpc_ctx *ctx, const TransitionCall &c)
         io.lT = cur; io.lT_next = nxt; io.info = nullptr;
         if (feedback) { io.x_p = feedback.x(0); io.x_v = feedback.x(1); }   // (the solver starts from the planning state)
         io.p_out = out[0]; io.v_out = out[1]; io.a_out = out[2];
-        io.scene_done = ctx->scene_done.as<int>(); io.lTf = mixed ? ctx->lTf.as<float>() : nullptr; io.post = c.hold || disturb ? nullptr : &post;   // (hold, a disturbance: the post step is a launch of its own)
+        io.scene_done = ctx->scene_done.as<int>(); io.lTf = mixed ? ctx->lTf.as<float>() : nullptr; io.post = c.hold || disturb || feedback ? nullptr : &post;   // (hold, a disturbance, a live policy: the post step is a launch of its own)
         const StepShape sh{S, /*G*/ 1, /*C*/ N, /*g_local*/ 0, /*c_first*/ 0, /*c_count*/ N_cmd};
         if (launch_step(ctx, sh, io, st)) return -1;
         hold.apply(k, cur, nxt);
@@ -514,7 +536,7 @@ static int part_context(dmpc_ctx *ctx, size_t i, int device)
         ch->opt.no_split = 1; ctx->children.push_back(ch);
     }
     dmpc_ctx *ch = ctx->children[i];
-    ch->dist = ctx->dist; ch->fb = ctx->fb;
+    ch->dist = ctx->dist; ch->fb = ctx->fb; ch->meas = ctx->meas;
     if (std::memcmp(&ch->prm, &ctx->prm, sizeof(dmpc_params)) != 0 && dmpc_set_params(ch, &ctx->prm)) FAIL(ctx, what + ch->err);
     return 0;
 }

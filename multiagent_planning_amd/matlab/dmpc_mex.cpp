@@ -24,6 +24,8 @@
 //   [pk,vk,ak,K_T_used,scene_status] = dmpc_mex('transition_disturbed', params, po, pf, K_T_max, error_tol, noise_p, noise_v, seed, wind, pushes)   see below
 //   [pk,vk,ak,K_T_used,scene_status,event_count,event_first,event_last,dev_p_max,dev_p_col,dev_v_max,dev_v_col,xh_p,xh_v,e_p,e_v] = dmpc_mex('transition_feedback',
 //                    params, po, pf, K_T_max, error_tol, trigger_p, trigger_v, reanchor, noise_p, noise_v, seed, wind, pushes)   see below
+//   [pk,vk,ak,K_T_used,scene_status,<'transition_feedback's log>,err_p_max,err_p_col,err_v_max,err_v_col,dev_p_max,dev_p_col,dev_v_max,dev_v_col,eh_p,eh_v] =
+//                    dmpc_mex('transition_estimated', <'transition_feedback's arguments>, meas_p, meas_v, gain_p, gain_v, meas_seed)   see below
 //   [pk,vk,ak,K_T_used,scene_status,stage_col] = dmpc_mex('mission', params, po, goals, K_T_max, error_tol[, deadline])   goals 3 x N_cmd x Q: see below
 //   [pk,vk,ak,K_T_used,scene_status,wp_col] = dmpc_mex('route', params, po, waypoints, K_T_max, error_tol, capture[, n_wp[, timeout]])   waypoints 3 x W x N_cmd: see below
 //   [perm,pf,cost,rounds] = dmpc_mex('assign', params, po, goals[, eps[, max_rounds]])  goal assignment (dmpc_assign_goals): po, goals 3 x N; perm 1 x N, 1-based:
@@ -69,6 +71,13 @@
 // (m/s; Inf: never, 0: on every column); reanchor (0 | 1): an event shifts the agent's announced plan onto the true state.  Behind the flight's
 // outputs come dmpc_feedback_log's, in the order of the list above: event_count, event_first, event_last, dev_p_col, dev_v_col (1 x N_cmd; 0-based history columns,
 // -1: none), dev_p_max, dev_v_max (1 x N_cmd) and xh_p, xh_v, e_p, e_v (3 x N_cmd).  The command sets the policy and the disturbance, flies, reads the log and clears both.
+// Measured state (dmpc_set_measurement, no reference counterpart): 'transition_estimated' is 'transition_feedback' in which the rule decides on an
+// estimate of the tracking error -- the true deviation plus uniform sensor noise of half-widths meas_p (metres), meas_v (m/s) from the stream
+// meas_seed, blended into the planner's belief with the fixed gains gain_p, gain_v in (0, 1] -- and re-initialises the planner to it; the vehicle is
+// never moved by it.  Behind 'transition_feedback's outputs (whose dev_* are then the norms the events were decided on) come dmpc_estimate_log's:
+// err_p_max, err_p_col, err_v_max, err_v_col (1 x N_cmd: the largest estimation error and its 0-based column), dev_p_max, dev_p_col, dev_v_max,
+// dev_v_col (the largest TRUE tracking error) and eh_p, eh_v (3 x N_cmd: the belief at the last column).  The command sets all three, flies, reads
+// both logs and clears all three.
 // Start in motion (dmpc_set_start, no reference counterpart): 'flight_end' returns where the last 'transition*' of the context ended -- x_p, x_v,
 // x_a (3 x N_cmd), every agent's plan of the step that produced the last column, plan_p, plan_v, plan_a (3 x K x N_cmd), and col, that column in the
 // caller's count; 'transition_from' is 'transition' whose column 0 is the state (po, vo, ao) and the plan given instead of initDMPC: vo, ao
@@ -549,6 +558,62 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
         static const int order[11] = {0, 1, 2, 5, 3, 6, 4, 7, 8, 9, 10};   // dmpc_feedback_log's order of outputs
         for (int u = 0; u < 11; ++u) if (nlhs > 5 + u) plhs[5 + u] = f[order[u]];
+        return;
+    }
+    if (!std::strcmp(cmd, "transition_estimated")) {   // 'transition_feedback' behind a measurement (dmpc_set_measurement): set all three, fly, read both logs, clear all three
+        need(nrhs == 19, "transition_estimated: (cmd, params, po, pf, K_T_max, error_tol, trigger_p, trigger_v, reanchor, noise_p, noise_v, seed, wind, pushes, meas_p, meas_v, gain_p, gain_v, meas_seed)");
+        const int N = (int)(mxGetNumberOfElements(prhs[2]) / 3), Nc = (int)(mxGetNumberOfElements(prhs[3]) / 3), KT = (int)mxGetScalar(prhs[4]);
+        need(N >= 1 && Nc >= 1 && Nc <= N && mxGetNumberOfElements(prhs[3]) == (size_t)3 * Nc && KT >= 2, "po must be 3 x N, pf 3 x N_cmd (N_cmd <= N), K_T_max >= 2");
+        const size_t nw = mxGetNumberOfElements(prhs[12]), np8 = mxGetNumberOfElements(prhs[13]);
+        need(nw == 0 || nw == 3, "wind must have 3 elements (or be empty)");
+        need(np8 == 0 || (mxGetM(prhs[13]) == 8 && np8 % 8 == 0), "pushes must be 8 x n: agent (1-based), column (0-based), dp (3), dv (3) (or empty)");
+        std::vector<dmpc_push> push(np8 / 8);
+        for (size_t j = 0; j < push.size(); ++j) {
+            const double *q = mxGetPr(prhs[13]) + 8 * j;
+            push[j].scene = 0; push[j].agent = (int32_t)q[0] - 1; push[j].column = (int32_t)q[1];
+            for (int c = 0; c < 3; ++c) { push[j].dp[c] = q[2 + c]; push[j].dv[c] = q[5 + c]; }
+        }
+        const dmpc_disturbance dist{(uint64_t)mxGetScalar(prhs[11]), mxGetScalar(prhs[9]), mxGetScalar(prhs[10]), nw ? mxGetPr(prhs[12]) : nullptr, nw ? 1 : 0,
+                                    push.empty() ? nullptr : push.data(), (int)push.size()};
+        const dmpc_feedback fbk{mxGetScalar(prhs[6]), mxGetScalar(prhs[7]), (int32_t)mxGetScalar(prhs[8])};
+        const dmpc_measurement meas{(uint64_t)mxGetScalar(prhs[18]), mxGetScalar(prhs[14]), mxGetScalar(prhs[15]), mxGetScalar(prhs[16]), mxGetScalar(prhs[17])};
+        const mwSize d3[3] = {3, (mwSize)KT, (mwSize)Nc};
+        plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        mxArray *v = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL), *a = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+        int32_t used = 0, sst = 0;
+        auto clear = [&]() { dmpc_set_disturbance(ctx, nullptr); dmpc_set_feedback(ctx, nullptr); dmpc_set_measurement(ctx, nullptr); };   // the contexts are kept between calls: the settings must not outlive this one
+        if (dmpc_set_feedback(ctx, &fbk) || dmpc_set_measurement(ctx, &meas) || dmpc_set_disturbance(ctx, &dist)) {
+            const std::string why = dmpc_last_error(ctx);
+            clear();
+            mexErrMsgIdAndTxt("dmpc:transition_estimated", "%s", why.c_str());
+        }
+        int rc = Nc == N ? dmpc_transition(ctx, 1, N, mxGetPr(prhs[2]), mxGetPr(prhs[3]), KT, mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v), mxGetPr(a),
+                                           &used, &sst)
+                         : dmpc_transition_cmd(ctx, 1, N, Nc, mxGetPr(prhs[2]), mxGetPr(prhs[3]), KT, mxGetScalar(prhs[5]), mxGetPr(plhs[0]), mxGetPr(v),
+                                               mxGetPr(a), &used, &sst);
+        mxArray *f[11];   // event_count, event_first, event_last, dev_p_col, dev_v_col | dev_p_max, dev_v_max | xh_p, xh_v, e_p, e_v
+        for (int u = 0; u < 11; ++u) f[u] = mxCreateDoubleMatrix(u < 7 ? 1 : 3, Nc, mxREAL);
+        mxArray *g[10];   // err_p_col, err_v_col, dev_p_col, dev_v_col | err_p_max, err_v_max, dev_p_max, dev_v_max | eh_p, eh_v
+        for (int u = 0; u < 10; ++u) g[u] = mxCreateDoubleMatrix(u < 8 ? 1 : 3, Nc, mxREAL);
+        std::vector<int32_t> li((size_t)5 * Nc), gi((size_t)4 * Nc);
+        if (!rc) rc = dmpc_feedback_log(ctx, 1, Nc, &li[0], &li[Nc], &li[2 * (size_t)Nc], mxGetPr(f[5]), &li[3 * (size_t)Nc], mxGetPr(f[6]), &li[4 * (size_t)Nc],
+                                        mxGetPr(f[7]), mxGetPr(f[8]), mxGetPr(f[9]), mxGetPr(f[10]));
+        if (!rc) rc = dmpc_estimate_log(ctx, 1, Nc, mxGetPr(g[4]), &gi[0], mxGetPr(g[5]), &gi[Nc], mxGetPr(g[6]), &gi[2 * (size_t)Nc], mxGetPr(g[7]), &gi[3 * (size_t)Nc],
+                                        mxGetPr(g[8]), mxGetPr(g[9]));
+        const std::string why = rc ? dmpc_last_error(ctx) : "";
+        clear();
+        if (rc) mexErrMsgIdAndTxt("dmpc:transition_estimated", "%s", why.c_str());
+        for (int u = 0; u < 5; ++u)
+            for (int i = 0; i < Nc; ++i) mxGetPr(f[u])[i] = (double)li[(size_t)u * Nc + i];
+        for (int u = 0; u < 4; ++u)
+            for (int i = 0; i < Nc; ++i) mxGetPr(g[u])[i] = (double)gi[(size_t)u * Nc + i];
+        if (nlhs > 1) plhs[1] = v; if (nlhs > 2) plhs[2] = a;
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)used);
+        if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)sst);
+        static const int order[11] = {0, 1, 2, 5, 3, 6, 4, 7, 8, 9, 10};   // dmpc_feedback_log's order of outputs
+        for (int u = 0; u < 11; ++u) if (nlhs > 5 + u) plhs[5 + u] = f[order[u]];
+        static const int eorder[10] = {4, 0, 5, 1, 6, 2, 7, 3, 8, 9};      // dmpc_estimate_log's
+        for (int u = 0; u < 10; ++u) if (nlhs > 16 + u) plhs[16 + u] = g[eorder[u]];
         return;
     }
     if (!std::strcmp(cmd, "flight_end")) {   // where the last 'transition*' of this context ended (dmpc_flight_end): what 'transition_from' takes
